@@ -9,7 +9,12 @@
             base + global trial index), no data-path collective; one RCCL all_gather
             of the success flags after the timed region  -> "scaling": "weak"
 
-Also reported on the same JSON line:
+A plain run sets up, warms up, times `--steps` steps and prints the headline line (metric, value, unit,
+higher_is_better, dtype, ms_per_step and the configuration).  `--dump-outputs DIR` writes what the last timed step
+computed to DIR/<name>.npy (float32, at most 64 MB in all: a fixed, seeded sample of codewords where the whole batch
+would not fit); the inputs are seeded, so two builds can be compared output for output.
+
+With --full, also reported on the same JSON line (and each taking runs of its own):
   roofline      `achieved` / `frac` = bytes REALLY MOVED (rocprofv3 FETCH_SIZE + WRITE_SIZE, taken live by two short child
                 runs) by a (check + variable) launch pair, all stream lanes, / the pair's HIP-event time, against the
                 8 TB/s HBM peak; `kernel` = the one with the larger share of the pair's time; `hbm_frac` = the same in
@@ -21,6 +26,8 @@ Also reported on the same JSON line:
                 message (iteration 1's table, degree-1 columns).  No field labelled `frac` exceeds 1 (self_check).
   cpu_baseline  the CPU oracle's f32 restatement (oracle/, a "port": the reference's own
                 decoder binaries cannot run here) on a bounded sample, host cores stated
+  parity        codewords of the timed output checked against the CPU oracle (--parity-rows)
+  success       decode_success_rate / converged_rate of the timed batch
 """
 import argparse
 import importlib
@@ -62,6 +69,7 @@ WORKLOADS = {
 }
 QARY_WORKLOADS = ("qary_config4", "kyber_sw6", "criterion_small", "criterion_medium")
 VALU_PEAK_OPS = 78.6e12  # MI355X_MICROARCH.md: 256 CUs x 128 fp32 lanes x 2.4 GHz, one (non-FMA) VALU op per lane per cycle
+DUMP_BYTES = 64 * 1000 * 1000  # --dump-outputs: at most this much in all (over every rank)
 
 
 def main():
@@ -91,18 +99,25 @@ def main():
                     "ids, print {rccl_ranks}; no decode (checks the N>1 launch path; works over gloo without a GPU)")
     ap.add_argument("--parity-rows", type=int, default=64, help="codewords of the timed output checked against the "
                     "CPU oracle after the timed region (0 = skip); a mismatch makes the run exit non-zero")
+    ap.add_argument("--full", action="store_true", help="everything besides the headline figure: PMC passes, kernel "
+                    "timings, roofline, ceilings, success rates, parity against the CPU oracle, cpu_baseline (the options "
+                    "--pmc, --pmc-save, --no-hbm-streaming, --parity-rows, --no-cpu-baseline and --cpu-seconds act only here)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last "
+                    "step computed to DIR/<name>.npy (float32, at most 64 MB in all; a fixed, seeded sample of codewords "
+                    "where the batch does not fit)")
     args = ap.parse_args()
     self_launch(args)
     # PMC passes first: children of a process that has not touched the GPU yet
     live_traffic = None
-    if args.gpus == 1 and args.pmc == "live" and not args.pmc_child and WORKLOADS[args.workload][0] and args.workload != "hqc128_mc":
+    if (args.full and args.gpus == 1 and args.pmc == "live" and not args.pmc_child and WORKLOADS[args.workload][0]
+            and args.workload != "hqc128_mc"):
         live_traffic = pmc_live(args.workload)
         if live_traffic and args.pmc_save:
             with open(args.pmc_save, "w") as fh:
                 json.dump(live_traffic, fh, indent=1)
 
     args.sq_live = None
-    if (args.gpus == 1 and args.pmc == "live" and not args.pmc_child and args.workload in ("qary_config4", "kyber_sw6")):
+    if (args.full and args.gpus == 1 and args.pmc == "live" and not args.pmc_child and args.workload in ("qary_config4", "kyber_sw6")):
         qb = {"qary_config4": 1024, "kyber_sw6": 256}[args.workload] if args.batch == 4096 else args.batch
         args.sq_live = sq_live(args.workload, qb)
         if args.sq_live and args.pmc_save:
@@ -192,6 +207,39 @@ def main():
     if world > 1:  # every rank's own time travels to rank 0 (a straggler must not hide behind the MAX)
         per_rank_ms = coll.gather_scalars(dt / args.steps * 1e3)
         dt = max(per_rank_ms) * args.steps / 1e3
+    if args.dump_outputs:  # the decisions and convergence flags the last timed step left behind
+        dump_outputs(args.dump_outputs, rank, world, {"converged": d_conv.cpu().numpy()}, ("bits", d_out.cpu().numpy()))
+    total_cw = batch * world * args.steps
+    head = {
+        "metric": "edge_message_updates_per_s",
+        "value": 2.0 * E * iters * total_cw / dt,
+        "unit": "directed edge-message updates/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": {
+            "workload": f"{hqc} H=[Hin|I] N={N} W=50 R={R} E={E}, batch {batch}/GPU, {iters} fixed iters, {method}",
+            "batch_per_gpu": batch,
+            "iters": iters,
+            "eps": args.eps,
+            "tile_group": args.tile_group,
+        },
+    }
+    if not args.full:
+        if rank == 0:
+            head.update({"collective_backend": coll.backend, "collective_note": coll.note or None,
+                         "codewords_per_s": total_cw / dt, "whole_job_algorithmic_GBps": 16.0 * E * iters * total_cw / dt / 1e9})
+            if per_rank_ms:
+                head["per_rank_ms_per_step"] = per_rank_ms
+            print(json.dumps(head), flush=True)
+        dec.close()
+        return finish(coll, 0)
 
     # per-kernel launch durations, HIP events on the launch stream -- taken right behind the timed region, on the very
     # state it left (before the HBM-streaming pass re-sizes the handle's arrays), and held to the driver-timed step: the
@@ -263,9 +311,6 @@ def main():
 
     rc = 0
     if rank == 0:
-        total_cw = batch * world * args.steps
-        updates = 2.0 * E * iters * total_cw
-        value = updates / dt
         check_gbs = 8.0 * E * swept / (ms_check * 1e-3) / 1e9  # 4 B read + 4 B written per edge per codeword
         var_gbs = 8.0 * E * kt["codewords_var"] / (ms_var_pass * 1e-3) / 1e9
         rec = bool(kt.get("record_form"))  # min-sum in its record form (knob minsum_rec): other kernels, same algorithmic bytes
@@ -274,25 +319,7 @@ def main():
         vname = "k_var_rec" if rec else "k_var"
         cpmc = ("k_check_minsum_rec" if rec else "k_check_minsum") if method == "min_sum" else "k_check_tanh"
         out = {
-            "metric": "edge_message_updates_per_s",
-            "value": value,
-            "unit": "directed edge-message updates/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic",
-            "config": {
-                "workload": f"{hqc} H=[Hin|I] N={N} W=50 R={R} E={E}, batch {batch}/GPU, {iters} fixed iters, {method}",
-                "batch_per_gpu": batch,
-                "iters": iters,
-                "eps": args.eps,
-                "tile_group": args.tile_group,
-            },
+            **head,
             "rccl_ranks": int(len(set(ranks_seen.tolist()))),  # ranks the end-of-run all_gather saw
             "collective_backend": coll.backend,  # "nccl" = RCCL; "gloo" = RCCL did not come up (collective_note says why); "none" = one rank
             "collective_note": coll.note or None,
@@ -462,6 +489,26 @@ def finish(coll, rc):
     coll.close()
     if rc:
         raise SystemExit(rc)
+
+
+def dump_outputs(path, rank, world, whole, sampled=None):
+    """--dump-outputs: write what the last timed step computed as `path`/<name>.npy in float32 (rank r > 0: <name>_rank<r>.npy).
+    `whole` = {name: array} written as they are; `sampled` = (name, [batch, ...] array) written whole if it fits this rank's
+    share of DUMP_BYTES, else as a fixed, seeded sample of its rows (sorted), their indices in <name>_rows.npy (float64)."""
+    os.makedirs(path, exist_ok=True)
+    sfx = f"_rank{rank}" if rank else ""
+    arrays = {k: np.asarray(v, dtype=np.float32) for k, v in whole.items()}
+    if sampled is not None:
+        name, a = sampled
+        budget = DUMP_BYTES // world - sum(v.nbytes for v in arrays.values()) - 8 * a.shape[0] - 4096  # (index array, headers)
+        take = int(min(a.shape[0], max(1, budget // (4 * max(1, a[0].size)))))
+        if take < a.shape[0]:
+            rows = np.sort(np.random.RandomState(0).choice(a.shape[0], take, replace=False))
+            arrays[name + "_rows"] = rows.astype(np.float64)
+            a = a[rows]
+        arrays[name] = np.asarray(a, dtype=np.float32)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + sfx + ".npy"), v)
 
 
 def parity_check(H, probs, msg, out_host, iters, method, rows, swept=128, lanes=2):
@@ -771,36 +818,49 @@ def qary_bench(args, S, rank, world, coll, local, iters):
         coll.barrier()
         dt = time.perf_counter() - t0
         out = d_out.cpu().numpy()
-        # the same call as the PyO3 class takes it: host arrays in, symbols out (PCIe both ways) -- reported, never `value`
-        for _ in range(2):
-            out_host = dec.min_sum_batch(*inputs)
-        t1 = time.perf_counter()
-        for _ in range(args.steps):
-            out_host = dec.min_sum_batch(*inputs)
-        dt_host = (time.perf_counter() - t1) / args.steps
-        assert np.array_equal(out_host, out), "host-buffer and device-buffer calls disagree"
-        # kernel times: one more call with the launches bracketed by HIP events on the handle's stream
-        dec.configure(timing=1)
-        step()
-        kt = dec.last_timing()
-        dec.configure(timing=0)
+        if args.dump_outputs:  # the symbols the last timed call left behind
+            dump_outputs(args.dump_outputs, rank, world, {}, ("symbols", out))
+        if args.full:
+            # the same call as the PyO3 class takes it: host arrays in, symbols out (PCIe both ways) -- reported, never `value`
+            for _ in range(2):
+                out_host = dec.min_sum_batch(*inputs)
+            t1 = time.perf_counter()
+            for _ in range(args.steps):
+                out_host = dec.min_sum_batch(*inputs)
+            dt_host = (time.perf_counter() - t1) / args.steps
+            assert np.array_equal(out_host, out), "host-buffer and device-buffer calls disagree"
+            # kernel times: one more call with the launches bracketed by HIP events on the handle's stream
+            dec.configure(timing=1)
+            step()
+            kt = dec.last_timing()
+            dec.configure(timing=0)
     per_rank_ms = None
     if world > 1:
         per_rank_ms = coll.gather_scalars(dt / args.steps * 1e3)
         dt = max(per_rank_ms) * args.steps / 1e3
     rc = 0
+    head = {
+        "metric": "edge_message_updates_per_s", "value": 2.0 * g.nnz * batch * iters * args.steps * world / dt,
+        "unit": "directed symbol-edge message updates/s", "n_gpus": world, "steps": args.steps, "warmup": max(1, args.warmup),
+        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"{what}, {iters} iterations, batch {batch}/GPU, pmf resident in HBM / symbols left in HBM "
+                               f"(probability->LLR conversion on the device, inside the timed call)", "batch_per_gpu": batch, "iters": iters},
+        "codewords_per_s": batch * args.steps * world / dt, "calls_per_s": args.steps * world / dt,
+        "collective_backend": coll.backend, "collective_note": coll.note or None,
+    }
+    if not args.full:
+        if rank == 0:
+            if per_rank_ms:
+                head["per_rank_ms_per_step"] = per_rank_ms
+            print(json.dumps(head), flush=True)
+        dec.close()
+        return rc
     if rank == 0:
         ops, assignments = qary_reference_ops(g, cls, special)
         ms_check = kt["ms_check"] / kt["iterations"]
         line = {
-            "metric": "edge_message_updates_per_s", "value": 2.0 * g.nnz * batch * iters * args.steps * world / dt,
-            "unit": "directed symbol-edge message updates/s", "n_gpus": world, "steps": args.steps, "warmup": max(1, args.warmup),
-            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"{what}, {iters} iterations, batch {batch}/GPU, pmf resident in HBM / symbols left in HBM "
-                                   f"(probability->LLR conversion on the device, inside the timed call)", "batch_per_gpu": batch, "iters": iters},
-            "codewords_per_s": batch * args.steps * world / dt, "calls_per_s": args.steps * world / dt,
-            "collective_backend": coll.backend, "collective_note": coll.note or None,
+            **head,
             "host_buffers": {"ms_per_step": dt_host * 1e3, "value": 2.0 * g.nnz * batch * iters / dt_host,
                              "what": "the same call with host arrays in and out, as the PyO3 class takes them (PCIe both ways included)"},
             "all_zero_rate": float((out == 0).all(axis=1).mean()),
@@ -945,6 +1005,8 @@ def mc_sweep(args, S, bp, lib, trials, H, N, omega, R, E, probs, iters, method, 
     torch.cuda.synchronize()
     coll.barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and succ:  # the last sub-batch's per-trial success flags and iteration counts
+        dump_outputs(args.dump_outputs, rank, world, {"success": succ[-1], "iters": its[-1]})
     succ = np.concatenate(succ) if succ else np.zeros(0, np.uint8)
     its = np.concatenate(its) if its else np.zeros(0, np.int32)
     dev = torch.device("cuda", local)
@@ -974,6 +1036,10 @@ def mc_sweep(args, S, bp, lib, trials, H, N, omega, R, E, probs, iters, method, 
         if per_rank_s:
             line["per_rank_wall_s"] = per_rank_s
             line["rank_wall_s_min_max"] = [min(per_rank_s), max(per_rank_s)]
+        if not args.full:
+            print(json.dumps(line), flush=True)
+            dec.close()
+            return rc
         # kernel launch times in the sweep's own schedule: one short fixed-iteration decode of 4096 of the sweep's
         # trials leaves a full tile group's message state behind, then the HIP-event series of time_kernels
         r4 = dec.mc_hqc_run(4096, omega, args.eps, seed=2, first_trial=0, early_exit=True, want_inputs=True)

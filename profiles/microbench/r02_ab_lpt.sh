@@ -5,7 +5,7 @@ B="--steps 5 --warmup 1 --no-cpu-baseline --pmc off --no-hbm-streaming"
 for W in hqc256_tanh hqc128_minsum hqc192_minsum; do
   for V in "order1:SCALDPC_VAR_ORDER=1" "order3:SCALDPC_VAR_ORDER=3" "order2:SCALDPC_VAR_ORDER=2"; do
     name=${V%%:*}; envs=${V#*:}
-    env $envs timeout -k 10 200 python bench.py $B --workload $W > $O/ab_${W}_${name}.json 2> $O/ab_${W}_${name}.err || echo "bench $W $name failed"
+    env $envs timeout -k 10 200 python bench.py --full $B --workload $W > $O/ab_${W}_${name}.json 2> $O/ab_${W}_${name}.err || echo "bench $W $name failed"
     python - <<PY
 import json
 try:

@@ -10,7 +10,7 @@ B="--steps 5 --warmup 1 --no-cpu-baseline --pmc off --no-hbm-streaming"
 for W in hqc128_minsum hqc256_tanh; do
   for V in "base:" "form1:SCALDPC_VAR_FORM=1" "order1:SCALDPC_VAR_ORDER=1" "both:SCALDPC_VAR_FORM=1 SCALDPC_VAR_ORDER=1"; do
     name=${V%%:*}; envs=${V#*:}
-    env $envs timeout -k 10 200 python bench.py $B --workload $W > $O/ab_${W}_${name}.json 2> $O/ab_${W}_${name}.err || echo "bench $W $name failed"
+    env $envs timeout -k 10 200 python bench.py --full $B --workload $W > $O/ab_${W}_${name}.json 2> $O/ab_${W}_${name}.err || echo "bench $W $name failed"
     python - <<PY
 import json
 try:

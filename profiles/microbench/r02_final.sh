@@ -4,7 +4,7 @@ O=gpurun_out/r02z
 export TMPDIR=/tmp
 timeout -k 10 900 python -m pytest tests -m gpu -q > $O/pytest_all.log 2>&1; echo "all tests rc=$?" | tee -a $O/pytest_all.log; tail -4 $O/pytest_all.log
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc=$?"; tail -1 $O/smoke.log
-timeout -k 10 400 python bench.py > $O/bench_default.log 2> $O/bench_default.err; echo "bench rc=$?"
+timeout -k 10 400 python bench.py --full > $O/bench_default.log 2> $O/bench_default.err; echo "bench rc=$?"
 python - <<PY
 import json
 d=json.loads([l for l in open("$O/bench_default.log") if l.startswith("{")][-1])

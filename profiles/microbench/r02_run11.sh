@@ -2,7 +2,7 @@ set -o pipefail
 mkdir -p gpurun_out/r02j
 O=gpurun_out/r02j
 for MB in 32768 131072 262144 524288; do
-  timeout -k 10 300 python bench.py --workload hqc128_mc --trials 1048576 --warmup 1 --mc-batch $MB > $O/mc_$MB.log 2> $O/mc_$MB.err || echo "mc $MB failed"
+  timeout -k 10 300 python bench.py --full --workload hqc128_mc --trials 1048576 --warmup 1 --mc-batch $MB > $O/mc_$MB.log 2> $O/mc_$MB.err || echo "mc $MB failed"
   python - <<PY
 import json
 try:

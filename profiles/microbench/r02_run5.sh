@@ -9,7 +9,7 @@ B="--steps 5 --warmup 1 --no-cpu-baseline --pmc off --no-hbm-streaming"
 for W in hqc256_tanh hqc128_tanh; do
   for V in "base:" "pipe256:SCALDPC_CHECK_PIPE=256" "pipe512:SCALDPC_CHECK_PIPE=512"; do
     name=${V%%:*}; envs=${V#*:}
-    env $envs timeout -k 10 200 python bench.py $B --workload $W > $O/ab_${W}_${name}.json 2> $O/ab_${W}_${name}.err || echo "bench $W $name failed"
+    env $envs timeout -k 10 200 python bench.py --full $B --workload $W > $O/ab_${W}_${name}.json 2> $O/ab_${W}_${name}.err || echo "bench $W $name failed"
     python - <<PY
 import json
 try:

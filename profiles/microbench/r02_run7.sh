@@ -8,10 +8,10 @@ timeout -k 10 300 python profiles/microbench/attack_loop_step.py > $O/attack_loo
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_kyber -o kyber --output-format csv -- python3 profiles/microbench/kyber_check.py 5 tree > $O/prof_kyber.log 2>&1; echo "prof kyber rc=$?"; tail -4 $O/prof_kyber.log
 : > $O/all_workloads.log
 for W in hqc128_minsum hqc128_tanh hqc192_minsum hqc256_tanh; do
-  timeout -k 10 400 python bench.py --workload $W --steps 5 --warmup 1 --no-cpu-baseline >> $O/all_workloads.log 2> $O/bench_$W.err || echo "bench $W failed"
+  timeout -k 10 400 python bench.py --full --workload $W --steps 5 --warmup 1 --no-cpu-baseline >> $O/all_workloads.log 2> $O/bench_$W.err || echo "bench $W failed"
 done
-timeout -k 10 300 python bench.py --workload hqc128_mc --trials 1000000 --warmup 1 >> $O/all_workloads.log 2> $O/bench_mc.err || echo "bench mc failed"
-timeout -k 10 300 python bench.py --workload qary_config4 --steps 20 --warmup 2 >> $O/all_workloads.log 2> $O/bench_q4.err || echo "bench q4 failed"
+timeout -k 10 300 python bench.py --full --workload hqc128_mc --trials 1000000 --warmup 1 >> $O/all_workloads.log 2> $O/bench_mc.err || echo "bench mc failed"
+timeout -k 10 300 python bench.py --full --workload qary_config4 --steps 20 --warmup 2 >> $O/all_workloads.log 2> $O/bench_q4.err || echo "bench q4 failed"
 python - <<PY
 import json
 for l in open("$O/all_workloads.log"):

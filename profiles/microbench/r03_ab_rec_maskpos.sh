@@ -5,7 +5,7 @@ O=gpurun_out/r03bb; mkdir -p $O
 SCALDPC_REC_MASKPOS=1 timeout -k 10 300 python -m pytest tests/test_bp_gpu.py -q -m gpu -x -p no:cacheprovider -k "min_sum or minsum or record" > $O/pytest.log 2>&1; echo "pytest (maskpos=1) rc=$?"; tail -2 $O/pytest.log
 for V in 1 0 1 0; do
   P=off; [ $V$R = 1 ] && P=off
-  SCALDPC_REC_MASKPOS=$V timeout -k 10 300 python bench.py --workload hqc128_minsum --steps 6 --warmup 2 --no-cpu-baseline --pmc live --no-hbm-streaming > $O/m$V.json 2> $O/b.err; echo "hqc128_minsum rec_maskpos=$V rc=$?"
+  SCALDPC_REC_MASKPOS=$V timeout -k 10 300 python bench.py --full --workload hqc128_minsum --steps 6 --warmup 2 --no-cpu-baseline --pmc live --no-hbm-streaming > $O/m$V.json 2> $O/b.err; echo "hqc128_minsum rec_maskpos=$V rc=$?"
   python - <<PY
 import json
 d=json.loads([l for l in open("$O/m$V.json") if l.startswith("{")][-1])

@@ -2,7 +2,7 @@
 # round 3 A/B: the convergence test beside the next check pass (side stream) vs in line, config-5 sweep
 O=gpurun_out/r03g; mkdir -p $O
 for V in 1 0 1 0; do
-  SCALDPC_TEST_OVERLAP=$V timeout -k 10 300 python bench.py --workload hqc128_mc --trials 1000000 --warmup 1 --no-cpu-baseline --parity-rows 0 > $O/mc_overlap$V.json 2> $O/mc.err; echo "overlap=$V rc=$?"
+  SCALDPC_TEST_OVERLAP=$V timeout -k 10 300 python bench.py --full --workload hqc128_mc --trials 1000000 --warmup 1 --no-cpu-baseline --parity-rows 0 > $O/mc_overlap$V.json 2> $O/mc.err; echo "overlap=$V rc=$?"
   python - <<PY
 import json
 d=json.loads([l for l in open("$O/mc_overlap$V.json") if l.startswith("{")][-1])

@@ -2,7 +2,7 @@
 # round 3, end of round: every HQC workload's bench line with the final library -> gpurun_out/r03p/all_workloads.log
 O=gpurun_out/r03p; mkdir -p $O; : > $O/all_workloads.log
 for W in hqc128_minsum hqc128_tanh hqc192_minsum hqc256_tanh; do
-  timeout -k 10 400 python bench.py --workload $W --steps 5 --warmup 1 --no-cpu-baseline > $O/$W.json 2> $O/$W.err; echo "$W rc=$?"
+  timeout -k 10 400 python bench.py --full --workload $W --steps 5 --warmup 1 --no-cpu-baseline > $O/$W.json 2> $O/$W.err; echo "$W rc=$?"
   grep '^{' $O/$W.json | tail -1 >> $O/all_workloads.log
 done
 python - <<'PY'

@@ -6,7 +6,7 @@ O=gpurun_out/r03r; mkdir -p $O; : > $O/mc_knob_equivalence.log
 for EPS in 0.0 0.02 0.05 0.08; do
   for V in on off; do
     if [ $V = on ]; then unset SCALDPC_FIRST_FUSED SCALDPC_FUSE_TEST; else export SCALDPC_FIRST_FUSED=0 SCALDPC_FUSE_TEST=0; fi
-    timeout -k 10 300 python bench.py --workload hqc128_mc --trials 262144 --eps $EPS --warmup 1 --no-cpu-baseline --cpu-seconds 3 > $O/mc_${EPS}_$V.json 2> $O/err; rc=$?
+    timeout -k 10 300 python bench.py --full --workload hqc128_mc --trials 262144 --eps $EPS --warmup 1 --no-cpu-baseline --cpu-seconds 3 > $O/mc_${EPS}_$V.json 2> $O/err; rc=$?
     python - <<PY >> $O/mc_knob_equivalence.log
 import json
 d=json.loads([l for l in open("$O/mc_${EPS}_$V.json") if l.startswith("{")][-1])

@@ -1,7 +1,7 @@
 O=gpurun_out/r03an; mkdir -p $O
 for X in 3 4; do
   cp profiles/microbench/libscaldpc_x$X.so sca-ldpc_amd/libscaldpc.so
-  timeout -k 10 300 python bench.py --workload hqc128_minsum --steps 5 --warmup 1 --no-cpu-baseline --pmc off --no-hbm-streaming --parity-rows 0 > $O/x$X.json 2> $O/b.err; echo "experiment=$X rc=$?"
+  timeout -k 10 300 python bench.py --full --workload hqc128_minsum --steps 5 --warmup 1 --no-cpu-baseline --pmc off --no-hbm-streaming --parity-rows 0 > $O/x$X.json 2> $O/b.err; echo "experiment=$X rc=$?"
   python - <<PY
 import json
 d=json.loads([l for l in open("$O/x$X.json") if l.startswith("{")][-1])

@@ -4,7 +4,7 @@
 # streaming beside it)
 O=gpurun_out/r03av; mkdir -p $O
 for C in "2 0" "1 4" "1 2" "1 1" "2 2"; do set -- $C
-  SCALDPC_SPLIT=$1 timeout -k 10 300 python bench.py --workload hqc128_minsum --steps 4 --warmup 1 --no-cpu-baseline --pmc live --no-hbm-streaming --tile-group $2 > $O/s$1_g$2.json 2> $O/b.err; echo "split=$1 group=$2 rc=$?"
+  SCALDPC_SPLIT=$1 timeout -k 10 300 python bench.py --full --workload hqc128_minsum --steps 4 --warmup 1 --no-cpu-baseline --pmc live --no-hbm-streaming --tile-group $2 > $O/s$1_g$2.json 2> $O/b.err; echo "split=$1 group=$2 rc=$?"
   python - <<PY
 import json
 d=json.loads([l for l in open("$O/s$1_g$2.json") if l.startswith("{")][-1])

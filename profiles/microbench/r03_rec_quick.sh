@@ -3,7 +3,7 @@
 O=gpurun_out/r03am; mkdir -p $O
 for R in 1 2 3; do
   P=off; [ $R = 3 ] && P=live
-  timeout -k 10 300 python bench.py --workload hqc128_minsum --steps 8 --warmup 2 --no-cpu-baseline --pmc $P --no-hbm-streaming > $O/run$R.json 2> $O/b.err; echo "run $R rc=$?"
+  timeout -k 10 300 python bench.py --full --workload hqc128_minsum --steps 8 --warmup 2 --no-cpu-baseline --pmc $P --no-hbm-streaming > $O/run$R.json 2> $O/b.err; echo "run $R rc=$?"
   python - <<PY
 import json
 d=json.loads([l for l in open("$O/run$R.json") if l.startswith("{")][-1])

@@ -1,7 +1,7 @@
 #!/bin/bash
 # every bench workload once with the shipped library; one JSON line each under $1
 out=$1; mkdir -p $out
-run() { name=$1; shift; timeout -k 10 420 python bench.py "$@" > $out/bench_$name.json 2> $out/bench_$name.err || echo "FAILED $name rc=$?"; tail -c 300 $out/bench_$name.err | grep -v "amdgpu.ids" | tail -2; echo "done $name"; }
+run() { name=$1; shift; timeout -k 10 420 python bench.py --full "$@" > $out/bench_$name.json 2> $out/bench_$name.err || echo "FAILED $name rc=$?"; tail -c 300 $out/bench_$name.err | grep -v "amdgpu.ids" | tail -2; echo "done $name"; }
 run hqc128_minsum --pmc-save $out/pmc_traffic_hqc128_minsum.json
 run hqc192_minsum --workload hqc192_minsum --pmc-save $out/pmc_traffic_hqc192_minsum.json
 run hqc128_tanh --workload hqc128_tanh --pmc-save $out/pmc_traffic_hqc128_tanh.json

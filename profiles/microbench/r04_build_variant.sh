@@ -1,6 +1,6 @@
 #!/bin/bash
 # usage: r04_build_variant.sh NAME "-DFOO -DBAR"   -> build/ab/libscaldpc_NAME.so: the library with the bp translation unit rebuilt under extra
-# defines, for A/B runs of compile-time variants (SCALDPC_SO=build/ab/libscaldpc_NAME.so python bench.py ...; build/ is not in history)
+# defines, for A/B runs of compile-time variants (SCALDPC_SO=build/ab/libscaldpc_NAME.so python bench.py --full ...; build/ is not in history)
 set -e
 name=$1; defs=$2
 out=/root/repo/build/ab; mkdir -p $out /tmp/var_$name

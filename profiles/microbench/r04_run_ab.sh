@@ -4,7 +4,7 @@ out=$1; shift
 mkdir -p $out
 for v in "$@"; do
   if [ "$v" = base ]; then unset SCALDPC_SO; else export SCALDPC_SO=$PWD/build/ab/libscaldpc_$v.so; fi
-  timeout -k 10 300 python bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-hbm-streaming > $out/$v.json 2> $out/$v.err || echo "FAILED $v"
+  timeout -k 10 300 python bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-hbm-streaming > $out/$v.json 2> $out/$v.err || echo "FAILED $v"
   python3 - "$out/$v.json" "$v" <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

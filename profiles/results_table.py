@@ -67,7 +67,7 @@ def main():
         rows.append(f"| `criterion_small` / `criterion_medium` | **{c[0]['ms_per_step']:.2f} / {c[1]['ms_per_step']:.2f} ms** per `min_sum` call at batch 1 | "
                     f"`bound: launch` ({c[0]['roofline']['launches_per_call']} launches per call); no VALU / HBM fraction claimed | one host core: "
                     f"{c[0]['cpu_baseline']['single_thread_ms_per_call']:.3f} / {c[1]['cpu_baseline']['single_thread_ms_per_call']:.2f} ms per call |")
-    print(f"**Results, one MI355X, round {rnd[1:].lstrip('0')}** (`python bench.py --workload …`; `profiles/{rnd}/bench_*.json`; every line `parity_ok`, "
+    print(f"**Results, one MI355X, round {rnd[1:].lstrip('0')}** (`python bench.py --full --workload …`; `profiles/{rnd}/bench_*.json`; every line `parity_ok`, "
           "`self_check` all true):\n")
     print("| workload | `value` / time | `roofline` | `cpu_baseline` (GPU box host, \"port\") |\n|---|---|---|---|")
     print("\n".join(rows))

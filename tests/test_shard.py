@@ -108,7 +108,9 @@ def _run_bench(*argv, **env):
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    e = dict(os.environ, **env)
+    # the ranks see no GPU, as on a machine without one: these are CPU rehearsals of the launch path, and on a one-GPU
+    # machine rank 1 would otherwise pick a device that does not exist
+    e = dict(os.environ, HIP_VISIBLE_DEVICES="-1", **env)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         e.pop(k, None)  # a plain shell, as the driver's `python3 bench.py --gpus N`
     return subprocess.run([sys.executable, os.path.join(root, "bench.py"), *argv], env=e, capture_output=True, text=True,
