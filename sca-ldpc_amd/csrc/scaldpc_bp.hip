@@ -79,70 +79,86 @@ struct Knobs {
     int minsum_rec = 1;       // min-sum on the tile kernels: check pass writes per-row records + lane masks instead of messages (k_check_minsum_rec / k_var_rec); 0 = message form
 };
 
-struct scaldpc_bp {
+// The handle's streams and events, released when the handle goes.  scaldpc_bp derives from it, so every buffer member
+// has returned its device memory before they are released.
+struct HandleStreams {
+    int device = 0;  // the device the handle (and its stream) was created on
+    hipStream_t own_stream = nullptr;
+    hipStream_t aux_stream[4] = {};  // further lanes of a tile group (iterate_tiles)
+    hipEvent_t ev_join[4] = {}, ev_phase[4] = {};
+    HandleStreams() = default;
+    HandleStreams(const HandleStreams &) = delete;
+    HandleStreams &operator=(const HandleStreams &) = delete;
+    ~HandleStreams()
+    {
+        if (own_stream) stream_release(own_stream, device);
+        for (int k = 0; k < 4; k++) {
+            if (aux_stream[k]) stream_release(aux_stream[k], device);
+            if (ev_join[k]) (void)hipEventDestroy(ev_join[k]);
+            if (ev_phase[k]) (void)hipEventDestroy(ev_phase[k]);
+        }
+    }
+};
+
+// Every block the handle owns is a Buf member; plain pointers below are views into one of them.
+struct scaldpc_bp : HandleStreams {
     Knobs kn;
     int m = 0, n = 0;
     long E = 0;
     int max_row_deg = 0, max_col_deg = 0, min_row_deg = 0;
-    // device graph
+    // device graph (views: into d_graph, or d_csr_rp / d_csr_ci once the graph grows; d_row_list, d_var_meta and
+    // d_csc_list into d_tile_tab)
     int *d_row_ptr = nullptr, *d_col_idx = nullptr, *d_col_ptr = nullptr, *d_csc_edge = nullptr;
     int *d_var_list = nullptr, *d_row_list = nullptr;
     int *d_var_meta = nullptr, *d_csc_list = nullptr;  // k_var: packed column descriptors + edge lists in launch order
     Buckets var_bk{}, row_bk{};
     bool need_scratch = false;
-    // priors
+    // priors (view: into d_graph, or d_prior_buf once the graph grows)
     float *d_prior = nullptr;
     bool have_prior = false;
     int prior_n = 0;  // columns whose prior is set (a grown graph needs scaldpc_bp_set_channel_probs_tail for the new ones)
     // workspace (state arrays sized for cap_tiles, messages for cap_group tiles)
     int cap_tiles = 0, cap_group = 0, tile_group = 0;
-    float *d_msg = nullptr, *d_scratch = nullptr, *d_post = nullptr;
-    u64 *d_synd = nullptr, *d_recv = nullptr, *d_hard = nullptr, *d_done = nullptr, *d_conv = nullptr,
-        *d_unsat = nullptr;
-    int *d_iters = nullptr, *d_remaining = nullptr;
-    int cap_remaining = 0;
+    Buf<float> d_msg, d_scratch, d_post;
+    Buf<u64> d_synd, d_recv, d_hard, d_done, d_conv, d_unsat;
+    Buf<int> d_iters, d_remaining;
+    int cap_remaining = 0;  // counters per row of d_remaining (and of h_remaining)
     // d_remaining holds rem_rows rows of cap_remaining "codewords still running after iteration it" counters: every tile
     // group of a call takes the next row (zeroed once per call, not once per group: a memset is a 5 us launch in the
     // group's dependency chain); rem_slot = next free row, rem_rows = all used (the next taker zeroes the array).
     // rem_rows follows the groups a call can run (at most REM_SLOTS): max_iter defaults to n, and 512 rows of n + 2
     // counters were 44 MB -- allocated and cleared -- on an HQC-sized decoder that decodes ONE codeword.
     int rem_slot = 0, rem_rows = 0;
-    bool post_alloc = false;
     // host-I/O staging
-    uint8_t *d_in = nullptr, *d_out_bits = nullptr, *d_out_conv = nullptr;
-    float *d_out_llr = nullptr;
-    int *d_out_iters = nullptr;
-    size_t cap_in = 0, cap_out_bits = 0, cap_out_llr = 0, cap_out_b = 0;
-    int *h_remaining = nullptr;  // pinned
+    Buf<uint8_t> d_in, d_out_bits, d_out_conv;
+    Buf<float> d_out_llr;
+    Buf<int> d_out_iters;
+    PinnedBuf<int> h_remaining;
     // small host calls (one tile, a handful of codewords): fused reshaping kernels, one pinned staging buffer
-    uint8_t *h_io = nullptr, *d_out_all = nullptr;
-    size_t cap_h_io = 0, cap_out_all = 0;
+    PinnedBuf<uint8_t> h_io;
+    Buf<uint8_t> d_out_all;
     bool small_prepared = false;  // k_small_prepare already reset the state this call (run_core / the early-exit loop skip theirs)
     // Monte-Carlo helpers
     pvec<double> h_probs;
-    u64 *d_thr = nullptr, *d_mc = nullptr, *d_diff = nullptr;
-    int *d_ylist = nullptr;
-    uint8_t *d_succ = nullptr;
-    size_t cap_mc = 0, cap_ylist = 0, cap_succ = 0, cap_diff = 0;
+    Buf<u64> d_thr, d_mc, d_diff;
+    Buf<int> d_ylist;
+    Buf<uint8_t> d_succ;
     bool thr_valid = false;
     // compact second pass over stragglers (early-exit runs)
     // (level k re-decodes the stragglers of level k-1 in dense tiles of their own; level 0 = the call's arrays)
     struct Level {
         int cap_tiles = 0;
-        u64 *synd = nullptr, *hard = nullptr, *done = nullptr, *conv = nullptr, *unsat = nullptr;
-        int *iters = nullptr, *ids = nullptr, *slot_of = nullptr;
-        float *post = nullptr;
-        size_t cap_post = 0, cap_slot_of = 0;
+        Buf<u64> synd, hard, done, conv, unsat;
+        Buf<int> iters, ids, slot_of;
+        Buf<float> post;
     };
     static constexpr int MAX_LEVELS = 3;
     Level lv[MAX_LEVELS + 1];  // [0] unused
     long stat_levels = 0;      // deepest compact level the last call reached
     long stat_deferred = 0;  // codewords re-decoded by the compact pass in the last call
     // row-parallel path (a handful of codewords): per-codeword message / prefix arrays [codeword][edge]
-    float *d_emsg = nullptr;
-    size_t cap_el = 0;
-    int *d_el_unsat = nullptr;  // [iteration][64] "some row unsatisfied" flags of the fused early-exit loop
-    size_t cap_el_unsat = 0;
+    Buf<float> d_emsg;
+    Buf<int> d_el_unsat;  // [iteration][64] "some row unsatisfied" flags of the fused early-exit loop
     // k_el_var: columns packed into waves ("bins") of 64 lane slots, each column a segment of `cap` lanes
     int *d_el_slots = nullptr, *d_el_slot_col = nullptr;  // views into d_el_tab: [2 * 64 * el_cap_bins] and [64 * el_cap_bins] ints
     int el_waves = 0;     // bins in use
@@ -158,48 +174,42 @@ struct scaldpc_bp {
     // tables) is marked stale and rebuilt from the host mirror when one of those paths is next taken.
     bool incremental = false, full_stale = false;
     pvec<int> hg_col_idx;  // host CSR mirror (incremental handles)
-    int *d_csr_rp = nullptr, *d_csr_ci = nullptr;
-    float *d_prior_buf = nullptr;
-    size_t cap_rows = 0, cap_edges = 0, cap_cols = 0;
+    Buf<int> d_csr_rp, d_csr_ci;
+    Buf<float> d_prior_buf;
     int ws_m = 0, ws_n = 0;  // what the workspace planes are sized for
     pvec<int> el_dirty_slot, el_dirty_col;  // words an append call changed (kept for their capacity)
-    int *d_pairs = nullptr;  // staging of table updates
-    int *h_pairs = nullptr;  // pinned
-    size_t cap_pairs = 0;
-    int *d_graph = nullptr;  // ONE allocation behind the arrays every path needs (CSR, CSC, var list, d_prior: views into it)
+    Buf<int> d_pairs;  // staging of table updates
+    PinnedBuf<int> h_pairs;
+    Buf<int> d_graph;  // ONE allocation behind the arrays every path needs (CSR, CSC, var list, d_prior: views into it)
     // The tables only one kernel family reads are built on that family's first use -- a decoder
     // that lives for one single decode (hqc.py:694) never pays for the tile kernels' tables, a
     // benchmark never for the row-parallel ones.  What the builders need stays on the host:
-    int *d_tile_tab = nullptr;  // row descriptors, k_var records, re-laid edge list (d_row_list, d_var_meta, d_csc_list)
+    Buf<int> d_tile_tab;  // row descriptors, k_var records, re-laid edge list (d_row_list, d_var_meta, d_csc_list)
     // iteration 1 without its check pass: {first check-to-variable message of a zero-syndrome codeword, row} per position
     // of the re-laid edge list; valid for one (method, alpha of iteration 1) and the current priors / graph
-    int2 *d_first_tab = nullptr;
-    size_t cap_first = 0;
+    Buf<int2> d_first_tab;
     // record form of min-sum on the tile kernels: per (tile, row) the two magnitudes, per (tile, edge) two lane masks;
     // d_csc_row = row of every position of the re-laid edge list (inside d_tile_tab)
-    float *d_rec = nullptr;
-    ulonglong2 *d_mask = nullptr;
+    Buf<float> d_rec;
+    Buf<ulonglong2> d_mask;
     int cap_rec_group = 0;
-    int *d_csc_row = nullptr, *d_var_rows = nullptr, *d_csr_pos = nullptr;
+    int *d_csc_row = nullptr, *d_var_rows = nullptr, *d_csr_pos = nullptr;  // views into d_tile_tab
     bool var_reversed = false;  // the column records are laid out heaviest first (var_order bit 1): the degree-1 bucket is at the END
     bool first_valid = false;
     int first_method = -1;
     float first_alpha = 0.0f;
-    int *d_el_tab = nullptr;    // k_el_var slots and wave info (d_el_slots, d_el_winfo)
+    Buf<int> d_el_tab;  // k_el_var slots and wave info (d_el_slots, d_el_winfo)
     pvec<int> hg_row_ptr, hg_cdeg, hg_col_ptr, hg_csc_edge;
     HostBuckets hg_var, hg_row;
     int stat_el = 0;  // codewords the row-parallel kernels decoded in the last call
     int identity_from = -1;  // n - m if the last m columns of H are I_m (H = [Hin | I]), else -1
-    hipStream_t own_stream = nullptr;
-    int device = 0;  // the device the handle (and its stream) was created on
-    hipStream_t aux_stream[4] = {};  // further lanes of a tile group (iterate_tiles)
-    hipEvent_t ev_join[4] = {}, ev_phase[4] = {};
     // Set by the first SCALDPC_F_ASYNC call and never cleared: work may be in flight when a later call
     // (or destroy) releases a buffer, so this handle's blocks go back through hipFree (which
     // waits for the device) instead of being parked for immediate reuse.
     bool async_used = false;
     // Set when scaldpc_bp_append_rows failed part-way (an allocation, a copy): host mirrors and device arrays may
-    // disagree, so every later call on the handle returns an error instead of decoding on it; destroy still frees all.
+    // disagree, so every later call on the handle returns an error instead of decoding on it (check_usable); destroy
+    // still frees all.
     bool broken = false;
     int last_group = 0;  // tiles of the last decoded group (for scaldpc_bp_time_kernels)
     bool last_early = false;  // ... and whether that decode ran with early exit (its variable passes then all write decisions)
@@ -287,16 +297,12 @@ void build_buckets(const pvec<int> &deg, const int *bounds, int nb, bool keep_is
     }
 }
 
-template <typename T>
-int grow(T **p, size_t *cap, size_t need)
+// room for `need` elements with a little headroom: the buffers of a decoder whose graph grows would otherwise be re-made
+// at every step
+template <typename T, bool P>
+int grow(Buf<T, P> &b, size_t need)
 {
-    if (need <= *cap && *p) return 0;
-    dev_free(*p);
-    *cap = 0;
-    const size_t want = need + need / 8;  // a little headroom: the buffers of a decoder whose graph grows would otherwise be re-made at every step
-    SC_TRY(dev_alloc(p, want));
-    *cap = want;
-    return 0;
+    return b.ensure(need, need + need / 8);
 }
 
 // tiles per group: the in-place message array of a group should stay resident in the
@@ -317,44 +323,39 @@ constexpr int REM_SLOTS = 512;
 int ensure_workspace(scaldpc_bp *h, int T, int G, bool want_post, int max_iter)
 {
     if (T > h->cap_tiles || h->m > h->ws_m || h->n > h->ws_n) {
-        dev_free(h->d_synd); dev_free(h->d_recv); dev_free(h->d_hard); dev_free(h->d_done);
-        dev_free(h->d_conv); dev_free(h->d_unsat); dev_free(h->d_iters); dev_free(h->d_post);
+        h->d_synd.reset(); h->d_recv.reset(); h->d_hard.reset(); h->d_done.reset();
+        h->d_conv.reset(); h->d_unsat.reset(); h->d_iters.reset(); h->d_post.reset();
         T = std::max(T, h->cap_tiles);
         h->cap_tiles = 0;
-        h->post_alloc = false;
         // a growing graph gets planes with room for the rows / columns still to come
         const int wm = h->incremental ? h->m + h->m / 2 + 64 : h->m, wn = h->incremental ? h->n + h->n / 2 + 64 : h->n;
         const size_t pw = (size_t)(wm + 4 * ROWS_PER_WAVE - 1) / (4 * ROWS_PER_WAVE) * 4;
-        SC_TRY(dev_alloc(&h->d_synd, (size_t)T * wm));
-        SC_TRY(dev_alloc(&h->d_recv, (size_t)T * wn));
-        SC_TRY(dev_alloc(&h->d_hard, (size_t)T * wn));
-        SC_TRY(dev_alloc(&h->d_done, (size_t)T));
-        SC_TRY(dev_alloc(&h->d_conv, (size_t)T));
-        SC_TRY(dev_alloc(&h->d_unsat, (size_t)T * pw));
-        SC_TRY(dev_alloc(&h->d_iters, (size_t)T * TW));
+        SC_TRY(h->d_synd.ensure((size_t)T * wm));
+        SC_TRY(h->d_recv.ensure((size_t)T * wn));
+        SC_TRY(h->d_hard.ensure((size_t)T * wn));
+        SC_TRY(h->d_done.ensure((size_t)T));
+        SC_TRY(h->d_conv.ensure((size_t)T));
+        SC_TRY(h->d_unsat.ensure((size_t)T * pw));
+        SC_TRY(h->d_iters.ensure((size_t)T * TW));
         h->cap_tiles = T;
         h->ws_m = wm;
         h->ws_n = wn;
     }
-    if (want_post && !h->post_alloc) {
-        SC_TRY(dev_alloc(&h->d_post, (size_t)h->cap_tiles * h->ws_n * TW));
-        h->post_alloc = true;
-    }
+    if (want_post) SC_TRY(h->d_post.ensure((size_t)h->cap_tiles * h->ws_n * TW));  // (released above whenever the planes move)
     // (the message arrays are allocated by the path that uses them: ensure_msg / ensure_el)
     // rows of counters: one per tile group of the call, the compact levels' groups (fewer tiles each) included, + row 0
     const int groups = (T + std::max(1, G) - 1) / std::max(1, G);
     const int want_rows = std::min(REM_SLOTS, 2 * groups + 8);
     if (max_iter + 2 > h->cap_remaining || want_rows > h->rem_rows) {
-        dev_free(h->d_remaining);
-        cached_free(h->h_remaining);
-        h->h_remaining = nullptr;
+        h->d_remaining.reset();
+        h->h_remaining.reset();
         h->cap_remaining = 0;
         h->rem_rows = 0;
-        const int len = std::max(max_iter + 2, h->cap_remaining), rows = std::max(want_rows, h->rem_rows);
-        SC_TRY(dev_alloc(&h->d_remaining, (size_t)rows * (size_t)len));
-        SC_TRY(cached_alloc((void **)&h->h_remaining, sizeof(int) * (size_t)len, true));
+        const int len = max_iter + 2;
+        SC_TRY(h->d_remaining.ensure((size_t)want_rows * (size_t)len));
+        SC_TRY(h->h_remaining.ensure((size_t)len));
         h->cap_remaining = len;
-        h->rem_rows = rows;
+        h->rem_rows = want_rows;
     }
     h->rem_slot = h->rem_rows;  // a new call: the first tile group that needs counters zeroes the array
     return 0;
@@ -392,10 +393,10 @@ int *stage_buffer(size_t ints)
     return stage.p;
 }
 
-int upload_table(int **dst, const int *host, size_t ints)
+int upload_table(Buf<int> &dst, const int *host, size_t ints)
 {
-    SC_TRY(dev_alloc(dst, ints));
-    SC_HIP(hipMemcpy(*dst, host, ints * sizeof(int), hipMemcpyHostToDevice));
+    SC_TRY(dst.ensure(ints));
+    SC_HIP(hipMemcpy(dst, host, ints * sizeof(int), hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -500,7 +501,7 @@ int ensure_tile_tables(scaldpc_bp *h)
             std::swap_ranges(rows + i * VAR_INLINE, rows + (i + 1) * VAR_INLINE, rows + j * VAR_INLINE);
         }
     }
-    SC_TRY(upload_table(&h->d_tile_tab, host, total));
+    SC_TRY(upload_table(h->d_tile_tab, host, total));
     h->first_valid = false;  // (first_tab follows the re-laid edge list)
     h->d_var_meta = h->d_tile_tab + o_var_meta;
     h->d_csc_list = h->d_tile_tab + o_csc_list;
@@ -551,13 +552,13 @@ int el_alloc_segment(scaldpc_bp *h, int cap)
 // new bin only sends the words it changes, and a launch covers whole bins.
 int el_upload(scaldpc_bp *h)
 {
-    dev_free(h->d_el_tab);
+    h->d_el_tab.reset();
     h->el_cap_bins = h->incremental ? h->el_waves + h->el_waves / 2 + 64 : h->el_waves;
     const size_t lanes = (size_t)64 * h->el_cap_bins, old = h->h_el_col.size();
     h->h_el_slots.resize(2 * lanes, 0);
     h->h_el_col.resize(lanes, 0);
     for (size_t i = old; i < lanes; i++) h->h_el_slots[2 * i] = -1;
-    SC_TRY(dev_alloc(&h->d_el_tab, 3 * lanes));
+    SC_TRY(h->d_el_tab.ensure(3 * lanes));
     h->d_el_slots = h->d_el_tab;
     h->d_el_slot_col = h->d_el_tab + el_col_off(h);
     if (lanes) {
@@ -611,17 +612,17 @@ int ensure_msg(scaldpc_bp *h, int G, int method)
 {
     SC_TRY(ensure_tile_tables(h));
     if (rec_form(h, method) && G > h->cap_rec_group) {  // (append_rows resets cap_rec_group too)
-        dev_free(h->d_rec); dev_free(h->d_mask);
+        h->d_rec.reset(); h->d_mask.reset();
         h->cap_rec_group = 0;
-        SC_TRY(dev_alloc(&h->d_rec, (size_t)G * h->m * 2 * TW));
-        SC_TRY(dev_alloc(&h->d_mask, (size_t)G * h->E));
+        SC_TRY(h->d_rec.ensure((size_t)G * h->m * 2 * TW));
+        SC_TRY(h->d_mask.ensure((size_t)G * h->E));
         h->cap_rec_group = G;
     }
     if (G > h->cap_group) {  // (append_rows resets cap_group: the arrays are sized by E)
-        dev_free(h->d_msg); dev_free(h->d_scratch);
+        h->d_msg.reset(); h->d_scratch.reset();
         h->cap_group = 0;
-        SC_TRY(dev_alloc(&h->d_msg, (size_t)G * h->E * TW));
-        if (h->need_scratch) SC_TRY(dev_alloc(&h->d_scratch, (size_t)G * h->E * TW));
+        SC_TRY(h->d_msg.ensure((size_t)G * h->E * TW));
+        if (h->need_scratch) SC_TRY(h->d_scratch.ensure((size_t)G * h->E * TW));
         h->cap_group = G;
     }
     return 0;
@@ -632,14 +633,7 @@ int ensure_el(scaldpc_bp *h, int nb)
 {
     SC_TRY(ensure_el_tables(h));
     const size_t need = (size_t)nb * h->E;
-    if (need > h->cap_el || !h->d_emsg) {
-        dev_free(h->d_emsg);
-        h->cap_el = 0;
-        const size_t want = h->incremental ? need + need / 4 : need;  // room for the edges still to come
-        SC_TRY(dev_alloc(&h->d_emsg, want));
-        h->cap_el = want;
-    }
-    return 0;
+    return h->d_emsg.ensure(need, h->incremental ? need + need / 4 : need);  // room for the edges still to come
 }
 
 // How many codewords the row-parallel kernels take (0 = none: use 64-codeword tiles).
@@ -772,23 +766,13 @@ bool first_fusable(const scaldpc_bp *h, int method)
 int ensure_first_table(scaldpc_bp *h, int method, float alpha1, hipStream_t s)
 {
     if (h->first_valid && h->first_method == method && h->first_alpha == alpha1) return 0;
-    const size_t need = (size_t)h->E + 128;  // (a column's scalar loads may run past its last edge, as in the edge list)
-    if (need > h->cap_first) {
-        dev_free(h->d_first_tab);
-        h->cap_first = 0;
-        SC_TRY(dev_alloc(&h->d_first_tab, need + need / 8));
-        h->cap_first = need + need / 8;
-    }
-    float *tmp = nullptr;
-    u64 *zero = nullptr;
-    SC_TRY(dev_alloc(&tmp, (size_t)h->E));
-    int rc = dev_alloc(&zero, (size_t)h->m + 1);
-    if (rc) {
-        dev_free(tmp);
-        return rc;
-    }
+    SC_TRY(grow(h->d_first_tab, (size_t)h->E + 128));  // (a column's scalar loads may run past its last edge, as in the edge list)
+    Buf<u64> zero;  // (declared first: released after tmp)
+    Buf<float> tmp;
+    SC_TRY(tmp.ensure((size_t)h->E));
+    SC_TRY(zero.ensure((size_t)h->m + 1));
     hipError_t e = hipMemsetAsync(zero, 0, sizeof(u64) * ((size_t)h->m + 1), s);
-    if (e == hipSuccess) e = hipMemsetAsync(h->d_first_tab, 0, sizeof(int2) * h->cap_first, s);
+    if (e == hipSuccess) e = hipMemsetAsync(h->d_first_tab, 0, sizeof(int2) * h->d_first_tab.cap(), s);
     if (e == hipSuccess) {
         dim3 grid((h->m + 3) / 4, 1);
         if (method == SCALDPC_BP_MIN_SUM)
@@ -801,9 +785,7 @@ int ensure_first_table(scaldpc_bp *h, int method, float alpha1, hipStream_t s)
                            h->E, h->d_first_tab);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(s);  // tmp / zero go back to the allocator below
-    dev_free(tmp);
-    dev_free(zero);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);  // tmp / zero go back to the allocator on return
     if (e != hipSuccess) return fail(SCALDPC_EHIP, "first-message table: %s", hipGetErrorString(e));
     h->first_valid = true;
     h->first_method = method;
@@ -922,17 +904,7 @@ struct TileState {
 // ordinary k_parity / k_finalize pair.  The host looks at "still running after it-1" one
 // iteration late, so a finished call enqueues one iteration of (skipped) launches more than
 // the four-launch form -- and half as many overall.
-int ensure_el_unsat(scaldpc_bp *h, int max_iter)
-{
-    const size_t flags = ((size_t)max_iter + 2) * TW;
-    if (flags > h->cap_el_unsat || !h->d_el_unsat) {
-        dev_free(h->d_el_unsat);
-        h->cap_el_unsat = 0;
-        SC_TRY(dev_alloc(&h->d_el_unsat, flags));
-        h->cap_el_unsat = flags;
-    }
-    return 0;
-}
+int ensure_el_unsat(scaldpc_bp *h, int max_iter) { return h->d_el_unsat.ensure(((size_t)max_iter + 2) * TW); }
 
 int iterate_el_early(scaldpc_bp *h, int nb, int max_iter, int method, float alpha, const u64 *synd_g, u64 *hard_g,
                      u64 *done_g, u64 *conv_g, u64 *unsat_g, int *iters_g, float *post_g, hipStream_t s)
@@ -1297,20 +1269,20 @@ int decode_level(scaldpc_bp *h, int lvl, const TileState &st, int batch, int T, 
     ids.resize((size_t)T2 * TW, -1);
     scaldpc_bp::Level &L = h->lv[lvl + 1];
     if (T2 > L.cap_tiles) {
-        dev_free(L.synd); dev_free(L.hard); dev_free(L.done); dev_free(L.conv); dev_free(L.unsat);
-        dev_free(L.iters); dev_free(L.ids);
+        L.synd.reset(); L.hard.reset(); L.done.reset(); L.conv.reset(); L.unsat.reset();
+        L.iters.reset(); L.ids.reset();
         L.cap_tiles = 0;
-        SC_TRY(dev_alloc(&L.synd, (size_t)T2 * h->m));
-        SC_TRY(dev_alloc(&L.hard, (size_t)T2 * h->n));
-        SC_TRY(dev_alloc(&L.done, (size_t)T2));
-        SC_TRY(dev_alloc(&L.conv, (size_t)T2));
-        SC_TRY(dev_alloc(&L.unsat, (size_t)T2 * parity_waves(h)));
-        SC_TRY(dev_alloc(&L.iters, (size_t)T2 * TW));
-        SC_TRY(dev_alloc(&L.ids, (size_t)T2 * TW));
+        SC_TRY(L.synd.ensure((size_t)T2 * h->m));
+        SC_TRY(L.hard.ensure((size_t)T2 * h->n));
+        SC_TRY(L.done.ensure((size_t)T2));
+        SC_TRY(L.conv.ensure((size_t)T2));
+        SC_TRY(L.unsat.ensure((size_t)T2 * parity_waves(h)));
+        SC_TRY(L.iters.ensure((size_t)T2 * TW));
+        SC_TRY(L.ids.ensure((size_t)T2 * TW));
         L.cap_tiles = T2;
     }
-    SC_TRY(grow(&L.slot_of, &L.cap_slot_of, (size_t)T * TW));
-    if (want_post) SC_TRY(grow(&L.post, &L.cap_post, (size_t)T2 * h->n * TW));
+    SC_TRY(grow(L.slot_of, (size_t)T * TW));
+    if (want_post) SC_TRY(grow(L.post, (size_t)T2 * h->n * TW));
     SC_HIP(hipMemcpyAsync(L.ids, ids.data(), sizeof(int) * ids.size(), hipMemcpyHostToDevice, s));
     SC_HIP(hipMemcpyAsync(L.slot_of, slot_of.data(), sizeof(int) * slot_of.size(), hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_gather_planes, dim3((h->m + 63) / 64, T2), dim3(256), 0, s, st.synd, h->m, L.ids, L.synd);
@@ -1453,7 +1425,7 @@ int finish_graph(scaldpc_bp *h, const int *row_ptr, const int *col_idx, const pv
     }
     std::copy(hv.list.begin(), hv.list.end(), host + o_var_list);
     TMARK("csc");
-    SC_TRY(dev_alloc(&h->d_graph, total));
+    SC_TRY(h->d_graph.ensure(total));
     if (hipMemcpy(h->d_graph, host, total * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
         return fail(SCALDPC_EHIP, "graph upload failed");
     TMARK("upload");
@@ -1484,12 +1456,9 @@ int make_incremental(scaldpc_bp *h)
 {
     if (h->incremental) return 0;
     const size_t rows = (size_t)h->m + 1, edges = (size_t)h->E, cols = (size_t)h->n;
-    h->cap_rows = rows + rows / 2 + 256;
-    h->cap_edges = edges + edges / 2 + 4096;
-    h->cap_cols = cols + cols / 2 + 256;
-    SC_TRY(dev_alloc(&h->d_csr_rp, h->cap_rows));
-    SC_TRY(dev_alloc(&h->d_csr_ci, h->cap_edges));
-    SC_TRY(dev_alloc(&h->d_prior_buf, h->cap_cols));
+    SC_TRY(h->d_csr_rp.ensure(rows + rows / 2 + 256));
+    SC_TRY(h->d_csr_ci.ensure(edges + edges / 2 + 4096));
+    SC_TRY(h->d_prior_buf.ensure(cols + cols / 2 + 256));
     SC_HIP(hipMemcpy(h->d_csr_rp, h->d_row_ptr, rows * sizeof(int), hipMemcpyDeviceToDevice));
     if (edges) SC_HIP(hipMemcpy(h->d_csr_ci, h->d_col_idx, edges * sizeof(int), hipMemcpyDeviceToDevice));
     SC_HIP(hipMemcpy(h->d_prior_buf, h->d_prior, cols * sizeof(float), hipMemcpyDeviceToDevice));
@@ -1500,29 +1469,16 @@ int make_incremental(scaldpc_bp *h)
     for (int j = 0; j < h->n; j++)
         for (int k = h->hg_col_ptr[j]; k < h->hg_col_ptr[j + 1]; k++) h->hg_col_idx[h->hg_csc_edge[k]] = j;
     h->incremental = true;
-    dev_free(h->d_el_tab);  // rebuilt with free lanes per column on the next use
+    h->d_el_tab.reset();  // rebuilt with free lanes per column on the next use
     h->d_el_slots = h->d_el_slot_col = nullptr;
     return 0;
 }
 
+// CSR and priors of a growing graph: room for `need` elements (and half as many again), the first `used` kept
 template <typename T>
-int grow_keep(T **p, size_t *cap, size_t used, size_t need)
+int grow_graph(Buf<T> &b, size_t used, size_t need)
 {
-    if (need <= *cap) return 0;
-    const size_t ncap = need + need / 2 + 256;
-    T *q = nullptr;
-    SC_TRY(dev_alloc(&q, ncap));
-    if (used) {
-        const hipError_t e = hipMemcpy(q, *p, used * sizeof(T), hipMemcpyDeviceToDevice);
-        if (e != hipSuccess) {
-            dev_free(q);
-            return fail(SCALDPC_EHIP, "copy into the grown buffer failed: %s", hipGetErrorString(e));
-        }
-    }
-    dev_free(*p);
-    *p = q;
-    *cap = ncap;
-    return 0;
+    return b.grow_keep(used, need, need + need / 2 + 256);
 }
 
 // The tile / LDS kernels' view of a grown graph: CSC, degree buckets, identity block, device CSC
@@ -1532,11 +1488,112 @@ int refresh_full(scaldpc_bp *h)
     if (!h->full_stale) return 0;
     pvec<int> rdeg(h->m), cdeg(h->hg_cdeg);
     for (int r = 0; r < h->m; r++) rdeg[r] = h->hg_row_ptr[r + 1] - h->hg_row_ptr[r];
-    dev_free(h->d_graph);
-    dev_free(h->d_tile_tab);
+    h->d_graph.reset();
+    h->d_tile_tab.reset();
     h->d_var_meta = h->d_csc_list = h->d_row_list = nullptr;
     SC_TRY(finish_graph(h, h->hg_row_ptr.data(), h->hg_col_idx.data(), rdeg, cdeg));
     h->full_stale = false;
+    return 0;
+}
+
+// ---- what the entry points share ------------------------------------------------------------------
+int check_usable(const scaldpc_bp *h)
+{
+    if (!h->broken) return 0;
+    return fail(SCALDPC_EHIP, "this decoder is unusable: an earlier scaldpc_bp_append_rows failed part-way; destroy it and build a new one");
+}
+
+// fp32 prior LLRs of `count` columns, the same expression as the oracle's f32 instantiation: log((1-p)/p).  Priors come
+// in long runs of one value -- [w/N]*N ++ [1-certainty]*R, hqc.py:686-691 -- so the previous result is reused while p
+// repeats.  `first` is the column of probs[0] (for the message).
+int prior_llrs(const double *probs, int first, int count, pvec<float> &llr)
+{
+    float last_p = 0.0f, last_llr = 0.0f;
+    for (int j = 0; j < count; j++) {
+        if (!(probs[j] >= 0.0 && probs[j] <= 1.0))
+            return fail(SCALDPC_EINVAL, "channel_probs[%d] = %g is not a probability", first + j, probs[j]);
+        const float p = (float)probs[j];
+        if (j == 0 || p != last_p) {
+            last_p = p;
+            last_llr = logf((1.0f - p) / p);
+        }
+        llr[j] = last_llr;
+    }
+    return 0;
+}
+
+// The preamble of the decoding entry points (decode_batch and the Monte-Carlo runs): priors set, max_iter default,
+// stream, tiles of 64 codewords (at most 65535: a grid dimension) and tiles per group.
+struct Call {
+    hipStream_t s;
+    int max_iter, T, G;
+};
+int begin_call(scaldpc_bp *h, int batch, int max_iter, void *stream, Call *c)
+{
+    if (!h->have_prior || h->prior_n < h->n)
+        return fail(SCALDPC_EINVAL, "channel probabilities not set (columns [%d, %d))", h->have_prior ? h->prior_n : 0, h->n);
+    c->max_iter = max_iter > 0 ? max_iter : h->n;
+    c->s = stream ? (hipStream_t)stream : h->own_stream;
+    c->T = (batch + TW - 1) / TW;
+    if (c->T > 65535) return fail(SCALDPC_EINVAL, "batch %d too large for one call (max %d)", batch, 65535 * TW);
+    c->G = (h->tile_group > 0) ? std::min(h->tile_group, c->T) : auto_group(h, c->T);
+    return 0;
+}
+
+// `bytes` of input on the device: the caller's own with SCALDPC_F_DEVICE_IO, else a copy in the handle's staging block
+int stage_input(scaldpc_bp *h, const uint8_t *in, size_t bytes, bool dev_io, hipStream_t s, const uint8_t **din)
+{
+    *din = in;
+    if (dev_io) return 0;
+    SC_TRY(grow(h->d_in, bytes));
+    SC_HIP(hipMemcpyAsync(h->d_in, in, bytes, hipMemcpyHostToDevice, s));
+    *din = h->d_in;
+    return 0;
+}
+
+// A call's per-codeword outputs (null: not wanted).  With SCALDPC_F_DEVICE_IO the caller's arrays are device memory and the
+// kernels write them directly; otherwise the handle's staging blocks stand in (stage_outputs) and copy_outputs brings them
+// to the caller.
+struct Outputs {
+    uint8_t *bits = nullptr;
+    float *llr = nullptr;
+    int32_t *iters = nullptr;
+    uint8_t *conv = nullptr;
+};
+// with_state: stage the iteration / convergence pair (one request each, always together) even where only one is wanted
+int stage_outputs(scaldpc_bp *h, const Outputs &out, int batch, bool dev_io, bool with_state, Outputs *dev)
+{
+    *dev = out;
+    if (dev_io) return 0;
+    const size_t planes = (size_t)batch * h->n;
+    if (out.bits) {
+        SC_TRY(grow(h->d_out_bits, planes));
+        dev->bits = h->d_out_bits;
+    }
+    if (out.llr) {
+        SC_TRY(grow(h->d_out_llr, planes));
+        dev->llr = h->d_out_llr;
+    }
+    if (with_state) {
+        if ((size_t)batch > h->d_out_conv.cap()) {  // (d_out_conv is requested last: its capacity is the pair's)
+            h->d_out_iters.reset();
+            h->d_out_conv.reset();
+            SC_TRY(h->d_out_iters.ensure((size_t)batch));
+            SC_TRY(h->d_out_conv.ensure((size_t)batch));
+        }
+        dev->iters = out.iters ? h->d_out_iters.get() : nullptr;
+        dev->conv = out.conv ? h->d_out_conv.get() : nullptr;
+    }
+    return 0;
+}
+int copy_outputs(const scaldpc_bp *h, const Outputs &out, const Outputs &dev, int batch, bool dev_io, hipStream_t s)
+{
+    if (dev_io) return 0;
+    const size_t planes = (size_t)batch * h->n;
+    if (out.bits) SC_HIP(hipMemcpyAsync(out.bits, dev.bits, planes, hipMemcpyDeviceToHost, s));
+    if (out.llr) SC_HIP(hipMemcpyAsync(out.llr, dev.llr, sizeof(float) * planes, hipMemcpyDeviceToHost, s));
+    if (out.iters) SC_HIP(hipMemcpyAsync(out.iters, dev.iters, sizeof(int) * (size_t)batch, hipMemcpyDeviceToHost, s));
+    if (out.conv) SC_HIP(hipMemcpyAsync(out.conv, dev.conv, (size_t)batch, hipMemcpyDeviceToHost, s));
     return 0;
 }
 
@@ -1591,23 +1648,10 @@ int scaldpc_bp_set_channel_probs(scaldpc_bp *h, const double *probs)
 {
     if (!h || !probs) return fail(SCALDPC_EINVAL, "NULL argument");
     std::lock_guard<std::mutex> lk(h->mu);
-    if (h->broken) return fail(SCALDPC_EHIP, "this decoder is unusable: an earlier scaldpc_bp_append_rows failed part-way; destroy it and build a new one");
+    SC_TRY(check_usable(h));
     DeviceGuard dg(h->device);
     pvec<float> llr(h->n);
-    float last_p = 0.0f, last_llr = 0.0f;
-    for (int j = 0; j < h->n; j++) {
-        if (!(probs[j] >= 0.0 && probs[j] <= 1.0))
-            return fail(SCALDPC_EINVAL, "channel_probs[%d] = %g is not a probability", j, probs[j]);
-        // same expression, in fp32, as the oracle's f32 instantiation: log((1-p)/p)
-        // (priors come in long runs of one value -- [w/N]*N ++ [1-certainty]*R, hqc.py:686-691 --
-        // so the previous result is reused while p repeats)
-        const float p = (float)probs[j];
-        if (j == 0 || p != last_p) {
-            last_p = p;
-            last_llr = logf((1.0f - p) / p);
-        }
-        llr[j] = last_llr;
-    }
+    SC_TRY(prior_llrs(probs, 0, h->n, llr));
     SC_HIP(hipMemcpy(h->d_prior, llr.data(), sizeof(float) * h->n, hipMemcpyHostToDevice));
     h->h_probs.assign(probs, probs + h->n);
     h->thr_valid = false;
@@ -1621,7 +1665,7 @@ int scaldpc_bp_set_channel_probs_tail(scaldpc_bp *h, int32_t first, int32_t coun
 {
     if (!h || (count > 0 && !probs)) return fail(SCALDPC_EINVAL, "NULL argument");
     std::lock_guard<std::mutex> lk(h->mu);
-    if (h->broken) return fail(SCALDPC_EHIP, "this decoder is unusable: an earlier scaldpc_bp_append_rows failed part-way; destroy it and build a new one");
+    SC_TRY(check_usable(h));
     DeviceGuard dg(h->device);
     if (first < 0 || count < 0 || (long)first + count > h->n)
         return fail(SCALDPC_EINVAL, "columns [%d, %d) are outside the graph (n = %d)", first, first + count, h->n);
@@ -1629,17 +1673,7 @@ int scaldpc_bp_set_channel_probs_tail(scaldpc_bp *h, int32_t first, int32_t coun
     if (count == 0) return 0;
     if (h->async_used) SC_HIP(hipDeviceSynchronize());
     pvec<float> llr(count);
-    float last_p = 0.0f, last_llr = 0.0f;
-    for (int j = 0; j < count; j++) {
-        if (!(probs[j] >= 0.0 && probs[j] <= 1.0))
-            return fail(SCALDPC_EINVAL, "channel_probs[%d] = %g is not a probability", first + j, probs[j]);
-        const float p = (float)probs[j];  // same expression as scaldpc_bp_set_channel_probs
-        if (j == 0 || p != last_p) {
-            last_p = p;
-            last_llr = logf((1.0f - p) / p);
-        }
-        llr[j] = last_llr;
-    }
+    SC_TRY(prior_llrs(probs, first, count, llr));
     SC_HIP(hipMemcpy(h->d_prior + first, llr.data(), sizeof(float) * count, hipMemcpyHostToDevice));
     h->h_probs.resize(h->n, 0.0);
     std::copy(probs, probs + count, h->h_probs.begin() + first);
@@ -1654,7 +1688,7 @@ int scaldpc_bp_append_rows(scaldpc_bp *h, int32_t nrows, const int32_t *row_ptr,
 {
     if (!h || nrows < 0 || (nrows > 0 && !row_ptr)) return fail(SCALDPC_EINVAL, "bad arguments");
     std::lock_guard<std::mutex> lk(h->mu);
-    if (h->broken) return fail(SCALDPC_EHIP, "this decoder is unusable: an earlier scaldpc_bp_append_rows failed part-way; destroy it and build a new one");
+    SC_TRY(check_usable(h));
     DeviceGuard dg(h->device);
     CacheBypass guard(h->async_used);
     if (new_n < h->n) return fail(SCALDPC_EINVAL, "new_n = %d is smaller than the current block length %d", new_n, h->n);
@@ -1685,11 +1719,11 @@ int scaldpc_bp_append_rows(scaldpc_bp *h, int32_t nrows, const int32_t *row_ptr,
     const int m0 = h->m, n0 = h->n;
     const long E0 = h->E;
     // (each view is re-pointed right after its own buffer moved: a later failure must not leave it dangling)
-    SC_TRY(grow_keep(&h->d_csr_rp, &h->cap_rows, (size_t)m0 + 1, (size_t)m0 + 1 + nrows));
+    SC_TRY(grow_graph(h->d_csr_rp, (size_t)m0 + 1, (size_t)m0 + 1 + nrows));
     h->d_row_ptr = h->d_csr_rp;
-    SC_TRY(grow_keep(&h->d_csr_ci, &h->cap_edges, (size_t)E0, (size_t)E0 + add));
+    SC_TRY(grow_graph(h->d_csr_ci, (size_t)E0, (size_t)E0 + add));
     h->d_col_idx = h->d_csr_ci;
-    SC_TRY(grow_keep(&h->d_prior_buf, &h->cap_cols, (size_t)n0, (size_t)new_n));
+    SC_TRY(grow_graph(h->d_prior_buf, (size_t)n0, (size_t)new_n));
     h->d_prior = h->d_prior_buf;
 
     // ---- host mirror: CSR, column degrees ------------------------------------------------------
@@ -1701,7 +1735,7 @@ int scaldpc_bp_append_rows(scaldpc_bp *h, int32_t nrows, const int32_t *row_ptr,
 
     TMARK("app:mirror");
     // ---- row-parallel tables, in place: one slot word per new edge while its column has a free lane
-    const bool had_tables = h->d_el_tab != nullptr;
+    const bool had_tables = h->d_el_tab;
     pvec<int> &dirty_slot = h->el_dirty_slot, &dirty_col = h->el_dirty_col;  // words of h_el_slots / h_el_col that changed
     dirty_slot.clear();
     dirty_col.clear();
@@ -1761,7 +1795,7 @@ int scaldpc_bp_append_rows(scaldpc_bp *h, int32_t nrows, const int32_t *row_ptr,
     h->E = E0 + add;
     h->el_ok = h->E > 0 && h->max_row_deg <= 64 && h->max_col_deg <= 64;
     if (had_tables && (!el_alive || !h->el_ok)) {
-        dev_free(h->d_el_tab);
+        h->d_el_tab.reset();
         h->d_el_slots = h->d_el_slot_col = nullptr;
         el_alive = false;
     }
@@ -1771,15 +1805,12 @@ int scaldpc_bp_append_rows(scaldpc_bp *h, int32_t nrows, const int32_t *row_ptr,
     const bool reupload = el_alive && h->el_waves > h->el_cap_bins;  // the bins outgrew the device table
     const size_t npairs = (el_alive && !reupload) ? dirty_slot.size() + dirty_col.size() : 0;
     const size_t stage_ints = (size_t)nrows + add + 2 * npairs;
-    if (stage_ints > h->cap_pairs) {
-        cached_free(h->h_pairs);
-        dev_free(h->d_pairs);
-        h->h_pairs = nullptr;
-        h->cap_pairs = 0;
+    if (stage_ints > h->d_pairs.cap()) {  // (d_pairs is requested last: its capacity is the pair's)
+        h->h_pairs.reset();
+        h->d_pairs.reset();
         const size_t want = stage_ints + stage_ints / 2 + 1024;
-        SC_TRY(cached_alloc((void **)&h->h_pairs, want * sizeof(int), true));
-        SC_TRY(dev_alloc(&h->d_pairs, want));
-        h->cap_pairs = want;
+        SC_TRY(h->h_pairs.ensure(want));
+        SC_TRY(h->d_pairs.ensure(want));
     }
     int *st = h->h_pairs;
     for (int r = 0; r < nrows; r++) st[r] = (int)(E0 + row_ptr[r + 1]);
@@ -1804,7 +1835,7 @@ int scaldpc_bp_append_rows(scaldpc_bp *h, int32_t nrows, const int32_t *row_ptr,
         }
         SC_HIP(hipMemcpyAsync(h->d_pairs, pp, sizeof(int) * 2 * npairs, hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(k_apply_pairs, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, s, h->d_el_tab,
-                           (const int2 *)h->d_pairs, (int)npairs);
+                           (const int2 *)h->d_pairs.get(), (int)npairs);
         LAUNCH_CHECK();
     }
     SC_HIP(hipStreamSynchronize(s));
@@ -1815,18 +1846,17 @@ int scaldpc_bp_append_rows(scaldpc_bp *h, int32_t nrows, const int32_t *row_ptr,
     h->h_probs.resize(new_n, 0.0);
     h->thr_valid = false;
     h->first_valid = false;
-    dev_free(h->d_thr);
-    dev_free(h->d_msg);
-    dev_free(h->d_scratch);
+    h->d_thr.reset();
+    h->d_msg.reset();
+    h->d_scratch.reset();
     h->cap_group = 0;
-    dev_free(h->d_rec);
-    dev_free(h->d_mask);
+    h->d_rec.reset();
+    h->d_mask.reset();
     h->cap_rec_group = 0;
     for (auto &L : h->lv) {
-        dev_free(L.synd); dev_free(L.hard); dev_free(L.done); dev_free(L.conv); dev_free(L.unsat);
-        dev_free(L.iters); dev_free(L.ids); dev_free(L.post);
+        L.synd.reset(); L.hard.reset(); L.done.reset(); L.conv.reset(); L.unsat.reset();
+        L.iters.reset(); L.ids.reset(); L.post.reset();
         L.cap_tiles = 0;
-        L.cap_post = 0;
     }
     h->last_group = 0;
     TMARK("app:tail");
@@ -1861,7 +1891,7 @@ int scaldpc_bp_set_tile_group(scaldpc_bp *h, int32_t tiles)
     return 0;
 }
 
-int scaldpc_bp_decode_batch(scaldpc_bp *h, const uint8_t *in, int32_t input_kind, int32_t batch, int32_t max_iter,
+int scaldpc_bp_decode_batch(scaldpc_bp *h, const uint8_t *in, int32_t input_kind, int32_t batch, int32_t max_iter_arg,
                             int32_t method, float alpha, uint32_t flags, void *stream, uint8_t *out_bits,
                             float *out_llr, int32_t *out_iters, uint8_t *out_conv)
 {
@@ -1873,23 +1903,21 @@ int scaldpc_bp_decode_batch(scaldpc_bp *h, const uint8_t *in, int32_t input_kind
         return fail(SCALDPC_EINVAL, "unknown bp method %d", method);
     if (!(alpha >= 0.0f)) return fail(SCALDPC_EINVAL, "ms_scaling_factor must be >= 0");
     std::lock_guard<std::mutex> lk(h->mu);
-    if (h->broken) return fail(SCALDPC_EHIP, "this decoder is unusable: an earlier scaldpc_bp_append_rows failed part-way; destroy it and build a new one");
+    SC_TRY(check_usable(h));
     DeviceGuard dg(h->device);
-    if (!h->have_prior || h->prior_n < h->n)
-        return fail(SCALDPC_EINVAL, "channel probabilities not set (columns [%d, %d))", h->have_prior ? h->prior_n : 0, h->n);
-    if (max_iter <= 0) max_iter = h->n;
+    Call c;
+    SC_TRY(begin_call(h, batch, max_iter_arg, stream, &c));
     const bool dev_io = flags & SCALDPC_F_DEVICE_IO;
     const bool early = flags & SCALDPC_F_EARLY_EXIT;
     if ((flags & SCALDPC_F_ASYNC) && (!dev_io || early))
         return fail(SCALDPC_EINVAL, "SCALDPC_F_ASYNC needs DEVICE_IO and no EARLY_EXIT (early exit polls the device)");
-    hipStream_t s = stream ? (hipStream_t)stream : h->own_stream;
     if (flags & SCALDPC_F_ASYNC) h->async_used = true;
     CacheBypass guard(h->async_used);
-
-    const int T = (batch + TW - 1) / TW;
-    if (T > 65535) return fail(SCALDPC_EINVAL, "batch %d too large for one call (max %d)", batch, 65535 * TW);
-    const int G = (h->tile_group > 0) ? std::min(h->tile_group, T) : auto_group(h, T);
+    const hipStream_t s = c.s;
+    const int T = c.T, G = c.G, max_iter = c.max_iter;
     const int len = input_kind == SCALDPC_IN_SYNDROME ? h->m : h->n;
+    const Outputs out{out_bits, out_llr, out_iters, out_conv};
+    Outputs dev;
 
     // Small graph: the LDS-resident single-launch decoder (k_bp_small).
     const size_t small_lds = (size_t)2 * h->E * sizeof(float) + (size_t)2 * h->n + h->m + 64;
@@ -1902,46 +1930,19 @@ int scaldpc_bp_decode_batch(scaldpc_bp *h, const uint8_t *in, int32_t input_kind
         return fail(SCALDPC_EINVAL, "SCALDPC_PATH=lds but the graph needs %zu B of LDS", small_lds);
     if (small_fits && h->kn.path != Knobs::STREAM && h->kn.path != Knobs::EDGE) {
         const uint8_t *din = in;
-        uint8_t *dbits = out_bits, *dconv = out_conv;
-        float *dllr = out_llr;
-        int *diters = out_iters;
-        if (!dev_io) {
-            SC_TRY(grow(&h->d_in, &h->cap_in, (size_t)batch * len));
-            SC_HIP(hipMemcpyAsync(h->d_in, in, (size_t)batch * len, hipMemcpyHostToDevice, s));
-            din = h->d_in;
-            SC_TRY(grow(&h->d_out_bits, &h->cap_out_bits, (size_t)batch * h->n));
-            dbits = h->d_out_bits;
-            if (out_llr) {
-                SC_TRY(grow(&h->d_out_llr, &h->cap_out_llr, (size_t)batch * h->n));
-                dllr = h->d_out_llr;
-            }
-            if ((size_t)batch > h->cap_out_b) {
-                dev_free(h->d_out_iters);
-                dev_free(h->d_out_conv);
-                h->cap_out_b = 0;
-                SC_TRY(dev_alloc(&h->d_out_iters, (size_t)batch));
-                SC_TRY(dev_alloc(&h->d_out_conv, (size_t)batch));
-                h->cap_out_b = batch;
-            }
-            diters = out_iters ? h->d_out_iters : nullptr;
-            dconv = out_conv ? h->d_out_conv : nullptr;
-        }
+        SC_TRY(stage_input(h, in, (size_t)batch * len, dev_io, s, &din));
+        SC_TRY(stage_outputs(h, out, batch, dev_io, true, &dev));
 #define SMALL_LAUNCH(M)                                                                                            \
     hipLaunchKernelGGL((k_bp_small<M, false>), dim3(batch), dim3(256), small_lds, s, h->d_row_ptr, h->d_col_idx, h->d_col_ptr, \
                        h->d_csc_edge, h->d_prior, h->m, h->n, (int)h->E, din, input_kind, max_iter, alpha,          \
-                       early ? 1 : 0, dbits, dllr, diters, dconv)
+                       early ? 1 : 0, dev.bits, dev.llr, dev.iters, dev.conv)
         if (method == SCALDPC_BP_MIN_SUM)
             SMALL_LAUNCH(SCALDPC_BP_MIN_SUM);
         else
             SMALL_LAUNCH(SCALDPC_BP_PRODUCT_SUM);
 #undef SMALL_LAUNCH
         LAUNCH_CHECK();
-        if (!dev_io) {
-            SC_HIP(hipMemcpyAsync(out_bits, dbits, (size_t)batch * h->n, hipMemcpyDeviceToHost, s));
-            if (out_llr) SC_HIP(hipMemcpyAsync(out_llr, dllr, sizeof(float) * (size_t)batch * h->n, hipMemcpyDeviceToHost, s));
-            if (out_iters) SC_HIP(hipMemcpyAsync(out_iters, diters, sizeof(int) * (size_t)batch, hipMemcpyDeviceToHost, s));
-            if (out_conv) SC_HIP(hipMemcpyAsync(out_conv, dconv, (size_t)batch, hipMemcpyDeviceToHost, s));
-        }
+        SC_TRY(copy_outputs(h, out, dev, batch, dev_io, s));
         h->stat_deferred = 0;
         if (!(flags & SCALDPC_F_ASYNC)) SC_HIP(hipStreamSynchronize(s));
         return 0;
@@ -1953,15 +1954,9 @@ int scaldpc_bp_decode_batch(scaldpc_bp *h, const uint8_t *in, int32_t input_kind
         const size_t bits_bytes = ((size_t)batch * h->n + 3) / 4 * 4;
         const size_t out_bytes = bits_bytes + (out_llr ? sizeof(float) * (size_t)batch * h->n : 0) + sizeof(int) * batch + batch;
         const size_t in_bytes = (size_t)batch * len, io_bytes = std::max(in_bytes, out_bytes);
-        if (io_bytes > h->cap_h_io) {
-            cached_free(h->h_io);
-            h->h_io = nullptr;
-            h->cap_h_io = 0;
-            SC_TRY(cached_alloc((void **)&h->h_io, io_bytes + io_bytes / 2, true));
-            h->cap_h_io = io_bytes + io_bytes / 2;
-        }
-        SC_TRY(grow(&h->d_in, &h->cap_in, in_bytes));
-        SC_TRY(grow(&h->d_out_all, &h->cap_out_all, out_bytes));
+        SC_TRY(h->h_io.ensure(io_bytes, io_bytes + io_bytes / 2));
+        SC_TRY(grow(h->d_in, in_bytes));
+        SC_TRY(grow(h->d_out_all, out_bytes));
         SC_TRY(ensure_el_unsat(h, max_iter));
         memcpy(h->h_io, in, in_bytes);
         SC_HIP(hipMemcpyAsync(h->d_in, h->h_io, in_bytes, hipMemcpyHostToDevice, s));
@@ -1998,11 +1993,7 @@ int scaldpc_bp_decode_batch(scaldpc_bp *h, const uint8_t *in, int32_t input_kind
 
     // ---- stage input --------------------------------------------------------
     const uint8_t *din = in;
-    if (!dev_io) {
-        SC_TRY(grow(&h->d_in, &h->cap_in, (size_t)batch * len));
-        SC_HIP(hipMemcpyAsync(h->d_in, in, (size_t)batch * len, hipMemcpyHostToDevice, s));
-        din = h->d_in;
-    }
+    SC_TRY(stage_input(h, in, (size_t)batch * len, dev_io, s, &din));
     if (input_kind == SCALDPC_IN_SYNDROME) {
         hipLaunchKernelGGL(k_pack_bits, dim3((h->m + 63) / 64, T), dim3(256), 0, s, din, h->m, batch, h->d_synd);
         LAUNCH_CHECK();
@@ -2016,45 +2007,19 @@ int scaldpc_bp_decode_batch(scaldpc_bp *h, const uint8_t *in, int32_t input_kind
     SC_TRY(run_core(h, batch, T, G, max_iter, method, alpha, early, out_llr != nullptr, s));
 
     // ---- outputs --------------------------------------------------------------
-    uint8_t *dbits = out_bits;
-    float *dllr = out_llr;
-    int *diters = out_iters;
-    uint8_t *dconv = out_conv;
-    if (!dev_io) {
-        SC_TRY(grow(&h->d_out_bits, &h->cap_out_bits, (size_t)batch * h->n));
-        dbits = h->d_out_bits;
-        if (out_llr) {
-            SC_TRY(grow(&h->d_out_llr, &h->cap_out_llr, (size_t)batch * h->n));
-            dllr = h->d_out_llr;
-        }
-        if ((size_t)batch > h->cap_out_b) {
-            dev_free(h->d_out_iters);
-            dev_free(h->d_out_conv);
-            h->cap_out_b = 0;
-            SC_TRY(dev_alloc(&h->d_out_iters, (size_t)batch));
-            SC_TRY(dev_alloc(&h->d_out_conv, (size_t)batch));
-            h->cap_out_b = batch;
-        }
-        diters = out_iters ? h->d_out_iters : nullptr;
-        dconv = out_conv ? h->d_out_conv : nullptr;
-    }
+    SC_TRY(stage_outputs(h, out, batch, dev_io, true, &dev));
     hipLaunchKernelGGL(k_unpack_bits, dim3((h->n + 255) / 256, T), dim3(256), 0, s, h->d_hard,
-                       input_kind == SCALDPC_IN_RECEIVED ? h->d_recv : (const u64 *)nullptr, h->n, batch, dbits);
+                       input_kind == SCALDPC_IN_RECEIVED ? h->d_recv : (const u64 *)nullptr, h->n, batch, dev.bits);
     LAUNCH_CHECK();
     if (out_llr) {
-        hipLaunchKernelGGL(k_unpack_llr, dim3((h->n + 63) / 64, T), dim3(256), 0, s, h->d_post, h->n, batch, dllr);
+        hipLaunchKernelGGL(k_unpack_llr, dim3((h->n + 63) / 64, T), dim3(256), 0, s, h->d_post, h->n, batch, dev.llr);
         LAUNCH_CHECK();
     }
-    if (diters || dconv) {
-        hipLaunchKernelGGL(k_unpack_state, dim3(T), dim3(64), 0, s, h->d_conv, h->d_iters, batch, diters, dconv);
+    if (dev.iters || dev.conv) {
+        hipLaunchKernelGGL(k_unpack_state, dim3(T), dim3(64), 0, s, h->d_conv, h->d_iters, batch, dev.iters, dev.conv);
         LAUNCH_CHECK();
     }
-    if (!dev_io) {
-        SC_HIP(hipMemcpyAsync(out_bits, dbits, (size_t)batch * h->n, hipMemcpyDeviceToHost, s));
-        if (out_llr) SC_HIP(hipMemcpyAsync(out_llr, dllr, sizeof(float) * (size_t)batch * h->n, hipMemcpyDeviceToHost, s));
-        if (out_iters) SC_HIP(hipMemcpyAsync(out_iters, diters, sizeof(int) * (size_t)batch, hipMemcpyDeviceToHost, s));
-        if (out_conv) SC_HIP(hipMemcpyAsync(out_conv, dconv, (size_t)batch, hipMemcpyDeviceToHost, s));
-    }
+    SC_TRY(copy_outputs(h, out, dev, batch, dev_io, s));
     if (!(flags & SCALDPC_F_ASYNC)) SC_HIP(hipStreamSynchronize(s));
     return 0;
 }
@@ -2079,78 +2044,61 @@ int mc_common_args(scaldpc_bp *h, int32_t batch, int32_t method, float alpha, ui
 int mc_finish(scaldpc_bp *h, int batch, int T, int nv, bool dev_io, hipStream_t s, uint8_t *out_success,
               int32_t *out_iters)
 {
-    SC_TRY(grow(&h->d_diff, &h->cap_diff, (size_t)T));
+    SC_TRY(grow(h->d_diff, (size_t)T));
     SC_HIP(hipMemsetAsync(h->d_diff, 0, sizeof(u64) * (size_t)T, s));
     hipLaunchKernelGGL(k_mc_compare, dim3((nv + 255) / 256, T), dim3(256), 0, s, h->d_hard, h->d_mc, h->n, nv,
                        h->d_diff);
     LAUNCH_CHECK();
     uint8_t *ds = out_success;
-    int *di = out_iters;
     if (!dev_io) {
-        SC_TRY(grow(&h->d_succ, &h->cap_succ, (size_t)batch));
+        SC_TRY(grow(h->d_succ, (size_t)batch));
         ds = h->d_succ;
-        if (out_iters) {
-            if ((size_t)batch > h->cap_out_b) {
-                dev_free(h->d_out_iters); dev_free(h->d_out_conv);
-                h->cap_out_b = 0;
-                SC_TRY(dev_alloc(&h->d_out_iters, (size_t)batch));
-                SC_TRY(dev_alloc(&h->d_out_conv, (size_t)batch));
-                h->cap_out_b = batch;
-            }
-            di = h->d_out_iters;
-        }
     }
-    hipLaunchKernelGGL(k_mc_result, dim3(T), dim3(64), 0, s, h->d_diff, h->d_iters, batch, ds, di);
+    Outputs out, dev;
+    out.iters = out_iters;
+    SC_TRY(stage_outputs(h, out, batch, dev_io, out_iters != nullptr, &dev));
+    hipLaunchKernelGGL(k_mc_result, dim3(T), dim3(64), 0, s, h->d_diff, h->d_iters, batch, ds, dev.iters);
     LAUNCH_CHECK();
-    if (!dev_io) {
-        SC_HIP(hipMemcpyAsync(out_success, ds, (size_t)batch, hipMemcpyDeviceToHost, s));
-        if (out_iters) SC_HIP(hipMemcpyAsync(out_iters, di, sizeof(int) * (size_t)batch, hipMemcpyDeviceToHost, s));
-    }
+    if (!dev_io) SC_HIP(hipMemcpyAsync(out_success, ds, (size_t)batch, hipMemcpyDeviceToHost, s));
+    SC_TRY(copy_outputs(h, out, dev, batch, dev_io, s));
     SC_HIP(hipStreamSynchronize(s));
     return 0;
 }
 
 int mc_export_bits(scaldpc_bp *h, const u64 *planes, int batch, int T, bool dev_io, hipStream_t s, uint8_t *out)
 {
-    uint8_t *d = out;
-    if (!dev_io) {
-        SC_TRY(grow(&h->d_out_bits, &h->cap_out_bits, (size_t)batch * h->n));
-        d = h->d_out_bits;
-    }
+    Outputs o, dev;
+    o.bits = out;
+    SC_TRY(stage_outputs(h, o, batch, dev_io, false, &dev));
     hipLaunchKernelGGL(k_unpack_bits, dim3((h->n + 255) / 256, T), dim3(256), 0, s, planes, (const u64 *)nullptr, h->n,
-                       batch, d);
+                       batch, dev.bits);
     LAUNCH_CHECK();
-    if (!dev_io) {
-        SC_HIP(hipMemcpyAsync(out, d, (size_t)batch * h->n, hipMemcpyDeviceToHost, s));
-        SC_HIP(hipStreamSynchronize(s));  // d_out_bits is reused below
-    }
+    SC_TRY(copy_outputs(h, o, dev, batch, dev_io, s));
+    if (!dev_io) SC_HIP(hipStreamSynchronize(s));  // d_out_bits is reused below
     return 0;
 }
 
 }  // namespace
 
-int scaldpc_mc_fer_run(scaldpc_bp *h, int64_t first_trial, int32_t batch, uint64_t seed, int32_t max_iter,
+int scaldpc_mc_fer_run(scaldpc_bp *h, int64_t first_trial, int32_t batch, uint64_t seed, int32_t max_iter_arg,
                        int32_t method, float alpha, uint32_t flags, void *stream, uint8_t *out_success,
                        int32_t *out_iters, uint8_t *out_error)
 {
     SC_TRY(mc_common_args(h, batch, method, alpha, out_success));
     std::lock_guard<std::mutex> lk(h->mu);
-    if (h->broken) return fail(SCALDPC_EHIP, "this decoder is unusable: an earlier scaldpc_bp_append_rows failed part-way; destroy it and build a new one");
+    SC_TRY(check_usable(h));
     DeviceGuard dg(h->device);
     CacheBypass guard(h->async_used);
-    if (!h->have_prior || h->prior_n < h->n)
-        return fail(SCALDPC_EINVAL, "channel probabilities not set (columns [%d, %d))", h->have_prior ? h->prior_n : 0, h->n);
-    if (max_iter <= 0) max_iter = h->n;
+    Call c;
+    SC_TRY(begin_call(h, batch, max_iter_arg, stream, &c));
     SC_TRY(refresh_full(h));
     const bool dev_io = flags & SCALDPC_F_DEVICE_IO, early = flags & SCALDPC_F_EARLY_EXIT;
-    hipStream_t s = stream ? (hipStream_t)stream : h->own_stream;
-    const int T = (batch + TW - 1) / TW;
-    if (T > 65535) return fail(SCALDPC_EINVAL, "batch %d too large for one call", batch);
-    const int G = (h->tile_group > 0) ? std::min(h->tile_group, T) : auto_group(h, T);
+    const hipStream_t s = c.s;
+    const int T = c.T, G = c.G, max_iter = c.max_iter;
     SC_TRY(ensure_workspace(h, T, G, false, max_iter));
-    SC_TRY(grow(&h->d_mc, &h->cap_mc, (size_t)T * h->n));
+    SC_TRY(grow(h->d_mc, (size_t)T * h->n));
     if (!h->thr_valid) {
-        if (!h->d_thr) SC_TRY(dev_alloc(&h->d_thr, (size_t)h->n));
+        if (!h->d_thr) SC_TRY(h->d_thr.ensure((size_t)h->n));
         pvec<u64> thr(h->n);
         for (int j = 0; j < h->n; j++) thr[j] = bernoulli_threshold(h->h_probs[j]);
         SC_HIP(hipMemcpy(h->d_thr, thr.data(), sizeof(u64) * h->n, hipMemcpyHostToDevice));
@@ -2171,35 +2119,32 @@ int scaldpc_mc_fer_run(scaldpc_bp *h, int64_t first_trial, int32_t batch, uint64
 }
 
 int scaldpc_mc_hqc_run(scaldpc_bp *h, int32_t omega, double eps, int64_t first_trial, int32_t batch, uint64_t seed,
-                       int32_t max_iter, int32_t method, float alpha, uint32_t flags, void *stream,
+                       int32_t max_iter_arg, int32_t method, float alpha, uint32_t flags, void *stream,
                        uint8_t *out_success, int32_t *out_iters, uint8_t *out_msg, int32_t *out_y)
 {
     SC_TRY(mc_common_args(h, batch, method, alpha, out_success));
     std::lock_guard<std::mutex> lk(h->mu);
-    if (h->broken) return fail(SCALDPC_EHIP, "this decoder is unusable: an earlier scaldpc_bp_append_rows failed part-way; destroy it and build a new one");
+    SC_TRY(check_usable(h));
     DeviceGuard dg(h->device);
     CacheBypass guard(h->async_used);
-    if (!h->have_prior || h->prior_n < h->n)
-        return fail(SCALDPC_EINVAL, "channel probabilities not set (columns [%d, %d))", h->have_prior ? h->prior_n : 0, h->n);
+    Call c;
+    SC_TRY(begin_call(h, batch, max_iter_arg, stream, &c));
     SC_TRY(refresh_full(h));
     if (h->identity_from < 0) return fail(SCALDPC_EINVAL, "parity-check matrix is not of the form [Hin | I] (hqc.py:680)");
     const int N = h->identity_from;
     if (omega < 0 || omega > N) return fail(SCALDPC_EINVAL, "omega must be in [0, N]");
     if (!(eps >= 0.0 && eps <= 1.0)) return fail(SCALDPC_EINVAL, "eps must be a probability");
     if ((size_t)omega * 64 * 4 > 64 * 1024) return fail(SCALDPC_EDEGREE, "omega %d too large for the LDS-resident sampler", omega);
-    if (max_iter <= 0) max_iter = h->n;
     const bool dev_io = flags & SCALDPC_F_DEVICE_IO, early = flags & SCALDPC_F_EARLY_EXIT;
-    hipStream_t s = stream ? (hipStream_t)stream : h->own_stream;
-    const int T = (batch + TW - 1) / TW;
-    if (T > 65535) return fail(SCALDPC_EINVAL, "batch %d too large for one call", batch);
-    const int G = (h->tile_group > 0) ? std::min(h->tile_group, T) : auto_group(h, T);
+    const hipStream_t s = c.s;
+    const int T = c.T, G = c.G, max_iter = c.max_iter;
     SC_TRY(ensure_workspace(h, T, G, false, max_iter));
-    SC_TRY(grow(&h->d_mc, &h->cap_mc, (size_t)T * h->n));
+    SC_TRY(grow(h->d_mc, (size_t)T * h->n));
     int *dy = nullptr;
     if (out_y) {
         dy = out_y;
         if (!dev_io) {
-            SC_TRY(grow(&h->d_ylist, &h->cap_ylist, (size_t)batch * std::max(omega, 1)));
+            SC_TRY(grow(h->d_ylist, (size_t)batch * std::max(omega, 1)));
             dy = h->d_ylist;
         }
     }
@@ -2241,7 +2186,7 @@ int scaldpc_bp_configure(scaldpc_bp *h, const char *key, const char *value)
     if (h->kn.var_order != old_order && h->d_tile_tab) {  // the k_var records are laid out in launch order: rebuild on next use
         CacheBypass guard(true);
         SC_HIP(hipDeviceSynchronize());
-        dev_free(h->d_tile_tab);
+        h->d_tile_tab.reset();
         h->d_var_meta = h->d_csc_list = h->d_row_list = nullptr;
     }
     return 0;
@@ -2262,7 +2207,7 @@ int scaldpc_bp_device_of(scaldpc_bp *h, int32_t *out)
     };
     out[0] = h->device;
     out[1] = where(h->d_graph);
-    out[2] = where(h->d_msg ? (const void *)h->d_msg : (const void *)h->d_emsg);
+    out[2] = where(h->d_msg ? h->d_msg.get() : h->d_emsg.get());
     out[3] = where(h->d_synd);
     return 0;
 }
@@ -2272,7 +2217,7 @@ int scaldpc_bp_time_kernels(scaldpc_bp *h, int32_t iters, int32_t method, float 
 {
     if (!h || !ms || !launches || iters <= 0) return fail(SCALDPC_EINVAL, "bad argument");
     std::lock_guard<std::mutex> lk(h->mu);
-    if (h->broken) return fail(SCALDPC_EHIP, "this decoder is unusable: an earlier scaldpc_bp_append_rows failed part-way; destroy it and build a new one");
+    SC_TRY(check_usable(h));
     DeviceGuard dg(h->device);
     if (h->last_group <= 0) return fail(SCALDPC_EINVAL, "no previous decode to time");
     hipStream_t s = stream ? (hipStream_t)stream : h->own_stream;
@@ -2424,34 +2369,7 @@ void scaldpc_bp_destroy(scaldpc_bp *h)
     // them for the next handle.  The guard must be in place BEFORE the first block is released.
     CacheBypass guard(h->async_used);
     if (h->async_used) (void)hipDeviceSynchronize();
-    dev_free(h->d_graph);  // graph arrays and d_prior are views into it (until the graph grows)
-    dev_free(h->d_csr_rp); dev_free(h->d_csr_ci); dev_free(h->d_prior_buf); dev_free(h->d_pairs);
-    cached_free(h->h_pairs);
-    dev_free(h->d_tile_tab);
-    dev_free(h->d_first_tab);
-    dev_free(h->d_el_tab);
-    dev_free(h->d_msg); dev_free(h->d_scratch); dev_free(h->d_post);
-    dev_free(h->d_rec); dev_free(h->d_mask);
-    dev_free(h->d_synd); dev_free(h->d_recv); dev_free(h->d_hard); dev_free(h->d_done);
-    dev_free(h->d_conv); dev_free(h->d_unsat); dev_free(h->d_iters); dev_free(h->d_remaining);
-    dev_free(h->d_in); dev_free(h->d_out_bits); dev_free(h->d_out_conv); dev_free(h->d_out_llr);
-    dev_free(h->d_out_iters);
-    for (auto &L : h->lv) {
-        dev_free(L.synd); dev_free(L.hard); dev_free(L.done); dev_free(L.conv); dev_free(L.unsat);
-        dev_free(L.iters); dev_free(L.ids); dev_free(L.slot_of); dev_free(L.post);
-    }
-    dev_free(h->d_emsg); dev_free(h->d_el_unsat);
-    dev_free(h->d_thr); dev_free(h->d_mc); dev_free(h->d_diff); dev_free(h->d_ylist); dev_free(h->d_succ);
-    cached_free(h->h_remaining);
-    cached_free(h->h_io);  // the small-call staging pair (decode_batch's fused host path)
-    dev_free(h->d_out_all);
-    if (h->own_stream) stream_release(h->own_stream, h->device);
-    for (int k = 0; k < 4; k++) {
-        if (h->aux_stream[k]) stream_release(h->aux_stream[k], h->device);
-        if (h->ev_join[k]) (void)hipEventDestroy(h->ev_join[k]);
-        if (h->ev_phase[k]) (void)hipEventDestroy(h->ev_phase[k]);
-    }
-    delete h;
+    delete h;  // the buffers, then the streams and events (HandleStreams)
 }
 
 }  // extern "C"

@@ -2,9 +2,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/scaldpc.h"
@@ -92,19 +94,78 @@ struct PoolAlloc {
 template <typename T>
 using pvec = std::vector<T, PoolAlloc<T>>;
 
-template <typename T>
-inline int dev_alloc(T **p, size_t count)
-{
-    *p = nullptr;
-    if (count == 0) count = 1;
-    return cached_alloc((void **)p, count * sizeof(T), false);
-}
+// One block of cached_alloc, owned: released (cached_free) by reset() and the destructor.  cap() is the element count
+// last requested; a request for 0 elements still takes one.  A failed request leaves the buffer empty with capacity 0, so
+// the next call retries.  Nothing here zeroes the memory or synchronises.  The buffer converts to T *, so kernel
+// launches and pointer arithmetic read as with a plain pointer.
+template <typename T, bool Pinned = false>
+class Buf {
+public:
+    Buf() = default;
+    Buf(Buf &&o) noexcept : p_(o.p_), cap_(o.cap_)
+    {
+        o.p_ = nullptr;
+        o.cap_ = 0;
+    }
+    Buf &operator=(Buf &&o) noexcept
+    {
+        if (this != &o) {
+            reset();
+            std::swap(p_, o.p_);
+            std::swap(cap_, o.cap_);
+        }
+        return *this;
+    }
+    Buf(const Buf &) = delete;
+    Buf &operator=(const Buf &) = delete;
+    ~Buf() { reset(); }
 
+    operator T *() const { return p_; }
+    T *get() const { return p_; }
+    size_t cap() const { return cap_; }
+
+    void reset()
+    {
+        if (p_) cached_free((void *)p_);
+        p_ = nullptr;
+        cap_ = 0;
+    }
+    // room for `need` elements; else the block is released and `alloc` (>= need) elements are requested
+    int ensure(size_t need, size_t alloc)
+    {
+        if (p_ && need <= cap_) return 0;
+        reset();
+        return request(alloc, &p_, &cap_);
+    }
+    int ensure(size_t need) { return ensure(need, need); }
+    // room for `need` elements with the first `used` kept: the new block of `alloc` elements is requested and filled
+    // before the old one is released; a failed request or copy leaves the old block in place
+    int grow_keep(size_t used, size_t need, size_t alloc)
+    {
+        if (need <= cap_) return 0;
+        Buf q;
+        SC_TRY(request(alloc, &q.p_, &q.cap_));
+        if (used) {
+            const hipError_t e = hipMemcpy(q.p_, p_, used * sizeof(T), hipMemcpyDeviceToDevice);
+            if (e != hipSuccess) return fail(SCALDPC_EHIP, "copy into the grown buffer failed: %s", hipGetErrorString(e));
+        }
+        *this = std::move(q);
+        return 0;
+    }
+
+private:
+    static int request(size_t count, T **p, size_t *cap)
+    {
+        void *q = nullptr;
+        SC_TRY(cached_alloc(&q, std::max<size_t>(count, 1) * sizeof(T), Pinned));
+        *p = (T *)q;
+        *cap = count;
+        return 0;
+    }
+    T *p_ = nullptr;
+    size_t cap_ = 0;
+};
 template <typename T>
-inline void dev_free(T *&p)
-{
-    if (p) cached_free((void *)p);
-    p = nullptr;
-}
+using PinnedBuf = Buf<T, true>;
 
 }  // namespace scaldpc

@@ -629,28 +629,41 @@ __global__ void k_q_unpack(const signed char *__restrict__ in, int N, int batch,
 
 }  // namespace
 
-struct scaldpc_qary {
+// The handle's stream and timing events, released when the handle goes.  scaldpc_qary derives from it, so every buffer
+// member has returned its device memory before they are released.
+struct QaryStreams {
+    int device = 0;  // the device the handle was created on; every entry point runs there
+    hipStream_t own_stream = nullptr;
+    std::vector<hipEvent_t> tev;
+    QaryStreams() = default;
+    QaryStreams(const QaryStreams &) = delete;
+    QaryStreams &operator=(const QaryStreams &) = delete;
+    ~QaryStreams()
+    {
+        for (auto &e : tev) (void)hipEventDestroy(e);
+        if (own_stream) (void)hipStreamDestroy(own_stream);
+    }
+};
+
+// Every block the handle owns is a Buf member; d_err and d_first_bad are views into d_status.
+struct scaldpc_qary : QaryStreams {
     bool special = false;
     int R = 0, N = 0, B = 0, BSUM = 0, Q = 0, QS = 0, W = 0, iterations = 0;
     int E = 0, maxdc = 0, mindc = 0, maxdv = 0;
     long llr_rows = 0;  // total alphabet rows over all variables
-    int *d_row_ptr = nullptr, *d_col_ptr = nullptr, *d_csc_edge = nullptr, *d_edge_var = nullptr, *d_edge_h = nullptr,
-        *d_var_q = nullptr;
-    long *d_var_off = nullptr;
+    Buf<int> d_row_ptr, d_col_ptr, d_csc_edge, d_edge_var, d_edge_h, d_var_q;
+    Buf<long> d_var_off;
     std::vector<int> h_var_q;
     std::vector<long> h_var_off;
-    long cap_bp = 0;
-    float *d_msg = nullptr, *d_llr = nullptr, *d_pmf = nullptr, *d_pmf2 = nullptr;
-    signed char *d_hard = nullptr, *d_out = nullptr;
-    size_t cap_pmf = 0, cap_pmf2 = 0, cap_out = 0;
+    long cap_bp = 0;  // codeword columns d_msg, d_llr and d_hard are sized for
+    Buf<float> d_msg, d_llr, d_pmf, d_pmf2;
+    Buf<signed char> d_hard, d_out;
     // one 16-byte status block per handle, zeroed by ONE fill and read back by ONE copy per call: [0] = the bitwise complement of
     // the smallest (codeword, variable) key whose pmf row fails the sum test (0: none; kept inverted so that "none" is zero
     // and the kernels lower the key with atomicMax), [1] = the call's error code (low word)
-    u64 *d_status = nullptr;
+    Buf<u64> d_status;
     int *d_err = nullptr;        // = (int *)(d_status + 1)
     u64 *d_first_bad = nullptr;  // = d_status
-    hipStream_t own_stream = nullptr;
-    int device = 0;      // the device the handle was created on; every entry point runs there
     int kn_wave = -1;    // -1: wave-parallel enumeration for batches <= 256 and the special decoder; 0 / 1 force
     int kn_unroll = 1;   // register-resident unrolled enumeration for small alphabets
     int kn_tree = 1;     // special decoder: tree-walk check kernel for the Kyber shape (QB = 5, 6 coefficient edges)
@@ -663,7 +676,6 @@ struct scaldpc_qary {
     int kn_llr_tiled = 1;  // probability -> LLR conversion through an LDS tile (coalesced reads); A/B knob "llr_tiled"
     int kn_var_small = 1;  // register-resident variable update for Q = 3 / 5 / 7 / 15 and columns of at most 4 checks (A/B knob "var_small")
     int kn_timing = 0;
-    std::vector<hipEvent_t> tev;
     float stat_ms_check = 0.f, stat_ms_var = 0.f, stat_ms_call = 0.f;
     int stat_iters = 0, stat_kernel = -1, stat_batch = 0;
     std::mutex mu;
@@ -746,48 +758,35 @@ int qary_build(int R, int N, int B, int BSUM, bool special, const int8_t *H, int
         off += h->h_var_q[v];
     }
     h->llr_rows = off;
-    int rc = 0;
-    auto up = [&](int **d, const int *src, size_t cnt) -> int {
-        SC_TRY(dev_alloc(d, cnt));
-        if (cnt) SC_HIP(hipMemcpy(*d, src, cnt * sizeof(int), hipMemcpyHostToDevice));
-        return 0;
-    };
-    if (!rc) rc = up(&h->d_row_ptr, row_ptr.data(), R + 1);
-    if (!rc) rc = up(&h->d_col_ptr, col_ptr.data(), N + 1);
-    if (!rc) rc = up(&h->d_csc_edge, csc_edge.data(), E);
-    if (!rc) rc = up(&h->d_edge_var, edge_var.data(), E);
-    if (!rc) rc = up(&h->d_edge_h, edge_h.data(), E);
-    if (!rc) rc = up(&h->d_var_q, h->h_var_q.data(), N);
-    if (!rc) rc = dev_alloc(&h->d_var_off, (size_t)N);
-    if (!rc && hipMemcpy(h->d_var_off, h->h_var_off.data(), sizeof(long) * N, hipMemcpyHostToDevice) != hipSuccess)
-        rc = fail(SCALDPC_EHIP, "hipMemcpy failed");
-    if (!rc) rc = dev_alloc(&h->d_status, 2);
-    if (!rc) {
-        h->d_first_bad = h->d_status;
-        h->d_err = (int *)(h->d_status + 1);
-    }
-    if (!rc && hipGetDevice(&h->device) != hipSuccess) rc = fail(SCALDPC_EHIP, "hipGetDevice failed");
     if (const char *e = getenv("SCALDPC_QARY_WAVE")) h->kn_wave = atoi(e) != 0;  // the environment is read once per handle
     if (getenv("SCALDPC_QARY_NO_UNROLL")) h->kn_unroll = 0;
     if (getenv("SCALDPC_QARY_NO_TREE")) h->kn_tree = 0;
-    if (!rc && hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess)
-        rc = fail(SCALDPC_EHIP, "hipStreamCreate failed");
-    if (rc) {
+    auto device_side = [&]() -> int {
+        auto up = [](auto &d, const auto *src, size_t cnt) -> int {
+            SC_TRY(d.ensure(cnt));
+            if (cnt) SC_HIP(hipMemcpy(d, src, cnt * sizeof(*src), hipMemcpyHostToDevice));
+            return 0;
+        };
+        SC_TRY(up(h->d_row_ptr, row_ptr.data(), R + 1));
+        SC_TRY(up(h->d_col_ptr, col_ptr.data(), N + 1));
+        SC_TRY(up(h->d_csc_edge, csc_edge.data(), E));
+        SC_TRY(up(h->d_edge_var, edge_var.data(), E));
+        SC_TRY(up(h->d_edge_h, edge_h.data(), E));
+        SC_TRY(up(h->d_var_q, h->h_var_q.data(), N));
+        SC_TRY(up(h->d_var_off, h->h_var_off.data(), N));
+        SC_TRY(h->d_status.ensure(2));
+        h->d_first_bad = h->d_status;
+        h->d_err = (int *)(h->d_status + 1);
+        if (hipGetDevice(&h->device) != hipSuccess) return fail(SCALDPC_EHIP, "hipGetDevice failed");
+        if (hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess)
+            return fail(SCALDPC_EHIP, "hipStreamCreate failed");
+        return 0;
+    };
+    if (const int rc = device_side()) {
         scaldpc_qary_destroy(h);
         return rc;
     }
     *out = h;
-    return 0;
-}
-
-template <typename T>
-int growq(T **p, size_t *cap, size_t need)
-{
-    if (need <= *cap && *p) return 0;
-    dev_free(*p);
-    *cap = 0;
-    SC_TRY(dev_alloc(p, need));
-    *cap = need;
     return 0;
 }
 
@@ -803,11 +802,11 @@ int qary_run(scaldpc_qary *h, const float *pmf_b, const float *pmf_s, int batch,
     const long Bp = ((long)batch + 63) / 64 * 64;
     const int BV = h->special ? h->N - h->R : h->N;
     if (Bp > h->cap_bp) {
-        dev_free(h->d_msg); dev_free(h->d_llr); dev_free(h->d_hard);
+        h->d_msg.reset(); h->d_llr.reset(); h->d_hard.reset();
         h->cap_bp = 0;
-        SC_TRY(dev_alloc(&h->d_msg, (size_t)std::max(h->E, 1) * h->W * Bp));
-        SC_TRY(dev_alloc(&h->d_llr, (size_t)h->llr_rows * Bp));
-        SC_TRY(dev_alloc(&h->d_hard, (size_t)h->N * Bp));
+        SC_TRY(h->d_msg.ensure((size_t)std::max(h->E, 1) * h->W * Bp));
+        SC_TRY(h->d_llr.ensure((size_t)h->llr_rows * Bp));
+        SC_TRY(h->d_hard.ensure((size_t)h->N * Bp));
         h->cap_bp = Bp;
     }
     SC_HIP(hipMemsetAsync(h->d_status, 0, 2 * sizeof(u64), s));
@@ -816,11 +815,11 @@ int qary_run(scaldpc_qary *h, const float *pmf_b, const float *pmf_s, int batch,
     const float *dp_b = pmf_b, *dp_s = pmf_s;
     if (!dev_io) {
         const size_t nb = (size_t)batch * BV * h->Q, ns = h->special ? (size_t)batch * h->R * h->QS : 0;
-        SC_TRY(growq(&h->d_pmf, &h->cap_pmf, nb));
+        SC_TRY(h->d_pmf.ensure(nb));
         SC_HIP(hipMemcpyAsync(h->d_pmf, pmf_b, nb * sizeof(float), hipMemcpyHostToDevice, s));
         dp_b = h->d_pmf;
         if (h->special) {
-            SC_TRY(growq(&h->d_pmf2, &h->cap_pmf2, ns));
+            SC_TRY(h->d_pmf2.ensure(ns));
             SC_HIP(hipMemcpyAsync(h->d_pmf2, pmf_s, ns * sizeof(float), hipMemcpyHostToDevice, s));
             dp_s = h->d_pmf2;
         }
@@ -983,7 +982,7 @@ int qary_run(scaldpc_qary *h, const float *pmf_b, const float *pmf_s, int batch,
     if (timing) SC_HIP(hipEventRecord(h->tev[2 * iters], s));
     signed char *dout = (signed char *)out;
     if (!dev_io) {
-        SC_TRY(growq(&h->d_out, &h->cap_out, (size_t)batch * h->N));
+        SC_TRY(h->d_out.ensure((size_t)batch * h->N));
         dout = h->d_out;
     }
     hipLaunchKernelGGL(k_q_unpack, dim3((h->N + 255) / 256, batch), dim3(256), 0, s, h->d_hard, h->N, batch, Bp, dout);
@@ -1043,23 +1042,12 @@ int scaldpc_qary_into_llr(const float *pmf, int64_t rows, int32_t Q, uint32_t fl
     const bool dev_io = flags & SCALDPC_F_DEVICE_IO;
     hipStream_t s = (hipStream_t)stream;  // NULL: the default stream (this call owns no handle)
     const size_t cnt = (size_t)rows * Q;
-    float *d_p = nullptr, *d_l = nullptr;
-    u64 *d_bad = nullptr;
-    auto cleanup = [&]() {
-        dev_free(d_bad);
-        if (!dev_io) {
-            dev_free(d_p);
-            dev_free(d_l);
-        }
-    };
-    int rc = dev_alloc(&d_bad, 1);
-    if (!rc && !dev_io) {
-        rc = dev_alloc(&d_p, cnt);
-        if (!rc) rc = dev_alloc(&d_l, cnt);
-    }
-    if (rc) {
-        cleanup();
-        return rc;
+    Buf<float> d_l, d_p;  // (declared in reverse: released in the order d_bad, d_p, d_l, after the synchronise below)
+    Buf<u64> d_bad;
+    SC_TRY(d_bad.ensure(1));
+    if (!dev_io) {
+        SC_TRY(d_p.ensure(cnt));
+        SC_TRY(d_l.ensure(cnt));
     }
     u64 bad = ~0ull;
     hipError_t e = hipMemsetAsync(d_bad, 0xFF, sizeof(u64), s);
@@ -1072,7 +1060,6 @@ int scaldpc_qary_into_llr(const float *pmf, int64_t rows, int32_t Q, uint32_t fl
     if (e == hipSuccess && !dev_io) e = hipMemcpyAsync(llr, d_l, cnt * sizeof(float), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, sizeof(u64), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    cleanup();
     if (e != hipSuccess) return fail(SCALDPC_EHIP, "into_llr failed: %s", hipGetErrorString(e));
     if (bad != ~0ull) {
         if (bad & 1) return fail(SCALDPC_EPMF, "No maximum probability found (row %lld)", (long long)(bad >> 1));
@@ -1143,13 +1130,7 @@ void scaldpc_qary_destroy(scaldpc_qary *h)
 {
     if (!h) return;
     DeviceGuard dg(h->device);
-    dev_free(h->d_status);
-    dev_free(h->d_row_ptr); dev_free(h->d_col_ptr); dev_free(h->d_csc_edge); dev_free(h->d_edge_var);
-    dev_free(h->d_edge_h); dev_free(h->d_var_q); dev_free(h->d_var_off); dev_free(h->d_msg); dev_free(h->d_llr);
-    dev_free(h->d_pmf); dev_free(h->d_pmf2); dev_free(h->d_hard); dev_free(h->d_out);
-    for (auto &e : h->tev) (void)hipEventDestroy(e);
-    if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
-    delete h;
+    delete h;  // the buffers, then the stream and events (QaryStreams)
 }
 
 }  // extern "C"

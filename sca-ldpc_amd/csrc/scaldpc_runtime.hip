@@ -1,5 +1,5 @@
 // libscaldpc -- process-wide plumbing shared by the binary and the q-ary decoders: the
-// thread-local error string, the block cache behind dev_alloc / dev_free, the pool of
+// thread-local error string, the block cache behind Buf (scaldpc_common.h), the pool of
 // recycled streams, and the handful of C-ABI entry points that belong to no handle.
 #include "scaldpc_common.h"
 
@@ -27,7 +27,7 @@ int fail(int code, const char *fmt, ...)
     return code;
 }
 
-// ---- block cache behind dev_alloc / dev_free (see scaldpc_common.h) ----------------------
+// ---- block cache behind Buf (see scaldpc_common.h) --------------------------------------
 namespace {
 struct Block {
     size_t bytes;
@@ -144,7 +144,7 @@ void cached_free(void *p)
     {
         std::lock_guard<std::mutex> lk(bc.mu);
         auto it = bc.live.find(p);
-        if (it == bc.live.end()) return;  // not ours (cannot happen through dev_free)
+        if (it == bc.live.end()) return;  // not ours (cannot happen through Buf)
         b = it->second;
         bc.live.erase(it);
         if (cache_enabled() && b.bytes <= CACHE_BLOCK_MAX && bc.idle_bytes + b.bytes <= CACHE_TOTAL_MAX) {
