@@ -169,7 +169,7 @@ int scaldpc_bp_decode_batch(scaldpc_bp *h, const uint8_t *in, int32_t input_kind
  *   launches[5]     bit 0: min-sum ran in its record form (k_check_minsum_rec / k_var_rec; knob "minsum_rec");
  *                   bit 1: the variable pass was timed WITH its decision output -- the form every pass of an
  *                   early-exit decode launches; the timing follows the last decode (fixed iterations: no output);
- *                   bit 2: the timed variable launch left out the columns of degree <= 1 (record form, no output)
+ *                   bit 2: record form and no output: the timed variable launch leaves out the columns of degree <= 1
  */
 int scaldpc_bp_time_kernels(scaldpc_bp *h, int32_t iters, int32_t method, float alpha, void *stream,
                             float *ms, int32_t *launches);
@@ -192,21 +192,18 @@ int scaldpc_bp_last_compacted(scaldpc_bp *h, int64_t *count);
  *   out[3] = reserved (0) */
 int scaldpc_bp_last_stats(scaldpc_bp *h, int64_t *out);
 /* Tuning / test knobs of one handle.  A new handle takes its defaults from the environment ONCE, at
- * creation (SCALDPC_PATH, SCALDPC_SPLIT, SCALDPC_GROUP_MB, SCALDPC_EL_MAX, SCALDPC_EL_FUSE,
- * SCALDPC_COMPACT_AFTER, SCALDPC_VAR_ORDER, SCALDPC_FIRST_FUSED, SCALDPC_FUSE_TEST, SCALDPC_MINSUM_REC,
- * SCALDPC_REC_SKIP1); the decode entry points never read the environment.  Every knob selects a path, a size or a
- * form that some graph or call still falls back to; the switches of variants that were measured and rejected
- * (round 3's test_overlap, var_form, rec_maskpos, rec_xmap, rec_sc1, fuse_finalize, speculate, minsum_loop) are gone
- * with their code (round 4; numbers in profiles/HISTORY.md) and are refused as unknown keys.  key / value (text):
+ * creation (SCALDPC_PATH, SCALDPC_SPLIT, SCALDPC_GROUP_MB, SCALDPC_EL_MAX, SCALDPC_COMPACT_AFTER,
+ * SCALDPC_FIRST_FUSED, SCALDPC_FUSE_TEST, SCALDPC_MINSUM_REC); the decode entry points never read the environment.
+ * Every knob selects a path, a size or a form that some graph or call still falls back to; the switches of variants
+ * that were measured and rejected (round 3's test_overlap, var_form, rec_maskpos, rec_xmap, rec_sc1, fuse_finalize,
+ * speculate, minsum_loop) are gone with their code (round 4; numbers in profiles/HISTORY.md), and so are the A/B-only
+ * el_fuse, var_order and rec_skip1 (what their defaults chose is what runs): all are refused as unknown keys.
+ * key / value (text):
  *   "path"          "auto" | "stream" (64-codeword tiles) | "edge" (row-parallel up to 64) | "lds"
  *   "split"         stream lanes per tile group (default 2)
  *   "group_mb"      budget of a cache-resident tile group in MB (default 215; large = stream from HBM)
  *   "el_max"        largest call the row-parallel kernels take (default 6 min-sum / 4 tanh)
- *   "el_fuse"       1 = two-launch early-exit loop of the row-parallel path (default), 0 = four-launch
  *   "compact_after" iteration from which stragglers may be handed to a compact pass (default 4, 0 = never)
- *   "var_order"     launch order of the columns in a variable-node pass: bit 0 = inside a degree by first
- *                   edge id (else by column id), bit 1 = heaviest columns first; -1 (default) = auto:
- *                   2 when a tile group runs as one stream lane, 1 otherwise
  *   "fuse_test"     1 (default) = in the early-exit tile loop the convergence test of an iteration rides on the check
  *                   pass of the next one (except where the host polls or stops), with sharded accumulators;
  *                   0 = a stand-alone launch after every variable pass (what poll iterations use anyway).
@@ -215,11 +212,6 @@ int scaldpc_bp_last_stats(scaldpc_bp *h, int64_t *out);
  *                   masks (sign, arg-min: 0.25 B per codeword) instead of 4 B per edge and codeword; the variable pass
  *                   rebuilds every message from them, bit for bit.  0 = messages both ways (what graphs with a row
  *                   wider than 64 or a column wider than 32 use anyway).
- *   "rec_skip1"     1 (default) = in the record form a variable pass WITHOUT output (fixed-iteration runs, every pass but
- *                   the first and the last) leaves out the columns of degree <= 1: such a column always sends its prior,
- *                   iteration 1 has written it into the message array and the record check pass never overwrites it
- *                   (the identity block of an HQC graph: 4000 of 21669 column waves per tile).  0 = all columns (what
- *                   passes with output launch anyway).
  *   "first_fused"   1 (default) = iteration 1 of the tile kernels runs without its check pass: the first variable
  *                   pass takes the first check-to-variable messages from a per-edge table (the message of a
  *                   zero-syndrome codeword) and the row's syndrome bit; 0 = check pass (reading the priors) + plain

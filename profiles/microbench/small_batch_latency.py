@@ -50,8 +50,7 @@ def main():
     rng = np.random.RandomState(0)
     xbad = np.concatenate([np.zeros(N, np.uint8), rng.randint(0, 2, H.m).astype(np.uint8)])
     # (knobs are per handle since round 2: the environment is only read when a decoder is created)
-    for label, kn in (("tiles", dict(path="stream", el_fuse=1)), ("row-parallel, 4 launches/iteration", dict(path="auto", el_fuse=0)),
-                      ("row-parallel, 2 launches/iteration", dict(path="auto", el_fuse=1))):
+    for label, kn in (("tiles", dict(path="stream")), ("row-parallel, 2 launches/iteration", dict(path="auto"))):
         warm.configure(**kn)
         warm.decode(xbad)
         t0 = time.perf_counter()

@@ -59,7 +59,7 @@ struct HostBuckets {
 // handle
 // ===========================================================================
 // Tuning / test knobs of a handle.  The environment is read ONCE, when the handle is created
-// (SCALDPC_PATH, _SPLIT, _GROUP_MB, _EL_MAX, _EL_FUSE, _COMPACT_AFTER, ...); afterwards
+// (SCALDPC_PATH, _SPLIT, _GROUP_MB, _EL_MAX, _COMPACT_AFTER, ...); afterwards
 // scaldpc_bp_configure() changes them -- the decode entry points never call getenv().
 // Round 4 pruned the knobs that only switched a measured-and-rejected variant back on (test_overlap, var_form = 0,
 // rec_maskpos = 0, rec_xmap = 0, rec_sc1 = 0, fuse_finalize = 0, speculate = 0, minsum_loop; numbers in
@@ -70,12 +70,9 @@ struct Knobs {
     int split = 2;            // stream lanes per tile group
     double group_mb = 215.0;  // cache-resident group budget (auto_group)
     int el_max = -1;          // row-parallel limit; -1 = per-method default (6 / 4)
-    int el_fuse = 1;          // early-exit row-parallel loop: fused two-launch form
     int compact_after = -1;   // -1 = default (4); 0 = no compact pass
-    int var_order = -1;       // k_var launch order: bit 0 = inside a degree by first edge id, bit 1 = heaviest columns first; -1 = auto
     int fuse_test = 1;        // early-exit tile loop: the convergence test of iteration it rides on the check pass of it + 1 wherever the host does not need the verdict in between
     int first_fused = 1;      // iteration 1 of the tile kernels without its check pass (k_var_first from the first-message table); 0 = check pass + plain variable pass
-    int rec_skip1 = 1;        // record form: passes without output leave out the columns of degree <= 1 (their message is the prior, written once by iteration 1; the record check pass never overwrites it); 0 = all columns every pass (A/B knob)
     int minsum_rec = 1;       // min-sum on the tile kernels: check pass writes per-row records + lane masks instead of messages (k_check_minsum_rec / k_var_rec); 0 = message form
 };
 
@@ -194,7 +191,7 @@ struct scaldpc_bp : HandleStreams {
     Buf<ulonglong2> d_mask;
     int cap_rec_group = 0;
     int *d_csc_row = nullptr, *d_var_rows = nullptr, *d_csr_pos = nullptr;  // views into d_tile_tab
-    bool var_reversed = false;  // the column records are laid out heaviest first (var_order bit 1): the degree-1 bucket is at the END
+    bool var_reversed = false;  // the column records are laid out heaviest first (column order 2): the degree-1 bucket is at the END
     bool first_valid = false;
     int first_method = -1;
     float first_alpha = 0.0f;
@@ -236,12 +233,9 @@ bool set_knob(Knobs &k, const char *key, const char *val)
     if (!strcmp(key, "split")) k.split = (int)x;
     else if (!strcmp(key, "group_mb")) k.group_mb = x;
     else if (!strcmp(key, "el_max")) k.el_max = (int)x;
-    else if (!strcmp(key, "el_fuse")) k.el_fuse = (int)x != 0;
     else if (!strcmp(key, "compact_after")) k.compact_after = (int)x;
-    else if (!strcmp(key, "var_order")) k.var_order = (int)x;
     else if (!strcmp(key, "first_fused")) k.first_fused = (int)x != 0;
     else if (!strcmp(key, "minsum_rec")) k.minsum_rec = (int)x != 0;
-    else if (!strcmp(key, "rec_skip1")) k.rec_skip1 = (int)x != 0;
     else if (!strcmp(key, "fuse_test")) k.fuse_test = (int)x != 0;
     else return false;
     return true;
@@ -251,10 +245,8 @@ void knobs_from_env(Knobs &k)
 {
     static const char *const names[][2] = {{"SCALDPC_PATH", "path"}, {"SCALDPC_SPLIT", "split"},
                                            {"SCALDPC_GROUP_MB", "group_mb"}, {"SCALDPC_EL_MAX", "el_max"},
-                                           {"SCALDPC_EL_FUSE", "el_fuse"}, {"SCALDPC_COMPACT_AFTER", "compact_after"},
-                                           {"SCALDPC_VAR_ORDER", "var_order"}, {"SCALDPC_FIRST_FUSED", "first_fused"},
-                                           {"SCALDPC_FUSE_TEST", "fuse_test"}, {"SCALDPC_MINSUM_REC", "minsum_rec"},
-                                           {"SCALDPC_REC_SKIP1", "rec_skip1"}};
+                                           {"SCALDPC_COMPACT_AFTER", "compact_after"}, {"SCALDPC_FIRST_FUSED", "first_fused"},
+                                           {"SCALDPC_FUSE_TEST", "fuse_test"}, {"SCALDPC_MINSUM_REC", "minsum_rec"}};
     for (auto &nm : names)
         if (const char *e = getenv(nm[0])) (void)set_knob(k, nm[1], e);
 }
@@ -315,8 +307,10 @@ int auto_group(const scaldpc_bp *h, int T)
     return std::max(1, std::min(g, T));
 }
 
-// waves per tile of a k_parity launch = words per tile of the unsat arrays
-int parity_waves(const scaldpc_bp *h) { return (h->m + 4 * ROWS_PER_WAVE - 1) / (4 * ROWS_PER_WAVE) * 4; }
+// blocks per tile of a k_parity / k_parity_fin launch over m rows: 4 waves of ROWS_PER_WAVE rows each
+int parity_blocks(int m) { return (m + 4 * ROWS_PER_WAVE - 1) / (4 * ROWS_PER_WAVE); }
+// waves per tile of such a launch = words per tile of the unsat arrays
+int parity_waves(const scaldpc_bp *h) { return 4 * parity_blocks(h->m); }
 
 constexpr int REM_SLOTS = 512;
 
@@ -329,7 +323,7 @@ int ensure_workspace(scaldpc_bp *h, int T, int G, bool want_post, int max_iter)
         h->cap_tiles = 0;
         // a growing graph gets planes with room for the rows / columns still to come
         const int wm = h->incremental ? h->m + h->m / 2 + 64 : h->m, wn = h->incremental ? h->n + h->n / 2 + 64 : h->n;
-        const size_t pw = (size_t)(wm + 4 * ROWS_PER_WAVE - 1) / (4 * ROWS_PER_WAVE) * 4;
+        const size_t pw = (size_t)4 * parity_blocks(wm);
         SC_TRY(h->d_synd.ensure((size_t)T * wm));
         SC_TRY(h->d_recv.ensure((size_t)T * wn));
         SC_TRY(h->d_hard.ensure((size_t)T * wn));
@@ -439,19 +433,19 @@ int ensure_tile_tables(scaldpc_bp *h)
     for (int r = 0; r < h->m; r++)
         for (int e = row_ptr[r]; e < row_ptr[r + 1]; e++) edge_row[e] = r;
     // launch order of the columns: the bucket lists are sorted by degree, ascending column id inside a
-    // degree.  var_order = 1 re-sorts each run of equal degree by the column's FIRST edge id, so that
+    // degree.  Order bit 0 re-sorts each run of equal degree by the column's FIRST edge id, so that
     // neighbouring waves of a launch start their gathers in neighbouring rows of the message array
     // (the records carry the column id, so the order is free; results cannot depend on it).
     pvec<int> order_buf;
     const int *vlist = hv.list.data();
-    // auto: a tile group that runs as ONE stream lane (a tile too large to share the cache with a second one:
-    // the HQC-256 graph) has nothing to fill the tail of its launches with, so its heaviest columns go first
+    // A tile group that runs as ONE stream lane (a tile too large to share the cache with a second one:
+    // the HQC-256 graph) has nothing to fill the tail of its launches with, so its heaviest columns go first (bit 1)
     // (measured 321.5 -> 315.5 ms per step, k_var 51.5 -> 49.9 us); with two lanes the other lane's kernel
     // lives in that tail and the same order costs 0.8 % (HQC-128: 95.2 -> 96.0 ms): there the columns of a
     // degree are ordered by their first edge instead (profiles/r02/ab_*order*.json)
     const bool single_lane = auto_group(h, 1 << 20) < 2 || h->kn.split < 2;
-    const int var_order = h->kn.var_order >= 0 ? h->kn.var_order : (single_lane ? 2 : 1);
-    if ((var_order & 1) && !hv.list.empty()) {
+    const int order = single_lane ? 2 : 1;
+    if ((order & 1) && !hv.list.empty()) {
         order_buf = hv.list;
         size_t i = 0;
         while (i < order_buf.size()) {
@@ -490,8 +484,8 @@ int ensure_tile_tables(scaldpc_bp *h)
             pos += d;
         }
     }
-    h->var_reversed = (var_order & 2) != 0;
-    if (var_order & 2) {
+    h->var_reversed = (order & 2) != 0;
+    if (order & 2) {
         // heaviest columns FIRST: the waves that start last are then the cheapest ones (degree-1 identity
         // columns), which shortens the tail of the launch (longest-processing-time-first)
         const size_t nrec = (size_t)4 * hv.bk.blk[hv.bk.nb];
@@ -654,6 +648,32 @@ int el_limit(const scaldpc_bp *h, int method)
 
 #define LAUNCH_CHECK() SC_HIP(hipGetLastError())
 
+// Compile-time dispatch of the launches.  with_cap<16, 32, 64>(deg, f) calls f(std::integral_constant<int, CAP>) with the
+// first CAP of the ladder that holds a node degree `deg` (the last CAP takes anything wider: the kernels' any-degree
+// fallback); every kernel is instantiated for exactly the ladder its launch names.  with_bool / with_method hand f a
+// runtime bool / update rule as a compile-time one.
+template <int CAP, int... WIDER, typename F>
+void with_cap(int deg, F &&f)
+{
+    if constexpr (sizeof...(WIDER) == 0)
+        f(std::integral_constant<int, CAP>{});
+    else if (deg <= CAP)
+        f(std::integral_constant<int, CAP>{});
+    else
+        with_cap<WIDER...>(deg, f);
+}
+template <typename F>
+void with_bool(bool b, F &&f)
+{
+    if (b) f(std::true_type{}); else f(std::false_type{});
+}
+template <typename F>
+void with_method(int method, F &&f)
+{
+    if (method == SCALDPC_BP_MIN_SUM) f(std::integral_constant<int, SCALDPC_BP_MIN_SUM>{});
+    else f(std::integral_constant<int, SCALDPC_BP_PRODUCT_SUM>{});
+}
+
 // No message initialisation pass: the first check update reads the priors (v2c = prior of the
 // edge's column by definition).  The tanh rule's any-degree fallback (rows wider than 64) keeps it.
 bool fused_init(const scaldpc_bp *h, int method)
@@ -677,76 +697,47 @@ int launch_check(scaldpc_bp *h, int method, float alpha, int G, const u64 *synd_
     if (h->E == 0) return 0;
     float *const msg0 = h->d_msg + (size_t)tile0 * h->E * TW;  // tile0: first tile of a sub-group inside the group's array
     float *const scr0 = h->d_scratch ? h->d_scratch + (size_t)tile0 * h->E * TW : nullptr;
-    if (method == SCALDPC_BP_MIN_SUM) {
-        dim3 grid((h->m + 3) / 4, G);
-#define MS_LAUNCH(F)                                                                                                 \
-    hipLaunchKernelGGL((k_check_minsum<F>), grid, dim3(256), 0, s, h->d_row_ptr, msg0, synd_g, done_g, skip_done, \
-                       h->m, h->E, alpha, h->d_col_idx, h->d_prior)
+    const dim3 grid(h->row_bk.blk[h->row_bk.nb], G), block(256);  // one wave per row descriptor
+    const bool test = ft && !first;
+    if (method != SCALDPC_BP_MIN_SUM) {
+        with_cap<16, 32, 64>(h->max_row_deg, [&](auto cap) {
+            if (test)
+                hipLaunchKernelGGL((k_check_tanh<cap, false, true>), grid, block, 0, s, h->row_bk, h->d_row_list, h->d_row_ptr,
+                                   msg0, scr0, synd_g, done_g, skip_done, h->m, h->E, h->d_col_idx, h->d_prior, *ft);
+            else
+                with_bool(first, [&](auto fst) {
+                    hipLaunchKernelGGL((k_check_tanh<cap, fst>), grid, block, 0, s, h->row_bk, h->d_row_list, h->d_row_ptr, msg0,
+                                       scr0, synd_g, done_g, skip_done, h->m, h->E, h->d_col_idx, h->d_prior);
+                });
+        });
+    } else if (rec_form(h, method) && !first) {
         // (a first check pass -- iteration 1 with first_fused off -- reads the priors and writes MESSAGES: the message
         // form's kernel, followed by the message form's variable pass; the records start with iteration 2)
-        if (rec_form(h, method) && !first) {
-            dim3 gridx(h->row_bk.blk[h->row_bk.nb], G);
-            float *const rec0 = h->d_rec + (size_t)tile0 * h->m * 2 * TW;
-            ulonglong2 *const mask0 = h->d_mask + (size_t)tile0 * h->E;
-#define MSR_LAUNCH(CAP)                                                                                             \
-    hipLaunchKernelGGL((k_check_minsum_rec<CAP>), gridx, dim3(256), 0, s, h->d_row_list, msg0, synd_g, done_g, skip_done, \
-                       h->m, h->E, alpha, h->d_col_idx, rec0, mask0, h->d_csr_pos)
-#define MSR_PAR(CAP)                                                                                                \
-    hipLaunchKernelGGL((k_check_minsum_rec<CAP, true>), gridx, dim3(256), 0, s, h->d_row_list, msg0, synd_g, done_g, \
-                       skip_done, h->m, h->E, alpha, h->d_col_idx, rec0, mask0, h->d_csr_pos, *ft)
-            if (ft) {
-                if (h->max_row_deg <= 16) MSR_PAR(16); else if (h->max_row_deg <= 32) MSR_PAR(32); else MSR_PAR(64);
-            } else if (h->max_row_deg <= 16) {
-                MSR_LAUNCH(16);
-            } else if (h->max_row_deg <= 32) {
-                MSR_LAUNCH(32);
-            } else {
-                MSR_LAUNCH(64);
-            }
-#undef MSR_PAR
-#undef MSR_LAUNCH
-        } else if (h->max_row_deg <= ROW_CAP) {
-            dim3 gridx(h->row_bk.blk[h->row_bk.nb], G);
-#define MSX_LAUNCH(CAP, F)                                                                                          \
-    hipLaunchKernelGGL((k_check_minsum_x<CAP, F>), gridx, dim3(256), 0, s, h->d_row_list, msg0, synd_g, done_g, skip_done, \
-                       h->m, h->E, alpha, h->d_col_idx, h->d_prior)
-#define MSX_PAR(CAP)                                                                                                \
-    hipLaunchKernelGGL((k_check_minsum_x<CAP, false, true>), gridx, dim3(256), 0, s, h->d_row_list, msg0, synd_g, done_g,  \
-                       skip_done, h->m, h->E, alpha, h->d_col_idx, h->d_prior, *ft)
-            if (ft && !first) {
-                if (h->max_row_deg <= 16) MSX_PAR(16); else if (h->max_row_deg <= 32) MSX_PAR(32); else MSX_PAR(64);
-            } else if (h->max_row_deg <= 16) {
-                if (first) MSX_LAUNCH(16, true); else MSX_LAUNCH(16, false);
-            } else if (h->max_row_deg <= 32) {
-                if (first) MSX_LAUNCH(32, true); else MSX_LAUNCH(32, false);
-            } else {
-                if (first) MSX_LAUNCH(64, true); else MSX_LAUNCH(64, false);
-            }
-#undef MSX_PAR
-#undef MSX_LAUNCH
-        } else {  // a row wider than 64: the loop form
-            if (first) MS_LAUNCH(true); else MS_LAUNCH(false);
-        }
-#undef MS_LAUNCH
-    } else {
-        dim3 grid(h->row_bk.blk[h->row_bk.nb], G);
-#define TANH_LAUNCH(CAP, F)                                                                                         \
-    hipLaunchKernelGGL((k_check_tanh<CAP, F>), grid, dim3(256), 0, s, h->row_bk, h->d_row_list, h->d_row_ptr, msg0, \
-                       scr0, synd_g, done_g, skip_done, h->m, h->E, h->d_col_idx, h->d_prior)
-#define TANH_PAR(CAP)                                                                                               \
-    hipLaunchKernelGGL((k_check_tanh<CAP, false, true>), grid, dim3(256), 0, s, h->row_bk, h->d_row_list, h->d_row_ptr, msg0, \
-                       scr0, synd_g, done_g, skip_done, h->m, h->E, h->d_col_idx, h->d_prior, *ft)
-        if (ft && !first) {
-            if (h->max_row_deg <= 16) TANH_PAR(16); else if (h->max_row_deg <= 32) TANH_PAR(32); else TANH_PAR(64);
-        } else if (h->max_row_deg <= 16) {
-            if (first) TANH_LAUNCH(16, true); else TANH_LAUNCH(16, false);
-        } else if (h->max_row_deg <= 32) {
-            if (first) TANH_LAUNCH(32, true); else TANH_LAUNCH(32, false);
-        } else {
-            if (first) TANH_LAUNCH(64, true); else TANH_LAUNCH(64, false);
-        }
-#undef TANH_PAR
-#undef TANH_LAUNCH
+        float *const rec0 = h->d_rec + (size_t)tile0 * h->m * 2 * TW;
+        ulonglong2 *const mask0 = h->d_mask + (size_t)tile0 * h->E;
+        const FusedTest ft0 = test ? *ft : FusedTest{};
+        with_cap<16, 32, 64>(h->max_row_deg, [&](auto cap) {
+            with_bool(test, [&](auto par) {
+                hipLaunchKernelGGL((k_check_minsum_rec<cap, par>), grid, block, 0, s, h->d_row_list, msg0, synd_g, done_g,
+                                   skip_done, h->m, h->E, alpha, h->d_col_idx, rec0, mask0, h->d_csr_pos, ft0);
+            });
+        });
+    } else if (h->max_row_deg <= ROW_CAP) {
+        with_cap<16, 32, 64>(h->max_row_deg, [&](auto cap) {
+            if (test)
+                hipLaunchKernelGGL((k_check_minsum_x<cap, false, true>), grid, block, 0, s, h->d_row_list, msg0, synd_g, done_g,
+                                   skip_done, h->m, h->E, alpha, h->d_col_idx, h->d_prior, *ft);
+            else
+                with_bool(first, [&](auto fst) {
+                    hipLaunchKernelGGL((k_check_minsum_x<cap, fst>), grid, block, 0, s, h->d_row_list, msg0, synd_g, done_g,
+                                       skip_done, h->m, h->E, alpha, h->d_col_idx, h->d_prior);
+                });
+        });
+    } else {  // a row wider than 64: the loop form
+        with_bool(first, [&](auto fst) {
+            hipLaunchKernelGGL((k_check_minsum<fst>), dim3((h->m + 3) / 4, G), block, 0, s, h->d_row_ptr, msg0, synd_g, done_g,
+                               skip_done, h->m, h->E, alpha, h->d_col_idx, h->d_prior);
+        });
     }
     LAUNCH_CHECK();
     return 0;
@@ -766,6 +757,7 @@ bool first_fusable(const scaldpc_bp *h, int method)
 int ensure_first_table(scaldpc_bp *h, int method, float alpha1, hipStream_t s)
 {
     if (h->first_valid && h->first_method == method && h->first_alpha == alpha1) return 0;
+    h->first_valid = false;  // (until the new table is complete)
     SC_TRY(grow(h->d_first_tab, (size_t)h->E + 128));  // (a column's scalar loads may run past its last edge, as in the edge list)
     Buf<u64> zero;  // (declared first: released after tmp)
     Buf<float> tmp;
@@ -774,13 +766,10 @@ int ensure_first_table(scaldpc_bp *h, int method, float alpha1, hipStream_t s)
     hipError_t e = hipMemsetAsync(zero, 0, sizeof(u64) * ((size_t)h->m + 1), s);
     if (e == hipSuccess) e = hipMemsetAsync(h->d_first_tab, 0, sizeof(int2) * h->d_first_tab.cap(), s);
     if (e == hipSuccess) {
-        dim3 grid((h->m + 3) / 4, 1);
-        if (method == SCALDPC_BP_MIN_SUM)
-            hipLaunchKernelGGL((k_el_check<SCALDPC_BP_MIN_SUM, true>), grid, dim3(256), 0, s, h->d_row_ptr, h->d_col_idx, h->d_prior,
-                               tmp, zero, zero + h->m, 0, h->m, h->E, alpha1, (const u64 *)nullptr, (int *)nullptr);
-        else
-            hipLaunchKernelGGL((k_el_check<SCALDPC_BP_PRODUCT_SUM, true>), grid, dim3(256), 0, s, h->d_row_ptr, h->d_col_idx,
+        with_method(method, [&](auto M) {
+            hipLaunchKernelGGL((k_el_check<M, true>), dim3((h->m + 3) / 4, 1), dim3(256), 0, s, h->d_row_ptr, h->d_col_idx,
                                h->d_prior, tmp, zero, zero + h->m, 0, h->m, h->E, alpha1, (const u64 *)nullptr, (int *)nullptr);
+        });
         hipLaunchKernelGGL(k_first_tab, dim3((unsigned)((h->E + 255) / 256)), dim3(256), 0, s, h->d_csc_list, tmp, h->d_row_ptr, h->m,
                            h->E, h->d_first_tab);
         e = hipGetLastError();
@@ -797,56 +786,38 @@ int ensure_first_table(scaldpc_bp *h, int method, float alpha1, hipStream_t s)
 int launch_var(scaldpc_bp *h, int G, float *post_g, u64 *hard_g, const u64 *done_g, int skip_done, int write_out,
                hipStream_t s, int tile0 = 0, const u64 *first_synd = nullptr, bool rec = false, bool light = false)
 {
-    dim3 grid(h->var_bk.blk[h->var_bk.nb], G);
     float *const msg0 = h->d_msg + (size_t)tile0 * h->E * TW;
     float *const scr0 = h->d_scratch ? h->d_scratch + (size_t)tile0 * h->E * TW : nullptr;
+    const int nblk = h->var_bk.blk[h->var_bk.nb];
     if (first_synd) {
-        const int nrec = 4 * h->var_bk.blk[h->var_bk.nb];  // one record per wave of a plain k_var launch; two per wave here
+        const int nrec = 4 * nblk;  // one record per wave of a plain k_var launch; two per wave here
         const dim3 grid2((unsigned)((nrec + 7) / 8), G);
-#define VAR_FIRST(CAP)                                                                                              \
-    hipLaunchKernelGGL((k_var_first<CAP>), grid2, dim3(256), 0, s, h->d_var_meta, h->d_csc_list, h->d_prior, msg0, post_g,  \
-                       hard_g, done_g, skip_done, h->n, h->E, write_out, (const int2 *)h->d_first_tab, first_synd, h->m, nrec)
-        if (h->max_col_deg <= 16)
-            VAR_FIRST(16);
-        else if (h->max_col_deg <= 32)
-            VAR_FIRST(32);
-        else
-            VAR_FIRST(64);
-#undef VAR_FIRST
-        LAUNCH_CHECK();
-        return 0;
-    }
-    if (rec) {  // the check pass left records, not messages (rec_form)
+        with_cap<16, 32, 64>(h->max_col_deg, [&](auto cap) {
+            hipLaunchKernelGGL((k_var_first<cap>), grid2, dim3(256), 0, s, h->d_var_meta, h->d_csc_list, h->d_prior, msg0, post_g,
+                               hard_g, done_g, skip_done, h->n, h->E, write_out, (const int2 *)h->d_first_tab, first_synd, h->m, nrec);
+        });
+    } else if (rec) {  // the check pass left records, not messages (rec_form)
         // light: a pass without output after iteration 1.  A column of degree <= 1 always sends its prior; iteration 1
         // has written that into the message array and the record check pass never overwrites it, so such a pass has
         // nothing to do for the first bucket (the identity block of an HQC graph: 4000 of 21669 column waves per tile).
-        const int nblk = h->var_bk.blk[h->var_bk.nb];
         const int n1 = (h->var_bk.nb > 0 && h->var_bk.maxd[0] == 1) ? h->var_bk.blk[1] : 0;
-        const bool slim = light && !write_out && h->kn.rec_skip1 && n1 > 0 && n1 < nblk;
+        const bool slim = light && !write_out && n1 > 0 && n1 < nblk;
         const int nb_launch = slim ? nblk - n1 : nblk;
         // XCD-aware tile placement where the launch's tiles divide the 8 XCDs (fetch 38.0 -> 29.5 MB per launch, profiles/r03/ab_rec_xmap.log)
         const bool xm = G == 2 || G == 4 || G == 8;
         const dim3 gridr((unsigned)(xm ? (nb_launch + 7) / 8 * 8 : nb_launch), G);
         const int blk0 = slim && !h->var_reversed ? n1 : 0, xmap = xm ? nb_launch : 0;
-#define VAR_REC_LAUNCH(CAP)                                                                                         \
-    hipLaunchKernelGGL((k_var_rec<CAP>), gridr, dim3(256), 0, s, h->d_var_meta, h->d_var_rows, h->d_csc_list, h->d_csc_row, \
-                       h->d_prior, msg0, h->d_rec + (size_t)tile0 * h->m * 2 * TW, h->d_mask + (size_t)tile0 * h->E, post_g,  \
-                       hard_g, done_g, skip_done, h->n, h->m, h->E, write_out, blk0, xmap)
-        if (h->max_col_deg <= 16) VAR_REC_LAUNCH(16); else VAR_REC_LAUNCH(32);
-#undef VAR_REC_LAUNCH
-        LAUNCH_CHECK();
-        return 0;
+        with_cap<16, 32>(h->max_col_deg, [&](auto cap) {  // (columns wider than 32 take the message form: rec_form)
+            hipLaunchKernelGGL((k_var_rec<cap>), gridr, dim3(256), 0, s, h->d_var_meta, h->d_var_rows, h->d_csc_list, h->d_csc_row,
+                               h->d_prior, msg0, h->d_rec + (size_t)tile0 * h->m * 2 * TW, h->d_mask + (size_t)tile0 * h->E,
+                               post_g, hard_g, done_g, skip_done, h->n, h->m, h->E, write_out, blk0, xmap);
+        });
+    } else {
+        with_cap<16, 32, 64>(h->max_col_deg, [&](auto cap) {
+            hipLaunchKernelGGL((k_var<cap>), dim3(nblk, G), dim3(256), 0, s, h->var_bk, h->d_var_meta, h->d_col_ptr, h->d_csc_list,
+                               h->d_prior, msg0, scr0, post_g, hard_g, done_g, skip_done, h->n, h->E, write_out);
+        });
     }
-#define VAR_LAUNCH(CAP)                                                                                             \
-    hipLaunchKernelGGL((k_var<CAP>), grid, dim3(256), 0, s, h->var_bk, h->d_var_meta, h->d_col_ptr, h->d_csc_list, \
-                       h->d_prior, msg0, scr0, post_g, hard_g, done_g, skip_done, h->n, h->E, write_out)
-    if (h->max_col_deg <= 16)
-        VAR_LAUNCH(16);
-    else if (h->max_col_deg <= 32)
-        VAR_LAUNCH(32);
-    else
-        VAR_LAUNCH(64);
-#undef VAR_LAUNCH
     LAUNCH_CHECK();
     return 0;
 }
@@ -854,16 +825,12 @@ int launch_var(scaldpc_bp *h, int G, float *post_g, u64 *hard_g, const u64 *done
 int launch_el_check(scaldpc_bp *h, int method, float alpha, int nb, const u64 *synd_g, const u64 *done_g,
                     int skip_done, hipStream_t s, bool first, const u64 *hard_g = nullptr, int *unsat_prev = nullptr)
 {
-    dim3 grid((h->m + 3) / 4, nb);
-#define EL_LAUNCH(M, F)                                                                                             \
-    hipLaunchKernelGGL((k_el_check<M, F>), grid, dim3(256), 0, s, h->d_row_ptr, h->d_col_idx, h->d_prior, h->d_emsg,  \
-                       synd_g, done_g, skip_done, h->m, h->E, alpha, hard_g, unsat_prev)
-    if (method == SCALDPC_BP_MIN_SUM) {
-        if (first) EL_LAUNCH(SCALDPC_BP_MIN_SUM, true); else EL_LAUNCH(SCALDPC_BP_MIN_SUM, false);
-    } else {
-        if (first) EL_LAUNCH(SCALDPC_BP_PRODUCT_SUM, true); else EL_LAUNCH(SCALDPC_BP_PRODUCT_SUM, false);
-    }
-#undef EL_LAUNCH
+    with_method(method, [&](auto M) {
+        with_bool(first, [&](auto fst) {
+            hipLaunchKernelGGL((k_el_check<M, fst>), dim3((h->m + 3) / 4, nb), dim3(256), 0, s, h->d_row_ptr, h->d_col_idx,
+                               h->d_prior, h->d_emsg, synd_g, done_g, skip_done, h->m, h->E, alpha, hard_g, unsat_prev);
+        });
+    });
     LAUNCH_CHECK();
     return 0;
 }
@@ -882,6 +849,40 @@ int launch_el_var(scaldpc_bp *h, int nb, float *post_g, u64 *hard_g, u64 *done_g
     return 0;
 }
 
+// syndrome planes of T tiles: synd = H x (k_parity without the convergence test)
+int launch_syndrome(const scaldpc_bp *h, const u64 *x, u64 *synd, int T, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_parity<false>, dim3(parity_blocks(h->m), T), dim3(256), 0, s, h->d_row_ptr, h->d_col_idx, x, h->m, h->n,
+                       synd, (u64 *)nullptr, (const u64 *)nullptr);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// The LDS-resident single-launch decoder (k_bp_small): LDS bytes of a launch on this graph ...
+size_t small_lds_bytes(const scaldpc_bp *h) { return (size_t)2 * h->E * sizeof(float) + (size_t)2 * h->n + h->m + 64; }
+// ... and whether a call takes it: those bytes, or 0 = another path (the graph does not fit, or "stream" / "edge" pin one)
+size_t small_lds(const scaldpc_bp *h)
+{
+    const size_t lds = small_lds_bytes(h);
+    const bool fits = h->E > 0 && lds <= 60 * 1024;
+    return fits && h->kn.path != Knobs::STREAM && h->kn.path != Knobs::EDGE ? lds : 0;
+}
+
+// k_bp_small over `batch` codewords, one workgroup each.  PLANES: input syndromes and outputs are the tile path's bit
+// planes (Monte-Carlo entry points); else bytes per codeword in the caller's layout.
+template <bool PLANES>
+int launch_small(scaldpc_bp *h, size_t lds, int method, int batch, const void *in, int input_kind, int max_iter, float alpha,
+                 bool early, void *bits, float *llr, int *iters, void *conv, hipStream_t s)
+{
+    with_method(method, [&](auto M) {
+        hipLaunchKernelGGL((k_bp_small<M, PLANES>), dim3(batch), dim3(256), lds, s, h->d_row_ptr, h->d_col_idx, h->d_col_ptr,
+                           h->d_csc_edge, h->d_prior, h->m, h->n, (int)h->E, in, input_kind, max_iter, alpha, early ? 1 : 0,
+                           bits, llr, iters, conv);
+    });
+    LAUNCH_CHECK();
+    return 0;
+}
+
 float alpha_for(float alpha, int it)
 {
     // ms_scaling_factor == 0 -> 1 - 2^-iter
@@ -895,25 +896,22 @@ struct TileState {
     float *post;
 };
 
-// All iterations of the tile group [g0, g0+g) of `st`.  With defer_after > 0 the group
-// stops at the first poll point from that iteration on at which at most half of its
-// codewords are still running, and reports *deferred = true: those go to the compact pass.
-// Early-exit loop of the row-parallel path: two launches per iteration.  check(it) also tests
-// H e == s on the decisions of iteration it-1, var(it) latches the codewords that passed
-// (frozen at it-1) before it updates the others; the last iteration is followed by the
-// ordinary k_parity / k_finalize pair.  The host looks at "still running after it-1" one
-// iteration late, so a finished call enqueues one iteration of (skipped) launches more than
-// the four-launch form -- and half as many overall.
 int ensure_el_unsat(scaldpc_bp *h, int max_iter) { return h->d_el_unsat.ensure(((size_t)max_iter + 2) * TW); }
 
-int iterate_el_early(scaldpc_bp *h, int nb, int max_iter, int method, float alpha, const u64 *synd_g, u64 *hard_g,
-                     u64 *done_g, u64 *conv_g, u64 *unsat_g, int *iters_g, float *post_g, hipStream_t s)
+// All iterations of the row-parallel kernels on the nb codewords of `st` (ONE tile: a handful of codewords, el_limit),
+// two launches per iteration.  With early exit check(it) also tests H e == s on the decisions of iteration it-1, and
+// var(it) latches the codewords that passed (frozen at it-1) before it updates the others.  The last iteration is
+// followed by the ordinary k_parity / k_finalize pair (latching only with early exit).  The host looks at "still running
+// after it-1" one iteration late, so a finished call enqueues one iteration of (skipped) launches more than a loop with
+// the test as launches of its own -- and half as many launches overall.
+int iterate_el(scaldpc_bp *h, const TileState &st, int nb, int max_iter, int method, float alpha, bool early, hipStream_t s)
 {
-    const size_t flags = ((size_t)max_iter + 2) * TW;
-    SC_TRY(ensure_el_unsat(h, max_iter));
-    if (!h->small_prepared) {
-        SC_HIP(hipMemsetAsync(h->d_el_unsat, 0, sizeof(int) * flags, s));
-        SC_HIP(hipMemsetAsync(h->d_remaining, 0, sizeof(int) * ((size_t)max_iter + 2), s));
+    if (early) {
+        SC_TRY(ensure_el_unsat(h, max_iter));
+        if (!h->small_prepared) {  // (k_small_prepare has zeroed both)
+            SC_HIP(hipMemsetAsync(h->d_el_unsat, 0, sizeof(int) * ((size_t)max_iter + 2) * TW, s));
+            SC_HIP(hipMemsetAsync(h->d_remaining, 0, sizeof(int) * ((size_t)max_iter + 2), s));
+        }
     }
     const bool fused = fused_init(h, method);
     if (!fused) {
@@ -922,16 +920,21 @@ int iterate_el_early(scaldpc_bp *h, int nb, int max_iter, int method, float alph
         LAUNCH_CHECK();
     }
     for (int it = 1; it <= max_iter; it++) {
-        int *up = it > 1 ? h->d_el_unsat + (size_t)(it - 1) * TW : nullptr;
-        SC_TRY(launch_el_check(h, method, alpha_for(alpha, it), nb, synd_g, done_g, 1, s, fused && it == 1, hard_g, up));
-        SC_TRY(launch_el_var(h, nb, post_g, hard_g, done_g, 1, 1, s, up, it - 1, conv_g, iters_g, h->d_remaining + it - 1));
-        if (it == max_iter) {
-            hipLaunchKernelGGL(k_parity<true>, dim3((h->m + 4 * ROWS_PER_WAVE - 1) / (4 * ROWS_PER_WAVE), 1), dim3(256), 0,
-                               s, h->d_row_ptr, h->d_col_idx, hard_g, h->m, h->n, const_cast<u64 *>(synd_g), unsat_g,
-                               (const u64 *)done_g);
+        const bool last = it == max_iter, first = fused && it == 1;
+        if (early) {
+            int *const up = it > 1 ? h->d_el_unsat + (size_t)(it - 1) * TW : nullptr;  // verdicts on iteration it - 1
+            SC_TRY(launch_el_check(h, method, alpha_for(alpha, it), nb, st.synd, st.done, 1, s, first, st.hard, up));
+            SC_TRY(launch_el_var(h, nb, st.post, st.hard, st.done, 1, 1, s, up, it - 1, st.conv, st.iters, h->d_remaining + it - 1));
+        } else {
+            SC_TRY(launch_el_check(h, method, alpha_for(alpha, it), nb, st.synd, st.done, 0, s, first));
+            SC_TRY(launch_el_var(h, nb, st.post, st.hard, st.done, 0, last ? 1 : 0, s));
+        }
+        if (last) {
+            hipLaunchKernelGGL(k_parity<true>, dim3(parity_blocks(h->m), 1), dim3(256), 0, s, h->d_row_ptr, h->d_col_idx, st.hard,
+                               h->m, h->n, const_cast<u64 *>(st.synd), st.unsat, (const u64 *)st.done);
             LAUNCH_CHECK();
-            hipLaunchKernelGGL(k_finalize, dim3(1), dim3(64), 0, s, it, 1, done_g, conv_g, unsat_g, parity_waves(h), iters_g,
-                               h->d_remaining + it);
+            hipLaunchKernelGGL(k_finalize, dim3(1), dim3(64), 0, s, it, early ? 1 : 0, st.done, st.conv, st.unsat, parity_waves(h),
+                               st.iters, h->d_remaining + it);
             LAUNCH_CHECK();
             break;
         }
@@ -941,7 +944,7 @@ int iterate_el_early(scaldpc_bp *h, int nb, int max_iter, int method, float alph
         // Graphs that come here are too large for LDS: a decode that converges does so in 3-5 iterations (the
         // attack loop once enough checks are in; measured 3-4 on the HQC-128 graph), one that does not runs to
         // max_iter.  Poll densely where convergence is likely, sparsely afterwards.
-        if ((ip >= 3 && ip <= 6) || (ip > 6 && ip <= 16 && ip % 2 == 0) || (ip > 16 && ip % 16 == 0)) {
+        if (early && ((ip >= 3 && ip <= 6) || (ip > 6 && ip <= 16 && ip % 2 == 0) || (ip > 16 && ip % 16 == 0))) {
             SC_HIP(hipMemcpyAsync(h->h_remaining + ip, h->d_remaining + ip, sizeof(int), hipMemcpyDeviceToHost, s));
             SC_HIP(hipStreamSynchronize(s));
             if (h->h_remaining[ip] == 0) break;
@@ -977,6 +980,49 @@ int ensure_lanes(scaldpc_bp *h, int nl)
     if (nl > 1 && !h->ev_join[0]) SC_HIP(hipEventCreateWithFlags(&h->ev_join[0], hipEventDisableTiming));  // [0]: the fork event
     return 0;
 }
+// a group of g tiles dealt to nl lanes: lane k takes the gs[k] tiles from t0[k] on, the first g % nl lanes one more
+void deal_tiles(int g, int nl, int *gs, int *t0)
+{
+    for (int k = 0, t = 0; k < nl; k++) {
+        gs[k] = g / nl + (k < g % nl ? 1 : 0);
+        t0[k] = t;
+        t += gs[k];
+    }
+}
+// The lanes of a call: lane 0 is the call's stream, lanes 1.. the handle's further streams.  fork() starts them behind
+// everything enqueued on the call's stream so far, join() orders everything enqueued on them before it.  Lanes left open
+// -- by a group the next one continues, or by an error return -- are joined when the scope ends.  So, held by decode_level:
+// when decode_level returns, successfully or with an error, all work on the lanes is ordered before the call's stream.
+struct Lanes {
+    scaldpc_bp *h;
+    hipStream_t s;
+    int n = 1;          // lanes in use
+    bool open = false;  // lanes 1.. may hold work that is not ordered before s yet
+    Lanes(scaldpc_bp *h_, hipStream_t s_) : h(h_), s(s_) {}
+    Lanes(const Lanes &) = delete;
+    Lanes &operator=(const Lanes &) = delete;
+    ~Lanes() { if (open) (void)join(); }
+    hipStream_t operator[](int k) const { return k ? h->aux_stream[k] : s; }
+    int fork(int nl)  // (ensure_lanes(h, nl) first)
+    {
+        n = nl;
+        open = nl > 1;
+        if (!open) return 0;
+        SC_HIP(hipEventRecord(h->ev_join[0], s));
+        for (int k = 1; k < n; k++) SC_HIP(hipStreamWaitEvent(h->aux_stream[k], h->ev_join[0], 0));
+        return 0;
+    }
+    int join()
+    {
+        for (int k = 1; k < n; k++) {
+            SC_HIP(hipEventRecord(h->ev_join[k], h->aux_stream[k]));
+            SC_HIP(hipStreamWaitEvent(s, h->ev_join[k], 0));
+        }
+        open = false;
+        return 0;
+    }
+};
+
 // What the groups of one call learn from each other about polling (a poll drains the queue: the GPU idles
 // while the host turns around, ~4 % of a group's time on the config-5 sweep):
 //   hint   poll points before this iteration saw no codeword finish in earlier groups: skip them
@@ -986,31 +1032,49 @@ int ensure_lanes(scaldpc_bp *h, int nl)
 //          A group stopped on a wrong guess only sends more codewords to the compact pass, which decodes
 //          them from their inputs: results cannot change.
 constexpr int SPEC_PERIOD = 16;  // (64 and 4096 measured the same to 0.5 % on the config-5 sweep: the polls are not where its time goes)
+constexpr int POLL_EVERY = 4;
 struct PollState {
     int hint = 1, streak = 0, since_poll = 0;
 };
+// Is iteration `it` a poll point of an early-exit tile group?  Every POLL_EVERY-th iteration, the first and the hand-over
+// point, from the hint on.  (Decided before anything of the iteration is enqueued: these are the host's own sync points.)
+bool poll_point(int it, int defer_after, const PollState &ps)
+{
+    return (it % POLL_EVERY == 0 || it == 1 || it == defer_after) && it >= ps.hint;
+}
+// Does a group stop at the hand-over point `defer_after` UNSEEN, as the last groups did?
+bool stops_unseen(int defer_after, int max_iter, const PollState &ps)
+{
+    return defer_after > 0 && 2 * defer_after < max_iter && ps.streak >= 2 && ps.since_poll < SPEC_PERIOD - 1 &&
+           poll_point(defer_after, defer_after, ps);
+}
+// ... and does it get there without the host: no poll point before it is live?  (decode_level chains such groups)
+bool runs_unseen(int defer_after, int max_iter, const PollState &ps)
+{
+    if (!stops_unseen(defer_after, max_iter, ps)) return false;
+    for (int it = 1; it < defer_after; it++)
+        if (poll_point(it, defer_after, ps)) return false;
+    return true;
+}
 
-// chain: bit 0 = this group CONTINUES the lanes of the group before it (same geometry, fixed iterations): no fork -- a lane's
-//        work on the new group is ordered behind its own work on the previous one by its stream, and nothing else feeds it;
+// All iterations of the tile group [g0, g0+g) of `st`.  With defer_after > 0 the group stops at the first poll point from
+// that iteration on at which at most half of its codewords are still running, and reports *deferred = true: those go to
+// the compact pass.
+// chain: bit 0 = this group CONTINUES the lanes of the group before it (same geometry, no host in between): no fork -- a
+//        lane's work on the new group is ordered behind its own work on the previous one by its stream, and nothing else
+//        feeds it;
 //        bit 1 = the group after this one will continue them: no join at the end.  Without the per-group join / fork the lane
 //        that runs a kernel ahead flows straight into the next group instead of idling for the other lane's last pass (and
 //        the other lane for its first): ~75 us per group of 3.7 ms on the HQC-128 bench.
-int iterate_tiles(scaldpc_bp *h, const TileState &st, int g0, int g, int max_iter, int method, float alpha, bool early,
-                  int defer_after, hipStream_t s, bool *deferred, int real_codewords, PollState *ps, int chain = 0)
+int iterate_tiles(scaldpc_bp *h, Lanes &lanes, const TileState &st, int g0, int g, int max_iter, int method, float alpha,
+                  bool early, int defer_after, bool *deferred, int real_codewords, PollState &ps, int chain)
 {
-    int *const poll_hint = ps ? &ps->hint : nullptr;
-    const int poll_every = 4;
+    const hipStream_t s = lanes.s;
     const int skip = early ? 1 : 0;
     const int nl = fixed_lanes(h, g);
     SC_TRY(ensure_lanes(h, nl));
-    hipStream_t lane[MAX_LANES];
     int gs[MAX_LANES], t0[MAX_LANES];
-    for (int k = 0, t = 0; k < nl; k++) {
-        lane[k] = k ? h->aux_stream[k] : s;
-        gs[k] = g / nl + (k < g % nl ? 1 : 0);
-        t0[k] = t;
-        t += gs[k];
-    }
+    deal_tiles(g, nl, gs, t0);
     const int pw = parity_waves(h);
     const bool fused = fused_init(h, method);
     if (h->E && !fused) {
@@ -1022,17 +1086,7 @@ int iterate_tiles(scaldpc_bp *h, const TileState &st, int g0, int g, int max_ite
     if (early) SC_TRY(next_remaining_row(h, s, &rem));
     // (the accumulators / block counters of k_parity_fin and fused_commit are zeroed once per level, in decode_level,
     // and every launch leaves them zero)
-    if (nl > 1 && !(chain & 1)) {  // fork: the other lanes start after everything enqueued on `s` so far
-        SC_HIP(hipEventRecord(h->ev_join[0], s));
-        for (int k = 1; k < nl; k++) SC_HIP(hipStreamWaitEvent(lane[k], h->ev_join[0], 0));
-    }
-    auto join = [&]() -> int {
-        for (int k = 1; k < nl; k++) {
-            SC_HIP(hipEventRecord(h->ev_join[k], lane[k]));
-            SC_HIP(hipStreamWaitEvent(s, h->ev_join[k], 0));
-        }
-        return 0;
-    };
+    if (!(chain & 1)) SC_TRY(lanes.fork(nl));  // the other lanes start after everything enqueued on `s` so far
     // iteration 1 without its check pass: the first variable pass reads the first-message table and the syndrome planes
     const bool first_fuse = first_fusable(h, method);
     if (first_fuse) SC_TRY(ensure_first_table(h, method, alpha_for(alpha, 1), s));
@@ -1048,8 +1102,8 @@ int iterate_tiles(scaldpc_bp *h, const TileState &st, int g0, int g, int max_ite
     for (int it = 1; it <= max_iter; it++) {
         const bool last = it == max_iter;
         const bool no_check = first_fuse && it == 1;
-        // (decided before anything of this iteration is enqueued: the host's own sync points)
-        const bool poll = (it % poll_every == 0 || it == 1 || it == defer_after) && (!poll_hint || it >= *poll_hint);
+        const bool poll = poll_point(it, defer_after, ps);
+        lanes.open = nl > 1;  // (this iteration enqueues on them)
         for (int k = 0; k < nl && !no_check; k++) {
             const int ta = g0 + t0[k];
             FusedTest ft{};
@@ -1058,11 +1112,11 @@ int iterate_tiles(scaldpc_bp *h, const TileState &st, int g0, int g, int max_ite
                                st.iters + (size_t)ta * TW, rem + (it - 1), h->n, pw, it - 1, 1};
                 verdict_pending[k] = false;
             }
-            SC_TRY(launch_check(h, method, alpha_for(alpha, it), gs[k], st.synd + (size_t)ta * h->m, st.done + ta, skip, lane[k],
+            SC_TRY(launch_check(h, method, alpha_for(alpha, it), gs[k], st.synd + (size_t)ta * h->m, st.done + ta, skip, lanes[k],
                                 fused && it == 1, t0[k], ft.hard ? &ft : nullptr));
             if (set_phase && k + 1 < nl) {
-                SC_HIP(hipEventRecord(h->ev_phase[k + 1], lane[k]));
-                SC_HIP(hipStreamWaitEvent(lane[k + 1], h->ev_phase[k + 1], 0));
+                SC_HIP(hipEventRecord(h->ev_phase[k + 1], lanes[k]));
+                SC_HIP(hipStreamWaitEvent(lanes[k + 1], h->ev_phase[k + 1], 0));
             }
         }
         if (!no_check) set_phase = false;  // (a first iteration without check passes leaves the offset to the second)
@@ -1070,106 +1124,56 @@ int iterate_tiles(scaldpc_bp *h, const TileState &st, int g0, int g, int max_ite
             const int ta = g0 + t0[k];
             // (the record form starts with iteration 2: an iteration 1 that has a check pass ran it in the message form)
             SC_TRY(launch_var(h, gs[k], st.post ? st.post + (size_t)ta * h->n * TW : nullptr, st.hard + (size_t)ta * h->n,
-                              st.done + ta, skip, (early || last) ? 1 : 0, lane[k], t0[k],
+                              st.done + ta, skip, (early || last) ? 1 : 0, lanes[k], t0[k],
                               no_check ? st.synd + (size_t)ta * h->m : nullptr, it > 1 && rec_form(h, method), it > 1));
             if (ride && !last && !poll) {
                 verdict_pending[k] = true;  // the next check pass of this lane carries the test
             } else if (early || last) {  // convergence test + latch, one launch
-                hipStream_t ts = lane[k];
+                const dim3 grid(parity_blocks(h->m), gs[k]);
                 if (pw >= FT_WORDS && h->kn.fuse_test) {  // sharded accumulators / counters (fused_commit)
                     const FusedTest pf{st.hard + (size_t)ta * h->n, st.unsat + (size_t)ta * pw, st.done + ta, st.conv + ta,
                                        st.iters + (size_t)ta * TW, rem + it, h->n, pw, it, early ? 1 : 0};
-                    hipLaunchKernelGGL(k_parity_fin_sharded, dim3((h->m + 4 * ROWS_PER_WAVE - 1) / (4 * ROWS_PER_WAVE), gs[k]),
-                                       dim3(256), 0, ts, h->d_row_ptr, h->d_col_idx, h->m, st.synd + (size_t)ta * h->m, pf);
+                    hipLaunchKernelGGL(k_parity_fin_sharded, grid, dim3(256), 0, lanes[k], h->d_row_ptr, h->d_col_idx, h->m,
+                                       st.synd + (size_t)ta * h->m, pf);
                 } else
-                    hipLaunchKernelGGL(k_parity_fin, dim3((h->m + 4 * ROWS_PER_WAVE - 1) / (4 * ROWS_PER_WAVE), gs[k]), dim3(256), 0,
-                                       ts, h->d_row_ptr, h->d_col_idx, st.hard + (size_t)ta * h->n, h->m, h->n,
-                                       st.synd + (size_t)ta * h->m, st.unsat + (size_t)ta * pw, pw, it, early ? 1 : 0, st.done + ta,
-                                       st.conv + ta, st.iters + (size_t)ta * TW, rem + it);
+                    hipLaunchKernelGGL(k_parity_fin, grid, dim3(256), 0, lanes[k], h->d_row_ptr, h->d_col_idx,
+                                       st.hard + (size_t)ta * h->n, h->m, h->n, st.synd + (size_t)ta * h->m,
+                                       st.unsat + (size_t)ta * pw, pw, it, early ? 1 : 0, st.done + ta, st.conv + ta,
+                                       st.iters + (size_t)ta * TW, rem + it);
                 LAUNCH_CHECK();
             }
         }
+        if (!early || last || !poll) continue;
         // a poll drains the queue (the GPU idles while the host turns around): skip the poll
-        // points at which the call's earlier groups saw no codeword finish yet (`poll`, above)
-        if (early && !last && poll && ps && it == defer_after && defer_after > 0 && 2 * it < max_iter && ps->streak >= 2 &&
-            ps->since_poll < SPEC_PERIOD - 1) {
-            ps->since_poll++;  // stop here unseen, as the last groups did
+        // points at which the call's earlier groups saw no codeword finish yet (poll_point)
+        if (it == defer_after && stops_unseen(defer_after, max_iter, ps)) {
+            ps.since_poll++;  // stop here unseen, as the last groups did
             *deferred = true;
             if (chain & 2) return 0;  // (the next group stops unseen too and continues these lanes: no host in between)
-            return join();
+            return lanes.join();
         }
-        if (early && !last && poll) {
-            SC_TRY(join());
-            SC_HIP(hipMemcpyAsync(h->h_remaining + it, rem + it, sizeof(int), hipMemcpyDeviceToHost, s));
-            SC_HIP(hipStreamSynchronize(s));
-            set_phase = true;
-            const int rem = h->h_remaining[it];
-            if (rem == 0) return 0;
-            if (poll_hint && rem >= real_codewords) *poll_hint = std::max(*poll_hint, it + 1);
-            // from `defer_after` on, any poll point may hand the stragglers over, provided the
-            // restart (it iterations redone) is cheap next to what is still ahead
-            // ... and the stragglers really get cheaper: fewer tiles, or few enough for the
-            // row-parallel kernels
-            const bool shrinks = (rem + TW - 1) / TW < g || rem <= el_limit(h, method);
-            if (defer_after > 0 && it >= defer_after && 2 * it < max_iter && 2 * rem <= real_codewords && shrinks) {
-                if (ps) {
-                    ps->streak = (it == defer_after && 8 * rem <= real_codewords) ? ps->streak + 1 : 0;
-                    ps->since_poll = 0;
-                }
-                *deferred = true;
-                return 0;
-            }
-            if (ps && it >= defer_after) ps->streak = 0;
+        SC_TRY(lanes.join());
+        SC_HIP(hipMemcpyAsync(h->h_remaining + it, rem + it, sizeof(int), hipMemcpyDeviceToHost, s));
+        SC_HIP(hipStreamSynchronize(s));
+        set_phase = true;
+        const int left = h->h_remaining[it];
+        if (left == 0) return 0;
+        if (left >= real_codewords) ps.hint = std::max(ps.hint, it + 1);
+        // from `defer_after` on, any poll point may hand the stragglers over, provided the
+        // restart (it iterations redone) is cheap next to what is still ahead
+        // ... and the stragglers really get cheaper: fewer tiles, or few enough for the
+        // row-parallel kernels
+        const bool shrinks = (left + TW - 1) / TW < g || left <= el_limit(h, method);
+        if (defer_after > 0 && it >= defer_after && 2 * it < max_iter && 2 * left <= real_codewords && shrinks) {
+            ps.streak = (it == defer_after && 8 * left <= real_codewords) ? ps.streak + 1 : 0;
+            ps.since_poll = 0;
+            *deferred = true;
+            return 0;
         }
+        if (it >= defer_after) ps.streak = 0;
     }
     if (chain & 2) return 0;  // (the next group continues these lanes; the last one of the chain joins)
-    return join();
-}
-
-// el > 0: the group is ONE tile holding `el` codewords, decoded by the row-parallel kernels.
-int iterate_group(scaldpc_bp *h, const TileState &st, int g0, int g, int max_iter, int method, float alpha, bool early,
-                  int defer_after, hipStream_t s, bool *deferred, int el = 0, int real_codewords = 0,
-                  PollState *poll_hint = nullptr, int chain = 0)
-{
-    *deferred = false;
-    if (!el)
-        return iterate_tiles(h, st, g0, g, max_iter, method, alpha, early, defer_after, s, deferred, real_codewords, poll_hint, chain);
-    const int skip = early ? 1 : 0;
-    const u64 *synd_g = st.synd + (size_t)g0 * h->m;
-    u64 *hard_g = st.hard + (size_t)g0 * h->n;
-    u64 *done_g = st.done + g0, *conv_g = st.conv + g0, *unsat_g = st.unsat + (size_t)g0 * parity_waves(h);
-    int *iters_g = st.iters + (size_t)g0 * TW;
-    float *post_g = st.post ? st.post + (size_t)g0 * h->n * TW : nullptr;
-    if (early && h->kn.el_fuse)
-        return iterate_el_early(h, el, max_iter, method, alpha, synd_g, hard_g, done_g, conv_g, unsat_g, iters_g, post_g, s);
-    // row-parallel kernels, fixed iterations (or the four-launch early-exit form, SCALDPC_EL_FUSE=0)
-    const bool fused = fused_init(h, method);
-    if (h->E && !fused) {
-        hipLaunchKernelGGL(k_el_init, dim3((unsigned)((h->E + 255) / 256), el), dim3(256), 0, s, h->d_col_idx, h->d_prior,
-                           h->d_emsg, h->E);
-        LAUNCH_CHECK();
-    }
-    if (early) SC_HIP(hipMemsetAsync(h->d_remaining, 0, sizeof(int) * ((size_t)max_iter + 2), s));
-    for (int it = 1; it <= max_iter; it++) {
-        const bool last = it == max_iter;
-        SC_TRY(launch_el_check(h, method, alpha_for(alpha, it), el, synd_g, done_g, skip, s, fused && it == 1));
-        SC_TRY(launch_el_var(h, el, post_g, hard_g, done_g, skip, (early || last) ? 1 : 0, s));
-        if (early || last) {
-            hipLaunchKernelGGL(k_parity<true>, dim3((h->m + 4 * ROWS_PER_WAVE - 1) / (4 * ROWS_PER_WAVE), 1), dim3(256), 0, s,
-                               h->d_row_ptr, h->d_col_idx, hard_g, h->m, h->n, const_cast<u64 *>(synd_g), unsat_g,
-                               (const u64 *)done_g);
-            LAUNCH_CHECK();
-            hipLaunchKernelGGL(k_finalize, dim3(1), dim3(64), 0, s, it, early ? 1 : 0, done_g, conv_g, unsat_g, parity_waves(h),
-                               iters_g, h->d_remaining + it);
-            LAUNCH_CHECK();
-        }
-        if (early && !last && (it % 4 == 0 || it == 1)) {
-            SC_HIP(hipMemcpyAsync(h->h_remaining + it, h->d_remaining + it, sizeof(int), hipMemcpyDeviceToHost, s));
-            SC_HIP(hipStreamSynchronize(s));
-            if (h->h_remaining[it] == 0) break;
-        }
-    }
-    return 0;
+    return lanes.join();
 }
 
 // One compaction level: the `batch` codewords of `st` (T tiles), all iterations of one
@@ -1193,53 +1197,50 @@ int decode_level(scaldpc_bp *h, int lvl, const TileState &st, int batch, int T, 
         h->last_group = el ? 0 : Gl;
         h->last_early = early;
     }
-    if (el) h->stat_el = el;
     h->stat_levels = lvl;
+    if (el) {
+        h->stat_el = el;
+        return iterate_el(h, st, el, max_iter, method, alpha, early, s);
+    }
 
     int defer_after = 0;
-    if (early && !el && lvl < scaldpc_bp::MAX_LEVELS) {
+    if (early && lvl < scaldpc_bp::MAX_LEVELS) {
         defer_after = 4;  // measured on the config-5 sweep: 4-5 best (177k trials/s), 8: 156k, 12: 136k
         if (h->kn.compact_after >= 0) defer_after = h->kn.compact_after;
         if (max_iter <= 2 * defer_after) defer_after = 0;  // nothing to gain
     }
-    if (!el)  // accumulators and block counters of the convergence tests: zero once, every launch leaves them zero
-        SC_HIP(hipMemsetAsync(st.unsat, 0, sizeof(u64) * (size_t)T * parity_waves(h), s));
+    // accumulators and block counters of the convergence tests: zero once, every launch leaves them zero
+    SC_HIP(hipMemsetAsync(st.unsat, 0, sizeof(u64) * (size_t)T * parity_waves(h), s));
     std::vector<char> deferred_tile(T, 0);
     bool any = false;
-    PollState poll_hint;
+    PollState poll;
     // fixed-iteration runs chain consecutive groups of the same geometry lane by lane (iterate_tiles): no host interaction,
     // every pass of a lane depends only on that lane's previous pass over the same slice of the message array
     // (A/B on the HQC-128 bench, best of five runs each: 60.43 against 61.12 ms per step; tanh rule 94.5 against 95.0-95.4:
     // profiles/r04/ab_chain_groups.log)
-    const bool lanes2 = !el && fused_init(h, method) && fixed_lanes(h, Gl) > 1;
-    const bool chainable = !early && lanes2;
-    // Early-exit runs chain too where the host stays out: a group that will stop at the hand-over point UNSEEN (two groups in
-    // a row handed a small remainder over there, the real poll of every 16th group is not due, and no earlier poll point is
-    // live) enqueues its launches without ever synchronising -- iterate_tiles decides exactly this from the PollState it is
-    // handed, so it can be foretold here.
-    auto unseen = [&](const PollState &p) {
-        return early && lanes2 && defer_after > 0 && 2 * defer_after < max_iter && p.streak >= 2 && p.since_poll < SPEC_PERIOD - 1 && p.hint > 1 &&
-               p.hint <= defer_after;
-    };
-    bool open = false;  // the previous group left its lanes un-joined
+    const bool lanes2 = fused_init(h, method) && fixed_lanes(h, Gl) > 1;
+    // Early-exit runs chain too where the host stays out: a group that will stop at the hand-over point UNSEEN and polls
+    // nowhere before (runs_unseen, from the same PollState and rules iterate_tiles decides by) enqueues its launches
+    // without ever synchronising.
+    auto unseen = [&](const PollState &p) { return early && lanes2 && runs_unseen(defer_after, max_iter, p); };
+    Lanes lanes(h, s);
     for (int g0 = 0; g0 < T; g0 += Gl) {
         const int g = std::min(Gl, T - g0);
         const int real = std::min(batch - g0 * TW, g * TW);
         bool d = false;
         int chain = 0;
         const bool next_full = g0 + Gl < T && std::min(Gl, T - (g0 + Gl)) == Gl;
-        if (chainable && g == Gl) {
+        if (!early && lanes2 && g == Gl) {
             if (g0 > 0) chain |= 1;       // (the group before it was a full one too)
             if (next_full) chain |= 2;    // ... and so is the next
-        } else if (g == Gl && unseen(poll_hint)) {
-            PollState nxt = poll_hint;
+        } else if (g == Gl && unseen(poll)) {
+            PollState nxt = poll;
             nxt.since_poll++;
-            if (open) chain |= 1;
+            if (lanes.open) chain |= 1;  // (the group before it left them un-joined)
             // (the next group takes the next row of "still running" counters: no chaining across the wrap, which clears them all)
             if (next_full && unseen(nxt) && h->rem_slot + 2 < h->rem_rows) chain |= 2;
         }
-        open = (chain & 2) != 0;
-        SC_TRY(iterate_group(h, st, g0, g, max_iter, method, alpha, early, defer_after, s, &d, el, real, &poll_hint, chain));
+        SC_TRY(iterate_tiles(h, lanes, st, g0, g, max_iter, method, alpha, early, defer_after, &d, real, poll, chain));
         if (d) {
             any = true;
             for (int t = g0; t < g0 + g; t++) deferred_tile[t] = 1;
@@ -1321,23 +1322,9 @@ int run_core(scaldpc_bp *h, int batch, int T, int G, int max_iter, int method, f
     h->stat_levels = 0;
 
     // small graph: the LDS-resident single-launch decoder, plane I/O (Monte-Carlo entry points)
-    {
-        const size_t small_lds = (size_t)2 * h->E * sizeof(float) + (size_t)2 * h->n + h->m + 64;
-        if (small_lds <= 60 * 1024 && h->E > 0 && h->kn.path != Knobs::STREAM && h->kn.path != Knobs::EDGE) {
-#define SMALL_PLANES(M)                                                                                              \
-    hipLaunchKernelGGL((k_bp_small<M, true>), dim3(batch), dim3(256), small_lds, s, h->d_row_ptr, h->d_col_idx,         \
-                       h->d_col_ptr, h->d_csc_edge, h->d_prior, h->m, h->n, (int)h->E, (const void *)h->d_synd,         \
-                       SCALDPC_IN_SYNDROME, max_iter, alpha, early ? 1 : 0, (void *)h->d_hard,                          \
-                       want_post ? h->d_post : (float *)nullptr, h->d_iters, (void *)h->d_conv)
-            if (method == SCALDPC_BP_MIN_SUM)
-                SMALL_PLANES(SCALDPC_BP_MIN_SUM);
-            else
-                SMALL_PLANES(SCALDPC_BP_PRODUCT_SUM);
-#undef SMALL_PLANES
-            LAUNCH_CHECK();
-            return 0;
-        }
-    }
+    if (const size_t lds = small_lds(h))
+        return launch_small<true>(h, lds, method, batch, h->d_synd, SCALDPC_IN_SYNDROME, max_iter, alpha, early, h->d_hard,
+                                  want_post ? h->d_post.get() : nullptr, h->d_iters, h->d_conv, s);
     const TileState st{h->d_synd, h->d_hard, h->d_done, h->d_conv, h->d_unsat, h->d_iters,
                        want_post ? h->d_post : nullptr};
     return decode_level(h, 0, st, batch, T, G, max_iter, method, alpha, early, want_post, s);
@@ -1539,6 +1526,32 @@ int begin_call(scaldpc_bp *h, int batch, int max_iter, void *stream, Call *c)
     c->G = (h->tile_group > 0) ? std::min(h->tile_group, c->T) : auto_group(h, c->T);
     return 0;
 }
+
+// An entry point that fails after its preamble synchronises the call's stream before it returns: nothing it enqueued
+// (on the stream, or on lanes decode_level has joined into it) is still in flight when a block it released is handed out
+// again.  Its success paths keep their own synchronisation and say done().
+struct SyncOnError {
+    hipStream_t s;
+    bool ok = false;
+    ~SyncOnError() { if (!ok) (void)hipStreamSynchronize(s); }
+    int done() { ok = true; return 0; }
+};
+
+// HIP events with timing (scaldpc_bp_time_kernels), destroyed with their owner
+struct TimingEvents {
+    std::vector<hipEvent_t> ev;
+    TimingEvents() = default;
+    TimingEvents(const TimingEvents &) = delete;
+    TimingEvents &operator=(const TimingEvents &) = delete;
+    ~TimingEvents() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+    int create(size_t count)
+    {
+        ev.assign(count, nullptr);
+        for (hipEvent_t &e : ev) SC_HIP(hipEventCreate(&e));
+        return 0;
+    }
+    hipEvent_t &operator[](size_t i) { return ev[i]; }
+};
 
 // `bytes` of input on the device: the caller's own with SCALDPC_F_DEVICE_IO, else a copy in the handle's staging block
 int stage_input(scaldpc_bp *h, const uint8_t *in, size_t bytes, bool dev_io, hipStream_t s, const uint8_t **din)
@@ -1914,38 +1927,28 @@ int scaldpc_bp_decode_batch(scaldpc_bp *h, const uint8_t *in, int32_t input_kind
     if (flags & SCALDPC_F_ASYNC) h->async_used = true;
     CacheBypass guard(h->async_used);
     const hipStream_t s = c.s;
+    SyncOnError settle{s};
     const int T = c.T, G = c.G, max_iter = c.max_iter;
     const int len = input_kind == SCALDPC_IN_SYNDROME ? h->m : h->n;
     const Outputs out{out_bits, out_llr, out_iters, out_conv};
     Outputs dev;
 
     // Small graph: the LDS-resident single-launch decoder (k_bp_small).
-    const size_t small_lds = (size_t)2 * h->E * sizeof(float) + (size_t)2 * h->n + h->m + 64;
-    const bool small_fits = small_lds <= 60 * 1024 && h->E > 0;
-    if (h->full_stale) {  // rows were appended: only the row-parallel path is up to date
-        const bool small_path = small_fits && h->kn.path != Knobs::STREAM && h->kn.path != Knobs::EDGE;
-        if (small_path || !(T == 1 && batch <= el_limit(h, method))) SC_TRY(refresh_full(h));
-    }
-    if (h->kn.path == Knobs::LDS && !small_fits)  // "stream" / "edge" / "lds" pin a path (tests)
-        return fail(SCALDPC_EINVAL, "SCALDPC_PATH=lds but the graph needs %zu B of LDS", small_lds);
-    if (small_fits && h->kn.path != Knobs::STREAM && h->kn.path != Knobs::EDGE) {
+    const size_t lds = small_lds(h);
+    if (h->full_stale && (lds || !(T == 1 && batch <= el_limit(h, method))))  // rows were appended: only the row-parallel path is up to date
+        SC_TRY(refresh_full(h));
+    if (h->kn.path == Knobs::LDS && !lds)  // "stream" / "edge" / "lds" pin a path (tests)
+        return fail(SCALDPC_EINVAL, "SCALDPC_PATH=lds but the graph needs %zu B of LDS", small_lds_bytes(h));
+    if (lds) {
         const uint8_t *din = in;
         SC_TRY(stage_input(h, in, (size_t)batch * len, dev_io, s, &din));
         SC_TRY(stage_outputs(h, out, batch, dev_io, true, &dev));
-#define SMALL_LAUNCH(M)                                                                                            \
-    hipLaunchKernelGGL((k_bp_small<M, false>), dim3(batch), dim3(256), small_lds, s, h->d_row_ptr, h->d_col_idx, h->d_col_ptr, \
-                       h->d_csc_edge, h->d_prior, h->m, h->n, (int)h->E, din, input_kind, max_iter, alpha,          \
-                       early ? 1 : 0, dev.bits, dev.llr, dev.iters, dev.conv)
-        if (method == SCALDPC_BP_MIN_SUM)
-            SMALL_LAUNCH(SCALDPC_BP_MIN_SUM);
-        else
-            SMALL_LAUNCH(SCALDPC_BP_PRODUCT_SUM);
-#undef SMALL_LAUNCH
-        LAUNCH_CHECK();
+        SC_TRY(launch_small<false>(h, lds, method, batch, din, input_kind, max_iter, alpha, early, dev.bits, dev.llr, dev.iters,
+                                   dev.conv, s));
         SC_TRY(copy_outputs(h, out, dev, batch, dev_io, s));
         h->stat_deferred = 0;
         if (!(flags & SCALDPC_F_ASYNC)) SC_HIP(hipStreamSynchronize(s));
-        return 0;
+        return settle.done();
     }
     SC_TRY(ensure_workspace(h, T, G, out_llr != nullptr, max_iter));
 
@@ -1965,11 +1968,7 @@ int scaldpc_bp_decode_batch(scaldpc_bp *h, const uint8_t *in, int32_t input_kind
                            recvd ? h->d_recv : h->d_synd, h->n, h->d_hard, max_iter, h->d_done, h->d_conv, h->d_iters,
                            h->d_remaining, max_iter + 2, h->d_el_unsat, (max_iter + 2) * TW);
         LAUNCH_CHECK();
-        if (recvd) {
-            hipLaunchKernelGGL(k_parity<false>, dim3((h->m + 4 * ROWS_PER_WAVE - 1) / (4 * ROWS_PER_WAVE), 1), dim3(256), 0, s,
-                               h->d_row_ptr, h->d_col_idx, h->d_recv, h->m, h->n, h->d_synd, (u64 *)nullptr, (const u64 *)nullptr);
-            LAUNCH_CHECK();
-        }
+        if (recvd) SC_TRY(launch_syndrome(h, h->d_recv, h->d_synd, 1, s));
         h->small_prepared = true;
         const int rc = run_core(h, batch, T, G, max_iter, method, alpha, early, out_llr != nullptr, s);
         h->small_prepared = false;
@@ -1988,7 +1987,7 @@ int scaldpc_bp_decode_batch(scaldpc_bp *h, const uint8_t *in, int32_t input_kind
         }
         if (out_iters) memcpy(out_iters, o, sizeof(int) * batch);
         if (out_conv) memcpy(out_conv, o + sizeof(int) * batch, batch);
-        return 0;
+        return settle.done();
     }
 
     // ---- stage input --------------------------------------------------------
@@ -2000,9 +1999,7 @@ int scaldpc_bp_decode_batch(scaldpc_bp *h, const uint8_t *in, int32_t input_kind
     } else {
         hipLaunchKernelGGL(k_pack_bits, dim3((h->n + 63) / 64, T), dim3(256), 0, s, din, h->n, batch, h->d_recv);
         LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_parity<false>, dim3((h->m + 4 * ROWS_PER_WAVE - 1) / (4 * ROWS_PER_WAVE), T), dim3(256), 0, s, h->d_row_ptr, h->d_col_idx,
-                           h->d_recv, h->m, h->n, h->d_synd, (u64 *)nullptr, (const u64 *)nullptr);
-        LAUNCH_CHECK();
+        SC_TRY(launch_syndrome(h, h->d_recv, h->d_synd, T, s));
     }
     SC_TRY(run_core(h, batch, T, G, max_iter, method, alpha, early, out_llr != nullptr, s));
 
@@ -2021,7 +2018,7 @@ int scaldpc_bp_decode_batch(scaldpc_bp *h, const uint8_t *in, int32_t input_kind
     }
     SC_TRY(copy_outputs(h, out, dev, batch, dev_io, s));
     if (!(flags & SCALDPC_F_ASYNC)) SC_HIP(hipStreamSynchronize(s));
-    return 0;
+    return settle.done();
 }
 
 // ---------------------------------------------------------------------------
@@ -2091,9 +2088,10 @@ int scaldpc_mc_fer_run(scaldpc_bp *h, int64_t first_trial, int32_t batch, uint64
     CacheBypass guard(h->async_used);
     Call c;
     SC_TRY(begin_call(h, batch, max_iter_arg, stream, &c));
+    const hipStream_t s = c.s;
+    SyncOnError settle{s};
     SC_TRY(refresh_full(h));
     const bool dev_io = flags & SCALDPC_F_DEVICE_IO, early = flags & SCALDPC_F_EARLY_EXIT;
-    const hipStream_t s = c.s;
     const int T = c.T, G = c.G, max_iter = c.max_iter;
     SC_TRY(ensure_workspace(h, T, G, false, max_iter));
     SC_TRY(grow(h->d_mc, (size_t)T * h->n));
@@ -2109,13 +2107,12 @@ int scaldpc_mc_fer_run(scaldpc_bp *h, int64_t first_trial, int32_t batch, uint64
     hipLaunchKernelGGL(k_mc_bernoulli<false>, dim3((h->n + 63) / 64, T), dim3(256), 0, s, h->d_mc, h->n, batch,
                        (long)first_trial, 0u, k0, k1, (const u64 *)h->d_thr, 0ull);
     LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_parity<false>, dim3((h->m + 4 * ROWS_PER_WAVE - 1) / (4 * ROWS_PER_WAVE), T), dim3(256), 0, s, h->d_row_ptr, h->d_col_idx,
-                       h->d_mc, h->m, h->n, h->d_synd, (u64 *)nullptr, (const u64 *)nullptr);
-    LAUNCH_CHECK();
+    SC_TRY(launch_syndrome(h, h->d_mc, h->d_synd, T, s));
     if (out_error) SC_TRY(mc_export_bits(h, h->d_mc, batch, T, dev_io, s, out_error));
     SC_TRY(run_core(h, batch, T, G, max_iter, method, alpha, early, false, s));
     // success iff decoding == error everywhere (decode.py:173-175)
-    return mc_finish(h, batch, T, h->n, dev_io, s, out_success, out_iters);
+    SC_TRY(mc_finish(h, batch, T, h->n, dev_io, s, out_success, out_iters));
+    return settle.done();
 }
 
 int scaldpc_mc_hqc_run(scaldpc_bp *h, int32_t omega, double eps, int64_t first_trial, int32_t batch, uint64_t seed,
@@ -2129,6 +2126,8 @@ int scaldpc_mc_hqc_run(scaldpc_bp *h, int32_t omega, double eps, int64_t first_t
     CacheBypass guard(h->async_used);
     Call c;
     SC_TRY(begin_call(h, batch, max_iter_arg, stream, &c));
+    const hipStream_t s = c.s;
+    SyncOnError settle{s};
     SC_TRY(refresh_full(h));
     if (h->identity_from < 0) return fail(SCALDPC_EINVAL, "parity-check matrix is not of the form [Hin | I] (hqc.py:680)");
     const int N = h->identity_from;
@@ -2136,7 +2135,6 @@ int scaldpc_mc_hqc_run(scaldpc_bp *h, int32_t omega, double eps, int64_t first_t
     if (!(eps >= 0.0 && eps <= 1.0)) return fail(SCALDPC_EINVAL, "eps must be a probability");
     if ((size_t)omega * 64 * 4 > 64 * 1024) return fail(SCALDPC_EDEGREE, "omega %d too large for the LDS-resident sampler", omega);
     const bool dev_io = flags & SCALDPC_F_DEVICE_IO, early = flags & SCALDPC_F_EARLY_EXIT;
-    const hipStream_t s = c.s;
     const int T = c.T, G = c.G, max_iter = c.max_iter;
     SC_TRY(ensure_workspace(h, T, G, false, max_iter));
     SC_TRY(grow(h->d_mc, (size_t)T * h->n));
@@ -2156,9 +2154,7 @@ int scaldpc_mc_hqc_run(scaldpc_bp *h, int32_t omega, double eps, int64_t first_t
                            batch, (long)first_trial, k0, k1, dy);
         LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(k_parity<false>, dim3((h->m + 4 * ROWS_PER_WAVE - 1) / (4 * ROWS_PER_WAVE), T), dim3(256), 0, s, h->d_row_ptr, h->d_col_idx,
-                       h->d_mc, h->m, h->n, h->d_synd, (u64 *)nullptr, (const u64 *)nullptr);
-    LAUNCH_CHECK();
+    SC_TRY(launch_syndrome(h, h->d_mc, h->d_synd, T, s));
     // each oracle answer wrong with probability eps
     hipLaunchKernelGGL(k_mc_bernoulli<true>, dim3((h->m + 63) / 64, T), dim3(256), 0, s, h->d_synd, h->m, batch,
                        (long)first_trial, 0u, k0, k1, (const u64 *)nullptr, bernoulli_threshold(eps));
@@ -2173,22 +2169,15 @@ int scaldpc_mc_hqc_run(scaldpc_bp *h, int32_t omega, double eps, int64_t first_t
         SC_HIP(hipMemcpyAsync(out_y, dy, sizeof(int) * (size_t)batch * omega, hipMemcpyDeviceToHost, s));
     }
     // decoded[:N] = e[:N] XOR msg[:N] = e[:N] must equal the indicator of y (hqc.py:742-749)
-    return mc_finish(h, batch, T, N, dev_io, s, out_success, out_iters);
+    SC_TRY(mc_finish(h, batch, T, N, dev_io, s, out_success, out_iters));
+    return settle.done();
 }
 
 int scaldpc_bp_configure(scaldpc_bp *h, const char *key, const char *value)
 {
     if (!h || !key || !value) return fail(SCALDPC_EINVAL, "NULL argument");
     std::lock_guard<std::mutex> lk(h->mu);
-    DeviceGuard dg(h->device);
-    const int old_order = h->kn.var_order;
     if (!set_knob(h->kn, key, value)) return fail(SCALDPC_EINVAL, "unknown knob or bad value: %s=%s", key, value);
-    if (h->kn.var_order != old_order && h->d_tile_tab) {  // the k_var records are laid out in launch order: rebuild on next use
-        CacheBypass guard(true);
-        SC_HIP(hipDeviceSynchronize());
-        h->d_tile_tab.reset();
-        h->d_var_meta = h->d_csc_list = h->d_row_list = nullptr;
-    }
     return 0;
 }
 
@@ -2224,140 +2213,126 @@ int scaldpc_bp_time_kernels(scaldpc_bp *h, int32_t iters, int32_t method, float 
     const int g = h->last_group;
     SC_TRY(ensure_msg(h, g, method));  // (a method other than the last decode's may want the record arrays)
     const int nl = std::min(fixed_lanes(h, g), 2);
+    SC_TRY(ensure_lanes(h, nl));
     // The variable pass is timed in the form the last decode launched it in: early-exit runs write decisions on EVERY
     // pass (all columns), fixed-iteration runs only on the last one (the passes before it leave out the columns of
     // degree <= 1 in the record form).  launches[5] says which.
     const int wo = h->last_early ? 1 : 0;
     const bool recf = rec_form(h, method);
-    const bool slim = recf && !wo && h->kn.rec_skip1;
-    const int form_bits = (recf ? 1 : 0) | (wo ? 2 : 0) | (slim ? 4 : 0);
+    const int form_bits = (recf ? 1 : 0) | (wo ? 2 : 0) | (recf && !wo ? 4 : 0);
+    TimingEvents ev;
+    SyncOnError settle{s};
+    Lanes lanes(h, s);
+    int gs[2], t0[2];
+    deal_tiles(g, nl, gs, t0);  // as iterate_tiles deals the tiles
+    auto check = [&](int it, int k) {
+        return launch_check(h, method, alpha_for(alpha, it + 1), gs[k], h->d_synd + (size_t)t0[k] * h->m, h->d_done + t0[k], 0,
+                            lanes[k], false, t0[k]);
+    };
+    auto var = [&](int k) {
+        return launch_var(h, gs[k], nullptr, h->d_hard + (size_t)t0[k] * h->n, h->d_done + t0[k], 0, wo, lanes[k], t0[k], nullptr,
+                          recf, true);
+    };
     // `iters` back-to-back launches of each kernel between two events: the event
     // overhead (a few us, comparable to a 65 us launch) is amortised, what remains is
     // the kernel plus the ~1.5 us dependent-launch gap it also pays in a real decode.
+    if (nl < 2) {
+        SC_TRY(ev.create(4));
+        SC_HIP(hipEventRecord(ev[0], s));
+        for (int it = 0; it < iters; it++) SC_TRY(check(it, 0));
+        SC_HIP(hipEventRecord(ev[1], s));
+        SC_HIP(hipEventRecord(ev[2], s));
+        for (int it = 0; it < iters; it++) SC_TRY(var(0));
+        SC_HIP(hipEventRecord(ev[3], s));
+        SC_HIP(hipStreamSynchronize(s));
+        SC_HIP(hipEventElapsedTime(&ms[0], ev[0], ev[1]));
+        SC_HIP(hipEventElapsedTime(&ms[1], ev[2], ev[3]));
+        launches[0] = launches[1] = iters;
+        launches[2] = launches[4] = g * TW;  // codewords swept per launch
+        launches[3] = 1;
+        launches[5] = form_bits;
+        return settle.done();
+    }
     // Two-lane schedule (what a fixed-iteration decode runs): the decode's own launch pattern --
     // each lane alternates check and variable launches over its half of the group, the second
     // lane one kernel out of phase -- with an event after EVERY launch; a launch's duration is
     // the distance between its event and the previous one on the same lane (it includes the
     // dependent-launch gap, as the single-lane series do).  ms[] = sum over the measured
     // launches of both lanes, the first two iterations (phase settling) excluded.
-    std::vector<hipEvent_t> ev(6);
-    for (auto &e : ev) SC_HIP(hipEventCreate(&e));
-    int rc = 0;
-    if (nl < 2) {
-        SC_HIP(hipEventRecord(ev[0], s));
-        for (int it = 0; it < iters && !rc; it++) rc = launch_check(h, method, alpha_for(alpha, it + 1), g, h->d_synd, h->d_done, 0, s);
-        SC_HIP(hipEventRecord(ev[1], s));
-        SC_HIP(hipEventRecord(ev[2], s));
-        for (int it = 0; it < iters && !rc; it++) rc = launch_var(h, g, nullptr, h->d_hard, h->d_done, 0, wo, s, 0, nullptr, recf, true);
-        SC_HIP(hipEventRecord(ev[3], s));
-        if (!rc) SC_HIP(hipStreamSynchronize(s));
-        if (!rc) {
-            SC_HIP(hipEventElapsedTime(&ms[0], ev[0], ev[1]));
-            SC_HIP(hipEventElapsedTime(&ms[1], ev[2], ev[3]));
-            launches[0] = launches[1] = iters;
-            launches[2] = launches[4] = g * TW;  // codewords swept per launch
-            launches[3] = 1;
-            launches[5] = form_bits;
+    const int total = iters + 2;
+    SC_TRY(ev.create((size_t)2 * (2 * total + 1)));  // per lane: start, then one per launch
+    auto M = [&](int k, int i) -> hipEvent_t & { return ev[(size_t)k * (2 * total + 1) + i]; };
+    auto phase = [&]() -> int {  // the second lane starts one kernel behind the first
+        SC_HIP(hipEventRecord(h->ev_phase[1], lanes[0]));
+        SC_HIP(hipStreamWaitEvent(lanes[1], h->ev_phase[1], 0));
+        return 0;
+    };
+    SC_TRY(lanes.fork(2));
+    for (int it = 0; it < total; it++) {
+        for (int k = 0; k < 2; k++) {
+            if (it == 0) SC_HIP(hipEventRecord(M(k, 0), lanes[k]));
+            SC_TRY(check(it, k));
+            SC_HIP(hipEventRecord(M(k, 2 * it + 1), lanes[k]));
+            if (it == 0 && k == 0) SC_TRY(phase());
         }
-    } else {
-        SC_TRY(ensure_lanes(h, 2));
-        hipStream_t lane[2] = {s, h->aux_stream[1]};
-        const int gs[2] = {g - g / 2, g / 2}, t0[2] = {0, g - g / 2};  // as iterate_tiles deals the tiles
-        const int total = iters + 2;
-        std::vector<hipEvent_t> mark((size_t)2 * (2 * total + 1));  // per lane: start, then one per launch
-        for (auto &e : mark) SC_HIP(hipEventCreate(&e));
-        auto M = [&](int k, int i) -> hipEvent_t & { return mark[(size_t)k * (2 * total + 1) + i]; };
-        SC_HIP(hipEventRecord(ev[4], s));
-        SC_HIP(hipStreamWaitEvent(lane[1], ev[4], 0));
-        for (int it = 0; it < total && !rc; it++) {
-            for (int k = 0; k < 2 && !rc; k++) {
-                if (it == 0) SC_HIP(hipEventRecord(M(k, 0), lane[k]));
-                rc = launch_check(h, method, alpha_for(alpha, it + 1), gs[k], h->d_synd + (size_t)t0[k] * h->m, h->d_done + t0[k],
-                                  0, lane[k], false, t0[k]);
-                SC_HIP(hipEventRecord(M(k, 2 * it + 1), lane[k]));
-                if (it == 0 && k == 0) {
-                    SC_HIP(hipEventRecord(h->ev_phase[1], lane[0]));
-                    SC_HIP(hipStreamWaitEvent(lane[1], h->ev_phase[1], 0));
-                }
-            }
-            for (int k = 0; k < 2 && !rc; k++) {
-                rc = launch_var(h, gs[k], nullptr, h->d_hard + (size_t)t0[k] * h->n, h->d_done + t0[k], 0, wo, lane[k], t0[k], nullptr,
-                                recf, true);
-                SC_HIP(hipEventRecord(M(k, 2 * it + 2), lane[k]));
-            }
+        for (int k = 0; k < 2; k++) {
+            SC_TRY(var(k));
+            SC_HIP(hipEventRecord(M(k, 2 * it + 2), lanes[k]));
         }
-        SC_HIP(hipEventRecord(ev[5], lane[1]));
-        SC_HIP(hipStreamWaitEvent(s, ev[5], 0));
-        if (!rc) SC_HIP(hipStreamSynchronize(s));
-        if (!rc) {
-            double tc = 0.0, tv = 0.0;
-            int nc = 0, nv = 0;
-            for (int k = 0; k < 2; k++)
-                for (int it = 2; it < total; it++) {
-                    float d = 0.0f;
-                    SC_HIP(hipEventElapsedTime(&d, M(k, 2 * it), M(k, 2 * it + 1)));
-                    tc += d;
-                    nc++;
-                    SC_HIP(hipEventElapsedTime(&d, M(k, 2 * it + 1), M(k, 2 * it + 2)));
-                    tv += d;
-                    nv++;
-                }
-            // The event after every launch costs the schedule its back-to-back dispatch (~2.5 us per launch: with the 30-50
-            // us launches of the record form the evented pair came out 6 % above rocprofv3's).  A second pass with the same
-            // launch pattern and NO events in between gives the pair's true duration per lane; the evented series supply
-            // only the check : variable ratio.
-            double pair_ms = 0.0;
-            {
-                hipEvent_t &b0 = M(0, 0), &e0 = M(0, 1), &b1 = M(1, 0), &e1 = M(1, 1);
-                SC_HIP(hipEventRecord(ev[4], s));
-                SC_HIP(hipStreamWaitEvent(lane[1], ev[4], 0));
-                for (int it = 0; it < total && !rc; it++) {
-                    if (it == 2) {
-                        SC_HIP(hipEventRecord(b0, lane[0]));
-                        SC_HIP(hipEventRecord(b1, lane[1]));
-                    }
-                    for (int k = 0; k < 2 && !rc; k++) {
-                        rc = launch_check(h, method, alpha_for(alpha, it + 1), gs[k], h->d_synd + (size_t)t0[k] * h->m, h->d_done + t0[k],
-                                          0, lane[k], false, t0[k]);
-                        if (it == 0 && k == 0) {
-                            SC_HIP(hipEventRecord(h->ev_phase[1], lane[0]));
-                            SC_HIP(hipStreamWaitEvent(lane[1], h->ev_phase[1], 0));
-                        }
-                    }
-                    for (int k = 0; k < 2 && !rc; k++)
-                        rc = launch_var(h, gs[k], nullptr, h->d_hard + (size_t)t0[k] * h->n, h->d_done + t0[k], 0, wo, lane[k], t0[k],
-                                        nullptr, recf, true);
-                }
-                SC_HIP(hipEventRecord(e0, lane[0]));
-                SC_HIP(hipEventRecord(e1, lane[1]));
-                SC_HIP(hipEventRecord(ev[5], lane[1]));
-                SC_HIP(hipStreamWaitEvent(s, ev[5], 0));
-                if (!rc) SC_HIP(hipStreamSynchronize(s));
-                if (!rc) {
-                    float d0 = 0.0f, d1 = 0.0f;
-                    SC_HIP(hipEventElapsedTime(&d0, b0, e0));
-                    SC_HIP(hipEventElapsedTime(&d1, b1, e1));
-                    pair_ms = 0.5 * ((double)d0 + (double)d1) / (total - 2);
-                }
-            }
-            if (pair_ms > 0.0 && tc + tv > 0.0 && nc == nv && nc > 0) {
-                const double evented_pair = (tc + tv) / nc, scale = pair_ms / evented_pair;
-                tc *= scale;
-                tv *= scale;
-            }
-            ms[0] = (float)tc;
-            ms[1] = (float)tv;
-            launches[0] = nc;
-            launches[1] = nv;
-            launches[2] = gs[0] * TW;
-            launches[4] = gs[0] * TW;  // (odd groups: the second lane's launches are one tile smaller)
-            launches[3] = 2;
-            launches[5] = form_bits;
-        }
-        for (auto &e : mark) (void)hipEventDestroy(e);
     }
-    for (auto &e : ev) (void)hipEventDestroy(e);
-    return rc;
+    SC_TRY(lanes.join());
+    SC_HIP(hipStreamSynchronize(s));
+    double tc = 0.0, tv = 0.0;
+    int nc = 0, nv = 0;
+    for (int k = 0; k < 2; k++)
+        for (int it = 2; it < total; it++) {
+            float d = 0.0f;
+            SC_HIP(hipEventElapsedTime(&d, M(k, 2 * it), M(k, 2 * it + 1)));
+            tc += d;
+            nc++;
+            SC_HIP(hipEventElapsedTime(&d, M(k, 2 * it + 1), M(k, 2 * it + 2)));
+            tv += d;
+            nv++;
+        }
+    // The event after every launch costs the schedule its back-to-back dispatch (~2.5 us per launch: with the 30-50
+    // us launches of the record form the evented pair came out 6 % above rocprofv3's).  A second pass with the same
+    // launch pattern and NO events in between gives the pair's true duration per lane; the evented series supply
+    // only the check : variable ratio.
+    hipEvent_t &b0 = M(0, 0), &e0 = M(0, 1), &b1 = M(1, 0), &e1 = M(1, 1);
+    SC_TRY(lanes.fork(2));
+    for (int it = 0; it < total; it++) {
+        if (it == 2) {
+            SC_HIP(hipEventRecord(b0, lanes[0]));
+            SC_HIP(hipEventRecord(b1, lanes[1]));
+        }
+        for (int k = 0; k < 2; k++) {
+            SC_TRY(check(it, k));
+            if (it == 0 && k == 0) SC_TRY(phase());
+        }
+        for (int k = 0; k < 2; k++) SC_TRY(var(k));
+    }
+    SC_HIP(hipEventRecord(e0, lanes[0]));
+    SC_HIP(hipEventRecord(e1, lanes[1]));
+    SC_TRY(lanes.join());
+    SC_HIP(hipStreamSynchronize(s));
+    float d0 = 0.0f, d1 = 0.0f;
+    SC_HIP(hipEventElapsedTime(&d0, b0, e0));
+    SC_HIP(hipEventElapsedTime(&d1, b1, e1));
+    const double pair_ms = 0.5 * ((double)d0 + (double)d1) / (total - 2);
+    if (pair_ms > 0.0 && tc + tv > 0.0 && nc == nv && nc > 0) {
+        const double evented_pair = (tc + tv) / nc, scale = pair_ms / evented_pair;
+        tc *= scale;
+        tv *= scale;
+    }
+    ms[0] = (float)tc;
+    ms[1] = (float)tv;
+    launches[0] = nc;
+    launches[1] = nv;
+    launches[2] = gs[0] * TW;
+    launches[4] = gs[0] * TW;  // (odd groups: the second lane's launches are one tile smaller)
+    launches[3] = 2;
+    launches[5] = form_bits;
+    return settle.done();
 }
 
 void scaldpc_bp_destroy(scaldpc_bp *h)

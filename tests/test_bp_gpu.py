@@ -153,6 +153,9 @@ def test_errors():
     dec = bp.bp_decoder(g, error_rate=0.1)
     with pytest.raises(ValueError):
         dec.decode(np.zeros(7, dtype=int))
+    for knob in (dict(el_fuse=0), dict(rec_skip1=0), dict(var_order=1)):  # A/B-only knobs removed with their code
+        with pytest.raises(ValueError):
+            dec.configure(**knob)
 
 
 @pytest.mark.parametrize("method", ["min_sum", "product_sum"])
@@ -387,7 +390,9 @@ def test_convergence_test_riding_on_the_check_pass_is_invisible(oracle, method):
     """Early-exit tile loop: the H e == s test of iteration it rides on the check pass of it + 1 (`fuse_test`, default
     on) except where the host polls or stops.  Decisions, posteriors, ITERATION COUNTS and flags are those of the
     stand-alone test launch, bit for bit: several tile groups with a ragged last one, one and two stream lanes,
-    compaction on and off, a graph with rows of mixed degree and an empty row, trials that converge at iteration 1."""
+    compaction on and off, a graph with rows of mixed degree and an empty row, trials that converge at iteration 1.
+    compact_after = 6 with two lanes: groups that stop unseen at the hand-over point while the poll at iteration 4 is
+    still live (they are not chained to their neighbours)."""
     H, Hin, probs, msg, y = hqc_instance(997, 9, 450, 6, 0.03, 700, seed=21)
     msg[:40, 997:] = H.syndrome(np.concatenate([y[:40], np.zeros((40, 450), np.uint8)], axis=1))  # noiseless checks: early convergers
     rng = np.random.RandomState(8)
@@ -400,7 +405,7 @@ def test_convergence_test_riding_on_the_check_pass_is_invisible(oracle, method):
         outs = {}
         for ft in (1, 0):
             res = []
-            for lanes, group, compact in ((2, 3, -1), (1, 2, 0), (2, 0, 2)):
+            for lanes, group, compact in ((2, 3, -1), (1, 2, 0), (2, 0, 2), (2, 2, 6)):
                 dec = bp.bp_decoder(graph, max_iter=40, bp_method=method, channel_probs=pr)
                 dec.configure(path="stream", fuse_test=ft, split=lanes, compact_after=compact)
                 dec.set_tile_group(group)
@@ -488,8 +493,8 @@ def test_minsum_record_form_is_invisible(oracle):
     (rows of degree 0, 1, 2 ... and columns beyond the records' inline edges), +-inf priors (NaN messages: inf - inf),
     the alpha = 1 - 2^-it schedule, early exit with the convergence test riding on the record check pass and without,
     the first iteration with and without its check pass (with one it runs in the message form, the records start with
-    iteration 2), one and two stream lanes, compaction, fixed-iteration passes with and without the columns of degree
-    <= 1 (`rec_skip1`: their message is the prior, written once), XCD-aware tile placement taken and not (groups of 2, 3
+    iteration 2), one and two stream lanes, compaction, fixed-iteration passes that leave out the columns of degree
+    <= 1 (their message is the prior, written once), XCD-aware tile placement taken and not (groups of 2, 3
     and 4 tiles), rows appended to a live decoder.  A graph with a row wider than 64 (or a column wider than 32) falls
     back to the message form by itself."""
     rng = np.random.RandomState(77)
@@ -512,27 +517,25 @@ def test_minsum_record_form_is_invisible(oracle):
     cases.append((G2, p2, s2, "syndrome", 0.75))
     for graph, pr, x, kind, alpha in cases:
         outs = {}
-        for form in ((1, 1), (1, 0), (0, 0)):  # (minsum_rec, rec_skip1)
+        for rec in (1, 0):  # minsum_rec
             res = []
             for lanes, group, compact, ff, ft in ((2, 3, -1, 1, 1), (1, 2, 0, 0, 1), (2, 0, 2, 1, 0)):
                 with np.errstate(divide="ignore"):
                     dec = bp.bp_decoder(graph, max_iter=30, bp_method="min_sum", channel_probs=pr, ms_scaling_factor=alpha)
-                dec.configure(path="stream", minsum_rec=form[0], rec_skip1=form[1], split=lanes, compact_after=compact,
-                              first_fused=ff, fuse_test=ft)
+                dec.configure(path="stream", minsum_rec=rec, split=lanes, compact_after=compact, first_fused=ff, fuse_test=ft)
                 dec.set_tile_group(group)
                 res.append(dec.decode_batch(x, early_exit=True, want_llr=True, input_vector_type=kind))
                 res.append(dec.decode_batch(x[:70], early_exit=False, want_llr=True, input_vector_type=kind))
-                assert dec.time_kernels(2)["record_form"] == bool(form[0])  # the form that ran is the one asked for
+                assert dec.time_kernels(2)["record_form"] == bool(rec)  # the form that ran is the one asked for
                 dec.close()
-            outs[form] = res
-        for form in ((1, 1), (1, 0)):
-            for a, b in zip(outs[form], outs[(0, 0)]):
-                for k in ("bits", "llr", "iters", "converged"):
-                    assert np.array_equal(a[k], b[k], equal_nan=(k == "llr")), (alpha, form, k)
+            outs[rec] = res
+        for a, b in zip(outs[1], outs[0]):
+            for k in ("bits", "llr", "iters", "converged"):
+                assert np.array_equal(a[k], b[k], equal_nan=(k == "llr")), (alpha, k)
         with np.errstate(divide="ignore", invalid="ignore"):
             ref = oracle.bp_decode_batch(graph, pr, x, 1 if kind == "received_vector" else 0, 30, "min_sum", alpha=alpha, dtype="f32",
                                          threads=8)
-        compare(outs[(1, 1)][0], ref, "min_sum")
+        compare(outs[1][0], ref, "min_sum")
     # rows appended to a live decoder: records and masks are sized by the graph
     H, Hin, probs, msg, y = hqc_instance(901, 9, 300, 6, 0.03, 150, seed=63)
     N = 901
@@ -683,19 +686,14 @@ def test_row_parallel_path_is_taken_and_agrees_with_tiles(oracle, method, monkey
         for x in (synd[:nb], msg[:nb]):
             for early in (True, False):
                 out = {}
-                # "edge4": the four-launch form of the early-exit loop (convergence test as separate
-                # kernels) instead of the fused two-launch form
-                for path in ("edge", "edge4", "stream"):
-                    monkeypatch.setenv("SCALDPC_PATH", path.rstrip("4"))
-                    monkeypatch.setenv("SCALDPC_EL_FUSE", "0" if path == "edge4" else "1")
+                for path in ("edge", "stream"):
+                    monkeypatch.setenv("SCALDPC_PATH", path)
                     dec = bp.bp_decoder(H, max_iter=30, bp_method=method, channel_probs=probs)
                     out[path] = dec.decode_batch(x, early_exit=early, want_llr=True)
                     assert dec.last_row_parallel() == (nb if path != "stream" else 0)
                     dec.close()
                 for k in ("bits", "llr", "iters", "converged"):
                     assert np.array_equal(out["edge"][k], out["stream"][k]), (nb, early, k)
-                    assert np.array_equal(out["edge4"][k], out["stream"][k]), (nb, early, k)
-    monkeypatch.delenv("SCALDPC_EL_FUSE")
     ref = oracle.bp_decode_batch(H, probs, msg[:64], 1, 30, ORACLE_METHOD[method], dtype="f32", threads=8,
                                  early_exit=False)
     compare(out["edge"], ref, method)  # nb = 64, received words, fixed iterations

@@ -207,6 +207,48 @@ def test_failed_append_leaves_a_refusing_handle_and_no_leak(fail_alloc):
         assert failed >= 1 and succeeded >= 2, (first_append, failed, succeeded)
 
 
+def test_failed_decode_leaves_a_working_handle_and_no_leak(fail_alloc):
+    """scaldpc_bp_decode_batch with the k-th allocation failing, k = 1, 2, ..., on a call that keeps the stream lanes busy:
+    64-codeword tiles on two lanes, groups of two tiles (four groups), early exit with the compact pass, iteration 1
+    without its check pass.  The failing call raises MemoryError and leaves nothing in flight; disarmed, the SAME handle
+    then decodes the batch as a clean decoder does -- decisions, posteriors, iteration counts, flags -- and destroy
+    (+ trim) returns every block.  Once k is past the call's allocations, the call itself succeeds."""
+    H, Hin, probs, msg, y = hqc_instance(997, 9, 450, 6, 0.03, 450, seed=21)
+
+    def decoder():
+        dec = bp.bp_decoder(H, max_iter=30, bp_method="min_sum", channel_probs=probs)
+        dec.configure(path="stream", split=2, compact_after=4, first_fused=1)
+        dec.set_tile_group(2)
+        return dec
+
+    clean = decoder()
+    want = clean.decode_batch(msg, early_exit=True, want_llr=True)
+    assert clean.last_stats()["compacted"] > 0  # (the call really hands stragglers to the compact pass)
+    clean.close()
+    lib.trim()
+    base = live()
+    failed = succeeded = 0
+    for k in range(1, 200):
+        dec = decoder()
+        assert fail_alloc(k) == 0  # (armed: SCALDPC_DEBUG=1, tests/conftest.py)
+        try:
+            got = dec.decode_batch(msg, early_exit=True, want_llr=True)
+            fail_alloc(0)
+            succeeded += 1
+        except MemoryError:
+            fail_alloc(0)
+            failed += 1
+            got = dec.decode_batch(msg, early_exit=True, want_llr=True)
+        for key in ("bits", "llr", "iters", "converged"):
+            assert np.array_equal(got[key], want[key]), (k, key)
+        dec.close()
+        lib.trim()
+        assert live() == base, f"k = {k}: {live()} != {base}"
+        if succeeded >= 2:
+            break
+    assert failed >= 1 and succeeded >= 2, (failed, succeeded)
+
+
 def test_accumulator_survives_a_bad_certainty():
     """driver.HqcCheckAccumulator keeps ONE decoder alive and appends rows to it; a certainty outside [0, 1] fails the
     append BEFORE the graph grows (bp.append_rows validates first) and the accumulator drops its live decoder instead
