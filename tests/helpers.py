@@ -1,5 +1,7 @@
 """Shared builders for the parity tests (seeded inputs, HQC-shaped instances)."""
 import importlib
+import json
+import os
 
 import numpy as np
 
@@ -57,6 +59,90 @@ def staircase_graph(rng, rows_per_degree=3, colmax=32, fillers=600):
             H[r, (colmax + 1) + rng.choice(fillers, size=left[r], replace=False)] = 1
     assert (H.sum(axis=1) == degs).all() and (H[:, : colmax + 1].sum(axis=0) == np.arange(colmax + 1)).all()
     return S.TannerGraph.from_dense(H), H
+
+
+def hqc_first_rows():
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "hqc_first_rows.json")) as fh:
+        return json.load(fh)
+
+
+def hqc_full_size_point(name, key, R, eps, batch, base_seed=2):
+    """One full-size point of the production range: H = [Hin | I_R] with Hin the first R rows of
+    `codes.hqc_bench_graph(name, first row `key` of tests/golden/hqc_first_rows.json)` (row_seed 1, so a graph with more
+    rows EXTENDS one with fewer: the attack loop's growth), `batch` synthetic trials (`trials.hqc_trials`, trial i seeded
+    base_seed + i) and their priors (eps = 0: certainty-1.0 checks, p = 0, hqc.py:689).
+    Returns (H, Hin, probs, msg, ys)."""
+    trials = importlib.import_module("sca-ldpc_amd.trials")
+    H, Hin, _ = S.codes.hqc_bench_graph(name, hqc_first_rows()[key], R=R)
+    N, omega = S.codes.HQC_PARAMS[name]
+    msg, ys = trials.hqc_trials(Hin, omega, eps, batch, base_seed=base_seed)
+    return H, Hin, trials.hqc_priors(N, R, omega, eps), msg, ys
+
+
+def sample_rows(batch, per_tile, tiles=None):
+    """Codeword indices for an oracle sample: the first `per_tile` codewords of each 64-codeword tile in `tiles`
+    (default: the first, a middle and the last tile); a last tile that is ragged gives what it has."""
+    T = (batch + 63) // 64
+    tiles = sorted({0, T // 2, T - 1}) if tiles is None else tiles
+    return np.concatenate([np.arange(t * 64, min(t * 64 + per_tile, batch, (t + 1) * 64)) for t in tiles])
+
+
+# The production range at full size (tests/test_production_range.py pins what each graph is and that its trials are
+# hard enough; tests/test_production_range_gpu.py holds the kernels to the oracle there).  Per point: the arguments of
+# `hqc_full_size_point`, the GPU batch, the table's facts (edges, row degree, maximum column degree, columns wider
+# than 32) and what the oracle sample must hold (`spread`: >= 3 distinct iteration counts; `stuck`: a codeword that does
+# not converge).  eps was raised from the bench's 0.05 where every codeword converges in 2-3 iterations there.
+PRODUCTION_POINTS = {
+    "hqc128_W50_R2000": dict(name="hqc128", key="N17669_W50_s0", R=2000, eps=0.0, batch=4096,
+                             E=102000, row_deg=51, max_col_deg=16, cols_over_32=0, spread=True, stuck=True),
+    "hqc128_W50_R4000": dict(name="hqc128", key="N17669_W50_s0", R=4000, eps=0.0, batch=4096,  # the literal `bench.py --eps 0` graph:
+                             E=204000, row_deg=51, max_col_deg=24, cols_over_32=0, spread=False, stuck=False),  # easy, kept for its priors
+    "hqc128_W20_R4000": dict(name="hqc128", key="N17669_W20_s0", R=4000, eps=0.01, batch=390,
+                             E=84000, row_deg=21, max_col_deg=13, cols_over_32=0, spread=True, stuck=True),
+    "hqc128_W50_R8000": dict(name="hqc128", key="N17669_W50_s0", R=8000, eps=0.2, batch=390,
+                             E=408000, row_deg=51, max_col_deg=36, cols_over_32=54, spread=True, stuck=True),
+    "hqc256_W60_R12000": dict(name="hqc256", key="N57637_W60_s0", R=12000, eps=0.08, batch=200,
+                              E=732000, row_deg=61, max_col_deg=27, cols_over_32=0, spread=True, stuck=True),
+    "hqc256_W60_R6000": dict(name="hqc256", key="N57637_W60_s0", R=6000, eps=0.0, batch=200,
+                             E=366000, row_deg=61, max_col_deg=18, cols_over_32=0, spread=True, stuck=True),
+    "hqc256_W60_R20000": dict(name="hqc256", key="N57637_W60_s0", R=20000, eps=0.2, batch=200,
+                              E=1220000, row_deg=61, max_col_deg=38, cols_over_32=61, spread=True, stuck=True),
+}
+# A live decoder grown across a line of the kernel selection: (first row key, start rows, end rows, the column degree
+# that is passed, the first row count at which the maximum column degree exceeds it, eps)
+PRODUCTION_GROWTH = {
+    "W50_across_16": dict(name="hqc128", key="N17669_W50_s0", R0=1900, R1=2100, line=16, crossing=2016, eps=0.0),
+    "W50_across_32": dict(name="hqc128", key="N17669_W50_s0", R0=6500, R1=7000, line=32, crossing=6708, eps=0.2),
+    "W20_across_16": dict(name="hqc128", key="N17669_W20_s0", R0=7200, R1=7400, line=16, crossing=7262, eps=0.1),
+}
+
+
+def growth_run(run, batch, base_seed=2):
+    """Inputs of one growth run: the END graph's Hin, priors and trials; `prefix_point` cuts them down to the first r
+    checks.  The eps = 0 run has noise-free answers and MIXED priors: half of the checks at certainty 1.0 (p = 0,
+    hqc.py:689), the others at certainty 0.95 -- infinite and finite check priors side by side (with a tenth at
+    certainty 1.0 the min-sum oracle converges on every codeword of its sample at 2100 rows).
+    Returns (Hin, probs, msg)."""
+    g = PRODUCTION_GROWTH[run]
+    _, Hin, probs, msg, _ = hqc_full_size_point(g["name"], g["key"], g["R1"], g["eps"], batch, base_seed=base_seed)
+    if g["eps"] == 0.0:
+        cert = np.where(np.random.RandomState(77).rand(g["R1"]) < 0.5, 1.0, 0.95)
+        probs = np.concatenate([probs[: Hin.n], 1.0 - cert])
+    return Hin, probs, msg
+
+
+def prefix_graph(Hin, r):
+    """[Hin[:r] | I_r] of a constant-row-weight Hin."""
+    N = Hin.n
+    rp = Hin.row_ptr[: r + 1]
+    cols = np.concatenate([Hin.col_idx[: rp[-1]].reshape(r, -1), N + np.arange(r, dtype=np.int32)[:, None]], axis=1)
+    return S.TannerGraph.from_csr(r, N + r, np.arange(r + 1, dtype=np.int64) * cols.shape[1], cols.reshape(-1))
+
+
+def prefix_point(Hin, probs, msg, r, nb=None):
+    """(H, priors, received words) of the first r checks and the first nb codewords."""
+    N = Hin.n
+    return prefix_graph(Hin, r), probs[: N + r], np.ascontiguousarray(msg[:nb, : N + r])
 
 
 # the f32 oracle instantiation that mirrors each kernel's operation order
