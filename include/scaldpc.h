@@ -16,6 +16,10 @@
  *     _set_channel_probs_tail    decoder rebuild of every decode (hqc.py:680,694) -> rows appended to a live decoder
  *   scaldpc_bp_decode_batch      ldpc.bp_decoder.decode(v), simulate/decode.py:171, simulate/hqc.py:708
  *                                (batched: one call = `batch` independent decode() calls)
+ *   scaldpc_bp_decode_batch_soft the same with the priors of the last columns given PER CODEWORD: hqc.decode()'s
+ *                                `channel_probs = [w/N]*N ++ [1 - certainty_i]`, simulate/hqc.py:684-699, whose check
+ *                                certainties differ from trial to trial (hqc.py:782-806)
+ *                                (entry point added under SCALDPC_VERSION 103: nothing that existed changed)
  *   scaldpc_bp_destroy           object lifetime
  *   scaldpc_mc_fer_run           the per-trial body of simulate_frame_error_rate,
  *                                simulate/decode.py:36-40,165-175 (noise, syndrome, decode, compare)
@@ -152,6 +156,25 @@ int scaldpc_bp_decode_batch(scaldpc_bp *h, const uint8_t *in, int32_t input_kind
                             void *stream, uint8_t *out_bits, float *out_llr, int32_t *out_iters,
                             uint8_t *out_conv);
 /*
+ * scaldpc_bp_decode_batch with per-codeword priors for the LAST prob_cols columns, [n - prob_cols, n):
+ *   probs  float32 [batch][prob_cols]: prior error probabilities of those columns for each codeword, 1 <= prob_cols <= n;
+ *          the columns below keep the handle's shared priors (scaldpc_bp_set_channel_probs).  For H = [Hin | I_R],
+ *          prob_cols = R is the `check_part` of hqc.py:689; prob_cols = n is a fully soft input.
+ *          `probs` lives where `in` lives: host memory, or device memory with SCALDPC_F_DEVICE_IO.
+ * Everything else means what it means in scaldpc_bp_decode_batch.  The handle's own priors are not changed: a plain call
+ * afterwards behaves as before.  The prior LLRs are logf((1.0f - p) / p) in float32, computed on the device with glibc's
+ * logf algorithm and the correctly rounded division: value for value what scaldpc_bp_set_channel_probs computes on the
+ * host for the same float32 p (p = 0 / p = 1 are legal: LLR = +-inf).
+ * Validation: a value outside [0, 1] or a NaN returns SCALDPC_EINVAL and names the codeword and the column.  Host input is
+ * checked before anything is enqueued; device input is checked by the conversion kernel and reported when the call
+ * synchronises (the outputs are then not to be used).  Under SCALDPC_F_ASYNC device input is NOT checked: the caller
+ * answers for it (a bad value decodes as p = 1/2).
+ */
+int scaldpc_bp_decode_batch_soft(scaldpc_bp *h, const uint8_t *in, int32_t input_kind, int32_t batch,
+                                 const float *probs, int32_t prob_cols,
+                                 int32_t max_iter, int32_t method, float alpha, uint32_t flags, void *stream,
+                                 uint8_t *out_bits, float *out_llr, int32_t *out_iters, uint8_t *out_conv);
+/*
  * Measurement aid for bench.py: on the message state left by the last (fixed-iteration)
  * decode, run `iters` back-to-back launches of the check kernel and of the variable kernel of
  * `method`, each series bracketed by HIP events on its launch stream.
@@ -215,7 +238,8 @@ int scaldpc_bp_last_stats(scaldpc_bp *h, int64_t *out);
  *   "first_fused"   1 (default) = iteration 1 of the tile kernels runs without its check pass: the first variable
  *                   pass takes the first check-to-variable messages from a per-edge table (the message of a
  *                   zero-syndrome codeword) and the row's syndrome bit; 0 = check pass (reading the priors) + plain
- *                   variable pass, both in the message form (what graphs with a row or column wider than 64 use anyway).
+ *                   variable pass, both in the message form (what graphs with a row or column wider than 64 use anyway,
+ *                   and every scaldpc_bp_decode_batch_soft call: the table is a function of the shared priors).
  *   Results never depend on any of these. */
 int scaldpc_bp_configure(scaldpc_bp *h, const char *key, const char *value);
 /* Where a handle lives, out[4]: the device it was created on; the device (hipPointerGetAttributes)

@@ -189,8 +189,13 @@ class BpDecoder:
         return self.bp_decoding
 
     # -- batched API ------------------------------------------------------------
-    def decode_batch(self, inputs, max_iter=None, early_exit=True, want_llr=False, input_vector_type=None):
+    def decode_batch(self, inputs, max_iter=None, early_exit=True, want_llr=False, input_vector_type=None,
+                     channel_probs=None):
         """inputs: [batch, m] syndromes or [batch, n] received words (any integer dtype).
+        channel_probs: None (the decoder's priors for every codeword), or a 2-D array [batch, k] of prior error
+        probabilities PER CODEWORD for the last k columns (1 <= k <= n; the columns below keep the decoder's priors):
+        hqc.decode()'s `1 - certainty` of every check with k = R on H = [Hin | I_R] (simulate/hqc.py:684-699).  Values are
+        taken as float32.  The decoder's own priors are left as they are.
         Returns dict(bits uint8 [batch, n], llr float32 [batch, n] or None,
         iters int32 [batch], converged uint8 [batch])."""
         x = np.asarray(inputs)
@@ -206,6 +211,20 @@ class BpDecoder:
         iters = np.empty(batch, dtype=np.int32)
         conv = np.empty(batch, dtype=np.uint8)
         flags = _lib.F_EARLY_EXIT if early_exit else 0
+        if channel_probs is not None:
+            cp = np.ascontiguousarray(channel_probs, dtype=np.float32)
+            if cp.ndim != 2 or cp.shape[0] != batch:
+                raise ValueError(f"channel_probs must be a 2-D array [batch = {batch}, k], got shape {cp.shape}")
+            if not 1 <= cp.shape[1] <= self.n:
+                raise ValueError(f"channel_probs covers {cp.shape[1]} columns: expected 1 to n = {self.n}")
+            _lib.check(
+                self._lib.scaldpc_bp_decode_batch_soft(
+                    self._h, _lib.ptr(x), kind, batch, _lib.ptr(cp), cp.shape[1],
+                    self.max_iter if max_iter is None else int(max_iter), self._method, self.ms_scaling_factor, flags, None,
+                    _lib.ptr(bits), _lib.ptr(llr), _lib.ptr(iters), _lib.ptr(conv),
+                )  # fmt: skip
+            )
+            return {"bits": bits, "llr": llr, "iters": iters, "converged": conv}
         _lib.check(
             self._lib.scaldpc_bp_decode_batch(
                 self._h, _lib.ptr(x), kind, batch, self.max_iter if max_iter is None else int(max_iter),
@@ -216,9 +235,22 @@ class BpDecoder:
         return {"bits": bits, "llr": llr, "iters": iters, "converged": conv}
 
     def decode_batch_device(self, d_in, kind, batch, d_out_bits, max_iter=None, early_exit=False, stream=0,
-                            d_out_llr=0, d_out_iters=0, d_out_conv=0, asynchronous=False):
-        """Device-pointer variant (ints, e.g. torch `tensor.data_ptr()`): nothing crosses PCIe."""
+                            d_out_llr=0, d_out_iters=0, d_out_conv=0, asynchronous=False, d_channel_probs=0, prob_cols=0):
+        """Device-pointer variant (ints, e.g. torch `tensor.data_ptr()`): nothing crosses PCIe.
+        d_channel_probs / prob_cols: float32 [batch, prob_cols] per-codeword priors of the last prob_cols columns (see
+        decode_batch); a value that is no probability raises ValueError when the call synchronises -- an asynchronous
+        call does not check."""
         flags = _lib.F_DEVICE_IO | (_lib.F_EARLY_EXIT if early_exit else 0) | (_lib.F_ASYNC if asynchronous else 0)
+        if d_channel_probs or prob_cols:
+            _lib.check(
+                self._lib.scaldpc_bp_decode_batch_soft(
+                    self._h, C.c_void_p(d_in), kind, batch, C.c_void_p(d_channel_probs or None), int(prob_cols),
+                    self.max_iter if max_iter is None else int(max_iter), self._method, self.ms_scaling_factor, flags,
+                    C.c_void_p(stream or None), C.c_void_p(d_out_bits), C.c_void_p(d_out_llr or None),
+                    C.c_void_p(d_out_iters or None), C.c_void_p(d_out_conv or None),
+                )  # fmt: skip
+            )
+            return
         _lib.check(
             self._lib.scaldpc_bp_decode_batch(
                 self._h, C.c_void_p(d_in), kind, batch, self.max_iter if max_iter is None else int(max_iter),

@@ -119,6 +119,10 @@ struct scaldpc_bp : HandleStreams {
     Buf<float> d_msg, d_scratch, d_post;
     Buf<u64> d_synd, d_recv, d_hard, d_done, d_conv, d_unsat;
     Buf<int> d_iters, d_remaining;
+    // a soft call's per-codeword prior LLRs (scaldpc_bp_decode_batch_soft): float [tile][prob_cols][64], sized by the call;
+    // d_soft_bad = the conversion kernel's "first value that is no probability" word; d_probs_in stages host input
+    Buf<float> d_pprior, d_probs_in;
+    Buf<u64> d_soft_bad;
     int cap_remaining = 0;  // counters per row of d_remaining (and of h_remaining)
     // d_remaining holds rem_rows rows of cap_remaining "codewords still running after iteration it" counters: every tile
     // group of a call takes the next row (zeroed once per call, not once per group: a memset is a 5 us launch in the
@@ -147,7 +151,7 @@ struct scaldpc_bp : HandleStreams {
         int cap_tiles = 0;
         Buf<u64> synd, hard, done, conv, unsat;
         Buf<int> iters, ids, slot_of;
-        Buf<float> post;
+        Buf<float> post, pprior;  // pprior: the stragglers' rows of a soft call's prior plane
     };
     static constexpr int MAX_LEVELS = 3;
     Level lv[MAX_LEVELS + 1];  // [0] unused
@@ -299,10 +303,11 @@ int grow(Buf<T, P> &b, size_t need)
 
 // tiles per group: the in-place message array of a group should stay resident in the
 // 256 MiB Infinity Cache (measured knee between 209 and 261 MB, profiles/microbench)
-int auto_group(const scaldpc_bp *h, int T)
+// plane_cols: columns of a soft call's prior plane the group's passes keep reading (256 B per tile and column next to the messages)
+int auto_group(const scaldpc_bp *h, int T, int plane_cols = 0)
 {
     const double budget = h->kn.group_mb * 1e6;  // default 215: 4 tiles of the HQC-128 bench graph = 208.9 MB, fastest measured; 261 MB falls off
-    const double per_tile = (double)h->E * TW * sizeof(float);
+    const double per_tile = ((double)h->E + plane_cols) * TW * sizeof(float);
     const int g = per_tile > 0 ? (int)(budget / per_tile) : T;
     return std::max(1, std::min(g, T));
 }
@@ -314,8 +319,9 @@ int parity_waves(const scaldpc_bp *h) { return 4 * parity_blocks(h->m); }
 
 constexpr int REM_SLOTS = 512;
 
-int ensure_workspace(scaldpc_bp *h, int T, int G, bool want_post, int max_iter)
+int ensure_workspace(scaldpc_bp *h, int T, int G, bool want_post, int max_iter, int prob_cols = 0)
 {
+    if (prob_cols) SC_TRY(grow(h->d_pprior, (size_t)T * prob_cols * TW));
     if (T > h->cap_tiles || h->m > h->ws_m || h->n > h->ws_n) {
         h->d_synd.reset(); h->d_recv.reset(); h->d_hard.reset(); h->d_done.reset();
         h->d_conv.reset(); h->d_unsat.reset(); h->d_iters.reset(); h->d_post.reset();
@@ -691,15 +697,30 @@ bool check_can_test(const scaldpc_bp *h, int method)
 }
 
 // ft: non-null = this pass also runs the convergence test of the previous iteration (check_can_test(h, method), never `first`)
+// sp: non-null = a soft call; its FIRST check pass (the only one that reads priors) takes them per codeword
 int launch_check(scaldpc_bp *h, int method, float alpha, int G, const u64 *synd_g, const u64 *done_g, int skip_done,
-                 hipStream_t s, bool first = false, int tile0 = 0, const FusedTest *ft = nullptr)
+                 hipStream_t s, bool first = false, int tile0 = 0, const FusedTest *ft = nullptr, const SoftPrior *sp = nullptr)
 {
     if (h->E == 0) return 0;
     float *const msg0 = h->d_msg + (size_t)tile0 * h->E * TW;  // tile0: first tile of a sub-group inside the group's array
     float *const scr0 = h->d_scratch ? h->d_scratch + (size_t)tile0 * h->E * TW : nullptr;
     const dim3 grid(h->row_bk.blk[h->row_bk.nb], G), block(256);  // one wave per row descriptor
     const bool test = ft && !first;
-    if (method != SCALDPC_BP_MIN_SUM) {
+    if (sp && first) {  // (first: fused_init holds, so the tanh rule's rows are register-resident)
+        if (method != SCALDPC_BP_MIN_SUM)
+            with_cap<16, 32, 64>(h->max_row_deg, [&](auto cap) {
+                hipLaunchKernelGGL((k_check_tanh_soft<cap>), grid, block, 0, s, h->d_row_list, msg0, scr0, synd_g, done_g, skip_done,
+                                   h->m, h->E, h->d_col_idx, *sp);
+            });
+        else if (h->max_row_deg <= ROW_CAP)
+            with_cap<16, 32, 64>(h->max_row_deg, [&](auto cap) {
+                hipLaunchKernelGGL((k_check_minsum_x_soft<cap>), grid, block, 0, s, h->d_row_list, msg0, synd_g, done_g, skip_done,
+                                   h->m, h->E, alpha, h->d_col_idx, *sp);
+            });
+        else
+            hipLaunchKernelGGL(k_check_minsum_soft, dim3((h->m + 3) / 4, G), block, 0, s, h->d_row_ptr, msg0, synd_g, done_g,
+                               skip_done, h->m, h->E, alpha, h->d_col_idx, *sp);
+    } else if (method != SCALDPC_BP_MIN_SUM) {
         with_cap<16, 32, 64>(h->max_row_deg, [&](auto cap) {
             if (test)
                 hipLaunchKernelGGL((k_check_tanh<cap, false, true>), grid, block, 0, s, h->row_bk, h->d_row_list, h->d_row_ptr,
@@ -783,8 +804,10 @@ int ensure_first_table(scaldpc_bp *h, int method, float alpha1, hipStream_t s)
 }
 
 // first_synd: non-null = iteration 1 without its check pass (the group's syndrome planes; ensure_first_table first)
+// sp: non-null = a soft call (never with first_synd: the first-message table is a function of shared priors)
 int launch_var(scaldpc_bp *h, int G, float *post_g, u64 *hard_g, const u64 *done_g, int skip_done, int write_out,
-               hipStream_t s, int tile0 = 0, const u64 *first_synd = nullptr, bool rec = false, bool light = false)
+               hipStream_t s, int tile0 = 0, const u64 *first_synd = nullptr, bool rec = false, bool light = false,
+               const SoftPrior *sp = nullptr)
 {
     float *const msg0 = h->d_msg + (size_t)tile0 * h->E * TW;
     float *const scr0 = h->d_scratch ? h->d_scratch + (size_t)tile0 * h->E * TW : nullptr;
@@ -808,14 +831,24 @@ int launch_var(scaldpc_bp *h, int G, float *post_g, u64 *hard_g, const u64 *done
         const dim3 gridr((unsigned)(xm ? (nb_launch + 7) / 8 * 8 : nb_launch), G);
         const int blk0 = slim && !h->var_reversed ? n1 : 0, xmap = xm ? nb_launch : 0;
         with_cap<16, 32>(h->max_col_deg, [&](auto cap) {  // (columns wider than 32 take the message form: rec_form)
-            hipLaunchKernelGGL((k_var_rec<cap>), gridr, dim3(256), 0, s, h->d_var_meta, h->d_var_rows, h->d_csc_list, h->d_csc_row,
-                               h->d_prior, msg0, h->d_rec + (size_t)tile0 * h->m * 2 * TW, h->d_mask + (size_t)tile0 * h->E,
-                               post_g, hard_g, done_g, skip_done, h->n, h->m, h->E, write_out, blk0, xmap);
+            if (sp)
+                hipLaunchKernelGGL((k_var_rec_soft<cap>), gridr, dim3(256), 0, s, h->d_var_meta, h->d_var_rows, h->d_csc_list,
+                                   h->d_csc_row, *sp, msg0, h->d_rec + (size_t)tile0 * h->m * 2 * TW,
+                                   h->d_mask + (size_t)tile0 * h->E, post_g, hard_g, done_g, skip_done, h->n, h->m, h->E, write_out,
+                                   blk0, xmap);
+            else
+                hipLaunchKernelGGL((k_var_rec<cap>), gridr, dim3(256), 0, s, h->d_var_meta, h->d_var_rows, h->d_csc_list, h->d_csc_row,
+                                   h->d_prior, msg0, h->d_rec + (size_t)tile0 * h->m * 2 * TW, h->d_mask + (size_t)tile0 * h->E,
+                                   post_g, hard_g, done_g, skip_done, h->n, h->m, h->E, write_out, blk0, xmap);
         });
     } else {
         with_cap<16, 32, 64>(h->max_col_deg, [&](auto cap) {
-            hipLaunchKernelGGL((k_var<cap>), dim3(nblk, G), dim3(256), 0, s, h->var_bk, h->d_var_meta, h->d_col_ptr, h->d_csc_list,
-                               h->d_prior, msg0, scr0, post_g, hard_g, done_g, skip_done, h->n, h->E, write_out);
+            if (sp)
+                hipLaunchKernelGGL((k_var_soft<cap>), dim3(nblk, G), dim3(256), 0, s, h->d_var_meta, h->d_csc_list, *sp, msg0, scr0,
+                                   post_g, hard_g, done_g, skip_done, h->n, h->E, write_out);
+            else
+                hipLaunchKernelGGL((k_var<cap>), dim3(nblk, G), dim3(256), 0, s, h->var_bk, h->d_var_meta, h->d_col_ptr, h->d_csc_list,
+                                   h->d_prior, msg0, scr0, post_g, hard_g, done_g, skip_done, h->n, h->E, write_out);
         });
     }
     LAUNCH_CHECK();
@@ -823,9 +856,15 @@ int launch_var(scaldpc_bp *h, int G, float *post_g, u64 *hard_g, const u64 *done
 }
 
 int launch_el_check(scaldpc_bp *h, int method, float alpha, int nb, const u64 *synd_g, const u64 *done_g,
-                    int skip_done, hipStream_t s, bool first, const u64 *hard_g = nullptr, int *unsat_prev = nullptr)
+                    int skip_done, hipStream_t s, bool first, const u64 *hard_g = nullptr, int *unsat_prev = nullptr,
+                    const SoftPrior *sp = nullptr)
 {
     with_method(method, [&](auto M) {
+        if (sp && first) {
+            hipLaunchKernelGGL((k_el_check_soft<M>), dim3((h->m + 3) / 4, nb), dim3(256), 0, s, h->d_row_ptr, h->d_col_idx, *sp,
+                               h->d_emsg, synd_g, done_g, skip_done, h->m, h->E, alpha, hard_g, unsat_prev);
+            return;
+        }
         with_bool(first, [&](auto fst) {
             hipLaunchKernelGGL((k_el_check<M, fst>), dim3((h->m + 3) / 4, nb), dim3(256), 0, s, h->d_row_ptr, h->d_col_idx,
                                h->d_prior, h->d_emsg, synd_g, done_g, skip_done, h->m, h->E, alpha, hard_g, unsat_prev);
@@ -837,14 +876,19 @@ int launch_el_check(scaldpc_bp *h, int method, float alpha, int nb, const u64 *s
 
 int launch_el_var(scaldpc_bp *h, int nb, float *post_g, u64 *hard_g, u64 *done_g, int skip_done, int write_out,
                   hipStream_t s, const int *unsat_prev = nullptr, int it_prev = 0, u64 *conv_g = nullptr,
-                  int *iters_g = nullptr, int *remaining_prev = nullptr)
+                  int *iters_g = nullptr, int *remaining_prev = nullptr, const SoftPrior *sp = nullptr)
 {
     // grid.x a multiple of 8: block x lands on the same XCD for every codeword row, so an XCD's L2
     // keeps its share of the slot table
     const unsigned gx = (unsigned)(((h->el_waves + 3) / 4 + 7) / 8 * 8);
-    hipLaunchKernelGGL(k_el_var, dim3(gx, nb), dim3(256), 0, s, (const int2 *)h->d_el_slots, h->d_el_slot_col,
-                       h->el_waves, h->d_prior, h->d_emsg, post_g, hard_g, done_g, skip_done, h->E,
-                       write_out, unsat_prev, it_prev, conv_g, iters_g, remaining_prev);
+    if (sp)
+        hipLaunchKernelGGL(k_el_var_soft, dim3(gx, nb), dim3(256), 0, s, (const int2 *)h->d_el_slots, h->d_el_slot_col,
+                           h->el_waves, *sp, h->d_emsg, post_g, hard_g, done_g, skip_done, h->E,
+                           write_out, unsat_prev, it_prev, conv_g, iters_g, remaining_prev);
+    else
+        hipLaunchKernelGGL(k_el_var, dim3(gx, nb), dim3(256), 0, s, (const int2 *)h->d_el_slots, h->d_el_slot_col,
+                           h->el_waves, h->d_prior, h->d_emsg, post_g, hard_g, done_g, skip_done, h->E,
+                           write_out, unsat_prev, it_prev, conv_g, iters_g, remaining_prev);
     LAUNCH_CHECK();
     return 0;
 }
@@ -883,6 +927,19 @@ int launch_small(scaldpc_bp *h, size_t lds, int method, int batch, const void *i
     return 0;
 }
 
+// ... with per-codeword priors (byte I/O: scaldpc_bp_decode_batch_soft)
+int launch_small_soft(scaldpc_bp *h, size_t lds, int method, int batch, const void *in, int input_kind, int max_iter, float alpha,
+                      bool early, void *bits, float *llr, int *iters, void *conv, const SoftPrior &sp, hipStream_t s)
+{
+    with_method(method, [&](auto M) {
+        hipLaunchKernelGGL((k_bp_small_soft<M>), dim3(batch), dim3(256), lds, s, h->d_row_ptr, h->d_col_idx, h->d_col_ptr,
+                           h->d_csc_edge, sp, h->m, h->n, (int)h->E, in, input_kind, max_iter, alpha, early ? 1 : 0, bits, llr,
+                           iters, conv);
+    });
+    LAUNCH_CHECK();
+    return 0;
+}
+
 float alpha_for(float alpha, int it)
 {
     // ms_scaling_factor == 0 -> 1 - 2^-iter
@@ -894,7 +951,16 @@ struct TileState {
     u64 *hard, *done, *conv, *unsat;
     int *iters;
     float *post;
+    // a soft call: prior LLRs per codeword for the columns [first_col, n), float [tile][n - first_col][64] (null: shared priors)
+    const float *pprior = nullptr;
+    int first_col = 0;
 };
+// the prior source of a launch whose first tile is `tile` of st
+SoftPrior soft_prior(const scaldpc_bp *h, const TileState &st, int tile)
+{
+    const int cols = h->n - st.first_col;
+    return SoftPrior{h->d_prior, st.pprior + (size_t)tile * cols * TW, st.first_col, cols};
+}
 
 int ensure_el_unsat(scaldpc_bp *h, int max_iter) { return h->d_el_unsat.ensure(((size_t)max_iter + 2) * TW); }
 
@@ -914,20 +980,26 @@ int iterate_el(scaldpc_bp *h, const TileState &st, int nb, int max_iter, int met
         }
     }
     const bool fused = fused_init(h, method);
+    const SoftPrior spv = st.pprior ? soft_prior(h, st, 0) : SoftPrior{};
+    const SoftPrior *const sp = st.pprior ? &spv : nullptr;
     if (!fused) {
-        hipLaunchKernelGGL(k_el_init, dim3((unsigned)((h->E + 255) / 256), nb), dim3(256), 0, s, h->d_col_idx, h->d_prior,
-                           h->d_emsg, h->E);
+        if (sp)
+            hipLaunchKernelGGL(k_el_init_soft, dim3((unsigned)((h->E + 255) / 256), nb), dim3(256), 0, s, h->d_col_idx, *sp, h->d_emsg,
+                               h->E);
+        else
+            hipLaunchKernelGGL(k_el_init, dim3((unsigned)((h->E + 255) / 256), nb), dim3(256), 0, s, h->d_col_idx, h->d_prior,
+                               h->d_emsg, h->E);
         LAUNCH_CHECK();
     }
     for (int it = 1; it <= max_iter; it++) {
         const bool last = it == max_iter, first = fused && it == 1;
         if (early) {
             int *const up = it > 1 ? h->d_el_unsat + (size_t)(it - 1) * TW : nullptr;  // verdicts on iteration it - 1
-            SC_TRY(launch_el_check(h, method, alpha_for(alpha, it), nb, st.synd, st.done, 1, s, first, st.hard, up));
-            SC_TRY(launch_el_var(h, nb, st.post, st.hard, st.done, 1, 1, s, up, it - 1, st.conv, st.iters, h->d_remaining + it - 1));
+            SC_TRY(launch_el_check(h, method, alpha_for(alpha, it), nb, st.synd, st.done, 1, s, first, st.hard, up, sp));
+            SC_TRY(launch_el_var(h, nb, st.post, st.hard, st.done, 1, 1, s, up, it - 1, st.conv, st.iters, h->d_remaining + it - 1, sp));
         } else {
-            SC_TRY(launch_el_check(h, method, alpha_for(alpha, it), nb, st.synd, st.done, 0, s, first));
-            SC_TRY(launch_el_var(h, nb, st.post, st.hard, st.done, 0, last ? 1 : 0, s));
+            SC_TRY(launch_el_check(h, method, alpha_for(alpha, it), nb, st.synd, st.done, 0, s, first, nullptr, nullptr, sp));
+            SC_TRY(launch_el_var(h, nb, st.post, st.hard, st.done, 0, last ? 1 : 0, s, nullptr, 0, nullptr, nullptr, nullptr, sp));
         }
         if (last) {
             hipLaunchKernelGGL(k_parity<true>, dim3(parity_blocks(h->m), 1), dim3(256), 0, s, h->d_row_ptr, h->d_col_idx, st.hard,
@@ -1077,9 +1149,14 @@ int iterate_tiles(scaldpc_bp *h, Lanes &lanes, const TileState &st, int g0, int 
     deal_tiles(g, nl, gs, t0);
     const int pw = parity_waves(h);
     const bool fused = fused_init(h, method);
+    const bool soft = st.pprior != nullptr;
     if (h->E && !fused) {
-        hipLaunchKernelGGL(k_init_msg, dim3((unsigned)((h->E + 3) / 4), g), dim3(256), 0, s, h->d_col_idx, h->d_prior,
-                           h->d_msg, h->E);
+        if (soft)
+            hipLaunchKernelGGL(k_init_msg_soft, dim3((unsigned)((h->E + 3) / 4), g), dim3(256), 0, s, h->d_col_idx, h->d_msg.get(), h->E,
+                               soft_prior(h, st, g0));
+        else
+            hipLaunchKernelGGL(k_init_msg, dim3((unsigned)((h->E + 3) / 4), g), dim3(256), 0, s, h->d_col_idx, h->d_prior,
+                               h->d_msg, h->E);
         LAUNCH_CHECK();
     }
     int *rem = h->d_remaining;  // this group's row of "still running" counters
@@ -1088,7 +1165,8 @@ int iterate_tiles(scaldpc_bp *h, Lanes &lanes, const TileState &st, int g0, int 
     // and every launch leaves them zero)
     if (!(chain & 1)) SC_TRY(lanes.fork(nl));  // the other lanes start after everything enqueued on `s` so far
     // iteration 1 without its check pass: the first variable pass reads the first-message table and the syndrome planes
-    const bool first_fuse = first_fusable(h, method);
+    // (a soft call runs iteration 1 WITH its check pass, reading the codewords' own priors: the first_fused = 0 sequence)
+    const bool first_fuse = first_fusable(h, method) && !soft;
     if (first_fuse) SC_TRY(ensure_first_table(h, method, alpha_for(alpha, 1), s));
     // The convergence test of iteration it rides on the check pass of it + 1 (fused_test) wherever the host does not need
     // its verdict in between: at the iterations it polls at, stops a group at, or ends with, the stand-alone launch stays.
@@ -1112,8 +1190,9 @@ int iterate_tiles(scaldpc_bp *h, Lanes &lanes, const TileState &st, int g0, int 
                                st.iters + (size_t)ta * TW, rem + (it - 1), h->n, pw, it - 1, 1};
                 verdict_pending[k] = false;
             }
+            const SoftPrior spv = soft ? soft_prior(h, st, ta) : SoftPrior{};
             SC_TRY(launch_check(h, method, alpha_for(alpha, it), gs[k], st.synd + (size_t)ta * h->m, st.done + ta, skip, lanes[k],
-                                fused && it == 1, t0[k], ft.hard ? &ft : nullptr));
+                                fused && it == 1, t0[k], ft.hard ? &ft : nullptr, soft ? &spv : nullptr));
             if (set_phase && k + 1 < nl) {
                 SC_HIP(hipEventRecord(h->ev_phase[k + 1], lanes[k]));
                 SC_HIP(hipStreamWaitEvent(lanes[k + 1], h->ev_phase[k + 1], 0));
@@ -1123,9 +1202,11 @@ int iterate_tiles(scaldpc_bp *h, Lanes &lanes, const TileState &st, int g0, int 
         for (int k = 0; k < nl; k++) {
             const int ta = g0 + t0[k];
             // (the record form starts with iteration 2: an iteration 1 that has a check pass ran it in the message form)
+            const SoftPrior spv = soft ? soft_prior(h, st, ta) : SoftPrior{};
             SC_TRY(launch_var(h, gs[k], st.post ? st.post + (size_t)ta * h->n * TW : nullptr, st.hard + (size_t)ta * h->n,
                               st.done + ta, skip, (early || last) ? 1 : 0, lanes[k], t0[k],
-                              no_check ? st.synd + (size_t)ta * h->m : nullptr, it > 1 && rec_form(h, method), it > 1));
+                              no_check ? st.synd + (size_t)ta * h->m : nullptr, it > 1 && rec_form(h, method), it > 1,
+                              soft ? &spv : nullptr));
             if (ride && !last && !poll) {
                 verdict_pending[k] = true;  // the next check pass of this lane carries the test
             } else if (early || last) {  // convergence test + latch, one launch
@@ -1284,15 +1365,22 @@ int decode_level(scaldpc_bp *h, int lvl, const TileState &st, int batch, int T, 
     }
     SC_TRY(grow(L.slot_of, (size_t)T * TW));
     if (want_post) SC_TRY(grow(L.post, (size_t)T2 * h->n * TW));
+    const int pcols = st.pprior ? h->n - st.first_col : 0;
+    if (pcols) SC_TRY(grow(L.pprior, (size_t)T2 * pcols * TW));
     SC_HIP(hipMemcpyAsync(L.ids, ids.data(), sizeof(int) * ids.size(), hipMemcpyHostToDevice, s));
     SC_HIP(hipMemcpyAsync(L.slot_of, slot_of.data(), sizeof(int) * slot_of.size(), hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_gather_planes, dim3((h->m + 63) / 64, T2), dim3(256), 0, s, st.synd, h->m, L.ids, L.synd);
     LAUNCH_CHECK();
+    if (pcols) {  // the stragglers' priors go with them
+        hipLaunchKernelGGL(k_gather_prior, dim3((pcols + 3) / 4, T2), dim3(256), 0, s, st.pprior, pcols, L.ids, L.pprior);
+        LAUNCH_CHECK();
+    }
     hipLaunchKernelGGL(k_init_state, dim3(T2), dim3(64), 0, s, batch2, max_iter, L.done, L.conv, L.iters);
     LAUNCH_CHECK();
     SC_HIP(hipMemsetAsync(L.hard, 0, sizeof(u64) * (size_t)T2 * h->n, s));
     SC_HIP(hipStreamSynchronize(s));  // ids / slot_of are locals, and the level below reuses the stream
-    const TileState st2{L.synd, L.hard, L.done, L.conv, L.unsat, L.iters, want_post ? L.post : nullptr};
+    const TileState st2{L.synd, L.hard, L.done, L.conv, L.unsat, L.iters, want_post ? L.post : nullptr,
+                        pcols ? L.pprior.get() : nullptr, st.first_col};
     SC_TRY(decode_level(h, lvl + 1, st2, batch2, T2, G, max_iter, method, alpha, early, want_post, s));
     hipLaunchKernelGGL(k_scatter_planes, dim3((h->n + 63) / 64, T), dim3(256), 0, s, st.hard, h->n, L.slot_of, L.hard);
     LAUNCH_CHECK();
@@ -1308,8 +1396,9 @@ int decode_level(scaldpc_bp *h, int lvl, const TileState &st, int batch, int T, 
 // The decode proper, on inputs already staged as planes (h->d_synd; h->d_recv when the
 // caller wants e XOR v): state reset, then decode_level.
 // Results stay on the device (h->d_hard / d_post / d_conv / d_iters).
+// pprior / first_col: a soft call's prior plane (h->d_pprior) and its first column; null = the handle's shared priors.
 int run_core(scaldpc_bp *h, int batch, int T, int G, int max_iter, int method, float alpha, bool early,
-             bool want_post, hipStream_t s)
+             bool want_post, hipStream_t s, const float *pprior = nullptr, int first_col = 0)
 {
     if (!h->small_prepared) {
         hipLaunchKernelGGL(k_init_state, dim3(T), dim3(64), 0, s, batch, max_iter, h->d_done, h->d_conv, h->d_iters);
@@ -1326,7 +1415,7 @@ int run_core(scaldpc_bp *h, int batch, int T, int G, int max_iter, int method, f
         return launch_small<true>(h, lds, method, batch, h->d_synd, SCALDPC_IN_SYNDROME, max_iter, alpha, early, h->d_hard,
                                   want_post ? h->d_post.get() : nullptr, h->d_iters, h->d_conv, s);
     const TileState st{h->d_synd, h->d_hard, h->d_done, h->d_conv, h->d_unsat, h->d_iters,
-                       want_post ? h->d_post : nullptr};
+                       want_post ? h->d_post : nullptr, pprior, first_col};
     return decode_level(h, 0, st, batch, T, G, max_iter, method, alpha, early, want_post, s);
 }
 
@@ -1868,7 +1957,7 @@ int scaldpc_bp_append_rows(scaldpc_bp *h, int32_t nrows, const int32_t *row_ptr,
     h->cap_rec_group = 0;
     for (auto &L : h->lv) {
         L.synd.reset(); L.hard.reset(); L.done.reset(); L.conv.reset(); L.unsat.reset();
-        L.iters.reset(); L.ids.reset(); L.post.reset();
+        L.iters.reset(); L.ids.reset(); L.post.reset(); L.pprior.reset();
         L.cap_tiles = 0;
     }
     h->last_group = 0;
@@ -1904,9 +1993,11 @@ int scaldpc_bp_set_tile_group(scaldpc_bp *h, int32_t tiles)
     return 0;
 }
 
-int scaldpc_bp_decode_batch(scaldpc_bp *h, const uint8_t *in, int32_t input_kind, int32_t batch, int32_t max_iter_arg,
-                            int32_t method, float alpha, uint32_t flags, void *stream, uint8_t *out_bits,
-                            float *out_llr, int32_t *out_iters, uint8_t *out_conv)
+// Both decode entry points.  probs / prob_cols: a soft call's per-codeword probabilities of the last prob_cols columns
+// (float [batch][prob_cols], where `in` lives); prob_cols = 0: the handle's shared priors, the plain call.
+static int decode_batch_impl(scaldpc_bp *h, const uint8_t *in, int32_t input_kind, int32_t batch, const float *probs,
+                             int32_t prob_cols, int32_t max_iter_arg, int32_t method, float alpha, uint32_t flags, void *stream,
+                             uint8_t *out_bits, float *out_llr, int32_t *out_iters, uint8_t *out_conv)
 {
     if (!h || !in || !out_bits) return fail(SCALDPC_EINVAL, "NULL argument");
     if (batch <= 0) return fail(SCALDPC_EINVAL, "batch must be positive (got %d)", batch);
@@ -1917,6 +2008,7 @@ int scaldpc_bp_decode_batch(scaldpc_bp *h, const uint8_t *in, int32_t input_kind
     if (!(alpha >= 0.0f)) return fail(SCALDPC_EINVAL, "ms_scaling_factor must be >= 0");
     std::lock_guard<std::mutex> lk(h->mu);
     SC_TRY(check_usable(h));
+    if (prob_cols > h->n) return fail(SCALDPC_EINVAL, "prob_cols = %d exceeds the block length n = %d", prob_cols, h->n);
     DeviceGuard dg(h->device);
     Call c;
     SC_TRY(begin_call(h, batch, max_iter_arg, stream, &c));
@@ -1928,10 +2020,18 @@ int scaldpc_bp_decode_batch(scaldpc_bp *h, const uint8_t *in, int32_t input_kind
     CacheBypass guard(h->async_used);
     const hipStream_t s = c.s;
     SyncOnError settle{s};
-    const int T = c.T, G = c.G, max_iter = c.max_iter;
+    const int T = c.T, max_iter = c.max_iter;
     const int len = input_kind == SCALDPC_IN_SYNDROME ? h->m : h->n;
     const Outputs out{out_bits, out_llr, out_iters, out_conv};
     Outputs dev;
+    const bool soft = prob_cols > 0;
+    const int first_col = h->n - prob_cols;
+    // host probabilities are checked before anything is enqueued (device ones by the conversion kernel: soft_verdict)
+    if (soft && !dev_io)
+        for (size_t i = 0, cnt = (size_t)batch * prob_cols; i < cnt; i++)
+            if (!(probs[i] >= 0.0f && probs[i] <= 1.0f))
+                return fail(SCALDPC_EINVAL, "channel_probs[%zu][%zu] = %g is not a probability (codeword %zu, column %zu)",
+                            i / prob_cols, i % prob_cols, (double)probs[i], i / prob_cols, first_col + i % prob_cols);
 
     // Small graph: the LDS-resident single-launch decoder (k_bp_small).
     const size_t lds = small_lds(h);
@@ -1939,18 +2039,65 @@ int scaldpc_bp_decode_batch(scaldpc_bp *h, const uint8_t *in, int32_t input_kind
         SC_TRY(refresh_full(h));
     if (h->kn.path == Knobs::LDS && !lds)  // "stream" / "edge" / "lds" pin a path (tests)
         return fail(SCALDPC_EINVAL, "SCALDPC_PATH=lds but the graph needs %zu B of LDS", small_lds_bytes(h));
+    // a soft call: probabilities -> the LLR plane h->d_pprior (enqueued once the plane is allocated) ...
+    auto soft_convert = [&]() -> int {
+        const float *dp = probs;
+        const size_t cnt = (size_t)batch * prob_cols;
+        if (!dev_io) {
+            SC_TRY(grow(h->d_probs_in, cnt));
+            SC_HIP(hipMemcpyAsync(h->d_probs_in, probs, sizeof(float) * cnt, hipMemcpyHostToDevice, s));
+            dp = h->d_probs_in;
+        }
+        SC_TRY(h->d_soft_bad.ensure(1));
+        SC_HIP(hipMemsetAsync(h->d_soft_bad, 0xff, sizeof(u64), s));
+        hipLaunchKernelGGL(k_soft_convert, dim3((prob_cols + 63) / 64, T), dim3(256), 0, s, dp, prob_cols, batch, h->d_pprior.get(),
+                           h->d_soft_bad.get());
+        LAUNCH_CHECK();
+        return 0;
+    };
+    // ... and what the conversion kernel found, at the call's synchronise (an SCALDPC_F_ASYNC call does not look)
+    auto soft_verdict = [&]() -> int {
+        u64 bad = ~0ull;
+        SC_HIP(hipMemcpyAsync(&bad, h->d_soft_bad, sizeof(u64), hipMemcpyDeviceToHost, s));
+        SC_HIP(hipStreamSynchronize(s));
+        if (bad != ~0ull)
+            return fail(SCALDPC_EINVAL, "channel_probs[%llu][%llu] is not a probability (codeword %llu, column %llu)", bad / prob_cols,
+                        bad % prob_cols, bad / prob_cols, first_col + bad % prob_cols);
+        return 0;
+    };
     if (lds) {
         const uint8_t *din = in;
         SC_TRY(stage_input(h, in, (size_t)batch * len, dev_io, s, &din));
         SC_TRY(stage_outputs(h, out, batch, dev_io, true, &dev));
-        SC_TRY(launch_small<false>(h, lds, method, batch, din, input_kind, max_iter, alpha, early, dev.bits, dev.llr, dev.iters,
-                                   dev.conv, s));
+        if (soft) {
+            SC_TRY(grow(h->d_pprior, (size_t)T * prob_cols * TW));
+            SC_TRY(soft_convert());
+            SC_TRY(launch_small_soft(h, lds, method, batch, din, input_kind, max_iter, alpha, early, dev.bits, dev.llr, dev.iters,
+                                     dev.conv, SoftPrior{h->d_prior, h->d_pprior, first_col, prob_cols}, s));
+        } else
+            SC_TRY(launch_small<false>(h, lds, method, batch, din, input_kind, max_iter, alpha, early, dev.bits, dev.llr, dev.iters,
+                                       dev.conv, s));
         SC_TRY(copy_outputs(h, out, dev, batch, dev_io, s));
         h->stat_deferred = 0;
+        if (soft && !(flags & SCALDPC_F_ASYNC)) SC_TRY(soft_verdict());
         if (!(flags & SCALDPC_F_ASYNC)) SC_HIP(hipStreamSynchronize(s));
         return settle.done();
     }
-    SC_TRY(ensure_workspace(h, T, G, out_llr != nullptr, max_iter));
+    int G = c.G;
+    if (soft && h->tile_group <= 0) {
+        // the plane's rows share the cache with the group's messages where its passes keep reading them: every pass of an
+        // early-exit run and every message-form pass reads all of them, a record-form pass without output only the
+        // columns of degree >= 2 (launch_var: `light`)
+        int cols = prob_cols;
+        if (!early && rec_form(h, method)) {
+            cols = 0;
+            for (int v = first_col; v < h->n; v++) cols += h->hg_cdeg[v] > 1;
+        }
+        G = auto_group(h, T, cols);
+    }
+    SC_TRY(ensure_workspace(h, T, G, out_llr != nullptr, max_iter, prob_cols));
+    if (soft) SC_TRY(soft_convert());
+    const float *const pprior = soft ? h->d_pprior.get() : nullptr;
 
     // ---- a handful of codewords from host buffers: fused reshaping, one copy each way ------------------
     if (!dev_io && T == 1 && batch <= 8 && max_iter <= 1024) {
@@ -1970,7 +2117,7 @@ int scaldpc_bp_decode_batch(scaldpc_bp *h, const uint8_t *in, int32_t input_kind
         LAUNCH_CHECK();
         if (recvd) SC_TRY(launch_syndrome(h, h->d_recv, h->d_synd, 1, s));
         h->small_prepared = true;
-        const int rc = run_core(h, batch, T, G, max_iter, method, alpha, early, out_llr != nullptr, s);
+        const int rc = run_core(h, batch, T, G, max_iter, method, alpha, early, out_llr != nullptr, s, pprior, first_col);
         h->small_prepared = false;
         SC_TRY(rc);
         hipLaunchKernelGGL(k_small_unpack, dim3((h->n + 255) / 256), dim3(256), 0, s, h->d_hard, recvd ? h->d_recv : (const u64 *)nullptr,
@@ -2001,7 +2148,7 @@ int scaldpc_bp_decode_batch(scaldpc_bp *h, const uint8_t *in, int32_t input_kind
         LAUNCH_CHECK();
         SC_TRY(launch_syndrome(h, h->d_recv, h->d_synd, T, s));
     }
-    SC_TRY(run_core(h, batch, T, G, max_iter, method, alpha, early, out_llr != nullptr, s));
+    SC_TRY(run_core(h, batch, T, G, max_iter, method, alpha, early, out_llr != nullptr, s, pprior, first_col));
 
     // ---- outputs --------------------------------------------------------------
     SC_TRY(stage_outputs(h, out, batch, dev_io, true, &dev));
@@ -2017,8 +2164,27 @@ int scaldpc_bp_decode_batch(scaldpc_bp *h, const uint8_t *in, int32_t input_kind
         LAUNCH_CHECK();
     }
     SC_TRY(copy_outputs(h, out, dev, batch, dev_io, s));
+    if (soft && !(flags & SCALDPC_F_ASYNC)) SC_TRY(soft_verdict());
     if (!(flags & SCALDPC_F_ASYNC)) SC_HIP(hipStreamSynchronize(s));
     return settle.done();
+}
+
+int scaldpc_bp_decode_batch(scaldpc_bp *h, const uint8_t *in, int32_t input_kind, int32_t batch, int32_t max_iter,
+                            int32_t method, float alpha, uint32_t flags, void *stream, uint8_t *out_bits,
+                            float *out_llr, int32_t *out_iters, uint8_t *out_conv)
+{
+    return decode_batch_impl(h, in, input_kind, batch, nullptr, 0, max_iter, method, alpha, flags, stream, out_bits, out_llr,
+                             out_iters, out_conv);
+}
+
+int scaldpc_bp_decode_batch_soft(scaldpc_bp *h, const uint8_t *in, int32_t input_kind, int32_t batch, const float *probs,
+                                 int32_t prob_cols, int32_t max_iter, int32_t method, float alpha, uint32_t flags, void *stream,
+                                 uint8_t *out_bits, float *out_llr, int32_t *out_iters, uint8_t *out_conv)
+{
+    if (!h || !probs) return fail(SCALDPC_EINVAL, "NULL argument");
+    if (prob_cols < 1) return fail(SCALDPC_EINVAL, "prob_cols = %d: at least one column", prob_cols);
+    return decode_batch_impl(h, in, input_kind, batch, probs, prob_cols, max_iter, method, alpha, flags, stream, out_bits, out_llr,
+                             out_iters, out_conv);
 }
 
 // ---------------------------------------------------------------------------

@@ -2,6 +2,7 @@
 // the scheduling and the C ABI).  Everything lives in an anonymous namespace of that one
 // translation unit; the split is for reading, not for linking.
 #pragma once
+#include "scaldpc_logf.h"  // glibc's logf on the device (k_soft_convert)
 
 // v_writelane_b32 as an instruction the COMPILER emits: ROCm 7.2's clang has no __builtin_amdgcn_writelane, but the LLVM
 // intrinsic is reachable through an asm label.  Unlike an `asm("v_writelane_b32 ...")` statement the hazard recogniser
@@ -28,6 +29,31 @@ constexpr int ROW_CAP = 64;  // largest register-resident row degree (also the s
 #endif
 
 __device__ __forceinline__ int rfl(int x) { return __builtin_amdgcn_readfirstlane(x); }
+
+// Where a kernel takes the prior LLR of column v for codeword `lane` of tile `tl` from.  Every kernel that consumes a
+// prior has a body templated on the source and two entry points: the plain one (SharedPrior: the handle's one prior per
+// column, a wave-uniform read) and a `_soft` one (SoftPrior: scaldpc_bp_decode_batch_soft).
+struct SharedPrior {
+    const float *prior;  // [n]
+    __device__ __forceinline__ float operator()(int v, int, int) const { return prior[v]; }
+};
+// Per-codeword priors for the columns [first_col, first_col + cols): plane = float [tile][cols][64] of LLRs, one coalesced
+// 256-B row per (tile, column) like every message access; the columns below keep the shared prior.  The address is
+// selected, then ONE load issued: straight-line code in the exact-degree kernels, and no read of the plane for a column it
+// does not hold.  (Measured against two other forms on the first check pass of the HQC-128 graph, 51-edge rows: a branch
+// per edge, and both loads followed by a select, need 151 / 133 VGPRs and up to 1414 SGPR spills against this form's 126
+// and none; profiles/soft_priors/README.md.)
+// (tl counts from the first tile of the launch: the host passes the plane of that tile.)
+struct SoftPrior {
+    const float *prior;  // [n]
+    const float *plane;  // [tile][cols][64]
+    int first_col, cols;
+    __device__ __forceinline__ float operator()(int v, int tl, int lane) const
+    {
+        const float *src = v >= first_col ? plane + ((size_t)tl * cols + (v - first_col)) * 64 + lane : prior + v;
+        return *src;
+    }
+};
 
 // Degree buckets of one fused launch: blocks [blk[b], blk[b+1]) work on the nodes
 // list[off[b] .. off[b]+cnt[b]) with unroll bound maxd[b] (0 = any-degree fallback).
@@ -91,6 +117,37 @@ __global__ __launch_bounds__(256) void k_unpack_llr(const float *__restrict__ po
         const long b = (long)t * TW + c;
         if (b < batch && v0 + lane < n) out[(size_t)b * n + v0 + lane] = tile[lane][c];
     }
+}
+
+// Per-codeword channel probabilities float [batch][cols] (one row per codeword, as scaldpc_bp_decode_batch_soft receives
+// them) -> the LLR plane float [tile][cols][64] SoftPrior reads: k_unpack_llr's 64 x 64 LDS transpose in the other
+// direction, both sides coalesced.  llr = logf((1 - p) / p) in f32 with glibc's logf and the correctly rounded division:
+// value for value what prior_llrs computes on the host (p = 0 / p = 1 -> +-inf).  The lanes of a ragged last tile get
+// LLR 0.  A value that is no probability (outside [0, 1], NaN) leaves the smallest such index b * cols + j in *bad
+// (preset to ~0) and an LLR of 0 in the plane.
+// grid (ceil(cols/64), T), block 256.
+__global__ __launch_bounds__(256) void k_soft_convert(const float *__restrict__ probs, int cols, int batch,
+                                                      float *__restrict__ plane, u64 *__restrict__ bad)
+{
+    __shared__ float tile[64][65];
+    const int t = blockIdx.y, j0 = blockIdx.x * 64;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    for (int c = w; c < 64; c += 4) {
+        const long b = (long)t * TW + c;
+        float l = 0.0f;
+        if (b < batch && j0 + lane < cols) {
+            const size_t i = (size_t)b * cols + j0 + lane;
+            const float p = probs[i];
+            if (p >= 0.0f && p <= 1.0f)
+                l = scaldpc::glibc_logf((1.0f - p) / p);
+            else
+                atomicMin(bad, (u64)i);
+        }
+        tile[c][lane] = l;
+    }
+    __syncthreads();
+    for (int j = w; j < 64; j += 4)
+        if (j0 + j < cols) plane[((size_t)t * cols + j0 + j) * TW + lane] = tile[lane][j];
 }
 
 // conv planes + iteration counters -> int32 iters[batch], uint8 conv[batch].  grid T, block 64.
@@ -505,13 +562,23 @@ __global__ __launch_bounds__(256) void k_parity_fin_sharded(const int *__restric
 // K1  initial bit-to-check messages: msg[tile][e][:] = LLR prior of the edge's column.
 // grid (ceil(E/4), G), block 256 = 4 waves, wave = one 256 B edge row.
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_init_msg(const int *__restrict__ col_idx, const float *__restrict__ prior,
-                                                  float *__restrict__ msg, long E)
+template <class P>
+__device__ __forceinline__ void init_msg_body(const int *__restrict__ col_idx, P pr, float *__restrict__ msg, long E)
 {
     const int lane = threadIdx.x & 63;
     const long e = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (e >= E) return;
-    msg[((size_t)blockIdx.y * E + e) * TW + lane] = prior[col_idx[e]];
+    msg[((size_t)blockIdx.y * E + e) * TW + lane] = pr(col_idx[e], blockIdx.y, lane);
+}
+__global__ __launch_bounds__(256) void k_init_msg(const int *__restrict__ col_idx, const float *__restrict__ prior,
+                                                  float *__restrict__ msg, long E)
+{
+    init_msg_body(col_idx, SharedPrior{prior}, msg, E);
+}
+__global__ __launch_bounds__(256) void k_init_msg_soft(const int *__restrict__ col_idx, float *__restrict__ msg, long E,
+                                                       SoftPrior sp)
+{
+    init_msg_body(col_idx, sp, msg, E);
 }
 
 // ---------------------------------------------------------------------------
@@ -527,11 +594,11 @@ __global__ __launch_bounds__(256) void k_init_msg(const int *__restrict__ col_id
 // ---------------------------------------------------------------------------
 // FIRST: iteration 1 takes its inputs straight from the priors (v2c = prior of the edge's
 // column by definition), so the message array needs no initialisation pass and is not read.
-template <bool FIRST>
-__global__ __launch_bounds__(256) void k_check_minsum(const int *__restrict__ row_ptr, float *msg,
-                                                      const u64 *__restrict__ synd, const u64 *__restrict__ done,
-                                                      int skip_done, int m, long E, float alpha,
-                                                      const int *__restrict__ col_idx, const float *__restrict__ prior)
+template <bool FIRST, class P>
+__device__ __forceinline__ void check_minsum_body(const int *__restrict__ row_ptr, float *msg,
+                                                  const u64 *__restrict__ synd, const u64 *__restrict__ done,
+                                                  int skip_done, int m, long E, float alpha,
+                                                  const int *__restrict__ col_idx, P prior)
 {
     const int lane = threadIdx.x & 63;
     const int r = rfl((int)blockIdx.x * 4 + (int)(threadIdx.x >> 6));  // uniform: row_ptr / synd / done go through scalar loads
@@ -546,7 +613,7 @@ __global__ __launch_bounds__(256) void k_check_minsum(const int *__restrict__ ro
     int ix = 0;
 #pragma unroll 16
     for (int k = 0; k < deg; k++) {
-        const float x = FIRST ? prior[rfl(col_idx[e0 + k])] : p[(size_t)k * TW];
+        const float x = FIRST ? prior(rfl(col_idx[e0 + k]), tl, lane) : p[(size_t)k * TW];
         const float a = fabsf(x);
         const unsigned n_ = x <= 0.0f;
         par ^= n_;
@@ -558,9 +625,25 @@ __global__ __launch_bounds__(256) void k_check_minsum(const int *__restrict__ ro
     const float nalpha = -alpha;
 #pragma unroll 8
     for (int k = 0; k < deg; k++) {
-        const unsigned b = (unsigned)((FIRST ? prior[rfl(col_idx[e0 + k])] : p[(size_t)k * TW]) <= 0.0f);
+        const unsigned b = (unsigned)((FIRST ? prior(rfl(col_idx[e0 + k]), tl, lane) : p[(size_t)k * TW]) <= 0.0f);
         p[(size_t)k * TW] = ((k == ix) ? m2 : m1) * ((par ^ b) ? nalpha : alpha);
     }
+}
+template <bool FIRST>
+__global__ __launch_bounds__(256) void k_check_minsum(const int *__restrict__ row_ptr, float *msg,
+                                                      const u64 *__restrict__ synd, const u64 *__restrict__ done,
+                                                      int skip_done, int m, long E, float alpha,
+                                                      const int *__restrict__ col_idx, const float *__restrict__ prior)
+{
+    check_minsum_body<FIRST>(row_ptr, msg, synd, done, skip_done, m, E, alpha, col_idx, SharedPrior{prior});
+}
+// the first check pass of a soft call (rows wider than 64)
+__global__ __launch_bounds__(256) void k_check_minsum_soft(const int *__restrict__ row_ptr, float *msg,
+                                                           const u64 *__restrict__ synd, const u64 *__restrict__ done,
+                                                           int skip_done, int m, long E, float alpha,
+                                                           const int *__restrict__ col_idx, SoftPrior sp)
+{
+    check_minsum_body<true>(row_ptr, msg, synd, done, skip_done, m, E, alpha, col_idx, sp);
 }
 
 // Register-resident form for rows of degree <= 64: straight-line code instantiated for the
@@ -569,13 +652,13 @@ __global__ __launch_bounds__(256) void k_check_minsum(const int *__restrict__ ro
 // results are identical.  One descriptor per wave of the launch {row or -1, first edge,
 // degree, bound} through scalar loads.  (The loop kernel keeps 8-16 loads in flight: 61.2 us
 // per 4-tile launch against this form's -- see DESIGN.md.)
-template <int DEG, bool FIRST>
-__device__ __forceinline__ void check_minsum_row(float *p, unsigned par, float alpha, const float *__restrict__ prior,
-                                                 const int *__restrict__ cidx)
+template <int DEG, bool FIRST, class P>
+__device__ __forceinline__ void check_minsum_row(float *p, unsigned par, float alpha, P prior, const int *__restrict__ cidx,
+                                                 int tl, int lane)
 {
     float x[DEG];
 #pragma unroll
-    for (int k = 0; k < DEG; k++) x[k] = FIRST ? prior[rfl(cidx[k])] : p[(size_t)k * TW];
+    for (int k = 0; k < DEG; k++) x[k] = FIRST ? prior(rfl(cidx[k]), tl, lane) : p[(size_t)k * TW];
     float m1 = FLT_MAX, m2 = FLT_MAX;
     int ix = 0;
 #pragma unroll
@@ -594,12 +677,11 @@ __device__ __forceinline__ void check_minsum_row(float *p, unsigned par, float a
 }
 
 // PAR: the convergence test of the previous iteration rides on this pass (fused_test; early-exit runs, never FIRST).
-template <int CAP, bool FIRST, bool PAR = false>
-__global__ __launch_bounds__(256) void k_check_minsum_x(const int *__restrict__ list, float *msg,
-                                                        const u64 *__restrict__ synd, const u64 *done,
-                                                        int skip_done, int m, long E, float alpha,
-                                                        const int *__restrict__ col_idx, const float *__restrict__ prior,
-                                                        FusedTest ft = FusedTest{})
+template <int CAP, bool FIRST, bool PAR, class P>
+__device__ __forceinline__ void check_minsum_x_body(const int *__restrict__ list, float *msg,
+                                                    const u64 *__restrict__ synd, const u64 *done,
+                                                    int skip_done, int m, long E, float alpha,
+                                                    const int *__restrict__ col_idx, P prior, const FusedTest &ft)
 {
     const int lane = threadIdx.x & 63;
     const int tl = blockIdx.y;
@@ -622,7 +704,7 @@ __global__ __launch_bounds__(256) void k_check_minsum_x(const int *__restrict__ 
         const unsigned sbit = (unsigned)(synd[(size_t)tl * m + r] >> lane) & 1u;
 #define MR(D)                                                                                   \
     case D:                                                                                     \
-        if constexpr (D <= CAP) check_minsum_row<D, FIRST>(p, sbit, alpha, prior, col_idx + e0); \
+        if constexpr (D <= CAP) check_minsum_row<D, FIRST>(p, sbit, alpha, prior, col_idx + e0, tl, lane); \
         break;
 #define MR8(D) MR(D) MR(D + 1) MR(D + 2) MR(D + 3) MR(D + 4) MR(D + 5) MR(D + 6) MR(D + 7)
         switch (deg) {
@@ -635,6 +717,24 @@ __global__ __launch_bounds__(256) void k_check_minsum_x(const int *__restrict__ 
 #undef MR
     }
     if constexpr (PAR) fused_commit(ft, tl, bad, dw);
+}
+template <int CAP, bool FIRST, bool PAR = false>
+__global__ __launch_bounds__(256) void k_check_minsum_x(const int *__restrict__ list, float *msg,
+                                                        const u64 *__restrict__ synd, const u64 *done,
+                                                        int skip_done, int m, long E, float alpha,
+                                                        const int *__restrict__ col_idx, const float *__restrict__ prior,
+                                                        FusedTest ft = FusedTest{})
+{
+    check_minsum_x_body<CAP, FIRST, PAR>(list, msg, synd, done, skip_done, m, E, alpha, col_idx, SharedPrior{prior}, ft);
+}
+// the first check pass of a soft call
+template <int CAP>
+__global__ __launch_bounds__(256) void k_check_minsum_x_soft(const int *__restrict__ list, float *msg,
+                                                             const u64 *__restrict__ synd, const u64 *done,
+                                                             int skip_done, int m, long E, float alpha,
+                                                             const int *__restrict__ col_idx, SoftPrior sp)
+{
+    check_minsum_x_body<CAP, true, false>(list, msg, synd, done, skip_done, m, E, alpha, col_idx, sp, FusedTest{});
 }
 
 // ---------------------------------------------------------------------------
@@ -802,9 +902,8 @@ __device__ __forceinline__ float compl_step(float U, float u) { return fmaf(u, 1
 
 // FIRST: iteration 1 takes its inputs from the priors of the row's columns (cidx = the row's
 // slice of col_idx), so the message array needs no initialisation pass and is not read.
-template <int DEG, bool FIRST>
-__device__ __forceinline__ void check_tanh_row(float *p, unsigned sbit, const float *__restrict__ prior,
-                                               const int *__restrict__ cidx)
+template <int DEG, bool FIRST, class P>
+__device__ __forceinline__ void check_tanh_row(float *p, unsigned sbit, P prior, const int *__restrict__ cidx, int tl, int lane)
 {
     // EXACT degree: straight-line code, no per-edge branches (a predicated `k < deg` unroll
     // makes every edge its own basic block, and the compiler then waits for all memory
@@ -814,7 +913,7 @@ __device__ __forceinline__ void check_tanh_row(float *p, unsigned sbit, const fl
     // the sign of exact zeros can differ from the `x < 0` convention), finally the output.
     float uu[DEG], pre[DEG];
 #pragma unroll
-    for (int k = 0; k < DEG; k++) uu[k] = FIRST ? prior[rfl(cidx[k])] : p[(size_t)k * TW];
+    for (int k = 0; k < DEG; k++) uu[k] = FIRST ? prior(rfl(cidx[k]), tl, lane) : p[(size_t)k * TW];
     unsigned acc = sbit << 31;  // running XOR of sign bits, syndrome folded in
     float U = 0.0f;
 #pragma unroll
@@ -870,12 +969,11 @@ __device__ __forceinline__ void check_tanh_row_generic(float *p, float *sc, int 
 // so graphs with narrow rows get the high-occupancy build).
 // grid (bk.blk[nb], G), block 256 = 4 rows of one bucket.
 // PAR: the convergence test of the previous iteration rides on this pass (fused_test; early-exit runs, never FIRST).
-template <int CAP, bool FIRST, bool PAR = false>
-__global__ __launch_bounds__(256) void k_check_tanh(Buckets bk, const int *__restrict__ list,
-                                                    const int *__restrict__ row_ptr, float *msg, float *scratch,
-                                                    const u64 *__restrict__ synd, const u64 *done,
-                                                    int skip_done, int m, long E, const int *__restrict__ col_idx,
-                                                    const float *__restrict__ prior, FusedTest ft = FusedTest{})
+template <int CAP, bool FIRST, bool PAR, class P>
+__device__ __forceinline__ void check_tanh_body(const int *__restrict__ list, float *msg, float *scratch,
+                                                const u64 *__restrict__ synd, const u64 *done,
+                                                int skip_done, int m, long E, const int *__restrict__ col_idx,
+                                                P prior, const FusedTest &ft)
 {
     const int lane = threadIdx.x & 63;
     const int tl = blockIdx.y;
@@ -902,7 +1000,7 @@ __global__ __launch_bounds__(256) void k_check_tanh(Buckets bk, const int *__res
         // dispatch on the row's exact degree (wave-uniform); CAP bounds what is compiled in
 #define TR(D)                                                                              \
     case D:                                                                                \
-        if constexpr (D <= CAP) check_tanh_row<D, FIRST>(p, sbit, prior, col_idx + e0);    \
+        if constexpr (D <= CAP) check_tanh_row<D, FIRST>(p, sbit, prior, col_idx + e0, tl, lane); \
         break;
 #define TR8(D) TR(D) TR(D + 1) TR(D + 2) TR(D + 3) TR(D + 4) TR(D + 5) TR(D + 6) TR(D + 7)
         if (md[3] == 0) {
@@ -919,6 +1017,24 @@ __global__ __launch_bounds__(256) void k_check_tanh(Buckets bk, const int *__res
 #undef TR
     }
     if constexpr (PAR) fused_commit(ft, tl, bad, dw);
+}
+template <int CAP, bool FIRST, bool PAR = false>
+__global__ __launch_bounds__(256) void k_check_tanh(Buckets bk, const int *__restrict__ list,
+                                                    const int *__restrict__ row_ptr, float *msg, float *scratch,
+                                                    const u64 *__restrict__ synd, const u64 *done,
+                                                    int skip_done, int m, long E, const int *__restrict__ col_idx,
+                                                    const float *__restrict__ prior, FusedTest ft = FusedTest{})
+{
+    check_tanh_body<CAP, FIRST, PAR>(list, msg, scratch, synd, done, skip_done, m, E, col_idx, SharedPrior{prior}, ft);
+}
+// the first check pass of a soft call
+template <int CAP>
+__global__ __launch_bounds__(256) void k_check_tanh_soft(const int *__restrict__ list, float *msg, float *scratch,
+                                                         const u64 *__restrict__ synd, const u64 *done,
+                                                         int skip_done, int m, long E, const int *__restrict__ col_idx,
+                                                         SoftPrior sp)
+{
+    check_tanh_body<CAP, true, false>(list, msg, scratch, synd, done, skip_done, m, E, col_idx, sp, FusedTest{});
 }
 
 // ---------------------------------------------------------------------------
@@ -938,14 +1054,14 @@ __global__ __launch_bounds__(256) void k_check_tanh(Buckets bk, const int *__res
 // PLANES = true : bit-plane I/O for the Monte-Carlo entry points (in = syndrome planes
 //                 u64 [tile][m]; out_bits = hard planes u64 [tile][n], zeroed by the caller;
 //                 out_conv = conv planes u64 [tile]; out_llr = posterior [tile][var][64]).
-template <int METHOD, bool PLANES>  // METHOD: SCALDPC_BP_PRODUCT_SUM / SCALDPC_BP_MIN_SUM
-__global__ __launch_bounds__(256) void k_bp_small(const int *__restrict__ row_ptr, const int *__restrict__ col_idx,
-                                                  const int *__restrict__ col_ptr, const int *__restrict__ csc_edge,
-                                                  const float *__restrict__ prior, int m, int n, int E,
-                                                  const void *__restrict__ in_, int kind, int max_iter, float alpha0,
-                                                  int early, void *__restrict__ out_bits_,
-                                                  float *__restrict__ out_llr, int *__restrict__ out_iters,
-                                                  void *__restrict__ out_conv_)
+template <int METHOD, bool PLANES, class P>  // METHOD: SCALDPC_BP_PRODUCT_SUM / SCALDPC_BP_MIN_SUM
+__device__ __forceinline__ void bp_small_body(const int *__restrict__ row_ptr, const int *__restrict__ col_idx,
+                                              const int *__restrict__ col_ptr, const int *__restrict__ csc_edge,
+                                              P prior, int m, int n, int E,
+                                              const void *__restrict__ in_, int kind, int max_iter, float alpha0,
+                                              int early, void *__restrict__ out_bits_,
+                                              float *__restrict__ out_llr, int *__restrict__ out_iters,
+                                              void *__restrict__ out_conv_)
 {
     const uint8_t *in = (const uint8_t *)in_;
     uint8_t *out_bits = (uint8_t *)out_bits_;
@@ -975,7 +1091,7 @@ __global__ __launch_bounds__(256) void k_bp_small(const int *__restrict__ row_pt
             synd[r] = p;
         }
     }
-    for (int e = tid; e < E; e += nt) msg[e] = prior[col_idx[e]];
+    for (int e = tid; e < E; e += nt) msg[e] = prior(col_idx[e], pt, pc);  // (a workgroup is a codeword: its lane of its tile)
     for (int v = tid; v < n; v += nt) hard[v] = 0;
     __syncthreads();
 
@@ -1034,7 +1150,7 @@ __global__ __launch_bounds__(256) void k_bp_small(const int *__restrict__ row_pt
         const bool outs = early || last;
         for (int v = tid; v < n; v += nt) {
             const int c0 = col_ptr[v], c1 = col_ptr[v + 1];
-            float temp = prior[v];
+            float temp = prior(v, pt, pc);
             for (int t = c0; t < c1; t++) {
                 const int e = csc_edge[t];
                 scr[e] = temp;
@@ -1084,6 +1200,31 @@ __global__ __launch_bounds__(256) void k_bp_small(const int *__restrict__ row_pt
         if (out_iters) out_iters[b] = it_done;
         if (out_conv) out_conv[b] = (uint8_t)conv;
     }
+}
+template <int METHOD, bool PLANES>
+__global__ __launch_bounds__(256) void k_bp_small(const int *__restrict__ row_ptr, const int *__restrict__ col_idx,
+                                                  const int *__restrict__ col_ptr, const int *__restrict__ csc_edge,
+                                                  const float *__restrict__ prior, int m, int n, int E,
+                                                  const void *__restrict__ in_, int kind, int max_iter, float alpha0,
+                                                  int early, void *__restrict__ out_bits_,
+                                                  float *__restrict__ out_llr, int *__restrict__ out_iters,
+                                                  void *__restrict__ out_conv_)
+{
+    bp_small_body<METHOD, PLANES>(row_ptr, col_idx, col_ptr, csc_edge, SharedPrior{prior}, m, n, E, in_, kind, max_iter, alpha0,
+                                  early, out_bits_, out_llr, out_iters, out_conv_);
+}
+// byte I/O, per-codeword priors
+template <int METHOD>
+__global__ __launch_bounds__(256) void k_bp_small_soft(const int *__restrict__ row_ptr, const int *__restrict__ col_idx,
+                                                       const int *__restrict__ col_ptr, const int *__restrict__ csc_edge,
+                                                       SoftPrior sp, int m, int n, int E,
+                                                       const void *__restrict__ in_, int kind, int max_iter, float alpha0,
+                                                       int early, void *__restrict__ out_bits_,
+                                                       float *__restrict__ out_llr, int *__restrict__ out_iters,
+                                                       void *__restrict__ out_conv_)
+{
+    bp_small_body<METHOD, false>(row_ptr, col_idx, col_ptr, csc_edge, sp, m, n, E, in_, kind, max_iter, alpha0, early, out_bits_,
+                                 out_llr, out_iters, out_conv_);
 }
 
 // ---------------------------------------------------------------------------
@@ -1247,13 +1388,12 @@ __device__ __forceinline__ float var_col_generic(float *mt, float *st, const int
 // write_out: also emit hard-decision planes (merged under the done mask) and, if
 // `post` is non-null, the posterior of every not-yet-frozen codeword.
 // CAP = largest unroll bound compiled in (see k_check_tanh).
-template <int CAP>
-__global__ __launch_bounds__(256) void k_var(Buckets bk, const int *__restrict__ list,
-                                             const int *__restrict__ col_ptr, const int *__restrict__ csc_edge,
-                                             const float *__restrict__ prior, float *msg, float *scratch,
-                                             float *__restrict__ post, u64 *__restrict__ hard,
-                                             const u64 *__restrict__ done, int skip_done, int n, long E,
-                                             int write_out)
+template <int CAP, class P>
+__device__ __forceinline__ void var_body(const int *__restrict__ list, const int *__restrict__ csc_edge,
+                                         P prior, float *msg, float *scratch,
+                                         float *__restrict__ post, u64 *__restrict__ hard,
+                                         const u64 *__restrict__ done, int skip_done, int n, long E,
+                                         int write_out)
 {
     const int lane = threadIdx.x & 63;
     const int tl = blockIdx.y;
@@ -1270,7 +1410,7 @@ __global__ __launch_bounds__(256) void k_var(Buckets bk, const int *__restrict__
     const int d = rec[2];
     float *mt = msg + (size_t)tl * E * TW + lane;
     const int *ce = csc_edge + cb;
-    const float pr = prior[v];
+    const float pr = prior(v, tl, lane);
     float L = pr;
     {
         float *tb = msg + (size_t)tl * E * TW;
@@ -1297,6 +1437,25 @@ __global__ __launch_bounds__(256) void k_var(Buckets bk, const int *__restrict__
         if (lane == 0) hard[hi] = (hard[hi] & dn) | (hb & ~dn);
         if (post && !((dn >> lane) & 1)) post[hi * TW + lane] = L;
     }
+}
+template <int CAP>
+__global__ __launch_bounds__(256) void k_var(Buckets bk, const int *__restrict__ list,
+                                             const int *__restrict__ col_ptr, const int *__restrict__ csc_edge,
+                                             const float *__restrict__ prior, float *msg, float *scratch,
+                                             float *__restrict__ post, u64 *__restrict__ hard,
+                                             const u64 *__restrict__ done, int skip_done, int n, long E,
+                                             int write_out)
+{
+    var_body<CAP>(list, csc_edge, SharedPrior{prior}, msg, scratch, post, hard, done, skip_done, n, E, write_out);
+}
+template <int CAP>
+__global__ __launch_bounds__(256) void k_var_soft(const int *__restrict__ list, const int *__restrict__ csc_edge,
+                                                  SoftPrior sp, float *msg, float *scratch,
+                                                  float *__restrict__ post, u64 *__restrict__ hard,
+                                                  const u64 *__restrict__ done, int skip_done, int n, long E,
+                                                  int write_out)
+{
+    var_body<CAP>(list, csc_edge, sp, msg, scratch, post, hard, done, skip_done, n, E, write_out);
 }
 
 // ITERATION 1 of the tile kernels (see var_col_first): every wave takes TWO column records of the launch order and
@@ -1455,13 +1614,13 @@ __device__ __forceinline__ float var_col_rec(float *tile_base, const float *__re
 }
 
 // grid (bk.blk[nb], G), block 256 = 4 column records (k_var's launch shape and records).
-template <int CAP>
-__global__ __launch_bounds__(256) void k_var_rec(const int *__restrict__ list, const int *__restrict__ var_rows,
-                                                 const int *__restrict__ csc_edge, const int *__restrict__ csc_row,
-                                                 const float *__restrict__ prior, float *msg, const float *__restrict__ rec,
-                                                 const ulonglong2 *__restrict__ mask, float *__restrict__ post,
-                                                 u64 *__restrict__ hard, const u64 *__restrict__ done, int skip_done, int n, int m,
-                                                 long E, int write_out, int blk0, int xmap)
+template <int CAP, class P>
+__device__ __forceinline__ void var_rec_body(const int *__restrict__ list, const int *__restrict__ var_rows,
+                                             const int *__restrict__ csc_edge, const int *__restrict__ csc_row,
+                                             P prior, float *msg, const float *__restrict__ rec,
+                                             const ulonglong2 *__restrict__ mask, float *__restrict__ post,
+                                             u64 *__restrict__ hard, const u64 *__restrict__ done, int skip_done, int n, int m,
+                                             long E, int write_out, int blk0, int xmap)
 {
     const unsigned lane = threadIdx.x & 63u;
     int tl = blockIdx.y, bx = blockIdx.x;
@@ -1487,7 +1646,7 @@ __global__ __launch_bounds__(256) void k_var_rec(const int *__restrict__ list, c
     const ulonglong2 *mt = mask + (size_t)tl * E;
     const int *ce = csc_edge + cb, *cr = csc_row + cb;
     const int4 *w4 = (const int4 *)(var_rows + (size_t)ri * VAR_INLINE);
-    const float pr = prior[v];
+    const float pr = prior(v, tl, (int)lane);
     float L = pr;
 #define VR(D)                                                                                   \
     case D:                                                                                     \
@@ -1507,6 +1666,29 @@ __global__ __launch_bounds__(256) void k_var_rec(const int *__restrict__ list, c
         if (lane == 0) hard[hi] = (hard[hi] & dn) | (hb & ~dn);
         if (post && !((dn >> lane) & 1)) post[hi * TW + lane] = L;
     }
+}
+template <int CAP>
+__global__ __launch_bounds__(256) void k_var_rec(const int *__restrict__ list, const int *__restrict__ var_rows,
+                                                 const int *__restrict__ csc_edge, const int *__restrict__ csc_row,
+                                                 const float *__restrict__ prior, float *msg, const float *__restrict__ rec,
+                                                 const ulonglong2 *__restrict__ mask, float *__restrict__ post,
+                                                 u64 *__restrict__ hard, const u64 *__restrict__ done, int skip_done, int n, int m,
+                                                 long E, int write_out, int blk0, int xmap)
+{
+    var_rec_body<CAP>(list, var_rows, csc_edge, csc_row, SharedPrior{prior}, msg, rec, mask, post, hard, done, skip_done, n, m, E,
+                      write_out, blk0, xmap);
+}
+// (tl is the tile the XCD map chose: the plane row follows it like the records do)
+template <int CAP>
+__global__ __launch_bounds__(256) void k_var_rec_soft(const int *__restrict__ list, const int *__restrict__ var_rows,
+                                                      const int *__restrict__ csc_edge, const int *__restrict__ csc_row,
+                                                      SoftPrior sp, float *msg, const float *__restrict__ rec,
+                                                      const ulonglong2 *__restrict__ mask, float *__restrict__ post,
+                                                      u64 *__restrict__ hard, const u64 *__restrict__ done, int skip_done, int n, int m,
+                                                      long E, int write_out, int blk0, int xmap)
+{
+    var_rec_body<CAP>(list, var_rows, csc_edge, csc_row, sp, msg, rec, mask, post, hard, done, skip_done, n, m, E, write_out, blk0,
+                      xmap);
 }
 
 // ---------------------------------------------------------------------------
@@ -1536,21 +1718,31 @@ __device__ __forceinline__ float readlane_f(float v, int l)
 }
 
 // unused by default (both rules' first check pass reads the priors); kept for rows the fused form does not cover.  grid (ceil(E/256), nb).
+template <class P>
+__device__ __forceinline__ void el_init_body(const int *__restrict__ col_idx, P prior, float *__restrict__ emsg, long E)
+{
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e < E) emsg[(size_t)blockIdx.y * E + e] = prior(col_idx[e], 0, blockIdx.y);  // (codeword c = lane c of the one tile)
+}
 __global__ __launch_bounds__(256) void k_el_init(const int *__restrict__ col_idx, const float *__restrict__ prior,
                                                  float *__restrict__ emsg, long E)
 {
-    const long e = (long)blockIdx.x * 256 + threadIdx.x;
-    if (e < E) emsg[(size_t)blockIdx.y * E + e] = prior[col_idx[e]];
+    el_init_body(col_idx, SharedPrior{prior}, emsg, E);
+}
+__global__ __launch_bounds__(256) void k_el_init_soft(const int *__restrict__ col_idx, SoftPrior sp, float *__restrict__ emsg,
+                                                      long E)
+{
+    el_init_body(col_idx, sp, emsg, E);
 }
 
 // METHOD as in the C ABI; FIRST: inputs are the priors (iteration 1).
 // grid (ceil(m/4), nb), block 256 = 4 rows of codeword blockIdx.y.
-template <int METHOD, bool FIRST>
-__global__ __launch_bounds__(256) void k_el_check(const int *__restrict__ row_ptr, const int *__restrict__ col_idx,
-                                                  const float *__restrict__ prior, float *emsg,
-                                                  const u64 *__restrict__ synd, const u64 *__restrict__ done,
-                                                  int skip_done, int m, long E, float alpha,
-                                                  const u64 *__restrict__ hard, int *__restrict__ unsat_prev)
+template <int METHOD, bool FIRST, class P>
+__device__ __forceinline__ void el_check_body(const int *__restrict__ row_ptr, const int *__restrict__ col_idx,
+                                              P prior, float *emsg,
+                                              const u64 *__restrict__ synd, const u64 *__restrict__ done,
+                                              int skip_done, int m, long E, float alpha,
+                                              const u64 *__restrict__ hard, int *__restrict__ unsat_prev)
 {
     const int lane = threadIdx.x & 63;
     int r = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -1572,7 +1764,7 @@ __global__ __launch_bounds__(256) void k_el_check(const int *__restrict__ row_pt
     if (deg == 0) return;
     float *p = emsg + (size_t)c * E + e0 + lane;
     float x = 0.0f;
-    if (act) x = FIRST ? prior[col_idx[e0 + lane]] : *p;
+    if (act) x = FIRST ? prior(col_idx[e0 + lane], 0, c) : *p;
     if (METHOD == SCALDPC_BP_MIN_SUM) {
         // the sequential form starts its running minima at FLT_MAX: |x| = inf never wins
         const float a = act ? fminf(fabsf(x), FLT_MAX) : FLT_MAX;
@@ -1602,6 +1794,25 @@ __global__ __launch_bounds__(256) void k_el_check(const int *__restrict__ row_pt
         if (act) *p = __uint_as_float(__float_as_uint(Lm) ^ sg);
     }
 }
+template <int METHOD, bool FIRST>
+__global__ __launch_bounds__(256) void k_el_check(const int *__restrict__ row_ptr, const int *__restrict__ col_idx,
+                                                  const float *__restrict__ prior, float *emsg,
+                                                  const u64 *__restrict__ synd, const u64 *__restrict__ done,
+                                                  int skip_done, int m, long E, float alpha,
+                                                  const u64 *__restrict__ hard, int *__restrict__ unsat_prev)
+{
+    el_check_body<METHOD, FIRST>(row_ptr, col_idx, SharedPrior{prior}, emsg, synd, done, skip_done, m, E, alpha, hard, unsat_prev);
+}
+// the first check pass of a soft call
+template <int METHOD>
+__global__ __launch_bounds__(256) void k_el_check_soft(const int *__restrict__ row_ptr, const int *__restrict__ col_idx,
+                                                       SoftPrior sp, float *emsg,
+                                                       const u64 *__restrict__ synd, const u64 *__restrict__ done,
+                                                       int skip_done, int m, long E, float alpha,
+                                                       const u64 *__restrict__ hard, int *__restrict__ unsat_prev)
+{
+    el_check_body<METHOD, true>(row_ptr, col_idx, sp, emsg, synd, done, skip_done, m, E, alpha, hard, unsat_prev);
+}
 
 // Variable nodes, lane = EDGE OF A COLUMN.  The host packs whole columns into waves of 64 lane
 // slots: a column owns a SEGMENT of `cap` neighbouring lanes, cap >= max(degree, 1), of which the
@@ -1621,12 +1832,13 @@ __global__ __launch_bounds__(256) void k_el_check(const int *__restrict__ row_pt
 // posterior and hard decision out); the codewords of one tile word are set / cleared with
 // atomics (each launch row owns one bit).
 // grid (waves padded to a multiple of 8 over 4, nb), block 256 = 4 packed waves.
-__global__ __launch_bounds__(256) void k_el_var(const int2 *__restrict__ slots, const int *__restrict__ slot_col,
-                                                int nwaves, const float *__restrict__ prior, float *emsg,
-                                                float *__restrict__ post, u64 *__restrict__ hard,
-                                                u64 *done, int skip_done, long E, int write_out,
-                                                const int *__restrict__ unsat_prev, int it_prev, u64 *conv,
-                                                int *__restrict__ iters, int *__restrict__ remaining_prev)
+template <class P>
+__device__ __forceinline__ void el_var_body(const int2 *__restrict__ slots, const int *__restrict__ slot_col,
+                                            int nwaves, P prior, float *emsg,
+                                            float *__restrict__ post, u64 *__restrict__ hard,
+                                            u64 *done, int skip_done, long E, int write_out,
+                                            const int *__restrict__ unsat_prev, int it_prev, u64 *conv,
+                                            int *__restrict__ iters, int *__restrict__ remaining_prev)
 {
     const int lane = threadIdx.x & 63;
     int w = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -1669,7 +1881,7 @@ __global__ __launch_bounds__(256) void k_el_var(const int2 *__restrict__ slots, 
     float pr = 0.0f;
     if (head) {
         v = slot_col[(size_t)w * 64 + lane];
-        pr = prior[v];
+        pr = prior(v, 0, c);
     }
     pr = __shfl(pr, start);
     float pre = pr, tot = pr, suf = 0.0f;
@@ -1690,6 +1902,26 @@ __global__ __launch_bounds__(256) void k_el_var(const int2 *__restrict__ slots, 
             atomicAnd(hard + v, ~(1ull << c));
         if (post) post[(size_t)v * TW + c] = tot;
     }
+}
+__global__ __launch_bounds__(256) void k_el_var(const int2 *__restrict__ slots, const int *__restrict__ slot_col,
+                                                int nwaves, const float *__restrict__ prior, float *emsg,
+                                                float *__restrict__ post, u64 *__restrict__ hard,
+                                                u64 *done, int skip_done, long E, int write_out,
+                                                const int *__restrict__ unsat_prev, int it_prev, u64 *conv,
+                                                int *__restrict__ iters, int *__restrict__ remaining_prev)
+{
+    el_var_body(slots, slot_col, nwaves, SharedPrior{prior}, emsg, post, hard, done, skip_done, E, write_out, unsat_prev, it_prev,
+                conv, iters, remaining_prev);
+}
+__global__ __launch_bounds__(256) void k_el_var_soft(const int2 *__restrict__ slots, const int *__restrict__ slot_col,
+                                                     int nwaves, SoftPrior sp, float *emsg,
+                                                     float *__restrict__ post, u64 *__restrict__ hard,
+                                                     u64 *done, int skip_done, long E, int write_out,
+                                                     const int *__restrict__ unsat_prev, int it_prev, u64 *conv,
+                                                     int *__restrict__ iters, int *__restrict__ remaining_prev)
+{
+    el_var_body(slots, slot_col, nwaves, sp, emsg, post, hard, done, skip_done, E, write_out, unsat_prev, it_prev, conv, iters,
+                remaining_prev);
 }
 
 // dst[idx] = val for a list of {idx, val} pairs (table updates of scaldpc_bp_append_rows).  grid ceil(n/256).
@@ -1838,6 +2070,19 @@ __global__ __launch_bounds__(256) void k_gather_planes(const u64 *__restrict__ s
         const u64 w = __ballot(bit);
         if (lane == 0) dst[(size_t)t2 * len + x0 + j] = w;
     }
+}
+
+// The same for the per-codeword prior plane of a soft call (float [tile][cols][64]): dst[t2][j][c2] = src[id>>6][j][id&63],
+// LLR 0 in the empty slots.  grid (ceil(cols/4), T2), block 256 = 4 columns, lane = compact slot.
+__global__ __launch_bounds__(256) void k_gather_prior(const float *__restrict__ src, int cols, const int *__restrict__ ids,
+                                                      float *__restrict__ dst)
+{
+    const int lane = threadIdx.x & 63;
+    const int j = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int t2 = blockIdx.y;
+    if (j >= cols) return;
+    const int id = ids[(size_t)t2 * TW + lane];
+    dst[((size_t)t2 * cols + j) * TW + lane] = id >= 0 ? src[((size_t)(id >> 6) * cols + j) * TW + (id & 63)] : 0.0f;
 }
 
 // dst[t][x] bits of the codewords with slot_of >= 0 are replaced by src2[slot>>6][x] bit (slot&63).

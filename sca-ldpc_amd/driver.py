@@ -7,6 +7,7 @@ decoder in ONE batched call.
   simulate_frame_error_rate       simulate/decode.py:130-177  (binary FER loop)
   simulate_frame_error_rate_rust  simulate/decode.py:180-286  (q-ary FER loop)
   hqc_decode                      simulate/hqc.py:661-759      (input assembly + 7 stats fields)
+  hqc_decode_batch                the same for many trials with their own certainties, one soft call
   regular_ldpc_code & co          main.py:189-276              (the four FER commands, as functions)
 
 The decoder classes are parameters (default: the HIP decoders) so that the host logic
@@ -170,6 +171,44 @@ def hqc_decode(N, Hin, checks, y_sparse, bp_decoder=None, max_iter=100):
     msg = np.concatenate([np.zeros(N, dtype=np.uint8), cvals])
     decoded = bpd.decode_batch(msg[None, :], early_exit=True, input_vector_type="received_vector")["bits"][0]
     return hqc_stats(N, decoded, cvals, y_sparse)
+
+
+def hqc_decode_batch(N, Hin, checks_per_trial, y_sparse_per_trial, bp_decoder=None, max_iter=100):
+    """The batched twin of `hqc_decode`: many trials over the SAME Hin, each with its own answers and its own
+    certainties (the oracles of hqc.py:782-806 raise a check's certainty with every repeated measurement, so two trials
+    differ on their R check columns).  ONE decoder, ONE call: the per-trial `1 - certainty` rows go in as per-codeword
+    priors of the last R columns (`decode_batch(..., channel_probs=)`), the first N columns share `len(y) / N`.
+    Trials whose secrets differ in weight cannot share that prior: all n columns then go in per codeword.
+
+      checks_per_trial    one [(value, certainty)] list of length R per trial
+      y_sparse_per_trial  the secrets' supports
+    Returns [(success, stats)]: per trial what `hqc_decode` returns for it."""
+    g = TannerGraph.coerce(Hin)
+    R = g.m
+    H = g.with_identity()
+    batch = len(checks_per_trial)
+    if batch == 0 or len(y_sparse_per_trial) != batch:
+        raise ValueError("hqc_decode_batch expects one list of checks and one secret per trial")
+    if any(len(c) != R for c in checks_per_trial):
+        raise ValueError(f"every trial needs one (value, certainty) pair per row of Hin ({R})")
+    cvals = np.array([[int(c) for (c, _) in checks] for checks in checks_per_trial], dtype=np.uint8).reshape(batch, R)
+    check_part = np.array([[1 - p for (_, p) in checks] for checks in checks_per_trial], dtype=np.float64).reshape(batch, R)
+    weights = [len(y) for y in y_sparse_per_trial]
+    shared = np.concatenate([np.full(N, weights[0] / N, dtype=np.float64), check_part[0]])
+    with np.errstate(divide="ignore"):
+        bpd = (bp_decoder or _default_bp())(H, max_iter=max_iter, bp_method="product_sum", channel_probs=shared)
+    if len(set(weights)) == 1:
+        soft = check_part
+    else:
+        soft = np.concatenate([np.repeat(np.array(weights, dtype=np.float64)[:, None] / N, N, axis=1), check_part], axis=1)
+    msg = np.concatenate([np.zeros((batch, N), dtype=np.uint8), cvals], axis=1)
+    try:
+        decoded = bpd.decode_batch(msg, early_exit=True, input_vector_type="received_vector",
+                                   channel_probs=soft.astype(np.float32))["bits"]
+    finally:
+        if hasattr(bpd, "close"):
+            bpd.close()
+    return [hqc_stats(N, decoded[i], cvals[i], y_sparse_per_trial[i]) for i in range(batch)]
 
 
 def hqc_stats(N, decoded, cvals, y_sparse):
