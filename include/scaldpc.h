@@ -34,6 +34,12 @@
  *   scaldpc_qary_special_create / _min_sum_batch
  *                                simulate_rs/src/pydecoder.rs:96-117,125-145
  *                                -> simulate_rs/src/decoder_special.rs:387-464, 471-617
+ *   scaldpc_qary_min_sum_batch_soft / scaldpc_qary_special_min_sum_batch_soft
+ *                                the same decodes, with what the last variable update (decoder.rs:634-658 /
+ *                                decoder_special.rs:566-609) computes and the reference drops at its arg-min
+ *                                (decoder.rs:654-657): the per-symbol totals, the margin of every decision, and the
+ *                                number of checks the decided word leaves unmet (the reference has no convergence test)
+ *                                (entry points added under SCALDPC_VERSION 103: nothing that existed changed)
  *
  * Threading: calls on distinct handles are independent; calls on one handle are
  * serialised internally, so one decoder object may be shared by many host
@@ -319,6 +325,31 @@ int scaldpc_qary_special_create(int32_t R, int32_t N, int32_t B, int32_t BSUM, c
 /* pmf_b: float [batch][N-R][2B+1]; pmf_sum: float [batch][R][2BSUM+1]; out int8 [batch][N]. */
 int scaldpc_qary_special_min_sum_batch(scaldpc_qary *h, const float *pmf_b, const float *pmf_sum,
                                        int32_t batch, uint32_t flags, void *stream, int8_t *out);
+
+/* Soft output of both q-ary decoders.  `out` is required and is byte for byte what the plain call returns; each of the
+ * other outputs is optional (NULL), and with all of them NULL the call IS the plain call.
+ *   out_cost    float [batch][N][Q]: the raw totals of the LAST variable update (decoder.rs:634-658), sum[q] = channel LLR +
+ *               the incoming check messages added in the reference's order (the column's checks in ascending row), the very
+ *               numbers whose first minimum (decoder.rs:694-704) is the symbol.  Index q stands for the value q - B.  Not
+ *               normalised: on a cycle-free graph a row minus its minimum is the exact min-marginal cost difference.  +inf
+ *               (zero-probability symbols, decoder.rs:688) and NaN entries come out as the arithmetic makes them.
+ *               DecoderSpecial (decoder_special.rs:566-609): two arrays shaped like its two inputs, out_cost_b float
+ *               [batch][N-R][2B+1] and out_cost_sum float [batch][R][2BSUM+1] (index q: the value q - BSUM); pass both or
+ *               neither (else SCALDPC_EINVAL).
+ *   out_margin  float [batch][N]: fl(m2 - m1), m1 the total at the decided symbol, m2 the smallest total over the OTHER
+ *               symbols by the reference's own scan rule (strict <, NaN never selected, +inf if there is no candidate):
+ *               two equal minima give 0.  The q-ary counterpart of |LLR|, N floats per codeword instead of N * Q.
+ *   out_unmet   int32 [batch]: the number of checks whose sum of h_e * x_e over the row's edges, OVER THE INTEGERS (the
+ *               constraint the check updates enumerate, decoder.rs:336-337; DecoderSpecial: the row-sum variable's edge
+ *               included, decoder_special.rs:507-522), is nonzero on the returned symbols.  0: the decision is a valid word.
+ * flags: SCALDPC_F_DEVICE_IO applies to the input and to every output alike; SCALDPC_F_ASYNC is refused (SCALDPC_EINVAL):
+ * a q-ary call is synchronous.  SCALDPC_EPMF / SCALDPC_ENOCONF / SCALDPC_EINVAL are reported as by the plain calls.  The
+ * staging buffers of an output are allocated by the first call that asks for it. */
+int scaldpc_qary_min_sum_batch_soft(scaldpc_qary *h, const float *pmf, int32_t batch, uint32_t flags, void *stream,
+                                    int8_t *out, float *out_cost, float *out_margin, int32_t *out_unmet);
+int scaldpc_qary_special_min_sum_batch_soft(scaldpc_qary *h, const float *pmf_b, const float *pmf_sum, int32_t batch,
+                                            uint32_t flags, void *stream, int8_t *out,
+                                            float *out_cost_b, float *out_cost_sum, float *out_margin, int32_t *out_unmet);
 
 #ifdef __cplusplus
 }

@@ -35,6 +35,7 @@ using namespace scaldpc;
 typedef unsigned long long u64;
 #include "scaldpc_qary_special.h"
 #include "scaldpc_qary_rows.h"
+#include "scaldpc_qary_soft.h"
 
 namespace {
 
@@ -470,12 +471,15 @@ __global__ __launch_bounds__(64) void k_q_special_check_wave(const int *__restri
 
 // Variable-node update (decoder.rs:634-658 / decoder_special.rs:566-609).
 // thread = (variable, codeword); LDS: sum[Qmax][T], tmp[Qmax][T].
-__global__ void k_q_var(int v0, const int *__restrict__ col_ptr, const int *__restrict__ csc_edge,
-                        const int *__restrict__ edge_h, const int *__restrict__ var_q,
-                        const long *__restrict__ var_off, const float *__restrict__ llr, float *msg, int W, long Bp,
-                        int batch, int Qmax, int last, signed char *__restrict__ out)
+// SOFT (the last pass of a soft call, scaldpc_qary_soft.h): the totals go to cost[var_off[v] + q][Bp] (laid out like llr;
+// nullptr: not wanted) and the margin of the decision to margin[v][Bp] (likewise), out of the same scan that decides.
+template <bool SOFT>
+__device__ __forceinline__ void var_body(unsigned char *smem, int v0, const int *__restrict__ col_ptr, const int *__restrict__ csc_edge,
+                                         const int *__restrict__ edge_h, const int *__restrict__ var_q,
+                                         const long *__restrict__ var_off, const float *__restrict__ llr, float *msg, int W, long Bp,
+                                         int batch, int Qmax, int last, signed char *__restrict__ out, float *__restrict__ cost,
+                                         float *__restrict__ margin)
 {
-    extern __shared__ unsigned char smem[];
     const int T = blockDim.x, tid = threadIdx.x;
     float *sum = (float *)smem;
     float *tmp = sum + (size_t)Qmax * T;
@@ -513,7 +517,16 @@ __global__ void k_q_var(int v0, const int *__restrict__ col_ptr, const int *__re
         const float mn = tmp[(size_t)ma * T + tid];
         for (int q = 0; q < Q; q++) io[(size_t)q * Bp] = tmp[(size_t)q * T + tid] - mn;
     }
-    if (last) {
+    if (SOFT) {
+        SoftScan sc;
+        for (int q = 0; q < Q; q++) {
+            const float x = sum[(size_t)q * T + tid];
+            if (cost) cost[(size_t)(var_off[v] + q) * Bp + b] = x;
+            sc.step(x, q);
+        }
+        out[(size_t)v * Bp + b] = (signed char)(sc.ma - Bv);
+        if (margin) margin[(size_t)v * Bp + b] = sc.m2 - sum[(size_t)sc.ma * T + tid];
+    } else if (last) {
         float mv = INFINITY;
         int ma = 0;
         for (int q = 0; q < Q; q++) {
@@ -527,16 +540,37 @@ __global__ void k_q_var(int v0, const int *__restrict__ col_ptr, const int *__re
     }
 }
 
+__global__ void k_q_var(int v0, const int *__restrict__ col_ptr, const int *__restrict__ csc_edge,
+                        const int *__restrict__ edge_h, const int *__restrict__ var_q,
+                        const long *__restrict__ var_off, const float *__restrict__ llr, float *msg, int W, long Bp,
+                        int batch, int Qmax, int last, signed char *__restrict__ out)
+{
+    extern __shared__ unsigned char smem[];
+    var_body<false>(smem, v0, col_ptr, csc_edge, edge_h, var_q, var_off, llr, msg, W, Bp, batch, Qmax, last, out, nullptr, nullptr);
+}
+
+__global__ void k_q_var_soft(int v0, const int *__restrict__ col_ptr, const int *__restrict__ csc_edge,
+                             const int *__restrict__ edge_h, const int *__restrict__ var_q,
+                             const long *__restrict__ var_off, const float *__restrict__ llr, float *msg, int W, long Bp,
+                             int batch, int Qmax, signed char *__restrict__ out, float *__restrict__ cost,
+                             float *__restrict__ margin)
+{
+    extern __shared__ unsigned char smem[];
+    var_body<true>(smem, v0, col_ptr, csc_edge, edge_h, var_q, var_off, llr, msg, W, Bp, batch, Qmax, 1, out, cost, margin);
+}
+
 // The same update with everything in registers, for the plain decoder with alphabets Q = 3, 5, 7, 15 and columns of at
 // most DMAX checks: every incoming message is loaded ONCE (the generic kernel reads each twice, with an LDS round trip
 // between global accesses), all of a column's loads are issued before the first add.  Same additions and subtractions in
 // the same order, the same first-minimum rule: identical symbols.  llr is [var][Q][Bp] here (one alphabet).
 // grid (N, Bp/64), block 64.
 //   v: variable (graph index: column of col_ptr, row of `out`);  llr: this variable's Q rows;  W: width of a message row
-template <int Q, int DMAX>
+//   SOFT (the last pass of a soft call): cost / margin point at THIS variable's rows of the staging arrays (nullptr: not wanted)
+template <int Q, int DMAX, bool SOFT = false>
 __device__ __forceinline__ void var_small_body(int v, const float *__restrict__ llr, const int *__restrict__ col_ptr,
                                                const int *__restrict__ csc_edge, const int *__restrict__ edge_h, float *msg, int W,
-                                               long Bp, long b, int last, signed char *__restrict__ out)
+                                               long Bp, long b, int last, signed char *__restrict__ out,
+                                               float *__restrict__ cost = nullptr, float *__restrict__ margin = nullptr)
 {
     const int c0 = col_ptr[v], deg = col_ptr[v + 1] - c0;
     float sum[Q], in[DMAX][Q];
@@ -577,7 +611,21 @@ __device__ __forceinline__ void var_small_body(int v, const float *__restrict__ 
 #pragma unroll
             for (int q = 0; q < Q; q++) msg[((size_t)ed[t] * W + q) * Bp + b] = tmp[q] - mn;
         }
-    if (last) {
+    if (SOFT) {
+        SoftScan sc;
+        float m1 = sum[0];  // the total at the decided symbol (index 0 when nothing is selected)
+#pragma unroll
+        for (int q = 0; q < Q; q++) {
+            if (sum[q] < sc.mv) m1 = sum[q];
+            sc.step(sum[q], q);
+        }
+        if (cost) {
+#pragma unroll
+            for (int q = 0; q < Q; q++) cost[(size_t)q * Bp + b] = sum[q];
+        }
+        out[(size_t)v * Bp + b] = (signed char)(sc.ma - (Q - 1) / 2);
+        if (margin) margin[b] = sc.m2 - m1;
+    } else if (last) {
         float mv = INFINITY;
         int ma = 0;
 #pragma unroll
@@ -601,6 +649,19 @@ __global__ __launch_bounds__(64) void k_q_var_small(const int *__restrict__ col_
     var_small_body<Q, DMAX>(v, llr + (size_t)v * Q * Bp, col_ptr, csc_edge, edge_h, msg, Q, Bp, b, last, out);
 }
 
+template <int Q, int DMAX>
+__global__ __launch_bounds__(64) void k_q_var_small_soft(const int *__restrict__ col_ptr, const int *__restrict__ csc_edge,
+                                                         const int *__restrict__ edge_h, const float *__restrict__ llr, float *msg,
+                                                         long Bp, int batch, signed char *__restrict__ out,
+                                                         float *__restrict__ cost, float *__restrict__ margin)
+{
+    const int v = blockIdx.x;
+    const long b = (long)blockIdx.y * 64 + threadIdx.x;
+    if (b >= batch) return;
+    var_small_body<Q, DMAX, true>(v, llr + (size_t)v * Q * Bp, col_ptr, csc_edge, edge_h, msg, Q, Bp, b, 1, out,
+                                  cost ? cost + (size_t)v * Q * Bp : nullptr, margin ? margin + (size_t)v * Bp : nullptr);
+}
+
 // DecoderSpecial (decoder_special.rs:566-609): the first BV variables over QA symbols (columns of at most DA checks), the
 // row-sum variables behind them over QS symbols, one check each; message rows are W = max(QA, QS) wide.
 // grid (N, Bp/64), block 64.
@@ -617,6 +678,26 @@ __global__ __launch_bounds__(64) void k_q_var_small_special(const int *__restric
         var_small_body<QA, DA>(v, llr + (size_t)v * QA * Bp, col_ptr, csc_edge, edge_h, msg, W, Bp, b, last, out);
     else
         var_small_body<QS, 1>(v, llr + ((size_t)BV * QA + (size_t)(v - BV) * QS) * Bp, col_ptr, csc_edge, edge_h, msg, W, Bp, b, last, out);
+}
+
+template <int QA, int DA, int QS>
+__global__ __launch_bounds__(64) void k_q_var_small_special_soft(const int *__restrict__ col_ptr, const int *__restrict__ csc_edge,
+                                                                 const int *__restrict__ edge_h, const float *__restrict__ llr,
+                                                                 float *msg, int BV, int W, long Bp, int batch,
+                                                                 signed char *__restrict__ out, float *__restrict__ cost,
+                                                                 float *__restrict__ margin)
+{
+    const int v = blockIdx.x;
+    const long b = (long)blockIdx.y * 64 + threadIdx.x;
+    if (b >= batch) return;
+    float *mg = margin ? margin + (size_t)v * Bp : nullptr;
+    if (v < BV) {
+        const size_t row = (size_t)v * QA;
+        var_small_body<QA, DA, true>(v, llr + row * Bp, col_ptr, csc_edge, edge_h, msg, W, Bp, b, 1, out, cost ? cost + row * Bp : nullptr, mg);
+    } else {
+        const size_t row = (size_t)BV * QA + (size_t)(v - BV) * QS;
+        var_small_body<QS, 1, true>(v, llr + row * Bp, col_ptr, csc_edge, edge_h, msg, W, Bp, b, 1, out, cost ? cost + row * Bp : nullptr, mg);
+    }
 }
 
 // [N][Bp] -> [batch][N]
@@ -658,6 +739,11 @@ struct scaldpc_qary : QaryStreams {
     long cap_bp = 0;  // codeword columns d_msg, d_llr and d_hard are sized for
     Buf<float> d_msg, d_llr, d_pmf, d_pmf2;
     Buf<signed char> d_hard, d_out;
+    // soft calls only (allocated by the first soft call that asks for the output they stage; a handle that only sees plain
+    // calls owns none of them): the last pass's totals [llr_rows][Bp] and margins [N][Bp] as the variable kernels write them,
+    // their [batch][...] forms for host callers, and the unmet-check counts
+    Buf<float> d_cost, d_margin, d_cost_out, d_margin_out;
+    Buf<int> d_unmet;
     // one 16-byte status block per handle, zeroed by ONE fill and read back by ONE copy per call: [0] = the bitwise complement of
     // the smallest (codeword, variable) key whose pmf row fails the sum test (0: none; kept inverted so that "none" is zero
     // and the kernels lower the key with atomicMax), [1] = the call's error code (low word)
@@ -790,11 +876,18 @@ int qary_build(int R, int N, int B, int BSUM, bool special, const int8_t *H, int
     return 0;
 }
 
+// The optional outputs of a soft call (each may be NULL; all NULL: the plain call).  cost_s: DecoderSpecial's row-sum rows.
+struct SoftOut {
+    float *cost_b = nullptr, *cost_s = nullptr, *margin = nullptr;
+    int32_t *unmet = nullptr;
+};
+
 int qary_run(scaldpc_qary *h, const float *pmf_b, const float *pmf_s, int batch, uint32_t flags, void *stream,
-             int8_t *out)
+             int8_t *out, const SoftOut &so = SoftOut())
 {
     if (!h || !pmf_b || !out || (h->special && !pmf_s)) return fail(SCALDPC_EINVAL, "NULL argument");
     if (batch <= 0) return fail(SCALDPC_EINVAL, "batch must be positive");
+    const bool want_cost = so.cost_b != nullptr, want_margin = so.margin != nullptr, want_unmet = so.unmet != nullptr;
     std::lock_guard<std::mutex> lk(h->mu);
     DeviceGuard dg(h->device);
     const bool dev_io = flags & SCALDPC_F_DEVICE_IO;
@@ -809,6 +902,16 @@ int qary_run(scaldpc_qary *h, const float *pmf_b, const float *pmf_s, int batch,
         SC_TRY(h->d_hard.ensure((size_t)h->N * Bp));
         h->cap_bp = Bp;
     }
+    const size_t n_cost = (size_t)batch * h->llr_rows, n_margin = (size_t)batch * h->N;
+    if (want_cost) {
+        SC_TRY(h->d_cost.ensure((size_t)h->llr_rows * Bp));
+        if (!dev_io) SC_TRY(h->d_cost_out.ensure(n_cost));
+    }
+    if (want_margin) {
+        SC_TRY(h->d_margin.ensure((size_t)h->N * Bp));
+        if (!dev_io) SC_TRY(h->d_margin_out.ensure(n_margin));
+    }
+    if (want_unmet && !dev_io) SC_TRY(h->d_unmet.ensure(batch));
     SC_HIP(hipMemsetAsync(h->d_status, 0, 2 * sizeof(u64), s));
     const int TB = 64;
     // probabilities -> LLRs on the device (host inputs are staged as they are: [batch][var][Q] floats)
@@ -961,7 +1064,29 @@ int qary_run(scaldpc_qary *h, const float *pmf_b, const float *pmf_s, int batch,
     hipLaunchKernelGGL((k_q_var_small<QQ, 4>), dim3(h->N, Bp / 64), dim3(64), 0, s, h->d_col_ptr, h->d_csc_edge, h->d_edge_h, \
                        h->d_llr, h->d_msg, Bp, batch, it == iters ? 1 : 0, h->d_hard)
         const bool vs = !h->special && h->kn_var_small && h->maxdv <= 4;
-        if (vs && h->Q == 3)
+        if (it == iters && (want_cost || want_margin)) {
+            // the soft form of whichever kernel the plain call runs: totals and margins staged next to the symbols
+            float *dc = want_cost ? h->d_cost.get() : nullptr, *dm = want_margin ? h->d_margin.get() : nullptr;
+#define QVAR_SMALL_SOFT(QQ)                                                                                                        \
+    hipLaunchKernelGGL((k_q_var_small_soft<QQ, 4>), dim3(h->N, Bp / 64), dim3(64), 0, s, h->d_col_ptr, h->d_csc_edge, h->d_edge_h, \
+                       h->d_llr, h->d_msg, Bp, batch, h->d_hard, dc, dm)
+            if (vs && h->Q == 3)
+                QVAR_SMALL_SOFT(3);
+            else if (vs && h->Q == 5)
+                QVAR_SMALL_SOFT(5);
+            else if (vs && h->Q == 7)
+                QVAR_SMALL_SOFT(7);
+            else if (vs && h->Q == 15)
+                QVAR_SMALL_SOFT(15);
+            else if (h->special && h->kn_var_small && h->Q == 5 && h->QS == 25 && h->maxdv <= 4)
+                hipLaunchKernelGGL((k_q_var_small_special_soft<5, 4, 25>), dim3(h->N, Bp / 64), dim3(64), 0, s, h->d_col_ptr,
+                                   h->d_csc_edge, h->d_edge_h, h->d_llr, h->d_msg, BV, h->W, Bp, batch, h->d_hard, dc, dm);
+            else
+                hipLaunchKernelGGL(k_q_var_soft, dim3(h->N, Bp / TB), dim3(TB), (size_t)2 * h->W * TB * 4, s, 0, h->d_col_ptr,
+                                   h->d_csc_edge, h->d_edge_h, h->d_var_q, h->d_var_off, h->d_llr, h->d_msg, h->W, Bp, batch, h->W,
+                                   h->d_hard, dc, dm);
+#undef QVAR_SMALL_SOFT
+        } else if (vs && h->Q == 3)
             QVAR_SMALL(3);
         else if (vs && h->Q == 5)
             QVAR_SMALL(5);
@@ -987,9 +1112,39 @@ int qary_run(scaldpc_qary *h, const float *pmf_b, const float *pmf_s, int batch,
     }
     hipLaunchKernelGGL(k_q_unpack, dim3((h->N + 255) / 256, batch), dim3(256), 0, s, h->d_hard, h->N, batch, Bp, dout);
     SC_HIP(hipGetLastError());
+    if (want_cost || want_margin) {
+        // staging [row][Bp] -> [batch][rows]: the cost table (two row ranges for DecoderSpecial) and the margins, one launch
+        const size_t nb = (size_t)batch * BV * h->Q;  // floats of the coefficient rows' table
+        float *oc = dev_io ? so.cost_b : h->d_cost_out.get(), *ocs = dev_io ? so.cost_s : h->d_cost_out.get() + nb;
+        SoftSegs sg = {};
+        if (want_cost) {
+            sg.src[0] = h->d_cost; sg.dst[0] = oc; sg.rows[0] = BV * h->Q;
+            if (h->special) { sg.src[1] = h->d_cost + (size_t)BV * h->Q * Bp; sg.dst[1] = ocs; sg.rows[1] = h->R * h->QS; }
+        }
+        if (want_margin) { sg.src[2] = h->d_margin; sg.dst[2] = dev_io ? so.margin : h->d_margin_out.get(); sg.rows[2] = h->N; }
+        for (int i = 0; i < 3; i++) sg.tile0[i + 1] = sg.tile0[i] + (sg.rows[i] + 63) / 64;
+        hipLaunchKernelGGL(k_q_soft_transpose, dim3(sg.tile0[3], Bp / 64), dim3(256), 0, s, sg, batch, Bp);
+        SC_HIP(hipGetLastError());
+    }
+    if (want_unmet) {
+        int *du = dev_io ? so.unmet : h->d_unmet.get();
+        SC_HIP(hipMemsetAsync(du, 0, (size_t)batch * sizeof(int), s));
+        hipLaunchKernelGGL((k_q_unmet<8>), dim3((h->R + 7) / 8, Bp / 64), dim3(64), 0, s, h->d_row_ptr, h->d_edge_var, h->d_edge_h,
+                           h->d_hard, h->R, batch, Bp, du);
+        SC_HIP(hipGetLastError());
+    }
     u64 status[2] = {0, 0};
     SC_HIP(hipMemcpyAsync(status, h->d_status, sizeof(status), hipMemcpyDeviceToHost, s));
-    if (!dev_io) SC_HIP(hipMemcpyAsync(out, dout, (size_t)batch * h->N, hipMemcpyDeviceToHost, s));
+    if (!dev_io) {
+        SC_HIP(hipMemcpyAsync(out, dout, (size_t)batch * h->N, hipMemcpyDeviceToHost, s));
+        if (want_cost) {
+            const size_t nb = (size_t)batch * BV * h->Q;
+            SC_HIP(hipMemcpyAsync(so.cost_b, h->d_cost_out, nb * sizeof(float), hipMemcpyDeviceToHost, s));
+            if (h->special) SC_HIP(hipMemcpyAsync(so.cost_s, h->d_cost_out + nb, (n_cost - nb) * sizeof(float), hipMemcpyDeviceToHost, s));
+        }
+        if (want_margin) SC_HIP(hipMemcpyAsync(so.margin, h->d_margin_out, n_margin * sizeof(float), hipMemcpyDeviceToHost, s));
+        if (want_unmet) SC_HIP(hipMemcpyAsync(so.unmet, h->d_unmet, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, s));
+    }
     SC_HIP(hipStreamSynchronize(s));
     const int err = (int)(unsigned)status[1];
     const u64 bad = ~status[0];
@@ -1124,6 +1279,34 @@ int scaldpc_qary_special_min_sum_batch(scaldpc_qary *h, const float *pmf_b, cons
 {
     if (h && !h->special) return fail(SCALDPC_EINVAL, "this handle is not a special decoder");
     return qary_run(h, pmf_b, pmf_sum, batch, flags, stream, out);
+}
+
+int scaldpc_qary_min_sum_batch_soft(scaldpc_qary *h, const float *pmf, int32_t batch, uint32_t flags, void *stream, int8_t *out,
+                                    float *out_cost, float *out_margin, int32_t *out_unmet)
+{
+    if (h && h->special) return fail(SCALDPC_EINVAL, "this handle is a special decoder: use scaldpc_qary_special_min_sum_batch_soft");
+    if (flags & SCALDPC_F_ASYNC) return fail(SCALDPC_EINVAL, "SCALDPC_F_ASYNC: a q-ary soft call is synchronous");
+    SoftOut so;
+    so.cost_b = out_cost;
+    so.margin = out_margin;
+    so.unmet = out_unmet;
+    return qary_run(h, pmf, nullptr, batch, flags, stream, out, so);
+}
+
+int scaldpc_qary_special_min_sum_batch_soft(scaldpc_qary *h, const float *pmf_b, const float *pmf_sum, int32_t batch,
+                                            uint32_t flags, void *stream, int8_t *out, float *out_cost_b, float *out_cost_sum,
+                                            float *out_margin, int32_t *out_unmet)
+{
+    if (h && !h->special) return fail(SCALDPC_EINVAL, "this handle is not a special decoder");
+    if (flags & SCALDPC_F_ASYNC) return fail(SCALDPC_EINVAL, "SCALDPC_F_ASYNC: a q-ary soft call is synchronous");
+    if ((out_cost_b == nullptr) != (out_cost_sum == nullptr))
+        return fail(SCALDPC_EINVAL, "out_cost_b and out_cost_sum: pass both or neither");
+    SoftOut so;
+    so.cost_b = out_cost_b;
+    so.cost_s = out_cost_sum;
+    so.margin = out_margin;
+    so.unmet = out_unmet;
+    return qary_run(h, pmf_b, pmf_sum, batch, flags, stream, out, so);
 }
 
 void scaldpc_qary_destroy(scaldpc_qary *h)

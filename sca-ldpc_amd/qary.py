@@ -6,7 +6,9 @@ simulate_rs/src/lib.rs:32-75) and looks them up by name
 (`getattr(simulate_rs, f"DecoderN{n}R{r}V{v}C{c}B{B}")`, simulate/decode.py:227-229).
 Here sizes are run-time values: `decoder_class("DecoderN450R150V3C7B1")` builds a class
 with the same constructor / `min_sum` surface for ANY name of that pattern, plus
-`min_sum_batch` for many channel outputs per call.
+`min_sum_batch` for many channel outputs per call, and `min_sum_soft` / `min_sum_soft_batch` for what the decoders
+compute beyond the symbols: the last variable update's per-symbol totals, the margin of every decision and the number
+of checks the decided word leaves unmet (include/scaldpc.h, scaldpc_qary_min_sum_batch_soft).
 
   DecoderN{N}R{R}V{DV}C{DC}B{B}(H: int8 [R, N], iterations)   .min_sum(pmf float32 [N, 2B+1]) -> list[int]
   DecoderN{N}R{R}SW{SW}(H: int8 [R, N], iterations)           .min_sum(pmf [N-R, 5], pmf_sum [R, 2*BSUM+1]) -> list[int]
@@ -110,6 +112,40 @@ class QaryDecoder(_QaryBase):
             raise ValueError(f"channel output has shape {p.shape}, expected ({self.N}, {self.Q})")
         return [int(x) for x in self.min_sum_batch(p[None])[0]]
 
+    def min_sum_soft_batch(self, channel_output, costs=True, margins=True, unmet=True):
+        """float32 [batch, N, Q] -> dict(symbols int8 [batch, N], costs float32 [batch, N, Q] (the last variable update's
+        totals, index q = value q - B), margins float32 [batch, N] (runner-up total minus the decided one), unmet int32
+        [batch] (checks the symbols leave unmet; 0 = a valid word)); entries not asked for are absent."""
+        p = np.ascontiguousarray(channel_output, dtype=np.float32)
+        if p.ndim != 3 or p.shape[1:] != (self.N, self.Q):
+            raise ValueError(f"channel output has shape {p.shape}, expected (batch, {self.N}, {self.Q})")
+        nb = p.shape[0]
+        res = {"symbols": np.empty((nb, self.N), dtype=np.int8)}
+        if costs:
+            res["costs"] = np.empty((nb, self.N, self.Q), dtype=np.float32)
+        if margins:
+            res["margins"] = np.empty((nb, self.N), dtype=np.float32)
+        if unmet:
+            res["unmet"] = np.empty(nb, dtype=np.int32)
+        _lib.check(self._lib.scaldpc_qary_min_sum_batch_soft(
+            self._h, _lib.ptr(p), nb, 0, None, _lib.ptr(res["symbols"]), _lib.ptr(res.get("costs")), _lib.ptr(res.get("margins")),
+            _lib.ptr(res.get("unmet"))))
+        return res
+
+    def min_sum_soft_batch_device(self, d_channel_output, batch, d_out, d_costs=0, d_margins=0, d_unmet=0, stream=0):
+        """Device-pointer variant (ints; 0 = not wanted): float32 [batch, N, Q] in HBM -> int8 [batch, N], float32
+        [batch, N, Q], float32 [batch, N], int32 [batch] in HBM.  Returns after the stream work is complete."""
+        _lib.check(self._lib.scaldpc_qary_min_sum_batch_soft(
+            self._h, C.c_void_p(d_channel_output), int(batch), _lib.F_DEVICE_IO, C.c_void_p(stream or None), C.c_void_p(d_out),
+            C.c_void_p(d_costs or None), C.c_void_p(d_margins or None), C.c_void_p(d_unmet or None)))
+
+    def min_sum_soft(self, py_channel_output, costs=True, margins=True, unmet=True):
+        """The single-codeword twin of `min_sum`: symbols as a list of ints, costs [N, Q], margins [N], unmet an int."""
+        p = np.asarray(py_channel_output)
+        if p.shape != (self.N, self.Q):
+            raise ValueError(f"channel output has shape {p.shape}, expected ({self.N}, {self.Q})")
+        return _single(self.min_sum_soft_batch(p[None], costs, margins, unmet))
+
 
 class QarySpecialDecoder(_QaryBase):
     """DecoderSpecial<N, R, N-R, DC-1, DC, DV, B, 2B+1, BSUM, 2BSUM+1, i8> (decoder_special.rs:294-322)."""
@@ -150,6 +186,53 @@ class QarySpecialDecoder(_QaryBase):
         if p.ndim != 2 or ps.ndim != 2:
             raise ValueError("channel outputs must be 2-D")
         return [int(x) for x in self.min_sum_batch(p[None], ps[None])[0]]
+
+    def min_sum_soft_batch(self, channel_output, channel_output_sum, costs=True, margins=True, unmet=True):
+        """As QaryDecoder.min_sum_soft_batch; the totals come as `costs` float32 [batch, N-R, 2B+1] and `costs_sum` float32
+        [batch, R, 2BSUM+1] (the shapes of the two inputs), margins and symbols cover all N variables, and a check's sum
+        includes its row-sum variable."""
+        p = np.ascontiguousarray(channel_output, dtype=np.float32)
+        ps = np.ascontiguousarray(channel_output_sum, dtype=np.float32)
+        if p.ndim != 3 or p.shape[1:] != (self.N - self.R, self.Q):
+            raise ValueError(f"channel output has shape {p.shape}, expected (batch, {self.N - self.R}, {self.Q})")
+        if ps.shape != (p.shape[0], self.R, self.QS):
+            raise ValueError(f"channel output sum has shape {ps.shape}, expected ({p.shape[0]}, {self.R}, {self.QS})")
+        nb = p.shape[0]
+        res = {"symbols": np.empty((nb, self.N), dtype=np.int8)}
+        if costs:
+            res["costs"] = np.empty((nb, self.N - self.R, self.Q), dtype=np.float32)
+            res["costs_sum"] = np.empty((nb, self.R, self.QS), dtype=np.float32)
+        if margins:
+            res["margins"] = np.empty((nb, self.N), dtype=np.float32)
+        if unmet:
+            res["unmet"] = np.empty(nb, dtype=np.int32)
+        _lib.check(self._lib.scaldpc_qary_special_min_sum_batch_soft(
+            self._h, _lib.ptr(p), _lib.ptr(ps), nb, 0, None, _lib.ptr(res["symbols"]), _lib.ptr(res.get("costs")),
+            _lib.ptr(res.get("costs_sum")), _lib.ptr(res.get("margins")), _lib.ptr(res.get("unmet"))))
+        return res
+
+    def min_sum_soft_batch_device(self, d_channel_output, d_channel_output_sum, batch, d_out, d_costs=0, d_costs_sum=0,
+                                  d_margins=0, d_unmet=0, stream=0):
+        """Device-pointer variant (ints; 0 = not wanted; d_costs and d_costs_sum together or not at all)."""
+        _lib.check(self._lib.scaldpc_qary_special_min_sum_batch_soft(
+            self._h, C.c_void_p(d_channel_output), C.c_void_p(d_channel_output_sum), int(batch), _lib.F_DEVICE_IO,
+            C.c_void_p(stream or None), C.c_void_p(d_out), C.c_void_p(d_costs or None), C.c_void_p(d_costs_sum or None),
+            C.c_void_p(d_margins or None), C.c_void_p(d_unmet or None)))
+
+    def min_sum_soft(self, py_channel_output, py_channel_output_sum, costs=True, margins=True, unmet=True):
+        p, ps = np.asarray(py_channel_output), np.asarray(py_channel_output_sum)
+        if p.ndim != 2 or ps.ndim != 2:
+            raise ValueError("channel outputs must be 2-D")
+        return _single(self.min_sum_soft_batch(p[None], ps[None], costs, margins, unmet))
+
+
+def _single(res):
+    """A batch-of-one soft result as `min_sum` returns its symbols: a list of ints, the arrays without the batch axis."""
+    out = {k: v[0] for k, v in res.items()}
+    out["symbols"] = [int(x) for x in out["symbols"]]
+    if "unmet" in out:
+        out["unmet"] = int(out["unmet"])
+    return out
 
 
 def into_llr(channel_output):
