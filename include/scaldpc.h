@@ -299,15 +299,18 @@ void scaldpc_qary_destroy(scaldpc_qary *h);
  * are bit for bit those of the host's logf (what the reference's f32::ln calls).  A row that does not
  * sum to 1 +- 1e-3 returns SCALDPC_EPMF (the reference asserts).  flags: SCALDPC_F_DEVICE_IO. */
 int scaldpc_qary_into_llr(const float *pmf, int64_t rows, int32_t Q, uint32_t flags, void *stream, float *llr);
-/* Test / tuning knobs of one q-ary handle (defaults from SCALDPC_QARY_WAVE / SCALDPC_QARY_NO_UNROLL, read
- * once at creation): "wave" = -1 auto | 0 codeword per lane | 1 wave per (check, codeword);
- * "unroll" = 1 register-resident unrolled enumeration for small alphabets | 0 off;
- * "tree" = 1 tree-walk check kernel for the Kyber shape (B = 2, six coefficient edges per check) | 0 off
- * (SCALDPC_QARY_NO_TREE); "dp" = 1 (default) the same shape's check update as a min-plus recursion over the edges in the
- * reference's order of additions -- no enumeration, the reference's messages bit for bit (scaldpc_qary_special.h) --
- * for calls of at least "dp_min" codewords (default 5; below, the tree walk), the row's edges split over four waves up
- * to "dp_split" codewords (default 64) and over two up to "dp_split2" (default 192) | 0 off; "llr_tiled", "var_small": forms of the conversion / variable kernels;
- * "timing" = 1: bracket the launches of a call with HIP events (scaldpc_qary_last_timing). */
+/* Test / tuning knobs of one q-ary handle (defaults from SCALDPC_QARY_WAVE / SCALDPC_QARY_NO_UNROLL / SCALDPC_QARY_NO_TREE,
+ * read once at creation):
+ *   "wave"       -1 auto | 0 codeword per lane | 1 wave per (check, codeword)
+ *   "unroll"     1 register-resident unrolled enumeration for small alphabets | 0 off
+ *   "tree"       1 tree-walk check kernel for the Kyber shape (B = 2, six coefficient edges per check) | 0 off
+ *   "dp"         1 (default) the same shape's check update as a min-plus recursion over the edges in the reference's order
+ *                of additions -- no enumeration, the reference's messages bit for bit (scaldpc_qary_special.h) | 0 off
+ *   "dp_min"     ... for calls of at least this many codewords (default 5; below, the tree walk)
+ *   "dp_split"   ... the row's edges split over four waves up to this many codewords (default 64)
+ *   "dp_split2"  ... and over two up to this many (default 192)
+ *   "llr_tiled", "var_small"  forms of the conversion / variable kernels
+ *   "timing"     1: bracket the launches of a call with HIP events (scaldpc_qary_last_timing) */
 int scaldpc_qary_configure(scaldpc_qary *h, const char *key, const char *value);
 /* Measurement aid for bench.py (the q-ary counterpart of scaldpc_bp_time_kernels): after
  * scaldpc_qary_configure(h, "timing", "1"), every check-node and variable-node launch of a call is bracketed by

@@ -24,6 +24,7 @@
 // roofline claim is made for it.
 #include "scaldpc_common.h"
 #include "scaldpc_logf.h"
+#include "scaldpc_qary_plan.h"
 
 #include <cmath>
 #include <cstring>
@@ -40,6 +41,28 @@ typedef unsigned long long u64;
 namespace {
 
 constexpr int QERR_PMF = 3;        // decoder.rs:683-684 assert
+
+// One pmf row as decoder.rs:668-692 reads it, symbol by symbol: the sum, left to right from 0.0, and the first strict maximum (a
+// NaN is never chosen).  bad(): the reference's assert (decoder.rs:683-684: the row sums to 1 +- 1e-3) or no maximum (all NaN).
+struct PmfScan {
+    float sum = 0.0f, mx = 0.0f;
+    bool have = false;
+    __device__ __forceinline__ void step(float x)
+    {
+        sum += x;
+        if (x == x && (!have || x > mx)) {
+            mx = x;
+            have = true;
+        }
+    }
+    __device__ __forceinline__ bool bad() const { return !have || !(sum < 1.0f + 0.001f) || !(sum > 1.0f - 0.001f); }
+};
+// key of a failing row, smaller = earlier: codeword, then alphabet (0 = coefficient rows, 1 = row-sum rows), then variable, then
+// "no maximum" (scaldpc_qary_into_llr: codeword 0, alphabet 0, variable = row)
+__device__ __forceinline__ u64 pmf_err_key(u64 b, int kind, u64 v, bool have)
+{
+    return (b << 32) | ((u64)kind << 31) | (v << 1) | (have ? 0ull : 1ull);
+}
 
 // decoder.rs:668-692 on the device: llr[q] = ln(max_p / p[q]) in f32, with glibc's logf restated
 // for the device (scaldpc_logf.h) and the correctly rounded f32 division, so the LLRs are bit for bit
@@ -58,23 +81,15 @@ __global__ void k_q_into_llr(const float *__restrict__ pmf, int nv, int Q, int b
         return;
     }
     const float *p = pmf + ((size_t)b * nv + v) * Q;
-    float sum = 0.0f, mx = 0.0f;
-    bool have = false;
-    for (int q = 0; q < Q; q++) {
-        sum += p[q];
-        if (p[q] == p[q] && (!have || p[q] > mx)) {
-            mx = p[q];
-            have = true;
-        }
-    }
-    if (!have || !(sum < 1.0f + 0.001f) || !(sum > 1.0f - 0.001f)) {
+    PmfScan sc;
+    for (int q = 0; q < Q; q++) sc.step(p[q]);
+    if (sc.bad()) {
         atomicMax(err, QERR_PMF);
-        // key: codeword, then alphabet (0 = coefficient rows, 1 = row-sum rows), then variable, then "no maximum"
-        atomicMax(first_bad, ~(((u64)b << 32) | ((u64)kind << 31) | ((u64)v << 1) | (have ? 0ull : 1ull)));  // (kept inverted: see scaldpc_qary::d_status)
+        atomicMax(first_bad, ~pmf_err_key((u64)b, kind, (u64)v, sc.have));  // (kept inverted: see scaldpc_qary::d_status)
     }
     // measured channel outputs repeat a handful of rows: no point caching across lanes, the double
     // pipe is idle anyway (18 double operations per symbol)
-    for (int q = 0; q < Q; q++) llr[((size_t)v * Q + q) * Bp + b] = glibc_logf(mx / p[q]);
+    for (int q = 0; q < Q; q++) llr[((size_t)v * Q + q) * Bp + b] = glibc_logf(sc.mx / p[q]);
 }
 
 // The same conversion through an LDS tile: the input is [codeword][variable][Q] (a codeword's pmf rows are contiguous), the
@@ -123,22 +138,15 @@ __global__ void k_q_into_llr_tiled(const float *__restrict__ pmf0, int nv0, int 
         return;
     }
     const float *p = tile + lane * 33 + w * Q;
-    float sum = 0.0f, mx = 0.0f;
-    bool have = false;
-    for (int q = 0; q < Q; q++) {
-        sum += p[q];
-        if (p[q] == p[q] && (!have || p[q] > mx)) {
-            mx = p[q];
-            have = true;
-        }
-    }
-    if (!have || !(sum < 1.0f + 0.001f) || !(sum > 1.0f - 0.001f)) {
+    PmfScan sc;
+    for (int q = 0; q < Q; q++) sc.step(p[q]);
+    if (sc.bad()) {
         atomicMax(err, QERR_PMF);
-        atomicMax(first_bad, ~(((u64)b << 32) | ((u64)kind << 31) | ((u64)v << 1) | (have ? 0ull : 1ull)));  // (kept inverted: see scaldpc_qary::d_status)
+        atomicMax(first_bad, ~pmf_err_key((u64)b, kind, (u64)v, sc.have));  // (kept inverted: see scaldpc_qary::d_status)
     }
     float *own = tile + lane * 33 + w * Q;  // (this thread's slots of the tile: probabilities in, LLRs out)
     for (int q = 0; q < Q; q++) {
-        const float l = glibc_logf(mx / p[q]);
+        const float l = glibc_logf(sc.mx / p[q]);
         llr[((size_t)v * Q + q) * Bp + b] = l;
         own[q] = l;
     }
@@ -157,17 +165,10 @@ __global__ void k_q_into_llr_rows(const float *__restrict__ pmf, long rows, int 
     const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= rows) return;
     const float *p = pmf + (size_t)r * Q;
-    float sum = 0.0f, mx = 0.0f;
-    bool have = false;
-    for (int q = 0; q < Q; q++) {
-        sum += p[q];
-        if (p[q] == p[q] && (!have || p[q] > mx)) {
-            mx = p[q];
-            have = true;
-        }
-    }
-    if (!have || !(sum < 1.0f + 0.001f) || !(sum > 1.0f - 0.001f)) atomicMin(first_bad, ((u64)r << 1) | (have ? 0ull : 1ull));
-    for (int q = 0; q < Q; q++) llr[(size_t)r * Q + q] = glibc_logf(mx / p[q]);
+    PmfScan sc;
+    for (int q = 0; q < Q; q++) sc.step(p[q]);
+    if (sc.bad()) atomicMin(first_bad, pmf_err_key(0, 0, (u64)r, sc.have));
+    for (int q = 0; q < Q; q++) llr[(size_t)r * Q + q] = glibc_logf(sc.mx / p[q]);
 }
 
 // decoder.rs:567-573: v2c = channel * h.  thread = (edge, codeword).
@@ -285,6 +286,37 @@ __device__ __forceinline__ float wave_min(float v)
     return v;
 }
 
+// The wave kernels' walk through the assignment space: assignment c goes to lane c mod 64.  Digits are 8 bits each, index 0
+// fastest, digit j below radix(j).  start: the digits of the lane's first assignment and of the stride 64.
+template <typename Radix>
+__device__ __forceinline__ void mixed_radix_start(int lane, int nd, Radix radix, u64 &idx, u64 &stp)
+{
+    idx = 0;
+    stp = 0;
+    unsigned a = (unsigned)lane, st = 64;  // (both start below 65: 32-bit division, not the 64-bit library routine)
+    for (int j = 0; j < nd; j++) {
+        const unsigned nj = (unsigned)radix(j);
+        idx |= (u64)(a % nj) << (8 * j);
+        a /= nj;
+        stp |= (u64)(st % nj) << (8 * j);
+        st /= nj;
+    }
+}
+// idx + stride (one conditional subtraction per digit)
+template <typename Radix>
+__device__ __forceinline__ u64 mixed_radix_step(u64 idx, u64 stp, int nd, Radix radix)
+{
+    int carry = 0;
+    u64 nidx = 0;
+    for (int j = 0; j < nd; j++) {
+        int d = ((int)(idx >> (8 * j)) & 255) + ((int)(stp >> (8 * j)) & 255) + carry;
+        carry = d >= radix(j);
+        if (carry) d -= radix(j);
+        nidx |= (u64)d << (8 * j);
+    }
+    return nidx;
+}
+
 // generic Decoder check (decoder.rs:585-631).  grid (R, batch), block 64.
 // LDS: A[k*Q] floats (shared), fin[k*Q] + num[k] bytes (shared), Bt[k*Q][64] floats (per lane).
 __global__ __launch_bounds__(64) void k_q_check_wave(const int *__restrict__ row_ptr, float *msg, int Q, int B, long Bp,
@@ -321,17 +353,9 @@ __global__ __launch_bounds__(64) void k_q_check_wave(const int *__restrict__ row
         if (lane == 0) atomicMax(err, QERR_NO_FINITE);
     } else {
         // digits of this lane's first assignment and of the stride 64, index 0 fastest
-        u64 idx = 0, stp = 0;
-        {
-            unsigned a = (unsigned)lane, st = 64;  // (both start below 65: 32-bit division, not the 64-bit library routine)
-            for (int j = 0; j < k - 1; j++) {
-                const unsigned nj = num[j];
-                idx |= (u64)(a % nj) << (8 * j);
-                a /= nj;
-                stp |= (u64)(st % nj) << (8 * j);
-                st /= nj;
-            }
-        }
+        const auto radix = [&](int j) { return (int)num[j]; };
+        u64 idx, stp;
+        mixed_radix_start(lane, k - 1, radix, idx, stp);
         int nconf = 0;
         for (unsigned long long cfg = lane; cfg < total; cfg += 64) {
             int dsum = 0;
@@ -357,35 +381,16 @@ __global__ __launch_bounds__(64) void k_q_check_wave(const int *__restrict__ row
                     }
                 }
             }
-            // idx += stride (mixed radix, one conditional subtraction per digit)
-            int carry = 0;
-            u64 nidx = 0;
-            for (int j = 0; j < k - 1; j++) {
-                int d = ((int)(idx >> (8 * j)) & 255) + ((int)(stp >> (8 * j)) & 255) + carry;
-                carry = d >= num[j];
-                if (carry) d -= num[j];
-                nidx |= (u64)d << (8 * j);
-            }
-            idx = nidx;
+            idx = mixed_radix_step(idx, stp, k - 1, radix);
         }
         const u64 any = __ballot(nconf > 0);
         if (!any && lane == 0) atomicMax(err, QERR_NO_CONFIG);
     }
-    // minimum over the 64 lanes' partial results, TRANSPOSED: lane L folds whole rows i = L, L + 64, ... of Bt (64 LDS reads
-    // each, rotated by the lane index so that the 64 lanes hit 32 different banks) instead of 6 dependent ds_bpermute steps
-    // per entry (k * Q entries: 630 of them for a degree-7 check over Q = 15)
+    // minimum over the 64 lanes' partial results, TRANSPOSED (fold_min_rows64): lane L folds whole rows i = L, L + 64, ... of Bt
+    // instead of 6 dependent ds_bpermute steps per entry (k * Q entries: 630 of them for a degree-7 check over Q = 15)
     __syncthreads();
     for (int i = lane; i < k * Q; i += 64) {
-        const float *row = Bt + (size_t)i * 64;
-        float m0 = INFINITY, m1 = INFINITY, m2 = INFINITY, m3 = INFINITY;
-#pragma unroll 4
-        for (int l = 0; l < 64; l += 4) {
-            m0 = vmin(m0, row[(l + lane) & 63]);
-            m1 = vmin(m1, row[(l + 1 + lane) & 63]);
-            m2 = vmin(m2, row[(l + 2 + lane) & 63]);
-            m3 = vmin(m3, row[(l + 3 + lane) & 63]);
-        }
-        msg[((size_t)(e0 + i / Q) * Q + i % Q) * Bp + b] = vmin(vmin(m0, m1), vmin(m2, m3));
+        msg[((size_t)(e0 + i / Q) * Q + i % Q) * Bp + b] = fold_min_rows64(Bt + (size_t)i * 64, lane);
     }
 }
 
@@ -412,17 +417,9 @@ __global__ __launch_bounds__(64) void k_q_special_check_wave(const int *__restri
     __syncthreads();
     unsigned long long total = 1;
     for (int j = 0; j < nb; j++) total *= QB;
-    u64 dq = 0, stp = 0;
-    {
-        unsigned a = (unsigned)lane, st = 64;  // (both start below 65: 32-bit division)
-        const unsigned uq = (unsigned)QB;
-        for (int j = 0; j < nb; j++) {
-            dq |= (u64)(a % uq) << (8 * j);
-            a /= uq;
-            stp |= (u64)(st % uq) << (8 * j);
-            st /= uq;
-        }
-    }
+    const auto radix = [=](int) { return QB; };
+    u64 dq, stp;
+    mixed_radix_start(lane, nb, radix, dq, stp);
     for (unsigned long long cfg = lane; cfg < total; cfg += 64) {
         int dsum = 0;
         float S = 0.0f;
@@ -439,29 +436,13 @@ __global__ __launch_bounds__(64) void k_q_special_check_wave(const int *__restri
             *bb = fminf(*bb, S - Ab[j * QB + q]);
         }
         Bs[(size_t)os * 64 + lane] = fminf(Bs[(size_t)os * 64 + lane], S - As[os]);
-        int carry = 0;
-        u64 ndq = 0;
-        for (int j = 0; j < nb; j++) {
-            int d = ((int)(dq >> (8 * j)) & 255) + ((int)(stp >> (8 * j)) & 255) + carry;
-            carry = d >= QB;
-            if (carry) d -= QB;
-            ndq |= (u64)d << (8 * j);
-        }
-        dq = ndq;
+        dq = mixed_radix_step(dq, stp, nb, radix);
     }
     // minima over the 64 lanes, transposed (see k_q_check_wave): the row's nb * QB coefficient entries, then its QS sum entries
     __syncthreads();
     for (int i = lane; i < nb * QB + QS; i += 64) {
         const float *row = i < nb * QB ? Bb + (size_t)i * 64 : Bs + (size_t)(i - nb * QB) * 64;
-        float m0 = INFINITY, m1 = INFINITY, m2 = INFINITY, m3 = INFINITY;
-#pragma unroll 4
-        for (int l = 0; l < 64; l += 4) {
-            m0 = vmin(m0, row[(l + lane) & 63]);
-            m1 = vmin(m1, row[(l + 1 + lane) & 63]);
-            m2 = vmin(m2, row[(l + 2 + lane) & 63]);
-            m3 = vmin(m3, row[(l + 3 + lane) & 63]);
-        }
-        const float v = vmin(vmin(m0, m1), vmin(m2, m3));
+        const float v = fold_min_rows64(row, lane);
         if (i < nb * QB)
             msg[((size_t)(e0 + i / QB) * W + i % QB) * Bp + b] = v;
         else
@@ -540,23 +521,16 @@ __device__ __forceinline__ void var_body(unsigned char *smem, int v0, const int 
     }
 }
 
+// SOFT = false: cost and margin are not read.  SOFT = true: `last` is not (a soft pass is the last one).
+template <bool SOFT>
 __global__ void k_q_var(int v0, const int *__restrict__ col_ptr, const int *__restrict__ csc_edge,
                         const int *__restrict__ edge_h, const int *__restrict__ var_q,
                         const long *__restrict__ var_off, const float *__restrict__ llr, float *msg, int W, long Bp,
-                        int batch, int Qmax, int last, signed char *__restrict__ out)
+                        int batch, int Qmax, int last, signed char *__restrict__ out, float *__restrict__ cost,
+                        float *__restrict__ margin)
 {
     extern __shared__ unsigned char smem[];
-    var_body<false>(smem, v0, col_ptr, csc_edge, edge_h, var_q, var_off, llr, msg, W, Bp, batch, Qmax, last, out, nullptr, nullptr);
-}
-
-__global__ void k_q_var_soft(int v0, const int *__restrict__ col_ptr, const int *__restrict__ csc_edge,
-                             const int *__restrict__ edge_h, const int *__restrict__ var_q,
-                             const long *__restrict__ var_off, const float *__restrict__ llr, float *msg, int W, long Bp,
-                             int batch, int Qmax, signed char *__restrict__ out, float *__restrict__ cost,
-                             float *__restrict__ margin)
-{
-    extern __shared__ unsigned char smem[];
-    var_body<true>(smem, v0, col_ptr, csc_edge, edge_h, var_q, var_off, llr, msg, W, Bp, batch, Qmax, 1, out, cost, margin);
+    var_body<SOFT>(smem, v0, col_ptr, csc_edge, edge_h, var_q, var_off, llr, msg, W, Bp, batch, Qmax, last, out, cost, margin);
 }
 
 // The same update with everything in registers, for the plain decoder with alphabets Q = 3, 5, 7, 15 and columns of at
@@ -638,66 +612,46 @@ __device__ __forceinline__ void var_small_body(int v, const float *__restrict__ 
     }
 }
 
-template <int Q, int DMAX>
+// (cost / margin: the staging arrays' bases, read only where SOFT)
+template <int Q, int DMAX, bool SOFT>
 __global__ __launch_bounds__(64) void k_q_var_small(const int *__restrict__ col_ptr, const int *__restrict__ csc_edge,
                                                     const int *__restrict__ edge_h, const float *__restrict__ llr, float *msg,
-                                                    long Bp, int batch, int last, signed char *__restrict__ out)
+                                                    long Bp, int batch, int last, signed char *__restrict__ out,
+                                                    float *__restrict__ cost, float *__restrict__ margin)
 {
     const int v = blockIdx.x;
     const long b = (long)blockIdx.y * 64 + threadIdx.x;
     if (b >= batch) return;
-    var_small_body<Q, DMAX>(v, llr + (size_t)v * Q * Bp, col_ptr, csc_edge, edge_h, msg, Q, Bp, b, last, out);
-}
-
-template <int Q, int DMAX>
-__global__ __launch_bounds__(64) void k_q_var_small_soft(const int *__restrict__ col_ptr, const int *__restrict__ csc_edge,
-                                                         const int *__restrict__ edge_h, const float *__restrict__ llr, float *msg,
-                                                         long Bp, int batch, signed char *__restrict__ out,
-                                                         float *__restrict__ cost, float *__restrict__ margin)
-{
-    const int v = blockIdx.x;
-    const long b = (long)blockIdx.y * 64 + threadIdx.x;
-    if (b >= batch) return;
-    var_small_body<Q, DMAX, true>(v, llr + (size_t)v * Q * Bp, col_ptr, csc_edge, edge_h, msg, Q, Bp, b, 1, out,
-                                  cost ? cost + (size_t)v * Q * Bp : nullptr, margin ? margin + (size_t)v * Bp : nullptr);
+    var_small_body<Q, DMAX, SOFT>(v, llr + (size_t)v * Q * Bp, col_ptr, csc_edge, edge_h, msg, Q, Bp, b, last, out,
+                                  SOFT && cost ? cost + (size_t)v * Q * Bp : nullptr, SOFT && margin ? margin + (size_t)v * Bp : nullptr);
 }
 
 // DecoderSpecial (decoder_special.rs:566-609): the first BV variables over QA symbols (columns of at most DA checks), the
 // row-sum variables behind them over QS symbols, one check each; message rows are W = max(QA, QS) wide.
 // grid (N, Bp/64), block 64.
-template <int QA, int DA, int QS>
+template <int QA, int DA, int QS, bool SOFT>
 __global__ __launch_bounds__(64) void k_q_var_small_special(const int *__restrict__ col_ptr, const int *__restrict__ csc_edge,
                                                             const int *__restrict__ edge_h, const float *__restrict__ llr,
                                                             float *msg, int BV, int W, long Bp, int batch, int last,
-                                                            signed char *__restrict__ out)
+                                                            signed char *__restrict__ out, float *__restrict__ cost,
+                                                            float *__restrict__ margin)
 {
     const int v = blockIdx.x;
     const long b = (long)blockIdx.y * 64 + threadIdx.x;
     if (b >= batch) return;
-    if (v < BV)
+    if constexpr (SOFT) {
+        float *mg = margin ? margin + (size_t)v * Bp : nullptr;
+        if (v < BV) {
+            const size_t row = (size_t)v * QA;
+            var_small_body<QA, DA, true>(v, llr + row * Bp, col_ptr, csc_edge, edge_h, msg, W, Bp, b, 1, out, cost ? cost + row * Bp : nullptr, mg);
+        } else {
+            const size_t row = (size_t)BV * QA + (size_t)(v - BV) * QS;
+            var_small_body<QS, 1, true>(v, llr + row * Bp, col_ptr, csc_edge, edge_h, msg, W, Bp, b, 1, out, cost ? cost + row * Bp : nullptr, mg);
+        }
+    } else if (v < BV)  // (one address expression for both forms compiles to other code: kept apart)
         var_small_body<QA, DA>(v, llr + (size_t)v * QA * Bp, col_ptr, csc_edge, edge_h, msg, W, Bp, b, last, out);
     else
         var_small_body<QS, 1>(v, llr + ((size_t)BV * QA + (size_t)(v - BV) * QS) * Bp, col_ptr, csc_edge, edge_h, msg, W, Bp, b, last, out);
-}
-
-template <int QA, int DA, int QS>
-__global__ __launch_bounds__(64) void k_q_var_small_special_soft(const int *__restrict__ col_ptr, const int *__restrict__ csc_edge,
-                                                                 const int *__restrict__ edge_h, const float *__restrict__ llr,
-                                                                 float *msg, int BV, int W, long Bp, int batch,
-                                                                 signed char *__restrict__ out, float *__restrict__ cost,
-                                                                 float *__restrict__ margin)
-{
-    const int v = blockIdx.x;
-    const long b = (long)blockIdx.y * 64 + threadIdx.x;
-    if (b >= batch) return;
-    float *mg = margin ? margin + (size_t)v * Bp : nullptr;
-    if (v < BV) {
-        const size_t row = (size_t)v * QA;
-        var_small_body<QA, DA, true>(v, llr + row * Bp, col_ptr, csc_edge, edge_h, msg, W, Bp, b, 1, out, cost ? cost + row * Bp : nullptr, mg);
-    } else {
-        const size_t row = (size_t)BV * QA + (size_t)(v - BV) * QS;
-        var_small_body<QS, 1, true>(v, llr + row * Bp, col_ptr, csc_edge, edge_h, msg, W, Bp, b, 1, out, cost ? cost + row * Bp : nullptr, mg);
-    }
 }
 
 // [N][Bp] -> [batch][N]
@@ -726,11 +680,10 @@ struct QaryStreams {
     }
 };
 
-// Every block the handle owns is a Buf member; d_err and d_first_bad are views into d_status.
-struct scaldpc_qary : QaryStreams {
-    bool special = false;
-    int R = 0, N = 0, B = 0, BSUM = 0, Q = 0, QS = 0, W = 0, iterations = 0;
-    int E = 0, maxdc = 0, mindc = 0, maxdv = 0;
+// Every block the handle owns is a Buf member; d_err and d_first_bad are views into d_status.  The graph's shape (QaryShape:
+// special, R, N, E, Q, QS, W, the degrees) is what qary_plan reads.
+struct scaldpc_qary : QaryStreams, QaryShape {
+    int B = 0, BSUM = 0, iterations = 0;
     long llr_rows = 0;  // total alphabet rows over all variables
     Buf<int> d_row_ptr, d_col_ptr, d_csc_edge, d_edge_var, d_edge_h, d_var_q;
     Buf<long> d_var_off;
@@ -750,18 +703,7 @@ struct scaldpc_qary : QaryStreams {
     Buf<u64> d_status;
     int *d_err = nullptr;        // = (int *)(d_status + 1)
     u64 *d_first_bad = nullptr;  // = d_status
-    int kn_wave = -1;    // -1: wave-parallel enumeration for batches <= 256 and the special decoder; 0 / 1 force
-    int kn_unroll = 1;   // register-resident unrolled enumeration for small alphabets
-    int kn_tree = 1;     // special decoder: tree-walk check kernel for the Kyber shape (QB = 5, 6 coefficient edges)
-    int kn_dp = 1;       // special decoder, same shape: min-plus recursion instead of the enumeration (k_q_special_check_dp); batches >= kn_dp_min
-    int kn_dp_min = 5;      // (below, one wave per (check, codeword) of the tree walk is as fast or faster: profiles/r04/kyber_form_sweep.log)
-    int kn_dp_split = 64;    // up to this batch the row's edges are split over four waves (same log)
-    int kn_dp_split2 = 192;  // ... and up to this one over two
-    // measurement aid (bench.py): with "timing" = 1 every check / variable launch of a call is bracketed by HIP events
-    // on the launch stream; scaldpc_qary_last_timing reads the sums.  Off by default: the product path records nothing.
-    int kn_llr_tiled = 1;  // probability -> LLR conversion through an LDS tile (coalesced reads); A/B knob "llr_tiled"
-    int kn_var_small = 1;  // register-resident variable update for Q = 3 / 5 / 7 / 15 and columns of at most 4 checks (A/B knob "var_small")
-    int kn_timing = 0;
+    QaryKnobs kn;  // (set by scaldpc_qary_configure; the environment is read once, at creation)
     float stat_ms_check = 0.f, stat_ms_var = 0.f, stat_ms_call = 0.f;
     int stat_iters = 0, stat_kernel = -1, stat_batch = 0;
     std::mutex mu;
@@ -844,9 +786,9 @@ int qary_build(int R, int N, int B, int BSUM, bool special, const int8_t *H, int
         off += h->h_var_q[v];
     }
     h->llr_rows = off;
-    if (const char *e = getenv("SCALDPC_QARY_WAVE")) h->kn_wave = atoi(e) != 0;  // the environment is read once per handle
-    if (getenv("SCALDPC_QARY_NO_UNROLL")) h->kn_unroll = 0;
-    if (getenv("SCALDPC_QARY_NO_TREE")) h->kn_tree = 0;
+    if (const char *e = getenv("SCALDPC_QARY_WAVE")) h->kn.wave = atoi(e) != 0;  // the environment is read once per handle
+    if (getenv("SCALDPC_QARY_NO_UNROLL")) h->kn.unroll = 0;
+    if (getenv("SCALDPC_QARY_NO_TREE")) h->kn.tree = 0;
     auto device_side = [&]() -> int {
         auto up = [](auto &d, const auto *src, size_t cnt) -> int {
             SC_TRY(d.ensure(cnt));
@@ -882,288 +824,274 @@ struct SoftOut {
     int32_t *unmet = nullptr;
 };
 
-int qary_run(scaldpc_qary *h, const float *pmf_b, const float *pmf_s, int batch, uint32_t flags, void *stream,
-             int8_t *out, const SoftOut &so = SoftOut())
+// One call on its way through qary_run's steps.
+struct QaryCall {
+    hipStream_t s = nullptr;
+    int batch = 0, BV = 0, iters = 1;  // BV: coefficient variables; the loop body runs at least once (decoder.rs:578-579)
+    long Bp = 0;                       // batch rounded up to whole waves
+    bool dev_io = false;
+    QaryPlan plan;
+    SoftOut so;
+    const float *dp_b = nullptr, *dp_s = nullptr;  // the probabilities on the device
+    signed char *dout = nullptr;                   // the symbols [batch][N] on the device
+    bool want_cost() const { return so.cost_b != nullptr; }
+    bool want_margin() const { return so.margin != nullptr; }
+    size_t n_pmf_b(const scaldpc_qary *h) const { return (size_t)batch * BV * h->Q; }  // floats of the coefficient rows' input (and cost table)
+    size_t n_pmf_s(const scaldpc_qary *h) const { return h->special ? (size_t)batch * h->R * h->QS : 0; }
+};
+
+// Everything the call will touch, before anything is queued.
+int ensure_buffers(scaldpc_qary *h, const QaryCall &c)
 {
-    if (!h || !pmf_b || !out || (h->special && !pmf_s)) return fail(SCALDPC_EINVAL, "NULL argument");
-    if (batch <= 0) return fail(SCALDPC_EINVAL, "batch must be positive");
-    const bool want_cost = so.cost_b != nullptr, want_margin = so.margin != nullptr, want_unmet = so.unmet != nullptr;
-    std::lock_guard<std::mutex> lk(h->mu);
-    DeviceGuard dg(h->device);
-    const bool dev_io = flags & SCALDPC_F_DEVICE_IO;
-    hipStream_t s = stream ? (hipStream_t)stream : h->own_stream;
-    const long Bp = ((long)batch + 63) / 64 * 64;
-    const int BV = h->special ? h->N - h->R : h->N;
-    if (Bp > h->cap_bp) {
+    if (c.Bp > h->cap_bp) {
         h->d_msg.reset(); h->d_llr.reset(); h->d_hard.reset();
         h->cap_bp = 0;
-        SC_TRY(h->d_msg.ensure((size_t)std::max(h->E, 1) * h->W * Bp));
-        SC_TRY(h->d_llr.ensure((size_t)h->llr_rows * Bp));
-        SC_TRY(h->d_hard.ensure((size_t)h->N * Bp));
-        h->cap_bp = Bp;
+        SC_TRY(h->d_msg.ensure((size_t)std::max(h->E, 1) * h->W * c.Bp));
+        SC_TRY(h->d_llr.ensure((size_t)h->llr_rows * c.Bp));
+        SC_TRY(h->d_hard.ensure((size_t)h->N * c.Bp));
+        h->cap_bp = c.Bp;
     }
-    const size_t n_cost = (size_t)batch * h->llr_rows, n_margin = (size_t)batch * h->N;
-    if (want_cost) {
-        SC_TRY(h->d_cost.ensure((size_t)h->llr_rows * Bp));
-        if (!dev_io) SC_TRY(h->d_cost_out.ensure(n_cost));
+    if (c.want_cost()) {
+        SC_TRY(h->d_cost.ensure((size_t)h->llr_rows * c.Bp));
+        if (!c.dev_io) SC_TRY(h->d_cost_out.ensure((size_t)c.batch * h->llr_rows));
     }
-    if (want_margin) {
-        SC_TRY(h->d_margin.ensure((size_t)h->N * Bp));
-        if (!dev_io) SC_TRY(h->d_margin_out.ensure(n_margin));
+    if (c.want_margin()) {
+        SC_TRY(h->d_margin.ensure((size_t)h->N * c.Bp));
+        if (!c.dev_io) SC_TRY(h->d_margin_out.ensure((size_t)c.batch * h->N));
     }
-    if (want_unmet && !dev_io) SC_TRY(h->d_unmet.ensure(batch));
-    SC_HIP(hipMemsetAsync(h->d_status, 0, 2 * sizeof(u64), s));
-    const int TB = 64;
-    // probabilities -> LLRs on the device (host inputs are staged as they are: [batch][var][Q] floats)
-    const float *dp_b = pmf_b, *dp_s = pmf_s;
-    if (!dev_io) {
-        const size_t nb = (size_t)batch * BV * h->Q, ns = h->special ? (size_t)batch * h->R * h->QS : 0;
-        SC_TRY(h->d_pmf.ensure(nb));
-        SC_HIP(hipMemcpyAsync(h->d_pmf, pmf_b, nb * sizeof(float), hipMemcpyHostToDevice, s));
-        dp_b = h->d_pmf;
+    if (c.dev_io) return 0;
+    if (c.so.unmet) SC_TRY(h->d_unmet.ensure(c.batch));
+    SC_TRY(h->d_pmf.ensure(c.n_pmf_b(h)));
+    if (h->special) SC_TRY(h->d_pmf2.ensure(c.n_pmf_s(h)));
+    return h->d_out.ensure((size_t)c.batch * h->N);
+}
+
+// One alphabet's rows of a conversion: nv variables of Q symbols from graph variable vbase on (kind 0: coefficient rows, 1: row-sum rows).
+struct LlrSeg {
+    const float *pmf;
+    int nv, Q, kind, vbase;
+    float *llr;
+};
+
+// k_q_into_llr_tiled over one alphabet or both (b != nullptr); fused: it writes the first messages too.
+void launch_llr_tiled(scaldpc_qary *h, const QaryCall &c, const LlrSeg &a, const LlrSeg *b, bool fused)
+{
+    const int VT0 = std::max(1, 32 / a.Q), nb0 = (a.nv + VT0 - 1) / VT0;
+    const int VT1 = b ? std::max(1, 32 / b->Q) : 0, nb1 = b ? (b->nv + VT1 - 1) / VT1 : 0;
+    hipLaunchKernelGGL(k_q_into_llr_tiled, dim3(nb0 + nb1, c.Bp / 64), dim3(64 * std::max(VT0, VT1)), 0, c.s, a.pmf, a.nv, a.Q, VT0,
+                       c.batch, c.Bp, a.llr, h->d_err, h->d_first_bad, a.kind, fused ? h->d_col_ptr.get() : nullptr,
+                       (const int *)h->d_csc_edge, (const int *)h->d_edge_h, h->d_msg, h->W, a.vbase, b ? nb0 : 0x7fffffff,
+                       b ? b->pmf : nullptr, b ? b->nv : 0, b ? b->Q : 0, VT1, b ? b->llr : nullptr, b ? b->vbase : 0);
+}
+
+// Host inputs are staged as they are ([batch][var][Q] floats); probabilities -> LLRs and the first messages on the device.
+int stage_and_convert(scaldpc_qary *h, QaryCall &c, const float *pmf_b, const float *pmf_s)
+{
+    c.dp_b = pmf_b;
+    c.dp_s = pmf_s;
+    if (!c.dev_io) {
+        SC_HIP(hipMemcpyAsync(h->d_pmf, pmf_b, c.n_pmf_b(h) * sizeof(float), hipMemcpyHostToDevice, c.s));
+        c.dp_b = h->d_pmf;
         if (h->special) {
-            SC_TRY(h->d_pmf2.ensure(ns));
-            SC_HIP(hipMemcpyAsync(h->d_pmf2, pmf_s, ns * sizeof(float), hipMemcpyHostToDevice, s));
-            dp_s = h->d_pmf2;
+            SC_HIP(hipMemcpyAsync(h->d_pmf2, pmf_s, c.n_pmf_s(h) * sizeof(float), hipMemcpyHostToDevice, c.s));
+            c.dp_s = h->d_pmf2;
         }
     }
-    // (alphabets of up to 32 symbols go through the LDS-tiled form: coalesced reads of [codeword][variable][Q])
-    // the tiled conversion also writes the first variable-to-check messages (k_q_init's job) when every alphabet takes it
-    const bool fused_init = h->kn_llr_tiled && h->Q <= 32 && (!h->special || h->QS <= 32) && h->E > 0;
-    auto into_llr = [&](const float *dp, int nv, int Q, float *llr, int kind) {
-        if (Q <= 32 && h->kn_llr_tiled) {
-            const int VT = std::max(1, 32 / Q);
-            if (fused_init)
-                hipLaunchKernelGGL(k_q_into_llr_tiled, dim3((nv + VT - 1) / VT, Bp / 64), dim3(64 * VT), 0, s, dp, nv, Q, VT, batch,
-                                   Bp, llr, h->d_err, h->d_first_bad, kind, (const int *)h->d_col_ptr, (const int *)h->d_csc_edge,
-                                   (const int *)h->d_edge_h, h->d_msg, h->W, kind ? BV : 0);
+    const LlrSeg seg[2] = {{c.dp_b, c.BV, h->Q, 0, 0, h->d_llr}, {c.dp_s, h->R, h->QS, 1, c.BV, h->d_llr + (size_t)c.BV * h->Q * c.Bp}};
+    if (c.plan.llr == QLlr::FUSED_BOTH) {
+        launch_llr_tiled(h, c, seg[0], &seg[1], true);
+        SC_HIP(hipGetLastError());
+    } else
+        for (int i = 0; i < (h->special ? 2 : 1); i++) {
+            if (c.plan.llr == QLlr::FUSED_EACH || (i ? c.plan.llr_tiled_s : c.plan.llr_tiled_b))
+                launch_llr_tiled(h, c, seg[i], nullptr, c.plan.llr == QLlr::FUSED_EACH);
             else
-                hipLaunchKernelGGL(k_q_into_llr_tiled, dim3((nv + VT - 1) / VT, Bp / 64), dim3(64 * VT), 0, s, dp, nv, Q, VT, batch,
-                                   Bp, llr, h->d_err, h->d_first_bad, kind);
-        } else
-            hipLaunchKernelGGL(k_q_into_llr, dim3(nv, Bp / TB), dim3(TB), 0, s, dp, nv, Q, batch, Bp, llr, h->d_err, h->d_first_bad,
-                               kind);
-    };
-    if (h->special && fused_init) {  // both alphabets in one launch
-        const int VT0 = std::max(1, 32 / h->Q), VT1 = std::max(1, 32 / h->QS), nb0 = (BV + VT0 - 1) / VT0, nb1 = (h->R + VT1 - 1) / VT1;
-        hipLaunchKernelGGL(k_q_into_llr_tiled, dim3(nb0 + nb1, Bp / 64), dim3(64 * std::max(VT0, VT1)), 0, s, dp_b, BV, h->Q, VT0, batch, Bp,
-                           h->d_llr, h->d_err, h->d_first_bad, 0, (const int *)h->d_col_ptr, (const int *)h->d_csc_edge,
-                           (const int *)h->d_edge_h, h->d_msg, h->W, 0, nb0, dp_s, h->R, h->QS, VT1,
-                           h->d_llr + (size_t)BV * h->Q * Bp, BV);
-        SC_HIP(hipGetLastError());
-    } else {
-        into_llr(dp_b, BV, h->Q, h->d_llr, 0);
-        SC_HIP(hipGetLastError());
-        if (h->special) {
-            into_llr(dp_s, h->R, h->QS, h->d_llr + (size_t)BV * h->Q * Bp, 1);
+                hipLaunchKernelGGL(k_q_into_llr, dim3(seg[i].nv, c.Bp / 64), dim3(64), 0, c.s, seg[i].pmf, seg[i].nv, seg[i].Q, c.batch,
+                                   c.Bp, seg[i].llr, h->d_err, h->d_first_bad, seg[i].kind);
             SC_HIP(hipGetLastError());
         }
-    }
-    if (h->E && !fused_init) {
-        hipLaunchKernelGGL(k_q_init, dim3(h->E, Bp / TB), dim3(TB), 0, s, h->d_edge_var, h->d_edge_h, h->d_var_q,
-                           h->d_var_off, h->d_llr, h->d_msg, h->W, Bp);
+    if (c.plan.init) {
+        hipLaunchKernelGGL(k_q_init, dim3(h->E, c.Bp / 64), dim3(64), 0, c.s, h->d_edge_var, h->d_edge_h, h->d_var_q, h->d_var_off,
+                           h->d_llr, h->d_msg, h->W, c.Bp);
         SC_HIP(hipGetLastError());
     }
-    // threads per block of the enumeration kernels: as many (<= 64) as fit 64 KB of LDS
-    size_t per_thread = h->special ? (size_t)2 * ((h->maxdc - 1) * h->Q + h->QS) * 4 : (size_t)h->maxdc * h->Q * 9;
-    int T = 64;
-    while (T > 8 && per_thread * T > 64 * 1024) T >>= 1;
-    if (per_thread * T > 64 * 1024)
-        return fail(SCALDPC_EDEGREE, "alphabet/degree too large for the LDS-staged enumeration (%zu B per codeword)",
-                    per_thread);
-    const int iters = std::max(1, h->iterations);  // the loop body runs at least once (decoder.rs:578-579)
-    // small batch: wave per (check, codeword), lanes share the assignment space
-    const size_t wave_lds = h->special
-                                ? (size_t)(((h->maxdc - 1) * h->Q + h->QS) * 65) * 4
-                                : (size_t)h->maxdc * h->Q * 4 * 65 + (size_t)h->maxdc * h->Q + h->maxdc + 16;
-    // measured: wave mode 0.69 vs 3.2 ms at batch 64 (config-4 decoder), 24 vs 70 ms (Kyber SW6);
-    // a tie at batch 1024, where one codeword per lane keeps global accesses coalesced
-    // the special decoder (15625 assignments per check at the Kyber shape) prefers wave mode at
-    // every batch size measured (93 vs 153 ms at batch 256)
-    bool wave_mode = (batch <= 256 || h->special) && wave_lds <= 64 * 1024;
-    if (h->kn_wave >= 0) wave_mode = h->kn_wave != 0 && wave_lds <= 64 * 1024;
-    if (h->maxdc > 8) wave_mode = false;  // 64-bit digit words in the wave kernels
-    // small alphabets: fully unrolled register enumeration (any batch size)
-    int unrolled = 0;
-    if (!h->special && h->kn_unroll) {
-        if (h->Q == 3 && h->maxdc <= 7) unrolled = 3;
-        if (h->Q == 5 && h->maxdc <= 5) unrolled = 5;
+    return 0;
+}
+
+void launch_check(scaldpc_qary *h, const QaryCall &c)
+{
+    const QaryPlan &p = c.plan;
+    const hipStream_t s = c.s;
+    // kernels of more than one instantiation: one launch site per signature
+    const auto rows = [&](auto kernel) {  // lane = codeword, registers only
+        hipLaunchKernelGGL(kernel, dim3(h->R, c.Bp / 64), dim3(64), 0, s, h->d_row_ptr, h->d_msg, c.Bp, c.batch, h->d_err);
+    };
+    const auto special_dp = [&](auto kernel, int parts) {
+        hipLaunchKernelGGL(kernel, dim3(h->R, c.Bp / 64), dim3(64 * parts), 0, s, h->d_row_ptr, h->d_msg, h->BSUM, h->W, c.Bp, c.batch);
+    };
+    const auto lane = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(h->R, c.Bp / p.T), dim3(p.T), p.check_lds, s, h->d_row_ptr, h->d_msg, h->Q, h->B, c.Bp, c.batch,
+                           h->maxdc, h->d_err);
+    };
+    // the special decoder's wave kernel: the form itself, or behind the tree walk / the min-plus recursion for the rows they leave
+    bool special_wave = p.wave_fallback_nb >= 0;
+    switch (p.check) {
+        case QCheck::NONE: return;
+        case QCheck::DP_3_7: rows(k_q_check_dp<3, 7>); break;
+        case QCheck::UNROLLED_3_7: rows(k_q_check_unrolled<3, 7>); break;
+        case QCheck::UNROLLED_5_5: rows(k_q_check_unrolled<5, 5>); break;
+        case QCheck::SPECIAL_DP:
+            // (a few dozen codewords: four waves per (check, 64 codewords); a few hundred: two)
+            if (p.check_parts == 4) special_dp(k_q_special_check_dp<5, 6, 4>, 4);
+            else if (p.check_parts == 2) special_dp(k_q_special_check_dp<5, 6, 2>, 2);
+            else special_dp(k_q_special_check_dp<5, 6, 1>, 1);
+            break;
+        case QCheck::SPECIAL_TREE:
+            hipLaunchKernelGGL((k_q_special_check_tree<5, 6>), dim3(h->R, c.batch), dim3(64), p.tree_lds, s, h->d_row_ptr, h->d_msg,
+                               h->BSUM, h->W, c.Bp);
+            break;
+        case QCheck::SPECIAL_WAVE: special_wave = true; break;
+        case QCheck::WAVE:
+            hipLaunchKernelGGL(k_q_check_wave, dim3(h->R, c.batch), dim3(64), p.wave_lds, s, h->d_row_ptr, h->d_msg, h->Q, h->B, c.Bp,
+                               h->maxdc, h->d_err);
+            break;
+        case QCheck::SPECIAL_LANE:
+            hipLaunchKernelGGL(k_q_special_check, dim3(h->R, c.Bp / p.T), dim3(p.T), p.check_lds, s, h->d_row_ptr, h->d_msg, h->B, h->BSUM,
+                               h->W, c.Bp, c.batch, h->maxdc - 1);
+            break;
+        case QCheck::LANE:
+            if (p.check_words128) lane(k_q_check<unsigned __int128>);
+            else lane(k_q_check<u64>);
+            break;
     }
-    // special decoder, Kyber shape (B = 2, rows of up to 6 coefficient edges + the row-sum edge): tree-walk kernel
-    const int tree_nb = (h->special && h->kn_tree && (h->kn_wave != 0) && h->Q == 5 && h->maxdc - 1 == 6 && wave_lds <= 64 * 1024) ? 6 : 0;
-    // ... and from a few codewords on, the min-plus recursion (lane = codeword) instead of any enumeration
-    const int dp_nb = (h->special && h->kn_dp && (h->kn_wave != 0) && h->Q == 5 && h->maxdc - 1 == 6 && wave_lds <= 64 * 1024 &&
-                       batch >= h->kn_dp_min) ? 6 : 0;
-    // which check kernel this call runs (scaldpc_qary_last_timing's info[1])
-    const int kernel_id = !h->E ? -1 : (unrolled == 3 && h->kn_dp) ? 8 : unrolled == 3 ? 0 : unrolled == 5 ? 1 : (h->special && dp_nb) ? 7 : (h->special && tree_nb) ? 2 : (wave_mode && h->special) ? 3
-                          : wave_mode ? 4 : h->special ? 5 : 6;
-    const bool timing = h->kn_timing != 0;
+    if (special_wave)  // (skip_nb -1, the form itself: no row is skipped)
+        hipLaunchKernelGGL(k_q_special_check_wave, dim3(h->R, c.batch), dim3(64), p.wave_lds, s, h->d_row_ptr, h->d_msg, h->B, h->BSUM,
+                           h->W, c.Bp, h->maxdc - 1, p.wave_fallback_nb);
+}
+
+// SOFT: the soft form of whichever kernel the plain call runs -- totals (dc) and margins (dm) staged next to the symbols.
+template <bool SOFT>
+void launch_var(scaldpc_qary *h, const QaryCall &c, int last, float *dc = nullptr, float *dm = nullptr)
+{
+    const auto small = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(h->N, c.Bp / 64), dim3(64), 0, c.s, h->d_col_ptr, h->d_csc_edge, h->d_edge_h, h->d_llr, h->d_msg,
+                           c.Bp, c.batch, last, h->d_hard, dc, dm);
+    };
+    switch (c.plan.var) {
+        case QVar::SMALL:
+            if (h->Q == 3) small(k_q_var_small<3, 4, SOFT>);
+            else if (h->Q == 5) small(k_q_var_small<5, 4, SOFT>);
+            else if (h->Q == 7) small(k_q_var_small<7, 4, SOFT>);
+            else small(k_q_var_small<15, 4, SOFT>);
+            break;
+        case QVar::SMALL_SPECIAL:
+            hipLaunchKernelGGL((k_q_var_small_special<5, 4, 25, SOFT>), dim3(h->N, c.Bp / 64), dim3(64), 0, c.s, h->d_col_ptr,
+                               h->d_csc_edge, h->d_edge_h, h->d_llr, h->d_msg, c.BV, h->W, c.Bp, c.batch, last, h->d_hard, dc, dm);
+            break;
+        case QVar::GENERIC:
+            hipLaunchKernelGGL(k_q_var<SOFT>, dim3(h->N, c.Bp / 64), dim3(64), c.plan.var_lds, c.s, 0, h->d_col_ptr, h->d_csc_edge,
+                               h->d_edge_h, h->d_var_q, h->d_var_off, h->d_llr, h->d_msg, h->W, c.Bp, c.batch, h->W, last, h->d_hard, dc,
+                               dm);
+            break;
+    }
+}
+
+// The iterations: check pass, variable pass.  With the timing knob every launch is bracketed by events:
+// tev[2 it], tev[2 it + 1]: before iteration it's check / variable pass;  tev[2 iters]: the end;  tev[2 iters + 1]: the start.
+int iterate(scaldpc_qary *h, const QaryCall &c)
+{
+    const int iters = c.iters;
+    const bool timing = h->kn.timing != 0;
     if (timing) {
         while (h->tev.size() < (size_t)2 * iters + 2) {
             hipEvent_t e;
             SC_HIP(hipEventCreate(&e));
             h->tev.push_back(e);
         }
-        SC_HIP(hipEventRecord(h->tev[2 * iters + 1], s));  // start of the call's device work is behind us: into_llr + init
+        SC_HIP(hipEventRecord(h->tev[2 * iters + 1], c.s));  // start of the call's device work is behind us: into_llr + init
     }
     for (int it = 1; it <= iters; it++) {
-        if (timing) SC_HIP(hipEventRecord(h->tev[2 * (it - 1)], s));
-        if (h->E) {
-#define QUNROLLED(QQ, KK)                                                                                         \
-    hipLaunchKernelGGL((k_q_check_unrolled<QQ, KK>), dim3(h->R, Bp / 64), dim3(64), 0, s, h->d_row_ptr, h->d_msg, Bp, \
-                       batch, h->d_err)
-            if (unrolled == 3 && h->kn_dp) {
-                hipLaunchKernelGGL((k_q_check_dp<3, 7>), dim3(h->R, Bp / 64), dim3(64), 0, s, h->d_row_ptr, h->d_msg, Bp, batch, h->d_err);
-            } else if (unrolled == 3) {
-                QUNROLLED(3, 7);
-            } else if (unrolled == 5) {
-                QUNROLLED(5, 5);
-            }
-#undef QUNROLLED
-            else if (h->special && dp_nb) {
-                if (batch <= h->kn_dp_split)  // (a few dozen codewords: four waves per (check, 64 codewords))
-                    hipLaunchKernelGGL((k_q_special_check_dp<5, 6, 4>), dim3(h->R, Bp / 64), dim3(256), 0, s, h->d_row_ptr, h->d_msg,
-                                       h->BSUM, h->W, Bp, batch);
-                else if (batch <= h->kn_dp_split2)  // (a few hundred: two)
-                    hipLaunchKernelGGL((k_q_special_check_dp<5, 6, 2>), dim3(h->R, Bp / 64), dim3(128), 0, s, h->d_row_ptr, h->d_msg,
-                                       h->BSUM, h->W, Bp, batch);
-                else
-                    hipLaunchKernelGGL((k_q_special_check_dp<5, 6, 1>), dim3(h->R, Bp / 64), dim3(64), 0, s, h->d_row_ptr, h->d_msg,
-                                       h->BSUM, h->W, Bp, batch);
-                if (h->mindc - 1 != dp_nb || h->maxdc - 1 != dp_nb)
-                    hipLaunchKernelGGL(k_q_special_check_wave, dim3(h->R, batch), dim3(64), wave_lds, s, h->d_row_ptr, h->d_msg,
-                                       h->B, h->BSUM, h->W, Bp, h->maxdc - 1, dp_nb);
-            } else if (h->special && tree_nb) {
-                // the Kyber shape: tree walk for the rows of 6 coefficient edges, the generic wave kernel for any others
-                const size_t tree_lds = ((size_t)tree_nb * h->Q + h->QS + (size_t)(tree_nb * h->Q + h->QS) * 64) * 4;
-                hipLaunchKernelGGL((k_q_special_check_tree<5, 6>), dim3(h->R, batch), dim3(64), tree_lds, s, h->d_row_ptr, h->d_msg,
-                                   h->BSUM, h->W, Bp);
-                if (h->mindc - 1 != tree_nb || h->maxdc - 1 != tree_nb)
-                    hipLaunchKernelGGL(k_q_special_check_wave, dim3(h->R, batch), dim3(64), wave_lds, s, h->d_row_ptr, h->d_msg,
-                                       h->B, h->BSUM, h->W, Bp, h->maxdc - 1, tree_nb);
-            } else if (wave_mode && h->special)
-                hipLaunchKernelGGL(k_q_special_check_wave, dim3(h->R, batch), dim3(64), wave_lds, s, h->d_row_ptr, h->d_msg,
-                                   h->B, h->BSUM, h->W, Bp, h->maxdc - 1, -1);
-            else if (wave_mode)
-                hipLaunchKernelGGL(k_q_check_wave, dim3(h->R, batch), dim3(64), wave_lds, s, h->d_row_ptr, h->d_msg, h->Q,
-                                   h->B, Bp, h->maxdc, h->d_err);
-            else if (h->special)
-                hipLaunchKernelGGL(k_q_special_check, dim3(h->R, Bp / T), dim3(T), per_thread * T, s, h->d_row_ptr,
-                                   h->d_msg, h->B, h->BSUM, h->W, Bp, batch, h->maxdc - 1);
-            else
-                if (h->maxdc <= 8)
-                    hipLaunchKernelGGL(k_q_check<u64>, dim3(h->R, Bp / T), dim3(T), per_thread * T, s, h->d_row_ptr, h->d_msg,
-                                       h->Q, h->B, Bp, batch, h->maxdc, h->d_err);
-                else
-                    hipLaunchKernelGGL(k_q_check<unsigned __int128>, dim3(h->R, Bp / T), dim3(T), per_thread * T, s, h->d_row_ptr,
-                                       h->d_msg, h->Q, h->B, Bp, batch, h->maxdc, h->d_err);
+        if (timing) SC_HIP(hipEventRecord(h->tev[2 * (it - 1)], c.s));
+        if (c.plan.check != QCheck::NONE) {
+            launch_check(h, c);
             SC_HIP(hipGetLastError());
         }
-        if (timing) SC_HIP(hipEventRecord(h->tev[2 * (it - 1) + 1], s));
-#define QVAR_SMALL(QQ)                                                                                              \
-    hipLaunchKernelGGL((k_q_var_small<QQ, 4>), dim3(h->N, Bp / 64), dim3(64), 0, s, h->d_col_ptr, h->d_csc_edge, h->d_edge_h, \
-                       h->d_llr, h->d_msg, Bp, batch, it == iters ? 1 : 0, h->d_hard)
-        const bool vs = !h->special && h->kn_var_small && h->maxdv <= 4;
-        if (it == iters && (want_cost || want_margin)) {
-            // the soft form of whichever kernel the plain call runs: totals and margins staged next to the symbols
-            float *dc = want_cost ? h->d_cost.get() : nullptr, *dm = want_margin ? h->d_margin.get() : nullptr;
-#define QVAR_SMALL_SOFT(QQ)                                                                                                        \
-    hipLaunchKernelGGL((k_q_var_small_soft<QQ, 4>), dim3(h->N, Bp / 64), dim3(64), 0, s, h->d_col_ptr, h->d_csc_edge, h->d_edge_h, \
-                       h->d_llr, h->d_msg, Bp, batch, h->d_hard, dc, dm)
-            if (vs && h->Q == 3)
-                QVAR_SMALL_SOFT(3);
-            else if (vs && h->Q == 5)
-                QVAR_SMALL_SOFT(5);
-            else if (vs && h->Q == 7)
-                QVAR_SMALL_SOFT(7);
-            else if (vs && h->Q == 15)
-                QVAR_SMALL_SOFT(15);
-            else if (h->special && h->kn_var_small && h->Q == 5 && h->QS == 25 && h->maxdv <= 4)
-                hipLaunchKernelGGL((k_q_var_small_special_soft<5, 4, 25>), dim3(h->N, Bp / 64), dim3(64), 0, s, h->d_col_ptr,
-                                   h->d_csc_edge, h->d_edge_h, h->d_llr, h->d_msg, BV, h->W, Bp, batch, h->d_hard, dc, dm);
-            else
-                hipLaunchKernelGGL(k_q_var_soft, dim3(h->N, Bp / TB), dim3(TB), (size_t)2 * h->W * TB * 4, s, 0, h->d_col_ptr,
-                                   h->d_csc_edge, h->d_edge_h, h->d_var_q, h->d_var_off, h->d_llr, h->d_msg, h->W, Bp, batch, h->W,
-                                   h->d_hard, dc, dm);
-#undef QVAR_SMALL_SOFT
-        } else if (vs && h->Q == 3)
-            QVAR_SMALL(3);
-        else if (vs && h->Q == 5)
-            QVAR_SMALL(5);
-        else if (vs && h->Q == 7)
-            QVAR_SMALL(7);
-        else if (vs && h->Q == 15)  // (B = 7: the reference's criterion and unit-test decoders)
-            QVAR_SMALL(15);
-        else if (h->special && h->kn_var_small && h->Q == 5 && h->QS == 25 && h->maxdv <= 4)  // the Kyber SW6 classes (lib.rs:54-75)
-            hipLaunchKernelGGL((k_q_var_small_special<5, 4, 25>), dim3(h->N, Bp / 64), dim3(64), 0, s, h->d_col_ptr, h->d_csc_edge,
-                               h->d_edge_h, h->d_llr, h->d_msg, BV, h->W, Bp, batch, it == iters ? 1 : 0, h->d_hard);
+        if (timing) SC_HIP(hipEventRecord(h->tev[2 * (it - 1) + 1], c.s));
+        if (it == iters && (c.want_cost() || c.want_margin()))
+            launch_var<true>(h, c, 1, c.want_cost() ? h->d_cost.get() : nullptr, c.want_margin() ? h->d_margin.get() : nullptr);
         else
-            hipLaunchKernelGGL(k_q_var, dim3(h->N, Bp / TB), dim3(TB), (size_t)2 * h->W * TB * 4, s, 0, h->d_col_ptr,
-                               h->d_csc_edge, h->d_edge_h, h->d_var_q, h->d_var_off, h->d_llr, h->d_msg, h->W, Bp, batch, h->W,
-                               it == iters ? 1 : 0, h->d_hard);
-#undef QVAR_SMALL
+            launch_var<false>(h, c, it == iters ? 1 : 0);
         SC_HIP(hipGetLastError());
     }
-    if (timing) SC_HIP(hipEventRecord(h->tev[2 * iters], s));
-    signed char *dout = (signed char *)out;
-    if (!dev_io) {
-        SC_TRY(h->d_out.ensure((size_t)batch * h->N));
-        dout = h->d_out;
-    }
-    hipLaunchKernelGGL(k_q_unpack, dim3((h->N + 255) / 256, batch), dim3(256), 0, s, h->d_hard, h->N, batch, Bp, dout);
+    if (timing) SC_HIP(hipEventRecord(h->tev[2 * iters], c.s));
+    return 0;
+}
+
+// Symbols and soft outputs into the caller's layout and memory, with the status block; returns with the stream drained.
+int emit(scaldpc_qary *h, QaryCall &c, int8_t *out, u64 (&status)[2])
+{
+    const hipStream_t s = c.s;
+    const int batch = c.batch;
+    const long Bp = c.Bp;
+    const size_t nb = c.n_pmf_b(h), n_cost = (size_t)batch * h->llr_rows, n_margin = (size_t)batch * h->N;
+    c.dout = c.dev_io ? (signed char *)out : h->d_out.get();
+    hipLaunchKernelGGL(k_q_unpack, dim3((h->N + 255) / 256, batch), dim3(256), 0, s, h->d_hard, h->N, batch, Bp, c.dout);
     SC_HIP(hipGetLastError());
-    if (want_cost || want_margin) {
+    if (c.want_cost() || c.want_margin()) {
         // staging [row][Bp] -> [batch][rows]: the cost table (two row ranges for DecoderSpecial) and the margins, one launch
-        const size_t nb = (size_t)batch * BV * h->Q;  // floats of the coefficient rows' table
-        float *oc = dev_io ? so.cost_b : h->d_cost_out.get(), *ocs = dev_io ? so.cost_s : h->d_cost_out.get() + nb;
+        float *oc = c.dev_io ? c.so.cost_b : h->d_cost_out.get(), *ocs = c.dev_io ? c.so.cost_s : h->d_cost_out.get() + nb;
         SoftSegs sg = {};
-        if (want_cost) {
-            sg.src[0] = h->d_cost; sg.dst[0] = oc; sg.rows[0] = BV * h->Q;
-            if (h->special) { sg.src[1] = h->d_cost + (size_t)BV * h->Q * Bp; sg.dst[1] = ocs; sg.rows[1] = h->R * h->QS; }
+        if (c.want_cost()) {
+            sg.src[0] = h->d_cost; sg.dst[0] = oc; sg.rows[0] = c.BV * h->Q;
+            if (h->special) { sg.src[1] = h->d_cost + (size_t)c.BV * h->Q * Bp; sg.dst[1] = ocs; sg.rows[1] = h->R * h->QS; }
         }
-        if (want_margin) { sg.src[2] = h->d_margin; sg.dst[2] = dev_io ? so.margin : h->d_margin_out.get(); sg.rows[2] = h->N; }
+        if (c.want_margin()) { sg.src[2] = h->d_margin; sg.dst[2] = c.dev_io ? c.so.margin : h->d_margin_out.get(); sg.rows[2] = h->N; }
         for (int i = 0; i < 3; i++) sg.tile0[i + 1] = sg.tile0[i] + (sg.rows[i] + 63) / 64;
         hipLaunchKernelGGL(k_q_soft_transpose, dim3(sg.tile0[3], Bp / 64), dim3(256), 0, s, sg, batch, Bp);
         SC_HIP(hipGetLastError());
     }
-    if (want_unmet) {
-        int *du = dev_io ? so.unmet : h->d_unmet.get();
+    if (c.so.unmet) {
+        int *du = c.dev_io ? c.so.unmet : h->d_unmet.get();
         SC_HIP(hipMemsetAsync(du, 0, (size_t)batch * sizeof(int), s));
         hipLaunchKernelGGL((k_q_unmet<8>), dim3((h->R + 7) / 8, Bp / 64), dim3(64), 0, s, h->d_row_ptr, h->d_edge_var, h->d_edge_h,
                            h->d_hard, h->R, batch, Bp, du);
         SC_HIP(hipGetLastError());
     }
-    u64 status[2] = {0, 0};
     SC_HIP(hipMemcpyAsync(status, h->d_status, sizeof(status), hipMemcpyDeviceToHost, s));
-    if (!dev_io) {
-        SC_HIP(hipMemcpyAsync(out, dout, (size_t)batch * h->N, hipMemcpyDeviceToHost, s));
-        if (want_cost) {
-            const size_t nb = (size_t)batch * BV * h->Q;
-            SC_HIP(hipMemcpyAsync(so.cost_b, h->d_cost_out, nb * sizeof(float), hipMemcpyDeviceToHost, s));
-            if (h->special) SC_HIP(hipMemcpyAsync(so.cost_s, h->d_cost_out + nb, (n_cost - nb) * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (!c.dev_io) {
+        SC_HIP(hipMemcpyAsync(out, c.dout, (size_t)batch * h->N, hipMemcpyDeviceToHost, s));
+        if (c.want_cost()) {
+            SC_HIP(hipMemcpyAsync(c.so.cost_b, h->d_cost_out, nb * sizeof(float), hipMemcpyDeviceToHost, s));
+            if (h->special) SC_HIP(hipMemcpyAsync(c.so.cost_s, h->d_cost_out + nb, (n_cost - nb) * sizeof(float), hipMemcpyDeviceToHost, s));
         }
-        if (want_margin) SC_HIP(hipMemcpyAsync(so.margin, h->d_margin_out, n_margin * sizeof(float), hipMemcpyDeviceToHost, s));
-        if (want_unmet) SC_HIP(hipMemcpyAsync(so.unmet, h->d_unmet, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, s));
+        if (c.want_margin()) SC_HIP(hipMemcpyAsync(c.so.margin, h->d_margin_out, n_margin * sizeof(float), hipMemcpyDeviceToHost, s));
+        if (c.so.unmet) SC_HIP(hipMemcpyAsync(c.so.unmet, h->d_unmet, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, s));
     }
     SC_HIP(hipStreamSynchronize(s));
-    const int err = (int)(unsigned)status[1];
-    const u64 bad = ~status[0];
-    if (timing) {
+    return 0;
+}
+
+// The timing sums (with the knob) and the call's verdict out of the status block.
+int report(scaldpc_qary *h, const QaryCall &c, const u64 (&status)[2])
+{
+    if (h->kn.timing) {
         h->stat_ms_check = h->stat_ms_var = 0.f;
-        for (int it = 0; it < iters; it++) {
+        for (int it = 0; it < c.iters; it++) {
             float a = 0.f, b = 0.f;
             SC_HIP(hipEventElapsedTime(&a, h->tev[2 * it], h->tev[2 * it + 1]));
             SC_HIP(hipEventElapsedTime(&b, h->tev[2 * it + 1], h->tev[2 * it + 2]));
             h->stat_ms_check += a;
             h->stat_ms_var += b;
         }
-        SC_HIP(hipEventElapsedTime(&h->stat_ms_call, h->tev[2 * iters + 1], h->tev[2 * iters]));
-        h->stat_iters = iters;
-        h->stat_kernel = kernel_id;
-        h->stat_batch = batch;
+        SC_HIP(hipEventElapsedTime(&h->stat_ms_call, h->tev[2 * c.iters + 1], h->tev[2 * c.iters]));
+        h->stat_iters = c.iters;
+        h->stat_kernel = (int)c.plan.check;
+        h->stat_batch = c.batch;
     }
+    const int err = (int)(unsigned)status[1];
+    const u64 bad = ~status[0];
     if (err == QERR_PMF) {
-        const int bb = (int)(bad >> 32), vv = (int)((bad & 0x7fffffffull) >> 1) + (((bad >> 31) & 1) ? BV : 0);
+        const int bb = (int)(bad >> 32), vv = (int)((bad & 0x7fffffffull) >> 1) + (((bad >> 31) & 1) ? c.BV : 0);
         if (bad & 1) return fail(SCALDPC_EPMF, "No maximum probability found (codeword %d, variable %d)", bb, vv);
         return fail(SCALDPC_EPMF, "channel output of codeword %d, variable %d does not sum to 1 +- 1e-3 (decoder.rs:683-684)",
                     bb, vv);
@@ -1173,6 +1101,33 @@ int qary_run(scaldpc_qary *h, const float *pmf_b, const float *pmf_s, int batch,
     if (err == QERR_NO_FINITE)
         return fail(SCALDPC_ENOCONF, "a message has no finite entry (the reference would not terminate, decoder.rs:368-375)");
     return 0;
+}
+
+int qary_run(scaldpc_qary *h, const float *pmf_b, const float *pmf_s, int batch, uint32_t flags, void *stream,
+             int8_t *out, const SoftOut &so = SoftOut())
+{
+    if (!h || !pmf_b || !out || (h->special && !pmf_s)) return fail(SCALDPC_EINVAL, "NULL argument");
+    if (batch <= 0) return fail(SCALDPC_EINVAL, "batch must be positive");
+    std::lock_guard<std::mutex> lk(h->mu);
+    DeviceGuard dg(h->device);
+    QaryCall c;
+    c.s = stream ? (hipStream_t)stream : h->own_stream;
+    c.batch = batch;
+    c.Bp = ((long)batch + 63) / 64 * 64;
+    c.BV = h->special ? h->N - h->R : h->N;
+    c.iters = std::max(1, h->iterations);
+    c.dev_io = flags & SCALDPC_F_DEVICE_IO;
+    c.so = so;
+    if (qary_plan(*h, h->kn, batch, &c.plan))  // (nothing is queued yet)
+        return fail(SCALDPC_EDEGREE, "alphabet/degree too large for the LDS-staged enumeration (%zu B per codeword)",
+                    c.plan.check_lds / c.plan.T);
+    SC_TRY(ensure_buffers(h, c));
+    SC_HIP(hipMemsetAsync(h->d_status, 0, 2 * sizeof(u64), c.s));
+    SC_TRY(stage_and_convert(h, c, pmf_b, pmf_s));
+    SC_TRY(iterate(h, c));
+    u64 status[2] = {0, 0};
+    SC_TRY(emit(h, c, out, status));
+    return report(h, c, status);
 }
 
 }  // namespace
@@ -1227,28 +1182,7 @@ int scaldpc_qary_configure(scaldpc_qary *h, const char *key, const char *value)
 {
     if (!h || !key || !value) return fail(SCALDPC_EINVAL, "NULL argument");
     std::lock_guard<std::mutex> lk(h->mu);
-    if (!strcmp(key, "wave"))
-        h->kn_wave = atoi(value) < 0 ? -1 : atoi(value) != 0;
-    else if (!strcmp(key, "unroll"))
-        h->kn_unroll = atoi(value) != 0;
-    else if (!strcmp(key, "tree"))
-        h->kn_tree = atoi(value) != 0;
-    else if (!strcmp(key, "dp"))
-        h->kn_dp = atoi(value) != 0;
-    else if (!strcmp(key, "dp_min"))
-        h->kn_dp_min = std::max(1, atoi(value));
-    else if (!strcmp(key, "dp_split"))
-        h->kn_dp_split = std::max(0, atoi(value));
-    else if (!strcmp(key, "dp_split2"))
-        h->kn_dp_split2 = std::max(0, atoi(value));
-    else if (!strcmp(key, "timing"))
-        h->kn_timing = atoi(value) != 0;
-    else if (!strcmp(key, "llr_tiled"))
-        h->kn_llr_tiled = atoi(value) != 0;
-    else if (!strcmp(key, "var_small"))
-        h->kn_var_small = atoi(value) != 0;
-    else
-        return fail(SCALDPC_EINVAL, "unknown knob %s", key);
+    if (!set_knob(h->kn, key, value)) return fail(SCALDPC_EINVAL, "unknown knob %s", key);
     return 0;
 }
 
@@ -1286,11 +1220,7 @@ int scaldpc_qary_min_sum_batch_soft(scaldpc_qary *h, const float *pmf, int32_t b
 {
     if (h && h->special) return fail(SCALDPC_EINVAL, "this handle is a special decoder: use scaldpc_qary_special_min_sum_batch_soft");
     if (flags & SCALDPC_F_ASYNC) return fail(SCALDPC_EINVAL, "SCALDPC_F_ASYNC: a q-ary soft call is synchronous");
-    SoftOut so;
-    so.cost_b = out_cost;
-    so.margin = out_margin;
-    so.unmet = out_unmet;
-    return qary_run(h, pmf, nullptr, batch, flags, stream, out, so);
+    return qary_run(h, pmf, nullptr, batch, flags, stream, out, SoftOut{out_cost, nullptr, out_margin, out_unmet});
 }
 
 int scaldpc_qary_special_min_sum_batch_soft(scaldpc_qary *h, const float *pmf_b, const float *pmf_sum, int32_t batch,
@@ -1301,12 +1231,7 @@ int scaldpc_qary_special_min_sum_batch_soft(scaldpc_qary *h, const float *pmf_b,
     if (flags & SCALDPC_F_ASYNC) return fail(SCALDPC_EINVAL, "SCALDPC_F_ASYNC: a q-ary soft call is synchronous");
     if ((out_cost_b == nullptr) != (out_cost_sum == nullptr))
         return fail(SCALDPC_EINVAL, "out_cost_b and out_cost_sum: pass both or neither");
-    SoftOut so;
-    so.cost_b = out_cost_b;
-    so.cost_s = out_cost_sum;
-    so.margin = out_margin;
-    so.unmet = out_unmet;
-    return qary_run(h, pmf_b, pmf_sum, batch, flags, stream, out, so);
+    return qary_run(h, pmf_b, pmf_sum, batch, flags, stream, out, SoftOut{out_cost_b, out_cost_sum, out_margin, out_unmet});
 }
 
 void scaldpc_qary_destroy(scaldpc_qary *h)

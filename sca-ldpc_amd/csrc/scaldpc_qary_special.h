@@ -44,6 +44,21 @@ __device__ __forceinline__ float fold_min(const float (&v)[N])
     return m;
 }
 
+// The wave-per-(check, codeword) kernels keep per-lane partial minima in LDS tables [slot][64]: the minimum of one slot's 64
+// entries, read by ONE lane, rotated by its own index so that the lanes of a wave (each on a row of its own) hit different
+// banks -- four independent chains instead of 6 dependent cross-lane steps per slot.
+__device__ __forceinline__ float fold_min_rows64(const float *row, int lane)
+{
+    float m0 = INFINITY, m1 = INFINITY, m2 = INFINITY, m3 = INFINITY;
+#pragma unroll 4
+    for (int l = 0; l < 64; l += 4) {
+        m0 = vmin(m0, row[(l + lane) & 63]);
+        m1 = vmin(m1, row[(l + 1 + lane) & 63]);
+        m2 = vmin(m2, row[(l + 2 + lane) & 63]);
+        m3 = vmin(m3, row[(l + 3 + lane) & 63]);
+    }
+    return vmin(vmin(m0, m1), vmin(m2, m3));
+}
 
 // Check-node update of DecoderSpecial (decoder_special.rs:506-563): the first k-1 edges
 // are B-variables (alphabet QB), the last is the row-sum variable (alphabet QS); ALL
@@ -249,16 +264,7 @@ __global__ __launch_bounds__(64) void k_q_special_check_tree(const int *__restri
     __syncthreads();
     const int nslots = NB * QB + QS;  // Bb and Bs are contiguous: one table of nslots rows
     for (int s = lane; s < nslots; s += 64) {
-        const float *row = Bb + (size_t)s * 64;
-        float m0 = INFINITY, m1 = INFINITY, m2 = INFINITY, m3 = INFINITY;
-#pragma unroll 4
-        for (int l = 0; l < 64; l += 4) {
-            m0 = vmin(m0, row[(l + lane) & 63]);
-            m1 = vmin(m1, row[(l + 1 + lane) & 63]);
-            m2 = vmin(m2, row[(l + 2 + lane) & 63]);
-            m3 = vmin(m3, row[(l + 3 + lane) & 63]);
-        }
-        const float mS = vmin(vmin(m0, m1), vmin(m2, m3));
+        const float mS = fold_min_rows64(Bb + (size_t)s * 64, lane);
         const float v = finite_f(mS) ? mS - Ab[s] : INFINITY;  // (Ab and As are contiguous: slot s's alpha is Ab[s])
         if (s < NB * QB)
             msg[((size_t)(e0 + s / QB) * W + s % QB) * Bp + b] = v;

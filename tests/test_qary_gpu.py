@@ -490,3 +490,76 @@ def test_full_size_invariances(golden):
     assert np.array_equal(deck.min_sum_batch(pb[::-1].copy(), ps[::-1].copy())[::-1], k)
     assert np.array_equal(deck.min_sum_batch(pb[33:34], ps[33:34])[0], k[33])
     deck.close()
+
+
+# -------------------------------------------------------------------------------------- the launch plan (csrc/scaldpc_qary_plan.h)
+TREE_H = np.array([[1, -1, 1, 0, 0, 0], [0, 0, -1, 1, 1, 0], [0, 0, 0, 0, -1, 1]], dtype=np.int8)  # smoke()'s cycle-free graph
+
+
+@pytest.fixture(scope="module")
+def plan_cases(oracle):
+    """name -> (decoder, inputs [70, ...], the oracle's symbols): the 3 x 6 tree (DecoderN6R3V2C3B1) and a Kyber-shaped special
+    graph of two checks, H = [H' | I_2] with a full first row and four entries in the second (DecoderN8R2SW6: mixed row
+    degrees, so the wave kernel follows the tree walk and the min-plus recursion).  2 iterations."""
+    rng = np.random.RandomState(2024)
+    pq = rng.dirichlet(np.ones(3) * 2, size=(70, 6)).astype(np.float32)
+    Hs = np.concatenate([np.array([[1, -1, 1, 1, -1, 1], [-1, 0, 1, 0, 1, -1]], dtype=np.int8), np.eye(2, dtype=np.int8)], axis=1)
+    pb = rng.dirichlet(np.ones(5), size=(70, 6)).astype(np.float32)
+    ps = rng.dirichlet(np.ones(25), size=(70, 2)).astype(np.float32)
+    cases = {
+        "generic": (qary.decoder_class("DecoderN6R3V2C3B1")(TREE_H, 2), (pq,),
+                    oracle.qary_min_sum_batch(S.TannerGraph.from_dense(TREE_H), 3, pq, 2, threads=4)),
+        "special": (qary.decoder_class("DecoderN8R2SW6")(Hs, 2), (pb, ps),
+                    oracle.qary_special_batch(S.TannerGraph.from_dense(Hs), 2, 12, pb, ps, 2, threads=4)),
+    }
+    yield cases
+    for dec, _, _ in cases.values():
+        dec.close()
+
+
+@pytest.mark.parametrize("case, knobs, batch, kernel", [
+    ("generic", dict(), 70, "k_q_check_dp<3,7>"),
+    ("generic", dict(dp=0), 70, "k_q_check_unrolled<3,7>"),
+    ("generic", dict(unroll=0), 3, "k_q_check_wave"),
+    ("generic", dict(unroll=0, wave=0), 3, "k_q_check"),
+    ("special", dict(), 1, "k_q_special_check_tree<5,6>"),
+    ("special", dict(), 5, "k_q_special_check_dp<5,6>"),
+    ("special", dict(), 70, "k_q_special_check_dp<5,6>"),
+    ("special", dict(dp=0), 5, "k_q_special_check_tree<5,6>"),
+    ("special", dict(tree=0, dp=0), 5, "k_q_special_check_wave"),
+    ("special", dict(wave=0), 5, "k_q_special_check"),
+])  # fmt: skip
+def test_the_plan_is_what_runs(plan_cases, case, knobs, batch, kernel):
+    """What qary_plan decides (tests/test_qary_plan.py holds it to the documented rules) is what a call launches: the check
+    kernel `last_timing` names, and the oracle's symbols out of it."""
+    dec, inputs, ref = plan_cases[case]
+    defaults = dict(wave=-1, unroll=1, tree=1, dp=1, dp_min=5, dp_split=64, dp_split2=192, llr_tiled=1, var_small=1)
+    dec.configure(**dict(defaults, timing=1, **knobs))
+    got = dec.min_sum_batch(*(a[:batch] for a in inputs))
+    t = dec.last_timing()
+    assert (t["check_kernel"], t["batch"], t["iterations"]) == (kernel, batch, 2)
+    assert np.array_equal(got, ref[:batch])
+
+
+def test_a_refused_shape_leaves_the_stream_alone(oracle):
+    """Q = 255 on a check of four edges does not fit the LDS-staged enumeration: the call is refused (SCALDPC_EDEGREE) before
+    anything is queued, and the next call on the same stream, on another handle, decodes."""
+    import torch
+
+    stream = torch.cuda.current_stream().cuda_stream
+    big = qary.decoder_class("DecoderN4R1V1C4B127")(np.ones((1, 4), dtype=np.int8), 1)
+    d_in = torch.full((1, 4, 255), 1 / 255, dtype=torch.float32, device="cuda")
+    d_out = torch.full((1, 4), 99, dtype=torch.int8, device="cuda")
+    with pytest.raises(qary._lib.ScaldpcError, match=r"^\[6\] alphabet/degree too large for the LDS-staged enumeration \(9180 B per codeword\)"):
+        big.min_sum_batch_device(d_in.data_ptr(), 1, d_out.data_ptr(), stream=stream)
+    with pytest.raises(qary._lib.ScaldpcError, match=r"^\[6\] alphabet/degree too large"):
+        big.min_sum_batch(np.full((1, 4, 255), 1 / 255, dtype=np.float32))
+    big.close()
+    rng = np.random.RandomState(5)
+    pq = rng.dirichlet(np.ones(3) * 2, size=(40, 6)).astype(np.float32)
+    dec = qary.decoder_class("DecoderN6R3V2C3B1")(TREE_H, 2)
+    d_pq = torch.from_numpy(pq).cuda()
+    d_sym = torch.full((40, 6), 99, dtype=torch.int8, device="cuda")
+    dec.min_sum_batch_device(d_pq.data_ptr(), 40, d_sym.data_ptr(), stream=stream)
+    dec.close()
+    assert np.array_equal(d_sym.cpu().numpy(), oracle.qary_min_sum_batch(S.TannerGraph.from_dense(TREE_H), 3, pq, 2, threads=4))
