@@ -309,6 +309,10 @@ int scaldpc_qary_into_llr(const float *pmf, int64_t rows, int32_t Q, uint32_t fl
  *   "dp_min"     ... for calls of at least this many codewords (default 5; below, the tree walk)
  *   "dp_split"   ... the row's edges split over four waves up to this many codewords (default 64)
  *   "dp_split2"  ... and over two up to this many (default 192)
+ *   "dp_any"     DecoderSpecial, B = 1, 2, 3: the min-plus recursion for rows of ANY number of coefficient edges, tables in LDS
+ *                (k_q_special_check_dp_any, one launch for every row of the graph).  -1 (default) for graphs with a check of more
+ *                than 8 edges, which no other kernel takes | 1 for every such decoder | 0 never (a call on a graph with a check
+ *                of more than 8 edges then returns SCALDPC_EDEGREE before anything is queued)
  *   "llr_tiled", "var_small"  forms of the conversion / variable kernels
  *   "timing"     1: bracket the launches of a call with HIP events (scaldpc_qary_last_timing) */
 int scaldpc_qary_configure(scaldpc_qary *h, const char *key, const char *value);
@@ -319,10 +323,14 @@ int scaldpc_qary_configure(scaldpc_qary *h, const char *key, const char *value);
  *                  variable launch (the iteration loop, without the probability -> LLR conversion and the copies)
  *   info[0] iterations run;  info[1] check kernel: 0 k_q_check_unrolled<3,7>, 1 k_q_check_unrolled<5,5>,
  *           2 k_q_special_check_tree<5,6> (+ wave kernel for other row degrees), 3 k_q_special_check_wave,
- *           4 k_q_check_wave, 5 k_q_special_check, 6 k_q_check, 7 k_q_special_check_dp<5,6> (either form), 8 k_q_check_dp<3,7>;  info[2] batch;  info[3] largest check degree */
+ *           4 k_q_check_wave, 5 k_q_special_check, 6 k_q_check, 7 k_q_special_check_dp<5,6> (either form), 8 k_q_check_dp<3,7>,
+ *           9 k_q_special_check_dp_any;  info[2] batch;  info[3] largest check degree */
 int scaldpc_qary_last_timing(scaldpc_qary *h, float *ms, int32_t *info);
 
-/* DecoderSpecial: H = [H' | I_R]; first N-R variables over [-B,B], last R over [-BSUM,BSUM]. */
+/* DecoderSpecial: H = [H' | I_R]; first N-R variables over [-B,B], last R over [-BSUM,BSUM].
+ * Checks of up to 8 edges (7 coefficient edges + the row-sum edge): any B, the enumeration kernels.  Longer checks: B = 1, 2, 3
+ * with 2 B (degree - 1) + 1 <= 85 (three LDS tables of that many entries x 64 codewords within 64 KB: 42 / 21 / 14 coefficient
+ * edges at B = 1 / 2 / 3), on the min-plus recursion for rows of any length; anything else returns SCALDPC_EDEGREE. */
 int scaldpc_qary_special_create(int32_t R, int32_t N, int32_t B, int32_t BSUM, const int8_t *H,
                                 int32_t iterations, scaldpc_qary **out);
 /* pmf_b: float [batch][N-R][2B+1]; pmf_sum: float [batch][R][2BSUM+1]; out int8 [batch][N]. */

@@ -742,7 +742,17 @@ int qary_build(int R, int N, int B, int BSUM, bool special, const int8_t *H, int
     for (int r = 0; r < R; r++) maxdc = std::max(maxdc, row_ptr[r + 1] - row_ptr[r]);
     // one 8-bit digit per edge of a check in a register word: 64 bits for degree <= 8 (all kernels), 128 bits for 9..16
     // (the lane-per-codeword kernel only: Decoder is const-generic in DC, decoder.rs:417-438; the reference registers 4 and 7)
-    if (maxdc > (special ? 8 : 16))
+    // DecoderSpecial beyond 8: the any-length min-plus recursion (k_q_special_check_dp_any), where the plan takes the shape
+    if (special && maxdc > 8) {
+        QaryShape g;
+        g.special = true;
+        g.R = R; g.N = N; g.E = E; g.Q = 2 * B + 1; g.QS = 2 * BSUM + 1; g.W = g.QS; g.maxdc = g.mindc = maxdc;
+        QaryPlan p;
+        if (qary_plan(g, QaryKnobs(), 1, &p))
+            return fail(SCALDPC_EDEGREE, "check degree %d > 8 is not supported by the enumeration kernels, and the min-plus recursion "
+                        "for rows of any length takes B = 1, 2, 3 with 2*B*(degree-1)+1 <= 85 table entries (here B = %d, %d entries)",
+                        maxdc, B, 2 * B * (maxdc - 1) + 1);
+    } else if (maxdc > (special ? 8 : 16))
         return fail(SCALDPC_EDEGREE, "check degree %d > %d is not supported by the enumeration kernels", maxdc, special ? 8 : 16);
     if (special) {
         for (int r = 0; r < R; r++) {
@@ -933,6 +943,10 @@ void launch_check(scaldpc_qary *h, const QaryCall &c)
         hipLaunchKernelGGL(kernel, dim3(h->R, c.Bp / p.T), dim3(p.T), p.check_lds, s, h->d_row_ptr, h->d_msg, h->Q, h->B, c.Bp, c.batch,
                            h->maxdc, h->d_err);
     };
+    const auto special_any = [&](auto kernel) {  // lane = codeword, tables in LDS
+        hipLaunchKernelGGL(kernel, dim3(h->R, c.Bp / 64), dim3(64), p.dp_any_lds, s, h->d_row_ptr, h->d_msg, h->BSUM, h->W, c.Bp, c.batch,
+                           (int)(p.dp_any_lds / (3 * 64 * 4)));
+    };
     // the special decoder's wave kernel: the form itself, or behind the tree walk / the min-plus recursion for the rows they leave
     bool special_wave = p.wave_fallback_nb >= 0;
     switch (p.check) {
@@ -945,6 +959,11 @@ void launch_check(scaldpc_qary *h, const QaryCall &c)
             if (p.check_parts == 4) special_dp(k_q_special_check_dp<5, 6, 4>, 4);
             else if (p.check_parts == 2) special_dp(k_q_special_check_dp<5, 6, 2>, 2);
             else special_dp(k_q_special_check_dp<5, 6, 1>, 1);
+            break;
+        case QCheck::SPECIAL_DP_ANY:
+            if (h->Q == 3) special_any(k_q_special_check_dp_any<3>);
+            else if (h->Q == 5) special_any(k_q_special_check_dp_any<5>);
+            else special_any(k_q_special_check_dp_any<7>);
             break;
         case QCheck::SPECIAL_TREE:
             hipLaunchKernelGGL((k_q_special_check_tree<5, 6>), dim3(h->R, c.batch), dim3(64), p.tree_lds, s, h->d_row_ptr, h->d_msg,
@@ -1118,7 +1137,11 @@ int qary_run(scaldpc_qary *h, const float *pmf_b, const float *pmf_s, int batch,
     c.iters = std::max(1, h->iterations);
     c.dev_io = flags & SCALDPC_F_DEVICE_IO;
     c.so = so;
-    if (qary_plan(*h, h->kn, batch, &c.plan))  // (nothing is queued yet)
+    const int refused = qary_plan(*h, h->kn, batch, &c.plan);  // (nothing is queued yet)
+    if (refused == 2)
+        return fail(SCALDPC_EDEGREE, "check degree %d > 8 runs on the min-plus recursion for rows of any length only, which the "
+                    "dp_any knob has switched off", h->maxdc);
+    if (refused)
         return fail(SCALDPC_EDEGREE, "alphabet/degree too large for the LDS-staged enumeration (%zu B per codeword)",
                     c.plan.check_lds / c.plan.T);
     SC_TRY(ensure_buffers(h, c));

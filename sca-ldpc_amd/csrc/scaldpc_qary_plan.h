@@ -26,6 +26,8 @@ struct QaryKnobs {
     int dp_split2 = 192;  // ... and up to this one over two
     int llr_tiled = 1;    // probability -> LLR conversion through an LDS tile (coalesced reads)
     int var_small = 1;    // register-resident variable update for Q = 3 / 5 / 7 / 15 and columns of at most 4 checks
+    int dp_any = -1;      // special decoder, Q = 3 / 5 / 7: min-plus recursion for rows of any length (tables in LDS). -1: for checks of
+                          // more than 8 edges, which nothing else takes; 1: for every shape; 0: never (such checks are then refused)
     int timing = 0;       // bracket every check / variable launch with HIP events (scaldpc_qary_last_timing); off: nothing is recorded
 };
 
@@ -43,6 +45,7 @@ inline bool set_knob(QaryKnobs &k, const char *key, const char *val)
     else if (!strcmp(key, "timing")) k.timing = x != 0;
     else if (!strcmp(key, "llr_tiled")) k.llr_tiled = x != 0;
     else if (!strcmp(key, "var_small")) k.var_small = x != 0;
+    else if (!strcmp(key, "dp_any")) k.dp_any = x < 0 ? -1 : x != 0;
     else return false;
     return true;
 }
@@ -59,6 +62,7 @@ enum class QCheck : int {
     LANE = 6,          // k_q_check
     SPECIAL_DP = 7,    // (any number of parts; + the wave kernel as for the tree)
     DP_3_7 = 8,
+    SPECIAL_DP_ANY = 9,  // k_q_special_check_dp_any<Q>: every row, whatever its length
 };
 enum class QVar : int { GENERIC = 0, SMALL = 1 /* <Q, 4> */, SMALL_SPECIAL = 2 /* <5, 4, 25> */ };
 enum class QLlr : int {
@@ -79,9 +83,12 @@ struct QaryPlan {
                                   // another degree; -1: no such launch (every row has that many coefficient edges, or another form)
     int T = 64;                   // threads (= codewords) per block of the LDS-staged lane kernels
     size_t check_lds = 0, wave_lds = 0, tree_lds = 0, var_lds = 0;  // dynamic LDS of LANE / SPECIAL_LANE, the wave kernels, the tree walk, k_q_var
+    size_t dp_any_lds = 0;        // SPECIAL_DP_ANY: three tables of (Q - 1)(maxdc - 1) + 1 entries, 64 lanes each
 };
 
-// Nonzero: the LDS-staged enumeration does not fit (plan->check_lds / plan->T then hold the bytes one codeword needs).
+// Nonzero: nothing runs this shape.  1: the LDS-staged enumeration does not fit (plan->check_lds / plan->T then hold the bytes
+// one codeword needs).  2: a special decoder's check of more than 8 edges that the any-length recursion does not take (another
+// alphabet than 3 / 5 / 7 symbols, tables beyond 64 KB (plan->dp_any_lds), or the dp_any knob at 0).
 inline int qary_plan(const QaryShape &g, const QaryKnobs &kn, int batch, QaryPlan *plan)
 {
     constexpr size_t LDS = 64 * 1024;
@@ -120,7 +127,16 @@ inline int qary_plan(const QaryShape &g, const QaryKnobs &kn, int batch, QaryPla
     // codewords on the min-plus recursion (lane = codeword) instead of any enumeration
     const bool kyber = g.special && kn.wave != 0 && g.Q == 5 && g.maxdc - 1 == 6 && wave_fits;
     p.tree_lds = ((size_t)6 * g.Q + g.QS + (size_t)(6 * g.Q + g.QS) * 64) * 4;
+    // special decoder, rows of any length: the recursion over LDS tables, for the checks no enumeration reaches (or on demand)
+    const bool any_q = g.special && g.E > 0 && (g.Q == 3 || g.Q == 5 || g.Q == 7);
+    p.dp_any_lds = g.special ? (size_t)3 * ((size_t)(g.Q - 1) * std::max(g.maxdc - 1, 0) + 1) * 64 * 4 : 0;
+    const bool any = any_q && p.dp_any_lds <= LDS && (kn.dp_any == 1 || (kn.dp_any == -1 && g.maxdc > 8));
+    if (g.special && g.maxdc > 8 && !any) {
+        *plan = p;
+        return 2;
+    }
     if (!g.E) p.check = QCheck::NONE;
+    else if (any) p.check = QCheck::SPECIAL_DP_ANY;
     else if (!g.special && kn.unroll && g.Q == 3 && g.maxdc <= 7) p.check = kn.dp ? QCheck::DP_3_7 : QCheck::UNROLLED_3_7;
     else if (!g.special && kn.unroll && g.Q == 5 && g.maxdc <= 5) p.check = QCheck::UNROLLED_5_5;
     else if (kyber && kn.dp && batch >= kn.dp_min) p.check = QCheck::SPECIAL_DP;

@@ -451,4 +451,115 @@ __global__ __launch_bounds__(64 * PARTS) void k_q_special_check_dp(const int *__
         DpEdge<QB, NB, 0, 1, 0x18u>::run(P0, a, asw, edge0, (size_t)Bp, (size_t)W * Bp, sum_top, store);
 }
 
+// ---------------------------------------------------------------------------
+// The same min-plus recursion for rows of ANY number of coefficient edges (a run-time value per row, 0 included) over an
+// alphabet of QB = 3, 5 or 7 symbols: what DecoderSpecial runs on checks of more than 8 edges, which no enumeration
+// reaches ((2B+1)^SW assignments: 1.95 M at B = 2, SW = 9).  Nothing about the identity above depends on the shape; what does
+// is where the tables live.  Their lengths are run-time values here, so they are LDS columns [entry][64] (lane = codeword:
+// a wave's 64 accesses to one entry are 64 neighbouring words, no bank is hit twice) instead of unrolled registers:
+//   P   the minimal partial sums over the edges before j, by digit sum;
+//   V0, V1  the pinned recursion's table, ping-pong;
+// L = (QB - 1) maxnb + 1 entries each (maxnb: the graph's longest row), 3 L 256 bytes per block.  One min-plus step keeps
+// its QB alphas and a sliding window of QB inputs in registers (compile-time indices): one LDS read and one LDS write per
+// entry.  A candidate that does not exist (u - q outside the input) is a quiet NaN, which fminf ignores like the NaN alphas;
+// every other operand of fminf is the result of an addition or of fminf, so each is ONE v_min_f32 (no canonicalising
+// v_max in front, see vmin above) without inline asm.
+// The messages are updated in place: alpha_j is read until P has moved past edge j, so beta_j waits in registers until then;
+// the row-sum variable's alphas are read by every close-out and its messages are written last.  A lane touches its own
+// codeword's column only: no barrier.  grid (R, Bp / 64), block 64; every row of the graph, nothing follows.
+// ---------------------------------------------------------------------------
+// out[u] = min over q of fl(in[u - q] + ak[q]) for u = len + QB - 2 .. 0.  Descending, so that out may be in: entry u is
+// written after entry u - QB + 1, the lowest it needs, has been read, and no later u reads at or above it.
+template <int QB>
+__device__ __forceinline__ void minplus_step_lds(const float *in, float *out, int len, const float (&ak)[QB])
+{
+    float w[QB];  // w[q] = in[u - q]
+#pragma unroll
+    for (int q = 0; q < QB; q++) w[q] = __builtin_nanf("");
+    for (int u = len + QB - 2; u >= 0; u--) {
+#pragma unroll
+        for (int q = 0; q < QB - 1; q++) w[q] = w[q + 1];
+        const int lo = u - (QB - 1);
+        w[QB - 1] = lo >= 0 ? in[(size_t)lo * 64] : __builtin_nanf("");
+        float m = w[0] + ak[0];
+#pragma unroll
+        for (int q = 1; q < QB; q++) m = __builtin_fminf(m, w[q] + ak[q]);
+        out[(size_t)u * 64] = m;
+    }
+}
+
+template <int QB>
+__global__ __launch_bounds__(64) void k_q_special_check_dp_any(const int *__restrict__ row_ptr, float *msg, int BSUM, int W, long Bp,
+                                                               int batch, int L)
+{
+    constexpr int B = (QB - 1) / 2;
+    extern __shared__ unsigned char smem[];
+    const int lane = threadIdx.x;
+    float *const P = (float *)smem + lane;  // [L][64], this lane's column
+    float *const V0 = P + (size_t)L * 64;
+    float *const V1 = V0 + (size_t)L * 64;
+    const int c = blockIdx.x;
+    const long b = (long)blockIdx.y * 64 + lane;  // (< Bp: the padding lanes compute on whatever is there and store nothing)
+    const bool store = b < batch;
+    const int e0 = row_ptr[c], nb = row_ptr[c + 1] - e0 - 1;
+    const size_t qs = (size_t)Bp, es = (size_t)W * Bp;
+    float *const edge0 = msg + (size_t)e0 * es + b;
+    // the alpha of the row-sum symbol that closes an assignment of digit sum w (digits q = d + B) is sum_top[-w Bp]
+    const int top = BSUM + nb * B;  // (<= 2 BSUM: nb B <= BSUM is checked when the decoder is built, decoder_special.rs:388-392)
+    float *const sum_top = edge0 + (size_t)nb * es + (size_t)top * qs;
+    P[0] = 0.0f;  // S starts at 0 (decoder_special.rs:536)
+    int plen = 1;
+    for (int j = 0; j < nb; j++) {
+        float aj[QB], bj[QB];
+#pragma unroll
+        for (int q = 0; q < QB; q++) {
+            aj[q] = edge0[(size_t)j * es + (size_t)q * qs];
+            bj[q] = INFINITY;
+        }
+#pragma unroll 1
+        for (int d = 0; d < QB; d++) {
+            float ajd = aj[0];  // (d is the same in every lane: selects, not an indexed array)
+#pragma unroll
+            for (int q = 1; q < QB; q++) ajd = d == q ? aj[q] : ajd;
+            float *in = V0, *out = V1;
+            for (int u = 0; u < plen; u++) in[(size_t)u * 64] = P[(size_t)u * 64] + ajd;
+            int len = plen;
+            for (int k = j + 1; k < nb; k++) {
+                float ak[QB];
+#pragma unroll
+                for (int q = 0; q < QB; q++) ak[q] = edge0[(size_t)k * es + (size_t)q * qs];
+                minplus_step_lds<QB>(in, out, len, ak);
+                len += QB - 1;
+                float *const t = in;
+                in = out;
+                out = t;
+            }
+            // u counts the other edges' digits: the row-sum symbol is top - (u + d)
+            const float *as = sum_top - (ptrdiff_t)d * (ptrdiff_t)qs;
+            float M = in[0] + as[0];
+            for (int u = 1; u < len; u++) M = __builtin_fminf(M, in[(size_t)u * 64] + *(as - (ptrdiff_t)u * (ptrdiff_t)qs));
+            const float r = finite_f(M) ? M - ajd : INFINITY;
+#pragma unroll
+            for (int q = 0; q < QB; q++) bj[q] = d == q ? r : bj[q];
+        }
+        minplus_step_lds<QB>(P, P, plen, aj);
+        plen += QB - 1;
+        if (store)
+#pragma unroll
+            for (int q = 0; q < QB; q++) edge0[(size_t)j * es + (size_t)q * qs] = bj[q];
+    }
+    // the row-sum variable's own messages: symbol top - w is reached by the assignments of digit sum w alone; the symbols no
+    // assignment reaches keep the reference's initial +inf (decoder_special.rs:527)
+    float *const sum0 = edge0 + (size_t)nb * es;
+    for (int w = 0; w < plen; w++) {
+        float *const p = sum_top - (ptrdiff_t)w * (ptrdiff_t)qs;
+        const float a = *p, M = P[(size_t)w * 64] + a;
+        if (store) *p = finite_f(M) ? M - a : INFINITY;
+    }
+    if (store) {
+        for (int t = 0; t < top - (plen - 1); t++) sum0[(size_t)t * qs] = INFINITY;
+        for (int t = top + 1; t < 2 * BSUM + 1; t++) sum0[(size_t)t * qs] = INFINITY;
+    }
+}
+
 }  // namespace

@@ -4,8 +4,10 @@ as the drivers use it: `getattr(simulate_rs, "DecoderN450R150V3C7B1")`
 
 Any `DecoderN{N}R{R}V{DV}C{DC}B{B}` / `DecoderN{N}R{R}SW{SW}` name with check degree DC <= 8 (the
 reference registers 4 and 7, lib.rs:32-75) and symbols within int8 resolves: sizes are run-time values
-here, not compile-time const generics.  A name beyond that is an AttributeError at look-up, exactly as a
-size the reference has not registered is.
+here, not compile-time const generics.  `DecoderN{N}R{R}SW{SW}B{B}` is this project's extension of the Kyber name to any
+B (BSUM = SW*B); with B = 1, 2, 3 it also resolves beyond eight edges per check, up to 2*B*SW + 1 <= 85
+(`DecoderN1024R256SW9B2` is the `DecoderN1024R256SW9` that kyber.py:379-435 tells its user to create).  A name beyond
+that is an AttributeError at look-up, exactly as a size the reference has not registered is.
 
 `Hqc128/192/256` (liboqs KEM wrappers, simulate_rs/src/hqc.rs) are outside the decode path.
 They exist here only so that `from simulate_rs import Hqc128, Hqc192, Hqc256`

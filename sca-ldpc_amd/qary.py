@@ -13,6 +13,10 @@ of checks the decided word leaves unmet (include/scaldpc.h, scaldpc_qary_min_sum
   DecoderN{N}R{R}V{DV}C{DC}B{B}(H: int8 [R, N], iterations)   .min_sum(pmf float32 [N, 2B+1]) -> list[int]
   DecoderN{N}R{R}SW{SW}(H: int8 [R, N], iterations)           .min_sum(pmf [N-R, 5], pmf_sum [R, 2*BSUM+1]) -> list[int]
       (B = 2, BSUM = SW*B, DC = SW+1: the Kyber decoders of lib.rs:54-75)
+  DecoderN{N}R{R}SW{SW}B{B}(H: int8 [R, N], iterations)       .min_sum(pmf [N-R, 2B+1], pmf_sum [R, 2*SW*B+1]) -> list[int]
+      (this project's extension of the name above to any B: BSUM = SW*B, DC = SW+1.  Rows of more than 7 coefficient
+      edges run on the min-plus recursion for rows of any length, B = 1, 2, 3 and 2*B*SW + 1 <= 85:
+      DecoderN1024R256SW9B2 is what the reference would call DecoderN1024R256SW9)
 
 Inputs are probabilities; the LLR conversion (decoder.rs:668-692) happens inside, as in
 the reference.  Errors: a pmf row not summing to 1 +- 1e-3 and a check without any
@@ -32,6 +36,7 @@ from . import _lib
 
 _GENERIC = re.compile(r"^DecoderN(\d+)R(\d+)V(\d+)C(\d+)B(\d+)$")
 _SPECIAL = re.compile(r"^DecoderN(\d+)R(\d+)SW(\d+)$")
+_SPECIAL_B = re.compile(r"^DecoderN(\d+)R(\d+)SW(\d+)B(\d+)$")
 
 
 class _QaryBase:
@@ -50,13 +55,14 @@ class _QaryBase:
         return np.ascontiguousarray(H)
 
     def configure(self, **knobs):
-        """wave = -1 (auto) / 0 / 1, unroll = 0 / 1, tree = 0 / 1, dp = 0 / 1, dp_min = batch from which dp applies, timing = 0 / 1
-        (include/scaldpc.h, scaldpc_qary_configure)."""
+        """wave = -1 (auto) / 0 / 1, unroll = 0 / 1, tree = 0 / 1, dp = 0 / 1, dp_min = batch from which dp applies,
+        dp_any = -1 (auto) / 0 / 1, timing = 0 / 1 (include/scaldpc.h, scaldpc_qary_configure)."""
         for k, v in knobs.items():
             _lib.check(self._lib.scaldpc_qary_configure(self._h, k.encode(), str(v).encode()))
 
     CHECK_KERNELS = ("k_q_check_unrolled<3,7>", "k_q_check_unrolled<5,5>", "k_q_special_check_tree<5,6>",
-                     "k_q_special_check_wave", "k_q_check_wave", "k_q_special_check", "k_q_check", "k_q_special_check_dp<5,6>", "k_q_check_dp<3,7>")
+                     "k_q_special_check_wave", "k_q_check_wave", "k_q_special_check", "k_q_check", "k_q_special_check_dp<5,6>", "k_q_check_dp<3,7>",
+                     "k_q_special_check_dp_any")
 
     def last_timing(self):
         """HIP-event times of the last call's launches (after `configure(timing=1)`; bench.py's measurement aid):
@@ -252,6 +258,10 @@ def into_llr(channel_output):
 # (degree <= 8: all sizes the reference registers), 128 bits in the lane-per-codeword kernel of the plain decoder (<= 16)
 MAX_CHECK_DEGREE = 16
 MAX_SPECIAL_CHECK_DEGREE = 8
+# beyond that, DecoderSpecial runs the min-plus recursion for rows of any length (k_q_special_check_dp_any): alphabets of 3, 5
+# and 7 symbols, three LDS tables of 2*B*SW + 1 entries x 64 codewords within 64 KB
+DP_ANY_B = (1, 2, 3)
+DP_ANY_MAX_ENTRIES = 85
 
 
 def _check_limits(name, DC, B, BSUM, special=False):
@@ -280,12 +290,21 @@ def decoder_class(name: str):
         _check_limits(name, DC, B, B)
         cls = type(name, (QaryDecoder,), dict(N=N, R=R, DV=DV, DC=DC, B=B, Q=2 * B + 1))
     else:
-        m = _SPECIAL.match(name)
-        if not m:
+        m, mb = _SPECIAL.match(name), _SPECIAL_B.match(name)
+        if m:
+            N, R, SW = map(int, m.groups())
+            B = 2  # Kyber eta (lib.rs:54-75: B = 2, BSUM = SW * B)
+            _check_limits(name, SW + 1, B, SW * B, special=True)
+        elif mb:
+            N, R, SW, B = map(int, mb.groups())
+            if SW + 1 <= MAX_SPECIAL_CHECK_DEGREE:
+                _check_limits(name, SW + 1, B, SW * B, special=True)
+            elif B not in DP_ANY_B or 2 * B * SW + 1 > DP_ANY_MAX_ENTRIES:
+                raise AttributeError(f"{name}: check degree {SW + 1} > {MAX_SPECIAL_CHECK_DEGREE} runs on the min-plus recursion for rows "
+                                     f"of any length, which takes B in {DP_ANY_B} and 2*B*SW + 1 <= {DP_ANY_MAX_ENTRIES} table entries "
+                                     f"(here B = {B}, {2 * B * SW + 1} entries)")
+        else:
             raise AttributeError(name)
-        N, R, SW = map(int, m.groups())
-        B = 2  # Kyber eta (lib.rs:54-75: B = 2, BSUM = SW * B)
-        _check_limits(name, SW + 1, B, SW * B, special=True)
         cls = type(
             name, (QarySpecialDecoder,),
             dict(N=N, R=R, DV=R, DC=SW + 1, B=B, Q=2 * B + 1, BSUM=SW * B, QS=2 * SW * B + 1),
