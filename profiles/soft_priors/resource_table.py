@@ -20,6 +20,7 @@ FIELDS = ["TotalSGPRs", "VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "Occupancy
 def parse(path):
     out, cur = {}, None
     for line in open(path, errors="replace"):
+        line = re.sub(r"^remark: \S+:\d+:\d+:", "remark:", line)  # (a compiler that prefixes the remark with file:line:col)
         m = re.search(r"remark: Function Name: (\S+)", line)
         if m:
             cur = out.setdefault(m.group(1), {})

@@ -47,6 +47,17 @@ using namespace scaldpc;
 
 namespace {
 
+// Degree buckets of one fused launch (a host-side notion: the kernels read per-wave descriptor lists built from it):
+// blocks [blk[b], blk[b+1]) work on the nodes list[off[b] .. off[b]+cnt[b]) with unroll bound maxd[b] (0 = any-degree
+// fallback).
+struct Buckets {
+    int nb;
+    int maxd[MAXB];
+    int off[MAXB];
+    int cnt[MAXB];
+    int blk[MAXB + 1];
+};
+
 struct HostBuckets {
     Buckets bk;
     pvec<int> list;
@@ -164,7 +175,7 @@ struct scaldpc_bp : HandleStreams {
     int *d_el_slots = nullptr, *d_el_slot_col = nullptr;  // views into d_el_tab: [2 * 64 * el_cap_bins] and [64 * el_cap_bins] ints
     int el_waves = 0;     // bins in use
     int el_cap_bins = 0;  // bins d_el_tab has room for
-    bool el_ok = false;   // the row-parallel path can take this graph (non-empty, no row / column wider than a wave)
+    bool el_ok = false;   // the row-parallel path can take this graph (non-empty, no row / column wider than a wave: rows <= ROW_CAP)
     pvec<int> h_el_slots, h_el_col;  // host mirrors of the two parts of d_el_tab
     pvec<int> seg_slot;            // per column: bin * 64 + first lane of its segment (-1: none)
     pvec<unsigned char> seg_cap;   // per column: lanes of its segment
@@ -657,7 +668,10 @@ int el_limit(const scaldpc_bp *h, int method)
 // Compile-time dispatch of the launches.  with_cap<16, 32, 64>(deg, f) calls f(std::integral_constant<int, CAP>) with the
 // first CAP of the ladder that holds a node degree `deg` (the last CAP takes anything wider: the kernels' any-degree
 // fallback); every kernel is instantiated for exactly the ladder its launch names.  with_bool / with_method hand f a
-// runtime bool / update rule as a compile-time one.
+// runtime bool / update rule as a compile-time one; with_prior hands it the prior source of the call as a type (a value of
+// it, for decltype) with the kernel argument that goes with it: sp non-null = a soft call, SoftPrior and *sp; else
+// SharedPrior and the handle's priors.  with_first_prior is for the check kernels, whose FIRST pass alone reads priors:
+// f(FIRST, source, argument), and FIRST = false comes with SharedPrior only -- no <.., false, .., SoftPrior> instantiation.
 template <int CAP, int... WIDER, typename F>
 void with_cap(int deg, F &&f)
 {
@@ -678,6 +692,19 @@ void with_method(int method, F &&f)
 {
     if (method == SCALDPC_BP_MIN_SUM) f(std::integral_constant<int, SCALDPC_BP_MIN_SUM>{});
     else f(std::integral_constant<int, SCALDPC_BP_PRODUCT_SUM>{});
+}
+template <typename F>
+void with_prior(const scaldpc_bp *h, const SoftPrior *sp, F &&f)
+{
+    sp ? f(SoftPrior{}, *sp) : f(SharedPrior{}, (const float *)h->d_prior);
+}
+template <typename F>
+void with_first_prior(const scaldpc_bp *h, bool first, const SoftPrior *sp, F &&f)
+{
+    if (first)
+        with_prior(h, sp, [&](auto P, auto prior) { f(std::true_type{}, P, prior); });
+    else
+        f(std::false_type{}, SharedPrior{}, (const float *)h->d_prior);
 }
 
 // No message initialisation pass: the first check update reads the priors (v2c = prior of the
@@ -706,34 +733,21 @@ int launch_check(scaldpc_bp *h, int method, float alpha, int G, const u64 *synd_
     float *const scr0 = h->d_scratch ? h->d_scratch + (size_t)tile0 * h->E * TW : nullptr;
     const dim3 grid(h->row_bk.blk[h->row_bk.nb], G), block(256);  // one wave per row descriptor
     const bool test = ft && !first;
-    if (sp && first) {  // (first: fused_init holds, so the tanh rule's rows are register-resident)
-        if (method != SCALDPC_BP_MIN_SUM)
-            with_cap<16, 32, 64>(h->max_row_deg, [&](auto cap) {
-                hipLaunchKernelGGL((k_check_tanh_soft<cap>), grid, block, 0, s, h->d_row_list, msg0, scr0, synd_g, done_g, skip_done,
-                                   h->m, h->E, h->d_col_idx, *sp);
-            });
-        else if (h->max_row_deg <= ROW_CAP)
-            with_cap<16, 32, 64>(h->max_row_deg, [&](auto cap) {
-                hipLaunchKernelGGL((k_check_minsum_x_soft<cap>), grid, block, 0, s, h->d_row_list, msg0, synd_g, done_g, skip_done,
-                                   h->m, h->E, alpha, h->d_col_idx, *sp);
-            });
-        else
-            hipLaunchKernelGGL(k_check_minsum_soft, dim3((h->m + 3) / 4, G), block, 0, s, h->d_row_ptr, msg0, synd_g, done_g,
-                               skip_done, h->m, h->E, alpha, h->d_col_idx, *sp);
-    } else if (method != SCALDPC_BP_MIN_SUM) {
+    if (method != SCALDPC_BP_MIN_SUM) {  // (first: fused_init holds, so the rows are register-resident)
         with_cap<16, 32, 64>(h->max_row_deg, [&](auto cap) {
             if (test)
-                hipLaunchKernelGGL((k_check_tanh<cap, false, true>), grid, block, 0, s, h->row_bk, h->d_row_list, h->d_row_ptr,
-                                   msg0, scr0, synd_g, done_g, skip_done, h->m, h->E, h->d_col_idx, h->d_prior, *ft);
+                hipLaunchKernelGGL((k_check_tanh<cap, false, true, SharedPrior>), grid, block, 0, s, h->d_row_list, msg0, scr0, synd_g,
+                                   done_g, skip_done, h->m, h->E, h->d_col_idx, h->d_prior, *ft);
             else
-                with_bool(first, [&](auto fst) {
-                    hipLaunchKernelGGL((k_check_tanh<cap, fst>), grid, block, 0, s, h->row_bk, h->d_row_list, h->d_row_ptr, msg0,
-                                       scr0, synd_g, done_g, skip_done, h->m, h->E, h->d_col_idx, h->d_prior);
+                with_first_prior(h, first, sp, [&](auto fst, auto P, auto prior) {
+                    hipLaunchKernelGGL((k_check_tanh<cap, fst, false, decltype(P)>), grid, block, 0, s, h->d_row_list, msg0, scr0,
+                                       synd_g, done_g, skip_done, h->m, h->E, h->d_col_idx, prior, FusedTest{});
                 });
         });
     } else if (rec_form(h, method) && !first) {
-        // (a first check pass -- iteration 1 with first_fused off -- reads the priors and writes MESSAGES: the message
-        // form's kernel, followed by the message form's variable pass; the records start with iteration 2)
+        // (a first check pass -- iteration 1 with first_fused off, or of a soft call -- reads the priors and writes
+        // MESSAGES: the message form's kernel, followed by the message form's variable pass; the records start with
+        // iteration 2)
         float *const rec0 = h->d_rec + (size_t)tile0 * h->m * 2 * TW;
         ulonglong2 *const mask0 = h->d_mask + (size_t)tile0 * h->E;
         const FusedTest ft0 = test ? *ft : FusedTest{};
@@ -746,18 +760,18 @@ int launch_check(scaldpc_bp *h, int method, float alpha, int G, const u64 *synd_
     } else if (h->max_row_deg <= ROW_CAP) {
         with_cap<16, 32, 64>(h->max_row_deg, [&](auto cap) {
             if (test)
-                hipLaunchKernelGGL((k_check_minsum_x<cap, false, true>), grid, block, 0, s, h->d_row_list, msg0, synd_g, done_g,
-                                   skip_done, h->m, h->E, alpha, h->d_col_idx, h->d_prior, *ft);
+                hipLaunchKernelGGL((k_check_minsum_x<cap, false, true, SharedPrior>), grid, block, 0, s, h->d_row_list, msg0, synd_g,
+                                   done_g, skip_done, h->m, h->E, alpha, h->d_col_idx, h->d_prior, *ft);
             else
-                with_bool(first, [&](auto fst) {
-                    hipLaunchKernelGGL((k_check_minsum_x<cap, fst>), grid, block, 0, s, h->d_row_list, msg0, synd_g, done_g,
-                                       skip_done, h->m, h->E, alpha, h->d_col_idx, h->d_prior);
+                with_first_prior(h, first, sp, [&](auto fst, auto P, auto prior) {
+                    hipLaunchKernelGGL((k_check_minsum_x<cap, fst, false, decltype(P)>), grid, block, 0, s, h->d_row_list, msg0,
+                                       synd_g, done_g, skip_done, h->m, h->E, alpha, h->d_col_idx, prior, FusedTest{});
                 });
         });
     } else {  // a row wider than 64: the loop form
-        with_bool(first, [&](auto fst) {
-            hipLaunchKernelGGL((k_check_minsum<fst>), dim3((h->m + 3) / 4, G), block, 0, s, h->d_row_ptr, msg0, synd_g, done_g,
-                               skip_done, h->m, h->E, alpha, h->d_col_idx, h->d_prior);
+        with_first_prior(h, first, sp, [&](auto fst, auto P, auto prior) {
+            hipLaunchKernelGGL((k_check_minsum<fst, decltype(P)>), dim3((h->m + 3) / 4, G), block, 0, s, h->d_row_ptr, msg0, synd_g,
+                               done_g, skip_done, h->m, h->E, alpha, h->d_col_idx, prior);
         });
     }
     LAUNCH_CHECK();
@@ -788,7 +802,7 @@ int ensure_first_table(scaldpc_bp *h, int method, float alpha1, hipStream_t s)
     if (e == hipSuccess) e = hipMemsetAsync(h->d_first_tab, 0, sizeof(int2) * h->d_first_tab.cap(), s);
     if (e == hipSuccess) {
         with_method(method, [&](auto M) {
-            hipLaunchKernelGGL((k_el_check<M, true>), dim3((h->m + 3) / 4, 1), dim3(256), 0, s, h->d_row_ptr, h->d_col_idx,
+            hipLaunchKernelGGL((k_el_check<M, true, SharedPrior>), dim3((h->m + 3) / 4, 1), dim3(256), 0, s, h->d_row_ptr, h->d_col_idx,
                                h->d_prior, tmp, zero, zero + h->m, 0, h->m, h->E, alpha1, (const u64 *)nullptr, (int *)nullptr);
         });
         hipLaunchKernelGGL(k_first_tab, dim3((unsigned)((h->E + 255) / 256)), dim3(256), 0, s, h->d_csc_list, tmp, h->d_row_ptr, h->m,
@@ -831,24 +845,19 @@ int launch_var(scaldpc_bp *h, int G, float *post_g, u64 *hard_g, const u64 *done
         const dim3 gridr((unsigned)(xm ? (nb_launch + 7) / 8 * 8 : nb_launch), G);
         const int blk0 = slim && !h->var_reversed ? n1 : 0, xmap = xm ? nb_launch : 0;
         with_cap<16, 32>(h->max_col_deg, [&](auto cap) {  // (columns wider than 32 take the message form: rec_form)
-            if (sp)
-                hipLaunchKernelGGL((k_var_rec_soft<cap>), gridr, dim3(256), 0, s, h->d_var_meta, h->d_var_rows, h->d_csc_list,
-                                   h->d_csc_row, *sp, msg0, h->d_rec + (size_t)tile0 * h->m * 2 * TW,
+            with_prior(h, sp, [&](auto P, auto prior) {
+                hipLaunchKernelGGL((k_var_rec<cap, decltype(P)>), gridr, dim3(256), 0, s, h->d_var_meta, h->d_var_rows, h->d_csc_list,
+                                   h->d_csc_row, prior, msg0, h->d_rec + (size_t)tile0 * h->m * 2 * TW,
                                    h->d_mask + (size_t)tile0 * h->E, post_g, hard_g, done_g, skip_done, h->n, h->m, h->E, write_out,
                                    blk0, xmap);
-            else
-                hipLaunchKernelGGL((k_var_rec<cap>), gridr, dim3(256), 0, s, h->d_var_meta, h->d_var_rows, h->d_csc_list, h->d_csc_row,
-                                   h->d_prior, msg0, h->d_rec + (size_t)tile0 * h->m * 2 * TW, h->d_mask + (size_t)tile0 * h->E,
-                                   post_g, hard_g, done_g, skip_done, h->n, h->m, h->E, write_out, blk0, xmap);
+            });
         });
     } else {
         with_cap<16, 32, 64>(h->max_col_deg, [&](auto cap) {
-            if (sp)
-                hipLaunchKernelGGL((k_var_soft<cap>), dim3(nblk, G), dim3(256), 0, s, h->d_var_meta, h->d_csc_list, *sp, msg0, scr0,
-                                   post_g, hard_g, done_g, skip_done, h->n, h->E, write_out);
-            else
-                hipLaunchKernelGGL((k_var<cap>), dim3(nblk, G), dim3(256), 0, s, h->var_bk, h->d_var_meta, h->d_col_ptr, h->d_csc_list,
-                                   h->d_prior, msg0, scr0, post_g, hard_g, done_g, skip_done, h->n, h->E, write_out);
+            with_prior(h, sp, [&](auto P, auto prior) {
+                hipLaunchKernelGGL((k_var<cap, decltype(P)>), dim3(nblk, G), dim3(256), 0, s, h->d_var_meta, h->d_csc_list, prior, msg0,
+                                   scr0, post_g, hard_g, done_g, skip_done, h->n, h->E, write_out);
+            });
         });
     }
     LAUNCH_CHECK();
@@ -860,14 +869,9 @@ int launch_el_check(scaldpc_bp *h, int method, float alpha, int nb, const u64 *s
                     const SoftPrior *sp = nullptr)
 {
     with_method(method, [&](auto M) {
-        if (sp && first) {
-            hipLaunchKernelGGL((k_el_check_soft<M>), dim3((h->m + 3) / 4, nb), dim3(256), 0, s, h->d_row_ptr, h->d_col_idx, *sp,
-                               h->d_emsg, synd_g, done_g, skip_done, h->m, h->E, alpha, hard_g, unsat_prev);
-            return;
-        }
-        with_bool(first, [&](auto fst) {
-            hipLaunchKernelGGL((k_el_check<M, fst>), dim3((h->m + 3) / 4, nb), dim3(256), 0, s, h->d_row_ptr, h->d_col_idx,
-                               h->d_prior, h->d_emsg, synd_g, done_g, skip_done, h->m, h->E, alpha, hard_g, unsat_prev);
+        with_first_prior(h, first, sp, [&](auto fst, auto P, auto prior) {
+            hipLaunchKernelGGL((k_el_check<M, fst, decltype(P)>), dim3((h->m + 3) / 4, nb), dim3(256), 0, s, h->d_row_ptr,
+                               h->d_col_idx, prior, h->d_emsg, synd_g, done_g, skip_done, h->m, h->E, alpha, hard_g, unsat_prev);
         });
     });
     LAUNCH_CHECK();
@@ -881,14 +885,11 @@ int launch_el_var(scaldpc_bp *h, int nb, float *post_g, u64 *hard_g, u64 *done_g
     // grid.x a multiple of 8: block x lands on the same XCD for every codeword row, so an XCD's L2
     // keeps its share of the slot table
     const unsigned gx = (unsigned)(((h->el_waves + 3) / 4 + 7) / 8 * 8);
-    if (sp)
-        hipLaunchKernelGGL(k_el_var_soft, dim3(gx, nb), dim3(256), 0, s, (const int2 *)h->d_el_slots, h->d_el_slot_col,
-                           h->el_waves, *sp, h->d_emsg, post_g, hard_g, done_g, skip_done, h->E,
-                           write_out, unsat_prev, it_prev, conv_g, iters_g, remaining_prev);
-    else
-        hipLaunchKernelGGL(k_el_var, dim3(gx, nb), dim3(256), 0, s, (const int2 *)h->d_el_slots, h->d_el_slot_col,
-                           h->el_waves, h->d_prior, h->d_emsg, post_g, hard_g, done_g, skip_done, h->E,
-                           write_out, unsat_prev, it_prev, conv_g, iters_g, remaining_prev);
+    with_prior(h, sp, [&](auto P, auto prior) {
+        hipLaunchKernelGGL((k_el_var<decltype(P)>), dim3(gx, nb), dim3(256), 0, s, (const int2 *)h->d_el_slots, h->d_el_slot_col,
+                           h->el_waves, prior, h->d_emsg, post_g, hard_g, done_g, skip_done, h->E, write_out, unsat_prev, it_prev,
+                           conv_g, iters_g, remaining_prev);
+    });
     LAUNCH_CHECK();
     return 0;
 }
@@ -913,28 +914,22 @@ size_t small_lds(const scaldpc_bp *h)
 }
 
 // k_bp_small over `batch` codewords, one workgroup each.  PLANES: input syndromes and outputs are the tile path's bit
-// planes (Monte-Carlo entry points); else bytes per codeword in the caller's layout.
+// planes (Monte-Carlo entry points); else bytes per codeword in the caller's layout, and sp non-null = per-codeword priors
+// (scaldpc_bp_decode_batch_soft).
 template <bool PLANES>
 int launch_small(scaldpc_bp *h, size_t lds, int method, int batch, const void *in, int input_kind, int max_iter, float alpha,
-                 bool early, void *bits, float *llr, int *iters, void *conv, hipStream_t s)
+                 bool early, void *bits, float *llr, int *iters, void *conv, hipStream_t s, const SoftPrior *sp = nullptr)
 {
     with_method(method, [&](auto M) {
-        hipLaunchKernelGGL((k_bp_small<M, PLANES>), dim3(batch), dim3(256), lds, s, h->d_row_ptr, h->d_col_idx, h->d_col_ptr,
-                           h->d_csc_edge, h->d_prior, h->m, h->n, (int)h->E, in, input_kind, max_iter, alpha, early ? 1 : 0,
-                           bits, llr, iters, conv);
-    });
-    LAUNCH_CHECK();
-    return 0;
-}
-
-// ... with per-codeword priors (byte I/O: scaldpc_bp_decode_batch_soft)
-int launch_small_soft(scaldpc_bp *h, size_t lds, int method, int batch, const void *in, int input_kind, int max_iter, float alpha,
-                      bool early, void *bits, float *llr, int *iters, void *conv, const SoftPrior &sp, hipStream_t s)
-{
-    with_method(method, [&](auto M) {
-        hipLaunchKernelGGL((k_bp_small_soft<M>), dim3(batch), dim3(256), lds, s, h->d_row_ptr, h->d_col_idx, h->d_col_ptr,
-                           h->d_csc_edge, sp, h->m, h->n, (int)h->E, in, input_kind, max_iter, alpha, early ? 1 : 0, bits, llr,
-                           iters, conv);
+        auto launch = [&](auto P, auto prior) {
+            hipLaunchKernelGGL((k_bp_small<M, PLANES, decltype(P)>), dim3(batch), dim3(256), lds, s, h->d_row_ptr, h->d_col_idx,
+                               h->d_col_ptr, h->d_csc_edge, prior, h->m, h->n, (int)h->E, in, input_kind, max_iter, alpha,
+                               early ? 1 : 0, bits, llr, iters, conv);
+        };
+        if constexpr (PLANES)  // (no <.., true, SoftPrior> instantiation)
+            launch(SharedPrior{}, (const float *)h->d_prior);
+        else
+            with_prior(h, sp, launch);
     });
     LAUNCH_CHECK();
     return 0;
@@ -979,20 +974,13 @@ int iterate_el(scaldpc_bp *h, const TileState &st, int nb, int max_iter, int met
             SC_HIP(hipMemsetAsync(h->d_remaining, 0, sizeof(int) * ((size_t)max_iter + 2), s));
         }
     }
-    const bool fused = fused_init(h, method);
+    static_assert(ROW_CAP == TW, "el_ok (a row = at most one wave of edge lanes) must imply fused_init's rows <= ROW_CAP");
+    // No initialisation pass: el_ok holds here (el_limit), i.e. a non-empty graph with no row wider than ROW_CAP, so
+    // fused_init does for either rule -- the first check pass reads the priors.
     const SoftPrior spv = st.pprior ? soft_prior(h, st, 0) : SoftPrior{};
     const SoftPrior *const sp = st.pprior ? &spv : nullptr;
-    if (!fused) {
-        if (sp)
-            hipLaunchKernelGGL(k_el_init_soft, dim3((unsigned)((h->E + 255) / 256), nb), dim3(256), 0, s, h->d_col_idx, *sp, h->d_emsg,
-                               h->E);
-        else
-            hipLaunchKernelGGL(k_el_init, dim3((unsigned)((h->E + 255) / 256), nb), dim3(256), 0, s, h->d_col_idx, h->d_prior,
-                               h->d_emsg, h->E);
-        LAUNCH_CHECK();
-    }
     for (int it = 1; it <= max_iter; it++) {
-        const bool last = it == max_iter, first = fused && it == 1;
+        const bool last = it == max_iter, first = it == 1;
         if (early) {
             int *const up = it > 1 ? h->d_el_unsat + (size_t)(it - 1) * TW : nullptr;  // verdicts on iteration it - 1
             SC_TRY(launch_el_check(h, method, alpha_for(alpha, it), nb, st.synd, st.done, 1, s, first, st.hard, up, sp));
@@ -1151,12 +1139,11 @@ int iterate_tiles(scaldpc_bp *h, Lanes &lanes, const TileState &st, int g0, int 
     const bool fused = fused_init(h, method);
     const bool soft = st.pprior != nullptr;
     if (h->E && !fused) {
-        if (soft)
-            hipLaunchKernelGGL(k_init_msg_soft, dim3((unsigned)((h->E + 3) / 4), g), dim3(256), 0, s, h->d_col_idx, h->d_msg.get(), h->E,
-                               soft_prior(h, st, g0));
-        else
-            hipLaunchKernelGGL(k_init_msg, dim3((unsigned)((h->E + 3) / 4), g), dim3(256), 0, s, h->d_col_idx, h->d_prior,
-                               h->d_msg, h->E);
+        const SoftPrior spv = soft ? soft_prior(h, st, g0) : SoftPrior{};
+        with_prior(h, soft ? &spv : nullptr, [&](auto P, auto prior) {
+            hipLaunchKernelGGL((k_init_msg<decltype(P)>), dim3((unsigned)((h->E + 3) / 4), g), dim3(256), 0, s, h->d_col_idx,
+                               h->d_msg.get(), h->E, prior);
+        });
         LAUNCH_CHECK();
     }
     int *rem = h->d_remaining;  // this group's row of "still running" counters
@@ -1473,7 +1460,7 @@ int finish_graph(scaldpc_bp *h, const int *row_ptr, const int *col_idx, const pv
         }
         h->identity_from = ident ? n - m : -1;
     }
-    h->el_ok = nnz > 0 && h->max_row_deg <= 64 && h->max_col_deg <= 64;  // the row-parallel path can take this graph
+    h->el_ok = nnz > 0 && h->max_row_deg <= ROW_CAP && h->max_col_deg <= 64;  // the row-parallel path can take this graph
     const bool own_csr = h->incremental;  // CSR and priors already live in growable buffers of their own
     size_t total = 0;
     auto reserve = [&](size_t cnt) {  // 256-byte aligned sections
@@ -1895,7 +1882,7 @@ int scaldpc_bp_append_rows(scaldpc_bp *h, int32_t nrows, const int32_t *row_ptr,
     h->m = m0 + nrows;
     h->n = new_n;
     h->E = E0 + add;
-    h->el_ok = h->E > 0 && h->max_row_deg <= 64 && h->max_col_deg <= 64;
+    h->el_ok = h->E > 0 && h->max_row_deg <= ROW_CAP && h->max_col_deg <= 64;
     if (had_tables && (!el_alive || !h->el_ok)) {
         h->d_el_tab.reset();
         h->d_el_slots = h->d_el_slot_col = nullptr;
@@ -2072,11 +2059,10 @@ static int decode_batch_impl(scaldpc_bp *h, const uint8_t *in, int32_t input_kin
         if (soft) {
             SC_TRY(grow(h->d_pprior, (size_t)T * prob_cols * TW));
             SC_TRY(soft_convert());
-            SC_TRY(launch_small_soft(h, lds, method, batch, din, input_kind, max_iter, alpha, early, dev.bits, dev.llr, dev.iters,
-                                     dev.conv, SoftPrior{h->d_prior, h->d_pprior, first_col, prob_cols}, s));
-        } else
-            SC_TRY(launch_small<false>(h, lds, method, batch, din, input_kind, max_iter, alpha, early, dev.bits, dev.llr, dev.iters,
-                                       dev.conv, s));
+        }
+        const SoftPrior spv{h->d_prior, h->d_pprior, first_col, prob_cols};
+        SC_TRY(launch_small<false>(h, lds, method, batch, din, input_kind, max_iter, alpha, early, dev.bits, dev.llr, dev.iters,
+                                   dev.conv, s, soft ? &spv : nullptr));
         SC_TRY(copy_outputs(h, out, dev, batch, dev_io, s));
         h->stat_deferred = 0;
         if (soft && !(flags & SCALDPC_F_ASYNC)) SC_TRY(soft_verdict());

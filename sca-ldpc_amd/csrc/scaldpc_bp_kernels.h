@@ -3,6 +3,7 @@
 // translation unit; the split is for reading, not for linking.
 #pragma once
 #include "scaldpc_logf.h"  // glibc's logf on the device (k_soft_convert)
+#include <type_traits>
 
 // v_writelane_b32 as an instruction the COMPILER emits: ROCm 7.2's clang has no __builtin_amdgcn_writelane, but the LLVM
 // intrinsic is reachable through an asm label.  Unlike an `asm("v_writelane_b32 ...")` statement the hazard recogniser
@@ -31,9 +32,13 @@ constexpr int ROW_CAP = 64;  // largest register-resident row degree (also the s
 __device__ __forceinline__ int rfl(int x) { return __builtin_amdgcn_readfirstlane(x); }
 
 // Where a kernel takes the prior LLR of column v for codeword `lane` of tile `tl` from.  Every kernel that consumes a
-// prior has a body templated on the source and two entry points: the plain one (SharedPrior: the handle's one prior per
-// column, a wave-uniform read) and a `_soft` one (SoftPrior: scaldpc_bp_decode_batch_soft).
+// prior is ONE __global__ template whose last parameter P is the source: SharedPrior (the handle's one prior per column,
+// a wave-uniform read) or SoftPrior (scaldpc_bp_decode_batch_soft).  The kernel takes a `typename P::Arg` and builds
+// P{arg} in its body: for SharedPrior the argument is the bare __restrict__ pointer -- a struct passed by value would lose
+// the noalias, and with it the proof that the uniform prior loads behind a message store are unclobbered (one VGPR more
+// and another instruction stream in the first check passes).
 struct SharedPrior {
+    typedef const float *__restrict__ Arg;
     const float *prior;  // [n]
     __device__ __forceinline__ float operator()(int v, int, int) const { return prior[v]; }
 };
@@ -45,6 +50,7 @@ struct SharedPrior {
 // and none; profiles/soft_priors/README.md.)
 // (tl counts from the first tile of the launch: the host passes the plane of that tile.)
 struct SoftPrior {
+    typedef SoftPrior Arg;
     const float *prior;  // [n]
     const float *plane;  // [tile][cols][64]
     int first_col, cols;
@@ -55,15 +61,25 @@ struct SoftPrior {
     }
 };
 
-// Degree buckets of one fused launch: blocks [blk[b], blk[b+1]) work on the nodes
-// list[off[b] .. off[b]+cnt[b]) with unroll bound maxd[b] (0 = any-degree fallback).
-struct Buckets {
-    int nb;
-    int maxd[MAXB];
-    int off[MAXB];
-    int cnt[MAXB];
-    int blk[MAXB + 1];
-};
+// Straight-line code for a node's EXACT degree, dispatched wave-uniformly: calls f(std::integral_constant<int, D>) for
+// D == deg, 1 <= D <= CAP (CAP bounds what is compiled in; any other degree does nothing).
+template <int CAP, class F>
+__device__ __forceinline__ void for_exact_degree(int deg, F &&f)
+{
+#define XD(D)                                                        \
+    case D:                                                          \
+        if constexpr (D <= CAP) f(std::integral_constant<int, D>{}); \
+        break;
+#define XD8(D) XD(D) XD(D + 1) XD(D + 2) XD(D + 3) XD(D + 4) XD(D + 5) XD(D + 6) XD(D + 7)
+    switch (deg) {
+        XD(1) XD(2) XD(3) XD(4) XD(5) XD(6) XD(7)
+        XD8(8) XD8(16) XD8(24) XD8(32) XD8(40) XD8(48) XD8(56)
+        XD(64)
+        default: break;
+    }
+#undef XD8
+#undef XD
+}
 
 // ---------------------------------------------------------------------------
 // input / output reshaping
@@ -562,6 +578,8 @@ __global__ __launch_bounds__(256) void k_parity_fin_sharded(const int *__restric
 // K1  initial bit-to-check messages: msg[tile][e][:] = LLR prior of the edge's column.
 // grid (ceil(E/4), G), block 256 = 4 waves, wave = one 256 B edge row.
 // ---------------------------------------------------------------------------
+// (The body stays a function of its own, here and in check_minsum_body / bp_small_body / el_var_body: written straight
+// into the entry point the same work comes out as other instructions -- profiles/bp_prior_entry/README.md.)
 template <class P>
 __device__ __forceinline__ void init_msg_body(const int *__restrict__ col_idx, P pr, float *__restrict__ msg, long E)
 {
@@ -570,15 +588,11 @@ __device__ __forceinline__ void init_msg_body(const int *__restrict__ col_idx, P
     if (e >= E) return;
     msg[((size_t)blockIdx.y * E + e) * TW + lane] = pr(col_idx[e], blockIdx.y, lane);
 }
-__global__ __launch_bounds__(256) void k_init_msg(const int *__restrict__ col_idx, const float *__restrict__ prior,
-                                                  float *__restrict__ msg, long E)
+template <class P>
+__global__ __launch_bounds__(256) void k_init_msg(const int *__restrict__ col_idx, float *__restrict__ msg, long E,
+                                                  typename P::Arg prior_arg)
 {
-    init_msg_body(col_idx, SharedPrior{prior}, msg, E);
-}
-__global__ __launch_bounds__(256) void k_init_msg_soft(const int *__restrict__ col_idx, float *__restrict__ msg, long E,
-                                                       SoftPrior sp)
-{
-    init_msg_body(col_idx, sp, msg, E);
+    init_msg_body(col_idx, P{prior_arg}, msg, E);
 }
 
 // ---------------------------------------------------------------------------
@@ -594,6 +608,8 @@ __global__ __launch_bounds__(256) void k_init_msg_soft(const int *__restrict__ c
 // ---------------------------------------------------------------------------
 // FIRST: iteration 1 takes its inputs straight from the priors (v2c = prior of the edge's
 // column by definition), so the message array needs no initialisation pass and is not read.
+// (a soft call reads its per-codeword priors in a FIRST pass only: P = SoftPrior is instantiated for FIRST = true alone,
+// here and in the other check kernels)
 template <bool FIRST, class P>
 __device__ __forceinline__ void check_minsum_body(const int *__restrict__ row_ptr, float *msg,
                                                   const u64 *__restrict__ synd, const u64 *__restrict__ done,
@@ -629,21 +645,13 @@ __device__ __forceinline__ void check_minsum_body(const int *__restrict__ row_pt
         p[(size_t)k * TW] = ((k == ix) ? m2 : m1) * ((par ^ b) ? nalpha : alpha);
     }
 }
-template <bool FIRST>
+template <bool FIRST, class P>
 __global__ __launch_bounds__(256) void k_check_minsum(const int *__restrict__ row_ptr, float *msg,
                                                       const u64 *__restrict__ synd, const u64 *__restrict__ done,
                                                       int skip_done, int m, long E, float alpha,
-                                                      const int *__restrict__ col_idx, const float *__restrict__ prior)
+                                                      const int *__restrict__ col_idx, typename P::Arg prior_arg)
 {
-    check_minsum_body<FIRST>(row_ptr, msg, synd, done, skip_done, m, E, alpha, col_idx, SharedPrior{prior});
-}
-// the first check pass of a soft call (rows wider than 64)
-__global__ __launch_bounds__(256) void k_check_minsum_soft(const int *__restrict__ row_ptr, float *msg,
-                                                           const u64 *__restrict__ synd, const u64 *__restrict__ done,
-                                                           int skip_done, int m, long E, float alpha,
-                                                           const int *__restrict__ col_idx, SoftPrior sp)
-{
-    check_minsum_body<true>(row_ptr, msg, synd, done, skip_done, m, E, alpha, col_idx, sp);
+    check_minsum_body<FIRST>(row_ptr, msg, synd, done, skip_done, m, E, alpha, col_idx, P{prior_arg});
 }
 
 // Register-resident form for rows of degree <= 64: straight-line code instantiated for the
@@ -678,11 +686,13 @@ __device__ __forceinline__ void check_minsum_row(float *p, unsigned par, float a
 
 // PAR: the convergence test of the previous iteration rides on this pass (fused_test; early-exit runs, never FIRST).
 template <int CAP, bool FIRST, bool PAR, class P>
-__device__ __forceinline__ void check_minsum_x_body(const int *__restrict__ list, float *msg,
-                                                    const u64 *__restrict__ synd, const u64 *done,
-                                                    int skip_done, int m, long E, float alpha,
-                                                    const int *__restrict__ col_idx, P prior, const FusedTest &ft)
+__global__ __launch_bounds__(256) void k_check_minsum_x(const int *__restrict__ list, float *msg,
+                                                        const u64 *__restrict__ synd, const u64 *done,
+                                                        int skip_done, int m, long E, float alpha,
+                                                        const int *__restrict__ col_idx, typename P::Arg prior_arg,
+                                                        FusedTest ft)
 {
+    const P prior{prior_arg};
     const int lane = threadIdx.x & 63;
     const int tl = blockIdx.y;
     const int *md = list + (size_t)rfl((int)blockIdx.x * 4 + (int)(threadIdx.x >> 6)) * 4;  // uniform address: scalar loads
@@ -702,39 +712,9 @@ __device__ __forceinline__ void check_minsum_x_body(const int *__restrict__ list
         const int deg = md[2];
         float *p = msg + ((size_t)tl * E + e0) * TW + lane;
         const unsigned sbit = (unsigned)(synd[(size_t)tl * m + r] >> lane) & 1u;
-#define MR(D)                                                                                   \
-    case D:                                                                                     \
-        if constexpr (D <= CAP) check_minsum_row<D, FIRST>(p, sbit, alpha, prior, col_idx + e0, tl, lane); \
-        break;
-#define MR8(D) MR(D) MR(D + 1) MR(D + 2) MR(D + 3) MR(D + 4) MR(D + 5) MR(D + 6) MR(D + 7)
-        switch (deg) {
-            MR(1) MR(2) MR(3) MR(4) MR(5) MR(6) MR(7)
-            MR8(8) MR8(16) MR8(24) MR8(32) MR8(40) MR8(48) MR8(56)
-            MR(64)
-            default: break;
-        }
-#undef MR8
-#undef MR
+        for_exact_degree<CAP>(deg, [&](auto d) { check_minsum_row<d, FIRST>(p, sbit, alpha, prior, col_idx + e0, tl, lane); });
     }
     if constexpr (PAR) fused_commit(ft, tl, bad, dw);
-}
-template <int CAP, bool FIRST, bool PAR = false>
-__global__ __launch_bounds__(256) void k_check_minsum_x(const int *__restrict__ list, float *msg,
-                                                        const u64 *__restrict__ synd, const u64 *done,
-                                                        int skip_done, int m, long E, float alpha,
-                                                        const int *__restrict__ col_idx, const float *__restrict__ prior,
-                                                        FusedTest ft = FusedTest{})
-{
-    check_minsum_x_body<CAP, FIRST, PAR>(list, msg, synd, done, skip_done, m, E, alpha, col_idx, SharedPrior{prior}, ft);
-}
-// the first check pass of a soft call
-template <int CAP>
-__global__ __launch_bounds__(256) void k_check_minsum_x_soft(const int *__restrict__ list, float *msg,
-                                                             const u64 *__restrict__ synd, const u64 *done,
-                                                             int skip_done, int m, long E, float alpha,
-                                                             const int *__restrict__ col_idx, SoftPrior sp)
-{
-    check_minsum_x_body<CAP, true, false>(list, msg, synd, done, skip_done, m, E, alpha, col_idx, sp, FusedTest{});
 }
 
 // ---------------------------------------------------------------------------
@@ -852,8 +832,10 @@ __global__ __launch_bounds__(256) void k_check_minsum_rec(const int *__restrict_
         ulonglong2 *mk = mask + (size_t)tl * E;  // (masks by position: the tile's base)
         const int *ps = csr_pos + e0;
         const u64 sw = synd[(size_t)tl * m + r];  // (uniform: a scalar load; the row's syndrome bits ARE a lane mask)
-#define MR(D)                                                                                                       \
-    case D:                                                                                                         \
+        // (the ladder for_exact_degree spells, kept as a macro here and in k_var_rec: through the helper's lambda the
+        // record-form kernels come out with other registers and an instruction more or less)
+#define MR(D)                                                                                 \
+    case D:                                                                                   \
         if constexpr (D <= CAP) check_minsum_row_rec<D>(p, sw, alpha, rc, rc2, mk, lane, ps); \
         break;
 #define MR8(D) MR(D) MR(D + 1) MR(D + 2) MR(D + 3) MR(D + 4) MR(D + 5) MR(D + 6) MR(D + 7)
@@ -967,14 +949,15 @@ __device__ __forceinline__ void check_tanh_row_generic(float *p, float *sc, int 
 // neighbouring waves run the same instantiation).  wave = (row, tile).
 // CAP = largest degree compiled in (the register budget follows the widest instantiation,
 // so graphs with narrow rows get the high-occupancy build).
-// grid (bk.blk[nb], G), block 256 = 4 rows of one bucket.
+// grid (row descriptors / 4, G), block 256 = 4 rows of one bucket.
 // PAR: the convergence test of the previous iteration rides on this pass (fused_test; early-exit runs, never FIRST).
 template <int CAP, bool FIRST, bool PAR, class P>
-__device__ __forceinline__ void check_tanh_body(const int *__restrict__ list, float *msg, float *scratch,
-                                                const u64 *__restrict__ synd, const u64 *done,
-                                                int skip_done, int m, long E, const int *__restrict__ col_idx,
-                                                P prior, const FusedTest &ft)
+__global__ __launch_bounds__(256) void k_check_tanh(const int *__restrict__ list, float *msg, float *scratch,
+                                                    const u64 *__restrict__ synd, const u64 *done,
+                                                    int skip_done, int m, long E, const int *__restrict__ col_idx,
+                                                    typename P::Arg prior_arg, FusedTest ft)
 {
+    const P prior{prior_arg};
     const int lane = threadIdx.x & 63;
     const int tl = blockIdx.y;
     // one descriptor per WAVE of the launch: {row or -1 (padding), first edge, degree, 0 = any-degree
@@ -998,43 +981,12 @@ __device__ __forceinline__ void check_tanh_body(const int *__restrict__ list, fl
         float *p = msg + base;
         const unsigned sbit = (unsigned)(synd[(size_t)tl * m + r] >> lane) & 1u;
         // dispatch on the row's exact degree (wave-uniform); CAP bounds what is compiled in
-#define TR(D)                                                                              \
-    case D:                                                                                \
-        if constexpr (D <= CAP) check_tanh_row<D, FIRST>(p, sbit, prior, col_idx + e0, tl, lane); \
-        break;
-#define TR8(D) TR(D) TR(D + 1) TR(D + 2) TR(D + 3) TR(D + 4) TR(D + 5) TR(D + 6) TR(D + 7)
-        if (md[3] == 0) {
+        if (md[3] == 0)
             check_tanh_row_generic(p, scratch + base, deg, sbit);
-        } else {
-            switch (deg) {
-                TR(1) TR(2) TR(3) TR(4) TR(5) TR(6) TR(7)
-                TR8(8) TR8(16) TR8(24) TR8(32) TR8(40) TR8(48) TR8(56)
-                TR(64)
-                default: break;
-            }
-        }
-#undef TR8
-#undef TR
+        else
+            for_exact_degree<CAP>(deg, [&](auto d) { check_tanh_row<d, FIRST>(p, sbit, prior, col_idx + e0, tl, lane); });
     }
     if constexpr (PAR) fused_commit(ft, tl, bad, dw);
-}
-template <int CAP, bool FIRST, bool PAR = false>
-__global__ __launch_bounds__(256) void k_check_tanh(Buckets bk, const int *__restrict__ list,
-                                                    const int *__restrict__ row_ptr, float *msg, float *scratch,
-                                                    const u64 *__restrict__ synd, const u64 *done,
-                                                    int skip_done, int m, long E, const int *__restrict__ col_idx,
-                                                    const float *__restrict__ prior, FusedTest ft = FusedTest{})
-{
-    check_tanh_body<CAP, FIRST, PAR>(list, msg, scratch, synd, done, skip_done, m, E, col_idx, SharedPrior{prior}, ft);
-}
-// the first check pass of a soft call
-template <int CAP>
-__global__ __launch_bounds__(256) void k_check_tanh_soft(const int *__restrict__ list, float *msg, float *scratch,
-                                                         const u64 *__restrict__ synd, const u64 *done,
-                                                         int skip_done, int m, long E, const int *__restrict__ col_idx,
-                                                         SoftPrior sp)
-{
-    check_tanh_body<CAP, true, false>(list, msg, scratch, synd, done, skip_done, m, E, col_idx, sp, FusedTest{});
 }
 
 // ---------------------------------------------------------------------------
@@ -1054,6 +1006,7 @@ __global__ __launch_bounds__(256) void k_check_tanh_soft(const int *__restrict__
 // PLANES = true : bit-plane I/O for the Monte-Carlo entry points (in = syndrome planes
 //                 u64 [tile][m]; out_bits = hard planes u64 [tile][n], zeroed by the caller;
 //                 out_conv = conv planes u64 [tile]; out_llr = posterior [tile][var][64]).
+// Per-codeword priors (P = SoftPrior) come with byte I/O only.
 template <int METHOD, bool PLANES, class P>  // METHOD: SCALDPC_BP_PRODUCT_SUM / SCALDPC_BP_MIN_SUM
 __device__ __forceinline__ void bp_small_body(const int *__restrict__ row_ptr, const int *__restrict__ col_idx,
                                               const int *__restrict__ col_ptr, const int *__restrict__ csc_edge,
@@ -1201,30 +1154,17 @@ __device__ __forceinline__ void bp_small_body(const int *__restrict__ row_ptr, c
         if (out_conv) out_conv[b] = (uint8_t)conv;
     }
 }
-template <int METHOD, bool PLANES>
+template <int METHOD, bool PLANES, class P>
 __global__ __launch_bounds__(256) void k_bp_small(const int *__restrict__ row_ptr, const int *__restrict__ col_idx,
                                                   const int *__restrict__ col_ptr, const int *__restrict__ csc_edge,
-                                                  const float *__restrict__ prior, int m, int n, int E,
+                                                  typename P::Arg prior_arg, int m, int n, int E,
                                                   const void *__restrict__ in_, int kind, int max_iter, float alpha0,
                                                   int early, void *__restrict__ out_bits_,
                                                   float *__restrict__ out_llr, int *__restrict__ out_iters,
                                                   void *__restrict__ out_conv_)
 {
-    bp_small_body<METHOD, PLANES>(row_ptr, col_idx, col_ptr, csc_edge, SharedPrior{prior}, m, n, E, in_, kind, max_iter, alpha0,
-                                  early, out_bits_, out_llr, out_iters, out_conv_);
-}
-// byte I/O, per-codeword priors
-template <int METHOD>
-__global__ __launch_bounds__(256) void k_bp_small_soft(const int *__restrict__ row_ptr, const int *__restrict__ col_idx,
-                                                       const int *__restrict__ col_ptr, const int *__restrict__ csc_edge,
-                                                       SoftPrior sp, int m, int n, int E,
-                                                       const void *__restrict__ in_, int kind, int max_iter, float alpha0,
-                                                       int early, void *__restrict__ out_bits_,
-                                                       float *__restrict__ out_llr, int *__restrict__ out_iters,
-                                                       void *__restrict__ out_conv_)
-{
-    bp_small_body<METHOD, false>(row_ptr, col_idx, col_ptr, csc_edge, sp, m, n, E, in_, kind, max_iter, alpha0, early, out_bits_,
-                                 out_llr, out_iters, out_conv_);
+    bp_small_body<METHOD, PLANES>(row_ptr, col_idx, col_ptr, csc_edge, P{prior_arg}, m, n, E, in_, kind, max_iter, alpha0, early,
+                                  out_bits_, out_llr, out_iters, out_conv_);
 }
 
 // ---------------------------------------------------------------------------
@@ -1384,17 +1324,18 @@ __device__ __forceinline__ float var_col_generic(float *mt, float *st, const int
 }
 
 // One fused launch over all column-degree buckets.  wave = (column, tile), lane = codeword.
-// grid (bk.blk[nb], G), block 256 = 4 columns of one bucket.
+// grid (column records / 4, G), block 256 = 4 columns of one bucket.
 // write_out: also emit hard-decision planes (merged under the done mask) and, if
 // `post` is non-null, the posterior of every not-yet-frozen codeword.
 // CAP = largest unroll bound compiled in (see k_check_tanh).
 template <int CAP, class P>
-__device__ __forceinline__ void var_body(const int *__restrict__ list, const int *__restrict__ csc_edge,
-                                         P prior, float *msg, float *scratch,
-                                         float *__restrict__ post, u64 *__restrict__ hard,
-                                         const u64 *__restrict__ done, int skip_done, int n, long E,
-                                         int write_out)
+__global__ __launch_bounds__(256) void k_var(const int *__restrict__ list, const int *__restrict__ csc_edge,
+                                             typename P::Arg prior_arg, float *msg, float *scratch,
+                                             float *__restrict__ post, u64 *__restrict__ hard,
+                                             const u64 *__restrict__ done, int skip_done, int n, long E,
+                                             int write_out)
 {
+    const P prior{prior_arg};
     const int lane = threadIdx.x & 63;
     const int tl = blockIdx.y;
     // one record per WAVE of the launch (VAR_REC ints: descriptor + the first VAR_INLINE edge ids), at
@@ -1438,26 +1379,6 @@ __device__ __forceinline__ void var_body(const int *__restrict__ list, const int
         if (post && !((dn >> lane) & 1)) post[hi * TW + lane] = L;
     }
 }
-template <int CAP>
-__global__ __launch_bounds__(256) void k_var(Buckets bk, const int *__restrict__ list,
-                                             const int *__restrict__ col_ptr, const int *__restrict__ csc_edge,
-                                             const float *__restrict__ prior, float *msg, float *scratch,
-                                             float *__restrict__ post, u64 *__restrict__ hard,
-                                             const u64 *__restrict__ done, int skip_done, int n, long E,
-                                             int write_out)
-{
-    var_body<CAP>(list, csc_edge, SharedPrior{prior}, msg, scratch, post, hard, done, skip_done, n, E, write_out);
-}
-template <int CAP>
-__global__ __launch_bounds__(256) void k_var_soft(const int *__restrict__ list, const int *__restrict__ csc_edge,
-                                                  SoftPrior sp, float *msg, float *scratch,
-                                                  float *__restrict__ post, u64 *__restrict__ hard,
-                                                  const u64 *__restrict__ done, int skip_done, int n, long E,
-                                                  int write_out)
-{
-    var_body<CAP>(list, csc_edge, sp, msg, scratch, post, hard, done, skip_done, n, E, write_out);
-}
-
 // ITERATION 1 of the tile kernels (see var_col_first): every wave takes TWO column records of the launch order and
 // fetches both columns' table entries, then both columns' syndrome words, before it processes either -- the pass is
 // three dependent round trips around half a pass's bytes, so a second column in flight per wave is what shortens it
@@ -1613,15 +1534,17 @@ __device__ __forceinline__ float var_col_rec(float *tile_base, const float *__re
     return temp;
 }
 
-// grid (bk.blk[nb], G), block 256 = 4 column records (k_var's launch shape and records).
+// grid (column records / 4, G), block 256 = 4 column records (k_var's launch shape and records).
+// (P = SoftPrior: tl is the tile the XCD map chose, the plane row follows it like the records do)
 template <int CAP, class P>
-__device__ __forceinline__ void var_rec_body(const int *__restrict__ list, const int *__restrict__ var_rows,
-                                             const int *__restrict__ csc_edge, const int *__restrict__ csc_row,
-                                             P prior, float *msg, const float *__restrict__ rec,
-                                             const ulonglong2 *__restrict__ mask, float *__restrict__ post,
-                                             u64 *__restrict__ hard, const u64 *__restrict__ done, int skip_done, int n, int m,
-                                             long E, int write_out, int blk0, int xmap)
+__global__ __launch_bounds__(256) void k_var_rec(const int *__restrict__ list, const int *__restrict__ var_rows,
+                                                 const int *__restrict__ csc_edge, const int *__restrict__ csc_row,
+                                                 typename P::Arg prior_arg, float *msg, const float *__restrict__ rec,
+                                                 const ulonglong2 *__restrict__ mask, float *__restrict__ post,
+                                                 u64 *__restrict__ hard, const u64 *__restrict__ done, int skip_done, int n, int m,
+                                                 long E, int write_out, int blk0, int xmap)
 {
+    const P prior{prior_arg};
     const unsigned lane = threadIdx.x & 63u;
     int tl = blockIdx.y, bx = blockIdx.x;
     if (xmap) {
@@ -1648,8 +1571,8 @@ __device__ __forceinline__ void var_rec_body(const int *__restrict__ list, const
     const int4 *w4 = (const int4 *)(var_rows + (size_t)ri * VAR_INLINE);
     const float pr = prior(v, tl, (int)lane);
     float L = pr;
-#define VR(D)                                                                                   \
-    case D:                                                                                     \
+#define VR(D)                                                                                       \
+    case D:                                                                                         \
         if constexpr (D <= CAP) L = var_col_rec<D>(tb, rb, rb2, mt + cb, lane, rc, w4, ce, cr, pr); \
         break;
 #define VR8(D) VR(D) VR(D + 1) VR(D + 2) VR(D + 3) VR(D + 4) VR(D + 5) VR(D + 6) VR(D + 7)
@@ -1667,30 +1590,6 @@ __device__ __forceinline__ void var_rec_body(const int *__restrict__ list, const
         if (post && !((dn >> lane) & 1)) post[hi * TW + lane] = L;
     }
 }
-template <int CAP>
-__global__ __launch_bounds__(256) void k_var_rec(const int *__restrict__ list, const int *__restrict__ var_rows,
-                                                 const int *__restrict__ csc_edge, const int *__restrict__ csc_row,
-                                                 const float *__restrict__ prior, float *msg, const float *__restrict__ rec,
-                                                 const ulonglong2 *__restrict__ mask, float *__restrict__ post,
-                                                 u64 *__restrict__ hard, const u64 *__restrict__ done, int skip_done, int n, int m,
-                                                 long E, int write_out, int blk0, int xmap)
-{
-    var_rec_body<CAP>(list, var_rows, csc_edge, csc_row, SharedPrior{prior}, msg, rec, mask, post, hard, done, skip_done, n, m, E,
-                      write_out, blk0, xmap);
-}
-// (tl is the tile the XCD map chose: the plane row follows it like the records do)
-template <int CAP>
-__global__ __launch_bounds__(256) void k_var_rec_soft(const int *__restrict__ list, const int *__restrict__ var_rows,
-                                                      const int *__restrict__ csc_edge, const int *__restrict__ csc_row,
-                                                      SoftPrior sp, float *msg, const float *__restrict__ rec,
-                                                      const ulonglong2 *__restrict__ mask, float *__restrict__ post,
-                                                      u64 *__restrict__ hard, const u64 *__restrict__ done, int skip_done, int n, int m,
-                                                      long E, int write_out, int blk0, int xmap)
-{
-    var_rec_body<CAP>(list, var_rows, csc_edge, csc_row, sp, msg, rec, mask, post, hard, done, skip_done, n, m, E, write_out, blk0,
-                      xmap);
-}
-
 // ---------------------------------------------------------------------------
 // Row-parallel ("edge-lane") kernels for a HANDFUL of codewords on a graph too large for
 // LDS: the single `decode()` of the attack loop (hqc.py:708 -- one codeword, n ~ 20 000,
@@ -1717,33 +1616,18 @@ __device__ __forceinline__ float readlane_f(float v, int l)
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
 }
 
-// unused by default (both rules' first check pass reads the priors); kept for rows the fused form does not cover.  grid (ceil(E/256), nb).
-template <class P>
-__device__ __forceinline__ void el_init_body(const int *__restrict__ col_idx, P prior, float *__restrict__ emsg, long E)
-{
-    const long e = (long)blockIdx.x * 256 + threadIdx.x;
-    if (e < E) emsg[(size_t)blockIdx.y * E + e] = prior(col_idx[e], 0, blockIdx.y);  // (codeword c = lane c of the one tile)
-}
-__global__ __launch_bounds__(256) void k_el_init(const int *__restrict__ col_idx, const float *__restrict__ prior,
-                                                 float *__restrict__ emsg, long E)
-{
-    el_init_body(col_idx, SharedPrior{prior}, emsg, E);
-}
-__global__ __launch_bounds__(256) void k_el_init_soft(const int *__restrict__ col_idx, SoftPrior sp, float *__restrict__ emsg,
-                                                      long E)
-{
-    el_init_body(col_idx, sp, emsg, E);
-}
-
+// (No message initialisation pass: these kernels serve rows of at most ROW_CAP edges -- the host's el_ok -- and for such
+// rows the first check pass of either rule reads the priors, fused_init.)
 // METHOD as in the C ABI; FIRST: inputs are the priors (iteration 1).
 // grid (ceil(m/4), nb), block 256 = 4 rows of codeword blockIdx.y.
 template <int METHOD, bool FIRST, class P>
-__device__ __forceinline__ void el_check_body(const int *__restrict__ row_ptr, const int *__restrict__ col_idx,
-                                              P prior, float *emsg,
-                                              const u64 *__restrict__ synd, const u64 *__restrict__ done,
-                                              int skip_done, int m, long E, float alpha,
-                                              const u64 *__restrict__ hard, int *__restrict__ unsat_prev)
+__global__ __launch_bounds__(256) void k_el_check(const int *__restrict__ row_ptr, const int *__restrict__ col_idx,
+                                                  typename P::Arg prior_arg, float *emsg,
+                                                  const u64 *__restrict__ synd, const u64 *__restrict__ done,
+                                                  int skip_done, int m, long E, float alpha,
+                                                  const u64 *__restrict__ hard, int *__restrict__ unsat_prev)
 {
+    const P prior{prior_arg};
     const int lane = threadIdx.x & 63;
     int r = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= m) return;
@@ -1794,26 +1678,6 @@ __device__ __forceinline__ void el_check_body(const int *__restrict__ row_ptr, c
         if (act) *p = __uint_as_float(__float_as_uint(Lm) ^ sg);
     }
 }
-template <int METHOD, bool FIRST>
-__global__ __launch_bounds__(256) void k_el_check(const int *__restrict__ row_ptr, const int *__restrict__ col_idx,
-                                                  const float *__restrict__ prior, float *emsg,
-                                                  const u64 *__restrict__ synd, const u64 *__restrict__ done,
-                                                  int skip_done, int m, long E, float alpha,
-                                                  const u64 *__restrict__ hard, int *__restrict__ unsat_prev)
-{
-    el_check_body<METHOD, FIRST>(row_ptr, col_idx, SharedPrior{prior}, emsg, synd, done, skip_done, m, E, alpha, hard, unsat_prev);
-}
-// the first check pass of a soft call
-template <int METHOD>
-__global__ __launch_bounds__(256) void k_el_check_soft(const int *__restrict__ row_ptr, const int *__restrict__ col_idx,
-                                                       SoftPrior sp, float *emsg,
-                                                       const u64 *__restrict__ synd, const u64 *__restrict__ done,
-                                                       int skip_done, int m, long E, float alpha,
-                                                       const u64 *__restrict__ hard, int *__restrict__ unsat_prev)
-{
-    el_check_body<METHOD, true>(row_ptr, col_idx, sp, emsg, synd, done, skip_done, m, E, alpha, hard, unsat_prev);
-}
-
 // Variable nodes, lane = EDGE OF A COLUMN.  The host packs whole columns into waves of 64 lane
 // slots: a column owns a SEGMENT of `cap` neighbouring lanes, cap >= max(degree, 1), of which the
 // first `degree` hold its edges in ascending row order.  A slot is
@@ -1903,27 +1767,17 @@ __device__ __forceinline__ void el_var_body(const int2 *__restrict__ slots, cons
         if (post) post[(size_t)v * TW + c] = tot;
     }
 }
+template <class P>
 __global__ __launch_bounds__(256) void k_el_var(const int2 *__restrict__ slots, const int *__restrict__ slot_col,
-                                                int nwaves, const float *__restrict__ prior, float *emsg,
+                                                int nwaves, typename P::Arg prior_arg, float *emsg,
                                                 float *__restrict__ post, u64 *__restrict__ hard,
                                                 u64 *done, int skip_done, long E, int write_out,
                                                 const int *__restrict__ unsat_prev, int it_prev, u64 *conv,
                                                 int *__restrict__ iters, int *__restrict__ remaining_prev)
 {
-    el_var_body(slots, slot_col, nwaves, SharedPrior{prior}, emsg, post, hard, done, skip_done, E, write_out, unsat_prev, it_prev,
-                conv, iters, remaining_prev);
+    el_var_body(slots, slot_col, nwaves, P{prior_arg}, emsg, post, hard, done, skip_done, E, write_out, unsat_prev, it_prev, conv,
+                iters, remaining_prev);
 }
-__global__ __launch_bounds__(256) void k_el_var_soft(const int2 *__restrict__ slots, const int *__restrict__ slot_col,
-                                                     int nwaves, SoftPrior sp, float *emsg,
-                                                     float *__restrict__ post, u64 *__restrict__ hard,
-                                                     u64 *done, int skip_done, long E, int write_out,
-                                                     const int *__restrict__ unsat_prev, int it_prev, u64 *conv,
-                                                     int *__restrict__ iters, int *__restrict__ remaining_prev)
-{
-    el_var_body(slots, slot_col, nwaves, sp, emsg, post, hard, done, skip_done, E, write_out, unsat_prev, it_prev, conv, iters,
-                remaining_prev);
-}
-
 // dst[idx] = val for a list of {idx, val} pairs (table updates of scaldpc_bp_append_rows).  grid ceil(n/256).
 __global__ __launch_bounds__(256) void k_apply_pairs(int *__restrict__ dst, const int2 *__restrict__ pairs, int n)
 {

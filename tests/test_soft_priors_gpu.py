@@ -157,6 +157,50 @@ def test_every_degree(oracle, method):
         _same(got, outs[0 if early else 1][1])
 
 
+@pytest.mark.parametrize("method", METHODS)
+def test_wide_rows_and_columns_soft(oracle, method):
+    """The graph of test_bp_gpu.test_wide_rows_and_columns (90 x 200: a row of 101 edges and one of 62, a column of 79 and
+    one of 42, a degree-1 row, an isolated variable) on the tile kernels, 130 codewords with priors of their own for all
+    n columns: the min-sum loop form's first pass, the initialisation pass in front of the tanh rule's any-degree rows,
+    and the variable pass at its widest build with any-degree columns -- none of which test_every_degree's 64-edge rows and
+    32-edge columns reach.  18 codewords against the oracle; the decoder's own priors in every row equal the plain call."""
+    rng = np.random.RandomState(5)
+    H = (rng.rand(90, 200) < 0.04).astype(np.int8)
+    H[0, :100] = 1  # row of degree >= 100
+    H[2, 100:150] = 1  # row of degree ~50
+    H[:80, 3] = 1  # column of degree >= 80
+    H[:40, 5] = 1  # column of degree ~40
+    H[1, :] = 0
+    H[1, 7] = 1  # degree-1 row
+    H[:, 150] = 0  # isolated variable
+    G = S.TannerGraph.from_dense(H)
+    deg_r, deg_c = H.sum(axis=1), H.sum(axis=0)
+    # any-degree row and column (> 64), the 33 .. 64 register builds, a degree-1 row, an isolated variable
+    assert deg_r[0] > 64 and deg_c[3] > 64 and 32 < deg_r[2] <= 64 and 32 < deg_c[5] <= 64 and deg_r[1] == 1 and deg_c[150] == 0
+    batch, max_iter = 130, 15
+    p = np.where(rng.rand(batch, G.n) < 0.85, rng.uniform(0.01, 0.2, (batch, G.n)), rng.uniform(0.55, 0.9, (batch, G.n)))
+    hard = rng.rand(batch, G.n) < 0.004
+    p[hard] = rng.randint(0, 2, size=int(hard.sum()))
+    p = p.astype(np.float32)
+    scale = np.array([0.0, 0.03, 0.1, 0.3, 1.0])[np.arange(batch) % 5]
+    err = (rng.rand(batch, G.n) < np.where(p < 0.5, p * scale[:, None], 1.0 - (1.0 - p) * scale[:, None])).astype(np.uint8)
+    assert not err[p == 0.0].any() and err[p == 1.0].all()  # (syndromes the codeword's own priors allow)
+    synd = G.syndrome(err)
+    pick = np.r_[0:6, 64:70, 124:130]
+    shared = rng.uniform(0.02, 0.1, size=G.n)
+    own = np.ascontiguousarray(np.broadcast_to(shared.astype(np.float32), (batch, G.n)))
+    own_synd = G.syndrome((rng.rand(batch, G.n) < 0.03).astype(np.uint8))
+    dec = _decoder(G, shared, method, max_iter, path="stream")  # (on `auto` this graph fits LDS)
+    for early in (True, False):
+        ref = oracle_per_codeword(oracle, G, shared, p[pick], synd[pick], 0, max_iter, method, early_exit=early)
+        got = dec.decode_batch(synd, early_exit=early, want_llr=True, input_vector_type="syndrome", channel_probs=p)
+        assert dec.last_stats()["row_parallel"] == 0
+        compare(take(got, pick), ref, method)
+        plain = dec.decode_batch(own_synd, early_exit=early, want_llr=True, input_vector_type="syndrome")
+        _same(dec.decode_batch(own_synd, early_exit=early, want_llr=True, input_vector_type="syndrome", channel_probs=own), plain)
+    dec.close()
+
+
 # ------------------------------------------------------------------------------------------------ 4. no decoder in the key
 @functools.lru_cache(maxsize=None)
 def _tree_case():
