@@ -40,6 +40,10 @@
  *                                (decoder.rs:654-657): the per-symbol totals, the margin of every decision, and the
  *                                number of checks the decided word leaves unmet (the reference has no convergence test)
  *                                (entry points added under SCALDPC_VERSION 103: nothing that existed changed)
+ *   scaldpc_mc_qary_run          the per-trial body of simulate_frame_error_rate_rust, simulate/decode.py:246-257,273-277:
+ *                                every symbol of an all-zero word gets the "good" or the "bad" pmf row, min_sum, is the
+ *                                decision all zero -- trials drawn on the device
+ *                                (entry point added under SCALDPC_VERSION 103: nothing that existed changed)
  *
  * Threading: calls on distinct handles are independent; calls on one handle are
  * serialised internally, so one decoder object may be shared by many host
@@ -361,6 +365,48 @@ int scaldpc_qary_min_sum_batch_soft(scaldpc_qary *h, const float *pmf, int32_t b
 int scaldpc_qary_special_min_sum_batch_soft(scaldpc_qary *h, const float *pmf_b, const float *pmf_sum, int32_t batch,
                                             uint32_t flags, void *stream, int8_t *out,
                                             float *out_cost_b, float *out_cost_sum, float *out_margin, int32_t *out_unmet);
+
+/* ------------------------------------------- Monte-Carlo trials of the q-ary decoders on the device */
+/*
+ * `batch` trials of the reference's q-ary sweep (simulate/decode.py:246-257: an all-zero word whose symbols each carry one of a
+ * few pmf rows) without a [batch][N][Q] input and without a [batch][N] output.  Every variable draws a LEVEL of its table:
+ *   levels_b  float  [k_b][2B+1]     the pmf rows of the coefficient variables (the plain decoder: of every variable)
+ *   weights_b double [k_b]           the probability of each row
+ *   levels_s / weights_s / k_s       the same for DecoderSpecial's row-sum variables, [k_s][2BSUM+1]; a plain handle takes
+ *                                    NULL, NULL, 0 and nothing else
+ * and the call decodes the word so made.  Tables and weights are HOST pointers whatever the flags say.
+ *
+ * Trial law (next to K6's above; a trial depends on (seed, first_trial + i) alone, not on batch, split or GPU count):
+ *   generator   Philox4x32-10, key = seed, counter = (x >> 2, 0, trial_lo, trial_hi): stream 0, word x & 3, with x the graph
+ *               variable index 0 .. N-1 (DecoderSpecial's row-sum variables continue at N-R) and the GLOBAL trial index
+ *   thresholds  T_k = thr(w_0 + ... + w_k), the sum accumulated left to right in float64, thr(p) = floor(p 2^32), 0 for p <= 0,
+ *               2^32 for p >= 1 (the rule of scaldpc_mc_fer_run); T_{K-1} is forced to 2^32 -- and so is every T_k from the last
+ *               level of nonzero weight on, so that a level of weight 0 is never drawn
+ *   level       the smallest k with word < T_k
+ * With K = 2, rows (bad, good) and weights (error_rate, 1 - error_rate), "bad" is drawn exactly where stream-0 word x of the
+ * trial is below floor(error_rate 2^32) -- the Bernoulli draw of scaldpc_mc_fer_run -- and out_errs is the reference's `errs`.
+ *
+ * Defining property: for every trial, out_symbols is what scaldpc_qary_min_sum_batch / scaldpc_qary_special_min_sum_batch
+ * returns for the materialised input pmf[i][v] = levels[out_levels[i][v]], bit for bit, in every kernel form and at any split of
+ * the trials into calls.  (The K (+ K_s) rows are converted to LLRs by the conversion of scaldpc_qary_into_llr, once: a call
+ * whose tables are bit for bit those of the handle's last finished call -- every chunk of a sweep -- reuses the converted rows.)
+ *
+ *   out_success uint8 [batch]     required: 1 iff every decided symbol is 0
+ *   out_errs    int32 [batch]     optional: variables drawn at a level other than the LAST of their table
+ *   out_wrong   int32 [batch]     optional: decided symbols != 0
+ *   out_levels  uint8 [batch][N]  optional: the level drawn for every variable
+ *   out_symbols int8  [batch][N]  optional: the decisions
+ * Validation (SCALDPC_EINVAL, nothing queued): 1 <= K <= 16 per table; every weight finite and in [0, 1]; |sum w - 1| <= 1e-6;
+ * first_trial >= 0; a plain handle refuses levels_s, a special handle requires it.  A table row that fails the reference's pmf
+ * test (decoder.rs:683-684) returns SCALDPC_EPMF and names the table and the level.
+ * flags: SCALDPC_F_DEVICE_IO: the five outputs are device pointers; SCALDPC_F_ASYNC is refused (SCALDPC_EINVAL).
+ * SCALDPC_ENOCONF is reported as by the plain call.
+ */
+int scaldpc_mc_qary_run(scaldpc_qary *h, const float *levels_b, const double *weights_b, int32_t k_b,
+                        const float *levels_s, const double *weights_s, int32_t k_s,
+                        int64_t first_trial, int32_t batch, uint64_t seed, uint32_t flags, void *stream,
+                        uint8_t *out_success, int32_t *out_errs, int32_t *out_wrong, uint8_t *out_levels,
+                        int8_t *out_symbols);
 
 #ifdef __cplusplus
 }

@@ -102,9 +102,13 @@ def _declare(lib):
     lib.scaldpc_qary_special_min_sum_batch.argtypes = [vp, vp, vp, C.c_int32, C.c_uint32, vp, vp]
     lib.scaldpc_qary_min_sum_batch_soft.argtypes = [vp, vp, C.c_int32, C.c_uint32, vp, vp, vp, vp, vp]
     lib.scaldpc_qary_special_min_sum_batch_soft.argtypes = [vp, vp, vp, C.c_int32, C.c_uint32, vp, vp, vp, vp, vp, vp]
+    lib.scaldpc_mc_qary_run.argtypes = [
+        vp, vp, vp, C.c_int32, vp, vp, C.c_int32, C.c_int64, C.c_int32, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp, vp,
+    ]  # fmt: skip
     for name in (
         "scaldpc_qary_create", "scaldpc_qary_min_sum_batch", "scaldpc_qary_special_create",
         "scaldpc_qary_special_min_sum_batch", "scaldpc_qary_min_sum_batch_soft", "scaldpc_qary_special_min_sum_batch_soft",
+        "scaldpc_mc_qary_run",
     ):  # fmt: skip
         getattr(lib, name).restype = C.c_int
 

@@ -3,6 +3,7 @@
 // translation unit; the split is for reading, not for linking.
 #pragma once
 #include "scaldpc_logf.h"  // glibc's logf on the device (k_soft_convert)
+#include "scaldpc_philox.h"
 #include <type_traits>
 
 // v_writelane_b32 as an instruction the COMPILER emits: ROCm 7.2's clang has no __builtin_amdgcn_writelane, but the LLVM
@@ -1796,20 +1797,7 @@ __global__ __launch_bounds__(256) void k_apply_pairs(int *__restrict__ dst, cons
 //   stream 1 word j : j-th candidate position of the HQC secret, pos = mulhi(word, N),
 //                     accepted if not chosen before, until omega are accepted
 // ---------------------------------------------------------------------------
-struct U4 { unsigned x, y, z, w; };
-
-__device__ __forceinline__ U4 philox4x32_10(U4 c, unsigned k0, unsigned k1)
-{
-#pragma unroll
-    for (int r = 0; r < 10; r++) {
-        const unsigned hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
-        const unsigned hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
-        c = U4{hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0};
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return c;
-}
+// (U4, philox4x32_10: scaldpc_philox.h, shared with the q-ary trial generator)
 
 // planes[t][x] (bit c) = [stream-`stream` word x of trial first + 64 t + c  <  thr_x]; XOR_INTO flips
 // an existing plane instead.  wave = (tile, 16 consecutive x).  grid (ceil(len/64), T), block 256.

@@ -37,6 +37,7 @@ typedef unsigned long long u64;
 #include "scaldpc_qary_special.h"
 #include "scaldpc_qary_rows.h"
 #include "scaldpc_qary_soft.h"
+#include "scaldpc_qary_mc.h"
 
 namespace {
 
@@ -47,7 +48,7 @@ constexpr int QERR_PMF = 3;        // decoder.rs:683-684 assert
 struct PmfScan {
     float sum = 0.0f, mx = 0.0f;
     bool have = false;
-    __device__ __forceinline__ void step(float x)
+    __host__ __device__ __forceinline__ void step(float x)  // (host: the level tables of scaldpc_mc_qary_run, before anything is queued)
     {
         sum += x;
         if (x == x && (!have || x > mx)) {
@@ -55,7 +56,7 @@ struct PmfScan {
             have = true;
         }
     }
-    __device__ __forceinline__ bool bad() const { return !have || !(sum < 1.0f + 0.001f) || !(sum > 1.0f - 0.001f); }
+    __host__ __device__ __forceinline__ bool bad() const { return !have || !(sum < 1.0f + 0.001f) || !(sum > 1.0f - 0.001f); }
 };
 // key of a failing row, smaller = earlier: codeword, then alphabet (0 = coefficient rows, 1 = row-sum rows), then variable, then
 // "no maximum" (scaldpc_qary_into_llr: codeword 0, alphabet 0, variable = row)
@@ -697,9 +698,18 @@ struct scaldpc_qary : QaryStreams, QaryShape {
     // their [batch][...] forms for host callers, and the unmet-check counts
     Buf<float> d_cost, d_margin, d_cost_out, d_margin_out;
     Buf<int> d_unmet;
+    // Monte-Carlo calls only (scaldpc_mc_qary_run; allocated by the first one): the drawn levels [N][Bp], the level tables (their pmf
+    // rows, then their LLR rows), and for host callers the per-trial results (errs, wrong, success) and the levels as [batch][N]
+    Buf<unsigned char> d_mc_lvl, d_mc_lvl_out;
+    Buf<float> d_mc_tab;
+    Buf<int> d_mc_res;
+    std::vector<float> mc_tab;  // host side of d_mc_tab's pmf rows and of d_mc_res: alive until the call has drained its stream
+    std::vector<int> mc_res;
+    bool mc_tab_ok = false;  // d_mc_tab holds the LLR rows of mc_tab (a finished call put them there): a sweep converts its tables once
     // one 16-byte status block per handle, zeroed by ONE fill and read back by ONE copy per call: [0] = the bitwise complement of
     // the smallest (codeword, variable) key whose pmf row fails the sum test (0: none; kept inverted so that "none" is zero
-    // and the kernels lower the key with atomicMax), [1] = the call's error code (low word)
+    // and the kernels lower the key with atomicMax), [1] = the call's error code (low word).  A third word behind the block is
+    // k_q_into_llr_rows's key in a Monte-Carlo call (never read: the level tables are tested on the host)
     Buf<u64> d_status;
     int *d_err = nullptr;        // = (int *)(d_status + 1)
     u64 *d_first_bad = nullptr;  // = d_status
@@ -812,7 +822,7 @@ int qary_build(int R, int N, int B, int BSUM, bool special, const int8_t *H, int
         SC_TRY(up(h->d_edge_h, edge_h.data(), E));
         SC_TRY(up(h->d_var_q, h->h_var_q.data(), N));
         SC_TRY(up(h->d_var_off, h->h_var_off.data(), N));
-        SC_TRY(h->d_status.ensure(2));
+        SC_TRY(h->d_status.ensure(3));
         h->d_first_bad = h->d_status;
         h->d_err = (int *)(h->d_status + 1);
         if (hipGetDevice(&h->device) != hipSuccess) return fail(SCALDPC_EHIP, "hipGetDevice failed");
@@ -1122,11 +1132,12 @@ int report(scaldpc_qary *h, const QaryCall &c, const u64 (&status)[2])
     return 0;
 }
 
-int qary_run(scaldpc_qary *h, const float *pmf_b, const float *pmf_s, int batch, uint32_t flags, void *stream,
-             int8_t *out, const SoftOut &so = SoftOut())
+// One call from the handle's lock to its verdict.  `prepare` makes sure of every block the call will touch (nothing is queued
+// yet), `first` queues what leaves the LLRs and the first messages in the workspaces, `last` delivers the outputs and returns
+// with the stream drained and the status block read.  The plan, the iterations and the verdict are the same for every entry.
+template <typename Prepare, typename First, typename Last>
+int qary_steps(scaldpc_qary *h, int batch, uint32_t flags, void *stream, const SoftOut &so, Prepare prepare, First first, Last last)
 {
-    if (!h || !pmf_b || !out || (h->special && !pmf_s)) return fail(SCALDPC_EINVAL, "NULL argument");
-    if (batch <= 0) return fail(SCALDPC_EINVAL, "batch must be positive");
     std::lock_guard<std::mutex> lk(h->mu);
     DeviceGuard dg(h->device);
     QaryCall c;
@@ -1144,13 +1155,161 @@ int qary_run(scaldpc_qary *h, const float *pmf_b, const float *pmf_s, int batch,
     if (refused)
         return fail(SCALDPC_EDEGREE, "alphabet/degree too large for the LDS-staged enumeration (%zu B per codeword)",
                     c.plan.check_lds / c.plan.T);
-    SC_TRY(ensure_buffers(h, c));
+    SC_TRY(prepare(c));
     SC_HIP(hipMemsetAsync(h->d_status, 0, 2 * sizeof(u64), c.s));
-    SC_TRY(stage_and_convert(h, c, pmf_b, pmf_s));
+    SC_TRY(first(c));
     SC_TRY(iterate(h, c));
     u64 status[2] = {0, 0};
-    SC_TRY(emit(h, c, out, status));
+    SC_TRY(last(c, status));
     return report(h, c, status);
+}
+
+int qary_run(scaldpc_qary *h, const float *pmf_b, const float *pmf_s, int batch, uint32_t flags, void *stream,
+             int8_t *out, const SoftOut &so = SoftOut())
+{
+    if (!h || !pmf_b || !out || (h->special && !pmf_s)) return fail(SCALDPC_EINVAL, "NULL argument");
+    if (batch <= 0) return fail(SCALDPC_EINVAL, "batch must be positive");
+    return qary_steps(
+        h, batch, flags, stream, so, [&](QaryCall &c) { return ensure_buffers(h, c); },
+        [&](QaryCall &c) { return stage_and_convert(h, c, pmf_b, pmf_s); },
+        [&](QaryCall &c, u64(&status)[2]) { return emit(h, c, out, status); });
+}
+
+// ---------------------------------------------------------------------------------------------- scaldpc_mc_qary_run
+// The level tables of a call (0: coefficient variables, 1: DecoderSpecial's row-sum variables) and its outputs.
+struct McTables {
+    const float *levels[2] = {nullptr, nullptr};
+    const double *weights[2] = {nullptr, nullptr};
+    int K[2] = {0, 0}, Q[2] = {0, 0};
+    int floats() const { return K[0] * Q[0] + K[1] * Q[1]; }
+};
+struct McOut {
+    uint8_t *success;
+    int32_t *errs, *wrong;
+    uint8_t *levels;
+    int8_t *symbols;
+};
+
+// floor(p 2^32), 0 for p <= 0, 2^32 for p >= 1: the rule of the binary helpers (bernoulli_threshold, scaldpc_bp.hip)
+u64 mc_threshold(double p) { return p >= 1.0 ? (1ull << 32) : p <= 0.0 ? 0ull : (u64)(p * 4294967296.0); }
+
+// Everything that can be refused about the tables, and their thresholds; nothing is queued, no handle state is touched.
+int mc_law(const McTables &t, int ntab, McLaw *law)
+{
+    static const char *const name[2] = {"levels_b", "levels_s"};
+    *law = McLaw();
+    for (int i = 0; i < ntab; i++) {
+        const int K = t.K[i];
+        if (K < 1 || K > MC_MAX_LEVELS) return fail(SCALDPC_EINVAL, "%s: %d levels, 1 .. %d are taken", name[i], K, MC_MAX_LEVELS);
+        double sum = 0.0;
+        int last = 0;  // the last level of nonzero weight: from there on the threshold is 2^32, so a level of weight 0 is never drawn
+        for (int k = 0; k < K; k++) {
+            const double w = t.weights[i][k];
+            if (!(w >= 0.0 && w <= 1.0)) return fail(SCALDPC_EINVAL, "%s: weight %d is %g, not a probability", name[i], k, w);
+            sum += w;
+            law->t[i][k] = mc_threshold(sum);
+            if (w > 0.0) last = k;
+        }
+        if (!(std::fabs(sum - 1.0) <= 1e-6)) return fail(SCALDPC_EINVAL, "%s: the weights sum to %.9g, not to 1 +- 1e-6", name[i], sum);
+        for (int k = last; k < K; k++) law->t[i][k] = 1ull << 32;
+        law->K[i] = K;
+    }
+    for (int i = 0; i < ntab; i++)
+        for (int k = 0; k < t.K[i]; k++) {
+            PmfScan sc;
+            for (int q = 0; q < t.Q[i]; q++) sc.step(t.levels[i][(size_t)k * t.Q[i] + q]);
+            if (sc.bad())
+                return fail(SCALDPC_EPMF, sc.have ? "%s: level %d does not sum to 1 +- 1e-3 (decoder.rs:683-684)"
+                                                  : "%s: level %d: No maximum probability found", name[i], k);
+        }
+    return 0;
+}
+
+// The workspaces of a device-pointer call (the pmf staging of a host call is not needed: there is no input), then the blocks of this entry.
+int mc_ensure(scaldpc_qary *h, const QaryCall &c, const McTables &t, const McOut &o)
+{
+    QaryCall work = c;
+    work.dev_io = true;
+    SC_TRY(ensure_buffers(h, work));
+    SC_TRY(h->d_mc_lvl.ensure((size_t)h->N * c.Bp));
+    if (h->d_mc_tab.cap() < (size_t)2 * t.floats()) h->mc_tab_ok = false;
+    SC_TRY(h->d_mc_tab.ensure((size_t)2 * t.floats()));
+    if (c.dev_io) return 0;
+    SC_TRY(h->d_mc_res.ensure((size_t)2 * c.batch + ((size_t)c.batch + 3) / 4));
+    if (o.levels) SC_TRY(h->d_mc_lvl_out.ensure((size_t)c.batch * h->N));
+    if (o.symbols) SC_TRY(h->d_out.ensure((size_t)c.batch * h->N));
+    return 0;
+}
+
+// The first step of a Monte-Carlo call: the tables' rows -> LLR rows (k_q_into_llr_rows: the plain call's glibc_logf(max / p);
+// skipped when the tables are those of the handle's last finished call), then
+// k_q_mc_draw leaves in d_llr and d_msg what stage_and_convert leaves there for the materialised input (fused or not: k_q_init
+// copies the same numbers), and the drawn levels in d_mc_lvl.
+int mc_draw(scaldpc_qary *h, const QaryCall &c, const McTables &t, const McLaw &law, long first_trial, uint64_t seed)
+{
+    const int nt = t.floats(), nb = t.K[0] * t.Q[0];
+    float *d_rows = h->d_mc_tab + nt;
+    // the tables of the last finished call, bit for bit (the chunks of a sweep): their LLR rows are still there -- no copy, no conversion
+    const bool kept = h->mc_tab_ok && h->mc_tab.size() == (size_t)nt && !memcmp(h->mc_tab.data(), t.levels[0], (size_t)nb * sizeof(float)) &&
+                      (nt == nb || !memcmp(h->mc_tab.data() + nb, t.levels[1], (size_t)(nt - nb) * sizeof(float)));
+    if (!kept) {
+        h->mc_tab_ok = false;
+        h->mc_tab.assign(t.levels[0], t.levels[0] + nb);
+        if (t.K[1]) h->mc_tab.insert(h->mc_tab.end(), t.levels[1], t.levels[1] + (nt - nb));
+        SC_HIP(hipMemcpyAsync(h->d_mc_tab, h->mc_tab.data(), (size_t)nt * sizeof(float), hipMemcpyHostToDevice, c.s));
+        for (int i = 0, off = 0; i < 2 && t.K[i]; off += t.K[i] * t.Q[i], i++) {
+            hipLaunchKernelGGL(k_q_into_llr_rows, dim3(1), dim3(256), 0, c.s, h->d_mc_tab + off, (long)t.K[i], t.Q[i], d_rows + off,
+                               h->d_status + 2);
+            SC_HIP(hipGetLastError());
+        }
+    }
+    hipLaunchKernelGGL(k_q_mc_draw, dim3((h->N + 3) / 4, c.Bp / 64), dim3(256), (size_t)nt * sizeof(float), c.s, law, d_rows, t.Q[0],
+                       t.Q[1], c.BV, h->N, c.batch, c.Bp, first_trial, (unsigned)seed, (unsigned)(seed >> 32), h->d_col_ptr,
+                       h->d_csc_edge, h->d_edge_h, h->d_llr, h->d_msg, h->W, h->d_mc_lvl);
+    SC_HIP(hipGetLastError());
+    return 0;
+}
+
+// The last step: the per-trial results out of the staged symbols and levels; the optional [batch][N] arrays through k_q_unpack.
+// Host callers get errs, wrong and success through ONE block and one copy.  Returns with the stream drained.
+int mc_emit(scaldpc_qary *h, const QaryCall &c, const McLaw &law, const McOut &o, u64 (&status)[2])
+{
+    const hipStream_t s = c.s;
+    const int batch = c.batch;
+    const size_t n_sym = (size_t)batch * h->N;
+    int *d_errs = c.dev_io ? o.errs : h->d_mc_res.get(), *d_wrong = c.dev_io ? o.wrong : h->d_mc_res.get() + batch;
+    unsigned char *d_success = c.dev_io ? o.success : (unsigned char *)(h->d_mc_res.get() + 2 * (size_t)batch);
+    unsigned char *d_levels = c.dev_io ? o.levels : h->d_mc_lvl_out.get();
+    signed char *d_symbols = c.dev_io ? (signed char *)o.symbols : h->d_out.get();
+    hipLaunchKernelGGL(k_q_mc_result, dim3(c.Bp / 64), dim3(1024), 0, s, h->d_hard, h->d_mc_lvl, h->N, c.BV, law.K[0] - 1, law.K[1] - 1,
+                       batch, c.Bp, d_success, d_errs, d_wrong);
+    SC_HIP(hipGetLastError());
+    const dim3 ug((h->N + 255) / 256, batch);
+    if (o.levels) {
+        hipLaunchKernelGGL(k_q_unpack, ug, dim3(256), 0, s, (const signed char *)h->d_mc_lvl.get(), h->N, batch, c.Bp, (signed char *)d_levels);
+        SC_HIP(hipGetLastError());
+    }
+    if (o.symbols) {
+        hipLaunchKernelGGL(k_q_unpack, ug, dim3(256), 0, s, h->d_hard, h->N, batch, c.Bp, d_symbols);
+        SC_HIP(hipGetLastError());
+    }
+    SC_HIP(hipMemcpyAsync(status, h->d_status, sizeof(status), hipMemcpyDeviceToHost, s));
+    const size_t n_res = (size_t)2 * batch + ((size_t)batch + 3) / 4;
+    if (!c.dev_io) {
+        h->mc_res.resize(n_res);
+        SC_HIP(hipMemcpyAsync(h->mc_res.data(), h->d_mc_res, n_res * sizeof(int), hipMemcpyDeviceToHost, s));
+        if (o.levels) SC_HIP(hipMemcpyAsync(o.levels, d_levels, n_sym, hipMemcpyDeviceToHost, s));
+        if (o.symbols) SC_HIP(hipMemcpyAsync(o.symbols, d_symbols, n_sym, hipMemcpyDeviceToHost, s));
+    }
+    SC_HIP(hipStreamSynchronize(s));
+    h->mc_tab_ok = true;
+    if (!c.dev_io) {
+        const int *res = h->mc_res.data();
+        if (o.errs) memcpy(o.errs, res, (size_t)batch * sizeof(int));
+        if (o.wrong) memcpy(o.wrong, res + batch, (size_t)batch * sizeof(int));
+        memcpy(o.success, res + 2 * (size_t)batch, batch);
+    }
+    return 0;
 }
 
 }  // namespace
@@ -1255,6 +1414,29 @@ int scaldpc_qary_special_min_sum_batch_soft(scaldpc_qary *h, const float *pmf_b,
     if ((out_cost_b == nullptr) != (out_cost_sum == nullptr))
         return fail(SCALDPC_EINVAL, "out_cost_b and out_cost_sum: pass both or neither");
     return qary_run(h, pmf_b, pmf_sum, batch, flags, stream, out, SoftOut{out_cost_b, out_cost_sum, out_margin, out_unmet});
+}
+
+int scaldpc_mc_qary_run(scaldpc_qary *h, const float *levels_b, const double *weights_b, int32_t k_b, const float *levels_s,
+                        const double *weights_s, int32_t k_s, int64_t first_trial, int32_t batch, uint64_t seed, uint32_t flags,
+                        void *stream, uint8_t *out_success, int32_t *out_errs, int32_t *out_wrong, uint8_t *out_levels,
+                        int8_t *out_symbols)
+{
+    if (!h || !levels_b || !weights_b || !out_success) return fail(SCALDPC_EINVAL, "NULL argument");
+    if (h->special && (!levels_s || !weights_s)) return fail(SCALDPC_EINVAL, "a special decoder needs levels_s and weights_s");
+    if (!h->special && (levels_s || weights_s || k_s)) return fail(SCALDPC_EINVAL, "levels_s / weights_s / k_s: this handle is not a special decoder");
+    if (batch <= 0) return fail(SCALDPC_EINVAL, "batch must be positive");
+    if (first_trial < 0) return fail(SCALDPC_EINVAL, "first_trial must not be negative");
+    if (flags & SCALDPC_F_ASYNC) return fail(SCALDPC_EINVAL, "SCALDPC_F_ASYNC: a q-ary Monte-Carlo call is synchronous");
+    McTables t;
+    t.levels[0] = levels_b; t.weights[0] = weights_b; t.K[0] = k_b; t.Q[0] = h->Q;
+    if (h->special) { t.levels[1] = levels_s; t.weights[1] = weights_s; t.K[1] = k_s; t.Q[1] = h->QS; }
+    McLaw law;
+    SC_TRY(mc_law(t, h->special ? 2 : 1, &law));
+    const McOut o = {out_success, out_errs, out_wrong, out_levels, out_symbols};
+    return qary_steps(
+        h, batch, flags, stream, SoftOut(), [&](QaryCall &c) { return mc_ensure(h, c, t, o); },
+        [&](QaryCall &c) { return mc_draw(h, c, t, law, (long)first_trial, seed); },
+        [&](QaryCall &c, u64(&status)[2]) { return mc_emit(h, c, law, o, status); });
 }
 
 void scaldpc_qary_destroy(scaldpc_qary *h)

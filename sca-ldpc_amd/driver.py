@@ -6,6 +6,7 @@ decoder in ONE batched call.
   ErrorsProvider                  simulate/decode.py:9-127
   simulate_frame_error_rate       simulate/decode.py:130-177  (binary FER loop)
   simulate_frame_error_rate_rust  simulate/decode.py:180-286  (q-ary FER loop)
+  qary_fer_sweep                  the same loop, its trials drawn on the device (Philox, sharded by global trial index)
   hqc_decode                      simulate/hqc.py:661-759      (input assembly + 7 stats fields)
   hqc_decode_batch                the same for many trials with their own certainties, one soft call
   regular_ldpc_code & co          main.py:189-276              (the four FER commands, as functions)
@@ -152,6 +153,59 @@ def simulate_frame_error_rate_rust(H, B, error_rate, runs, rng, threads=1, decod
         frames.append(np.where(mask[:, None], bad, good).astype(np.float32))
     decoding = decoder.min_sum_batch(np.stack(frames))
     return int((decoding == 0).all(axis=1).sum())
+
+
+def qary_fer_sweep(H, B, error_rate, runs, seed, chunk=4096, decoder_class=None):
+    """The loop of simulate/decode.py:246-277 with its trials drawn on the device (`mc_run`; the generator is Philox keyed by
+    (seed, global trial index), not the reference's MT19937 stream: `simulate_frame_error_rate_rust` keeps that one).
+    Global trial indices 0, 1, ... are scanned `chunk` at a time; frames without a bad symbol are skipped as the reference
+    skips them (decode.py:258-259), and the FIRST `runs` frames with one are counted.  Returns dict(successes,
+    max_errs_success, min_errs_fail (None: nothing failed) -- the three numbers of decode.py:265-286 -- and trials_drawn, the
+    index behind the last counted frame).  The result does not depend on `chunk`."""
+    Hd = H.to_dense(np.int8) if isinstance(H, TannerGraph) else np.asarray(H)
+    r, n = Hd.shape
+    v = int(np.count_nonzero(Hd, axis=0).max())
+    c = int(np.count_nonzero(Hd, axis=1).max())
+    B = 1  # decode.py:222 overrides the argument
+    BB = 2 * B + 1
+    if not 0.0 < error_rate <= 1.0:
+        raise ValueError("error_rate must be in (0, 1]: a frame without a bad symbol is never counted")
+    if runs < 0 or chunk < 1:
+        raise ValueError("runs must not be negative and chunk must be positive")
+    if decoder_class is None:
+        from .qary import decoder_class as _dc
+
+        decoder_class = _dc
+    decoder = decoder_class(f"DecoderN{n}R{r}V{v}C{c}B{B}")(Hd.astype(np.int8), 5)
+    p = 1 / BB
+    good = np.full(BB, p)
+    bad = np.full(BB, p)
+    good[[B, -1]] = [1.75 * p, 0.25 * p]
+    bad[[-1, B]] = [1.75 * p, 0.25 * p]
+    levels = np.stack([bad, good]).astype(np.float32)  # the last level is the good row: `errs` counts the bad symbols
+    weights = np.array([error_rate, 1.0 - error_rate])
+    res = dict(successes=0, max_errs_success=0, min_errs_fail=None, trials_drawn=0)
+    counted, first = 0, 0
+    try:
+        while counted < runs:
+            out = decoder.mc_run(chunk, seed, levels, weights, first_trial=first)
+            errs, ok = np.asarray(out["errs"]), np.asarray(out["success"]).astype(bool)
+            framed = np.flatnonzero(errs > 0)[: runs - counted]
+            if framed.size:
+                e, s = errs[framed], ok[framed]
+                res["successes"] += int(s.sum())
+                if s.any():
+                    res["max_errs_success"] = max(res["max_errs_success"], int(e[s].max()))
+                if (~s).any():
+                    low = int(e[~s].min())
+                    res["min_errs_fail"] = low if res["min_errs_fail"] is None else min(res["min_errs_fail"], low)
+                counted += framed.size
+                res["trials_drawn"] = first + int(framed[-1]) + 1
+            first += chunk
+    finally:
+        if hasattr(decoder, "close"):
+            decoder.close()
+    return res
 
 
 def hqc_decode(N, Hin, checks, y_sparse, bp_decoder=None, max_iter=100):

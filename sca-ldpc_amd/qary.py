@@ -9,6 +9,8 @@ with the same constructor / `min_sum` surface for ANY name of that pattern, plus
 `min_sum_batch` for many channel outputs per call, and `min_sum_soft` / `min_sum_soft_batch` for what the decoders
 compute beyond the symbols: the last variable update's per-symbol totals, the margin of every decision and the number
 of checks the decided word leaves unmet (include/scaldpc.h, scaldpc_qary_min_sum_batch_soft).
+`mc_run` / `mc_run_device` run whole Monte-Carlo trials of the reference's q-ary sweep on the device: the symbols' pmf rows
+are drawn there from a small table of levels, and one flag per trial comes back (include/scaldpc.h, scaldpc_mc_qary_run).
 
   DecoderN{N}R{R}V{DV}C{DC}B{B}(H: int8 [R, N], iterations)   .min_sum(pmf float32 [N, 2B+1]) -> list[int]
   DecoderN{N}R{R}SW{SW}(H: int8 [R, N], iterations)           .min_sum(pmf [N-R, 5], pmf_sum [R, 2*BSUM+1]) -> list[int]
@@ -73,6 +75,38 @@ class _QaryBase:
         return {"ms_check": ms[0], "ms_var": ms[1], "ms_loop": ms[2], "iterations": info[0],
                 "check_kernel": self.CHECK_KERNELS[info[1]] if info[1] >= 0 else None, "batch": info[2],
                 "max_check_degree": info[3]}
+
+    # -- Monte-Carlo trials drawn on the device (include/scaldpc.h, scaldpc_mc_qary_run) -------------------------------
+    @staticmethod
+    def _mc_table(levels, weights, Q, what):
+        """One level table as the C entry point takes it: float32 [K, Q] pmf rows, float64 [K] probabilities."""
+        lv = np.ascontiguousarray(levels, dtype=np.float32)
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if lv.ndim != 2 or lv.shape[1] != Q or w.shape != (lv.shape[0],):
+            raise ValueError(f"{what}: levels {lv.shape} / weights {w.shape}, expected (K, {Q}) pmf rows and (K,) probabilities")
+        return lv, w
+
+    def _mc_call(self, tables, first_trial, runs, seed, flags, stream, outs):
+        (lb, wb), (ls, ws) = tables
+        _lib.check(self._lib.scaldpc_mc_qary_run(
+            self._h, _lib.ptr(lb), _lib.ptr(wb), lb.shape[0], _lib.ptr(ls), _lib.ptr(ws), 0 if ls is None else ls.shape[0],
+            int(first_trial), int(runs), int(seed), flags, C.c_void_p(stream or None), *outs))
+
+    def _mc_host(self, tables, runs, seed, first_trial, want_levels, want_symbols):
+        runs = int(runs)
+        if runs <= 0:
+            raise ValueError("runs must be positive")
+        res = {"success": np.empty(runs, dtype=np.uint8), "errs": np.empty(runs, dtype=np.int32),
+               "wrong": np.empty(runs, dtype=np.int32)}
+        if want_levels:
+            res["levels"] = np.empty((runs, self.N), dtype=np.uint8)
+        if want_symbols:
+            res["symbols"] = np.empty((runs, self.N), dtype=np.int8)
+        self._mc_call(tables, first_trial, runs, seed, 0, 0, [_lib.ptr(res.get(k)) for k in ("success", "errs", "wrong", "levels", "symbols")])
+        return res
+
+    def _mc_device(self, tables, runs, seed, first_trial, stream, d_outs):
+        self._mc_call(tables, first_trial, runs, seed, _lib.F_DEVICE_IO, stream, [C.c_void_p(d or None) for d in d_outs])
 
     def close(self):
         if getattr(self, "_h", None):
@@ -144,6 +178,23 @@ class QaryDecoder(_QaryBase):
         _lib.check(self._lib.scaldpc_qary_min_sum_batch_soft(
             self._h, C.c_void_p(d_channel_output), int(batch), _lib.F_DEVICE_IO, C.c_void_p(stream or None), C.c_void_p(d_out),
             C.c_void_p(d_costs or None), C.c_void_p(d_margins or None), C.c_void_p(d_unmet or None)))
+
+    def mc_run(self, runs, seed, levels, weights, first_trial=0, want_levels=False, want_symbols=False):
+        """`runs` trials of the reference's q-ary sweep (decode.py:246-257), drawn on the device: every variable of an all-zero
+        word takes the pmf row levels[k] (float32 [K, Q]) with probability weights[k], Philox-keyed by (seed, first_trial + i)
+        -- a trial does not depend on how the sweep is cut into calls.  Returns dict(success uint8 [runs] (every decision 0),
+        errs int32 [runs] (variables NOT at the last level: with levels (bad, good) the reference's `errs`), wrong int32 [runs]
+        (decisions != 0)), with want_levels / want_symbols also levels uint8 [runs, N] / symbols int8 [runs, N]: the symbols
+        are `min_sum_batch(levels[res["levels"]])`, bit for bit."""
+        tables = (self._mc_table(levels, weights, self.Q, "levels"), (None, None))
+        return self._mc_host(tables, runs, seed, first_trial, want_levels, want_symbols)
+
+    def mc_run_device(self, runs, seed, levels, weights, d_success, d_errs=0, d_wrong=0, d_levels=0, d_symbols=0, first_trial=0,
+                      stream=0):
+        """Device-pointer variant (ints; 0 = not wanted): the outputs of `mc_run` into HBM; the tables stay host arrays.
+        Returns after the stream work is complete."""
+        tables = (self._mc_table(levels, weights, self.Q, "levels"), (None, None))
+        self._mc_device(tables, runs, seed, first_trial, stream, (d_success, d_errs, d_wrong, d_levels, d_symbols))
 
     def min_sum_soft(self, py_channel_output, costs=True, margins=True, unmet=True):
         """The single-codeword twin of `min_sum`: symbols as a list of ints, costs [N, Q], margins [N], unmet an int."""
@@ -224,6 +275,19 @@ class QarySpecialDecoder(_QaryBase):
             self._h, C.c_void_p(d_channel_output), C.c_void_p(d_channel_output_sum), int(batch), _lib.F_DEVICE_IO,
             C.c_void_p(stream or None), C.c_void_p(d_out), C.c_void_p(d_costs or None), C.c_void_p(d_costs_sum or None),
             C.c_void_p(d_margins or None), C.c_void_p(d_unmet or None)))
+
+    def mc_run(self, runs, seed, levels, weights, levels_sum, weights_sum, first_trial=0, want_levels=False, want_symbols=False):
+        """As QaryDecoder.mc_run, with a table of their own for the R row-sum variables: levels_sum float32 [K_s, 2BSUM+1],
+        weights_sum [K_s].  `levels` and `symbols` cover all N variables (the row-sum variables last); the symbols are
+        `min_sum_batch(levels[lv[:, :N-R]], levels_sum[lv[:, N-R:]])`, bit for bit."""
+        tables = (self._mc_table(levels, weights, self.Q, "levels"), self._mc_table(levels_sum, weights_sum, self.QS, "levels_sum"))
+        return self._mc_host(tables, runs, seed, first_trial, want_levels, want_symbols)
+
+    def mc_run_device(self, runs, seed, levels, weights, levels_sum, weights_sum, d_success, d_errs=0, d_wrong=0, d_levels=0,
+                      d_symbols=0, first_trial=0, stream=0):
+        """Device-pointer variant (ints; 0 = not wanted); the tables stay host arrays."""
+        tables = (self._mc_table(levels, weights, self.Q, "levels"), self._mc_table(levels_sum, weights_sum, self.QS, "levels_sum"))
+        self._mc_device(tables, runs, seed, first_trial, stream, (d_success, d_errs, d_wrong, d_levels, d_symbols))
 
     def min_sum_soft(self, py_channel_output, py_channel_output_sum, costs=True, margins=True, unmet=True):
         p, ps = np.asarray(py_channel_output), np.asarray(py_channel_output_sum)
