@@ -318,7 +318,13 @@ int scaldpc_qary_into_llr(const float *pmf, int64_t rows, int32_t Q, uint32_t fl
  *                than 8 edges, which no other kernel takes | 1 for every such decoder | 0 never (a call on a graph with a check
  *                of more than 8 edges then returns SCALDPC_EDEGREE before anything is queued)
  *   "llr_tiled", "var_small"  forms of the conversion / variable kernels
- *   "timing"     1: bracket the launches of a call with HIP events (scaldpc_qary_last_timing) */
+ *   "timing"     1: bracket the launches of a call with HIP events (scaldpc_qary_last_timing)
+ * LDS limits (no launch of a call asks for more than 64 KB of dynamic LDS; the plan is made before anything is queued):
+ *   enumeration, codeword per lane: maxdc * Q * 9 B per codeword (DecoderSpecial: 2 * ((maxdc - 1) * Q + QS) * 4 B); a block
+ *                takes 64 codewords, halved down to 8 while that exceeds 64 KB; what does not fit at 8 returns SCALDPC_EDEGREE
+ *   enumeration, wave per (check, codeword): used where its tables fit 64 KB (and the check has at most 8 edges), else the above
+ *   variable update, generic kernel (k_q_var): two rows of W = max(Q, QS) floats per codeword, 2 * W * 4 B; a block takes 64
+ *                codewords, halved while that exceeds 64 KB: 64 up to W = 128, 32 beyond (W = 255: 65 280 B) */
 int scaldpc_qary_configure(scaldpc_qary *h, const char *key, const char *value);
 /* Measurement aid for bench.py (the q-ary counterpart of scaldpc_bp_time_kernels): after
  * scaldpc_qary_configure(h, "timing", "1"), every check-node and variable-node launch of a call is bracketed by

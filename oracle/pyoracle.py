@@ -93,43 +93,70 @@ def qary_into_llr(pmf):
     return out
 
 
-def qary_min_sum_batch(g, Q, pmf, max_iter, threads=1):
-    """pmf float32 [batch, N, Q] (or [N, Q]) -> int8 [batch, N] hard decisions."""
+def _qary_min_sum(g, Q, pmf, max_iter, threads, soft):
     pmf = np.ascontiguousarray(pmf, dtype=np.float32)
-    single = pmf.ndim == 2
-    if single:
-        pmf = pmf[None]
+    assert pmf.ndim == 3 and pmf.shape[1:] == (g.n, Q)
     batch = pmf.shape[0]
-    assert pmf.shape[1:] == (g.n, Q)
     out = np.zeros((batch, g.n), dtype=np.int8)
-    rc = lib().oracle_qary_min_sum_batch(
+    cost = np.zeros((batch, g.n, Q), dtype=np.float32) if soft else None
+    rc = lib().oracle_qary_min_sum_batch_soft(
         C.c_int(g.m), C.c_int(g.n), C.c_int(Q), _p(g.row_ptr, C.c_int32), _p(g.col_idx, C.c_int32),
         _p(g.val, C.c_int8), _p(g.col_ptr, C.c_int32), _p(g.csc_edge, C.c_int32), _p(pmf, C.c_float),
-        C.c_int(batch), C.c_int(max_iter), _p(out, C.c_int8), C.c_int(threads),
+        C.c_int(batch), C.c_int(max_iter), _p(out, C.c_int8), _p(cost, C.c_float) if soft else None, C.c_int(threads),
     )  # fmt: skip
     if rc:
         raise RuntimeError(QERR.get(rc, str(rc)))
+    return out, cost
+
+
+def qary_min_sum_batch(g, Q, pmf, max_iter, threads=1):
+    """pmf float32 [batch, N, Q] (or [N, Q]) -> int8 [batch, N] hard decisions."""
+    pmf = np.asarray(pmf)
+    single = pmf.ndim == 2
+    out, _ = _qary_min_sum(g, Q, pmf[None] if single else pmf, max_iter, threads, False)
     return out[0] if single else out
 
 
-def qary_special_batch(g, B, BSUM, pmf_b, pmf_s, max_iter, threads=1):
+def qary_min_sum_soft_batch(g, Q, pmf, max_iter, threads=1):
+    """pmf float32 [batch, N, Q] -> (int8 [batch, N] hard decisions, float32 [batch, N, Q] totals of the last variable pass:
+    what the deciding arg-min is taken of, in the layout of `min_sum_soft_batch`'s costs)."""
+    return _qary_min_sum(g, Q, pmf, max_iter, threads, True)
+
+
+def _qary_special(g, B, BSUM, pmf_b, pmf_s, max_iter, threads, soft):
     pmf_b = np.ascontiguousarray(pmf_b, dtype=np.float32)
     pmf_s = np.ascontiguousarray(pmf_s, dtype=np.float32)
-    single = pmf_b.ndim == 2
-    if single:
-        pmf_b, pmf_s = pmf_b[None], pmf_s[None]
     batch = pmf_b.shape[0]
-    assert pmf_b.shape[1:] == (g.n - g.m, 2 * B + 1) and pmf_s.shape[1:] == (g.m, 2 * BSUM + 1)
+    BV, QB, QS = g.n - g.m, 2 * B + 1, 2 * BSUM + 1
+    assert pmf_b.shape[1:] == (BV, QB) and pmf_s.shape == (batch, g.m, QS)
     out = np.zeros((batch, g.n), dtype=np.int8)
-    rc = lib().oracle_qary_special_batch(
+    cost = np.zeros((batch, BV * QB + g.m * QS), dtype=np.float32) if soft else None
+    rc = lib().oracle_qary_special_batch_soft(
         C.c_int(g.m), C.c_int(g.n), C.c_int(B), C.c_int(BSUM), _p(g.row_ptr, C.c_int32),
         _p(g.col_idx, C.c_int32), _p(g.val, C.c_int8), _p(g.col_ptr, C.c_int32), _p(g.csc_edge, C.c_int32),
         _p(pmf_b, C.c_float), _p(pmf_s, C.c_float), C.c_int(batch), C.c_int(max_iter), _p(out, C.c_int8),
-        C.c_int(threads),
+        _p(cost, C.c_float) if soft else None, C.c_int(threads),
     )  # fmt: skip
     if rc:
         raise RuntimeError(QERR.get(rc, str(rc)))
+    if not soft:
+        return out, None, None
+    return out, cost[:, : BV * QB].reshape(batch, BV, QB), cost[:, BV * QB:].reshape(batch, g.m, QS)
+
+
+def qary_special_batch(g, B, BSUM, pmf_b, pmf_s, max_iter, threads=1):
+    pmf_b, pmf_s = np.asarray(pmf_b), np.asarray(pmf_s)
+    single = pmf_b.ndim == 2
+    if single:
+        pmf_b, pmf_s = pmf_b[None], pmf_s[None]
+    out, _, _ = _qary_special(g, B, BSUM, pmf_b, pmf_s, max_iter, threads, False)
     return out[0] if single else out
+
+
+def qary_special_soft_batch(g, B, BSUM, pmf_b, pmf_s, max_iter, threads=1):
+    """-> (int8 [batch, N] hard decisions, float32 [batch, N-R, 2B+1] and [batch, R, 2BSUM+1] totals of the last variable
+    pass: `min_sum_soft_batch`'s costs and costs_sum)."""
+    return _qary_special(g, B, BSUM, pmf_b, pmf_s, max_iter, threads, True)
 
 
 def philox4x32_10(ctr, key):

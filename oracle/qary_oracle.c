@@ -100,10 +100,11 @@ static int var_update(int Q, const float *channel, int deg, const int32_t *edges
     return arg_min(sum, Q);
 }
 
-/* Decoder::min_sum, decoder.rs:560-666.  llr: [N][Q]; out: int8 [N]. */
-int oracle_qary_min_sum(int R, int N, int Q, const int32_t *row_ptr, const int32_t *col_idx,
-                        const int8_t *val, const int32_t *col_ptr, const int32_t *csc_edge,
-                        const float *llr, int max_iter, int8_t *out)
+/* Decoder::min_sum, decoder.rs:560-666.  llr: [N][Q]; out: int8 [N].
+ * cost (may be NULL): the last variable pass's totals `sum`, [N][Q] -- what the arg-min that decides is taken of. */
+static int qary_min_sum_impl(int R, int N, int Q, const int32_t *row_ptr, const int32_t *col_idx,
+                             const int8_t *val, const int32_t *col_ptr, const int32_t *csc_edge,
+                             const float *llr, int max_iter, int8_t *out, float *cost)
 {
     if (Q < 1 || (Q & 1) == 0) return QERR_SHAPE;
     const int B = (Q - 1) / 2;
@@ -174,11 +175,21 @@ int oracle_qary_min_sum(int R, int N, int Q, const int32_t *row_ptr, const int32
         for (int v = 0; v < N; v++) {
             int am = var_update(Q, llr + (size_t)v * Q, col_ptr[v + 1] - col_ptr[v], csc_edge + col_ptr[v], val,
                                 c2v, v2c, sum, sum + Q);
-            if (it >= max_iter) out[v] = (int8_t)(am - B);
+            if (it >= max_iter) {
+                out[v] = (int8_t)(am - B);
+                if (cost) memcpy(cost + (size_t)v * Q, sum, sizeof(float) * (size_t)Q); /* var_update leaves the totals there */
+            }
         }
     }
     free(v2c); free(c2v); free(fin); free(num); free(idx); free(dv); free(sum);
     return rc;
+}
+
+int oracle_qary_min_sum(int R, int N, int Q, const int32_t *row_ptr, const int32_t *col_idx,
+                        const int8_t *val, const int32_t *col_ptr, const int32_t *csc_edge,
+                        const float *llr, int max_iter, int8_t *out)
+{
+    return qary_min_sum_impl(R, N, Q, row_ptr, col_idx, val, col_ptr, csc_edge, llr, max_iter, out, NULL);
 }
 
 /*
@@ -186,10 +197,11 @@ int oracle_qary_min_sum(int R, int N, int Q, const int32_t *row_ptr, const int32
  * N-R columns are B-variables (alphabet 2B+1), the last R columns are the
  * row-sum variables (alphabet 2*BSUM+1, one per check, its LAST entry).
  * llr_b: [N-R][2B+1]; llr_s: [R][2BSUM+1]; out: int8 [N].
+ * cost (may be NULL): the last variable pass's totals, the N-R rows of 2B+1 entries, then the R rows of 2BSUM+1.
  */
-int oracle_qary_special(int R, int N, int B, int BSUM, const int32_t *row_ptr, const int32_t *col_idx,
-                        const int8_t *val, const int32_t *col_ptr, const int32_t *csc_edge,
-                        const float *llr_b, const float *llr_s, int max_iter, int8_t *out)
+static int qary_special_impl(int R, int N, int B, int BSUM, const int32_t *row_ptr, const int32_t *col_idx,
+                             const int8_t *val, const int32_t *col_ptr, const int32_t *csc_edge,
+                             const float *llr_b, const float *llr_s, int max_iter, int8_t *out, float *cost)
 {
     const int BV = N - R, QB = 2 * B + 1, QS = 2 * BSUM + 1;
     if (B < 1 || BSUM % B != 0) return QERR_SHAPE; /* decoder_special.rs:388-392 */
@@ -282,7 +294,11 @@ int oracle_qary_special(int R, int N, int B, int BSUM, const int32_t *row_ptr, c
                 float mn = tmp[am];
                 for (int q = 0; q < Q; q++) o[q] = tmp[q] - mn;
             }
-            if (it >= max_iter) out[v] = (int8_t)(arg_min(sum, Q) - (v < BV ? B : BSUM));
+            if (it >= max_iter) {
+                out[v] = (int8_t)(arg_min(sum, Q) - (v < BV ? B : BSUM));
+                if (cost)
+                    memcpy(cost + (v < BV ? (size_t)v * QB : (size_t)BV * QB + (size_t)(v - BV) * QS), sum, sizeof(float) * (size_t)Q);
+            }
         }
     }
 done:
@@ -290,11 +306,21 @@ done:
     return rc;
 }
 
-/* batch front ends: pmf in, hard decisions out; threads over the batch */
-int oracle_qary_min_sum_batch(int R, int N, int Q, const int32_t *row_ptr, const int32_t *col_idx,
-                              const int8_t *val, const int32_t *col_ptr, const int32_t *csc_edge,
-                              const float *pmf /* [batch][N][Q] */, int batch, int max_iter,
-                              int8_t *out /* [batch][N] */, int threads)
+int oracle_qary_special(int R, int N, int B, int BSUM, const int32_t *row_ptr, const int32_t *col_idx,
+                        const int8_t *val, const int32_t *col_ptr, const int32_t *csc_edge,
+                        const float *llr_b, const float *llr_s, int max_iter, int8_t *out)
+{
+    return qary_special_impl(R, N, B, BSUM, row_ptr, col_idx, val, col_ptr, csc_edge, llr_b, llr_s, max_iter, out, NULL);
+}
+
+/* batch front ends: pmf in, hard decisions out; threads over the batch.
+ * The _soft forms also return the last variable pass's totals (cost, may be NULL): per codeword the rows of all variables
+ * one after the other, variable v's symbol q at var_off[v] + q -- the layout of scaldpc_qary_min_sum_batch_soft's out_cost
+ * (DecoderSpecial: out_cost_b's rows, then out_cost_sum's, in ONE array of [batch][(N-R)(2B+1) + R(2BSUM+1)]). */
+int oracle_qary_min_sum_batch_soft(int R, int N, int Q, const int32_t *row_ptr, const int32_t *col_idx,
+                                   const int8_t *val, const int32_t *col_ptr, const int32_t *csc_edge,
+                                   const float *pmf /* [batch][N][Q] */, int batch, int max_iter,
+                                   int8_t *out /* [batch][N] */, float *cost /* [batch][N][Q] or NULL */, int threads)
 {
     int rc = 0;
     if (threads <= 0) threads = 1;
@@ -305,8 +331,8 @@ int oracle_qary_min_sum_batch(int R, int N, int Q, const int32_t *row_ptr, const
         for (int b = 0; b < batch; b++) {
             int r = oracle_qary_into_llr(N, Q, pmf + (size_t)b * N * Q, llr);
             if (!r)
-                r = oracle_qary_min_sum(R, N, Q, row_ptr, col_idx, val, col_ptr, csc_edge, llr, max_iter,
-                                        out + (size_t)b * N);
+                r = qary_min_sum_impl(R, N, Q, row_ptr, col_idx, val, col_ptr, csc_edge, llr, max_iter,
+                                      out + (size_t)b * N, cost ? cost + (size_t)b * N * Q : NULL);
             if (r) rc = r;
         }
         free(llr);
@@ -314,14 +340,22 @@ int oracle_qary_min_sum_batch(int R, int N, int Q, const int32_t *row_ptr, const
     return rc;
 }
 
-int oracle_qary_special_batch(int R, int N, int B, int BSUM, const int32_t *row_ptr, const int32_t *col_idx,
+int oracle_qary_min_sum_batch(int R, int N, int Q, const int32_t *row_ptr, const int32_t *col_idx,
                               const int8_t *val, const int32_t *col_ptr, const int32_t *csc_edge,
-                              const float *pmf_b /* [batch][N-R][2B+1] */,
-                              const float *pmf_s /* [batch][R][2BSUM+1] */, int batch, int max_iter,
-                              int8_t *out, int threads)
+                              const float *pmf, int batch, int max_iter, int8_t *out, int threads)
+{
+    return oracle_qary_min_sum_batch_soft(R, N, Q, row_ptr, col_idx, val, col_ptr, csc_edge, pmf, batch, max_iter, out, NULL, threads);
+}
+
+int oracle_qary_special_batch_soft(int R, int N, int B, int BSUM, const int32_t *row_ptr, const int32_t *col_idx,
+                                   const int8_t *val, const int32_t *col_ptr, const int32_t *csc_edge,
+                                   const float *pmf_b /* [batch][N-R][2B+1] */,
+                                   const float *pmf_s /* [batch][R][2BSUM+1] */, int batch, int max_iter,
+                                   int8_t *out, float *cost /* [batch][(N-R)(2B+1) + R(2BSUM+1)] or NULL */, int threads)
 {
     int rc = 0;
     const int BV = N - R, QB = 2 * B + 1, QS = 2 * BSUM + 1;
+    const size_t rows = (size_t)BV * QB + (size_t)R * QS;
     if (threads <= 0) threads = 1;
 #pragma omp parallel num_threads(threads)
     {
@@ -332,12 +366,20 @@ int oracle_qary_special_batch(int R, int N, int B, int BSUM, const int32_t *row_
             int r = oracle_qary_into_llr(BV, QB, pmf_b + (size_t)b * BV * QB, lb);
             if (!r) r = oracle_qary_into_llr(R, QS, pmf_s + (size_t)b * R * QS, ls);
             if (!r)
-                r = oracle_qary_special(R, N, B, BSUM, row_ptr, col_idx, val, col_ptr, csc_edge, lb, ls,
-                                        max_iter, out + (size_t)b * N);
+                r = qary_special_impl(R, N, B, BSUM, row_ptr, col_idx, val, col_ptr, csc_edge, lb, ls,
+                                      max_iter, out + (size_t)b * N, cost ? cost + (size_t)b * rows : NULL);
             if (r) rc = r;
         }
         free(lb);
         free(ls);
     }
     return rc;
+}
+
+int oracle_qary_special_batch(int R, int N, int B, int BSUM, const int32_t *row_ptr, const int32_t *col_idx,
+                              const int8_t *val, const int32_t *col_ptr, const int32_t *csc_edge,
+                              const float *pmf_b, const float *pmf_s, int batch, int max_iter, int8_t *out, int threads)
+{
+    return oracle_qary_special_batch_soft(R, N, B, BSUM, row_ptr, col_idx, val, col_ptr, csc_edge, pmf_b, pmf_s, batch, max_iter, out,
+                                          NULL, threads);
 }

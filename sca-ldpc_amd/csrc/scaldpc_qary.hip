@@ -1018,9 +1018,9 @@ void launch_var(scaldpc_qary *h, const QaryCall &c, int last, float *dc = nullpt
                                h->d_csc_edge, h->d_edge_h, h->d_llr, h->d_msg, c.BV, h->W, c.Bp, c.batch, last, h->d_hard, dc, dm);
             break;
         case QVar::GENERIC:
-            hipLaunchKernelGGL(k_q_var<SOFT>, dim3(h->N, c.Bp / 64), dim3(64), c.plan.var_lds, c.s, 0, h->d_col_ptr, h->d_csc_edge,
-                               h->d_edge_h, h->d_var_q, h->d_var_off, h->d_llr, h->d_msg, h->W, c.Bp, c.batch, h->W, last, h->d_hard, dc,
-                               dm);
+            hipLaunchKernelGGL(k_q_var<SOFT>, dim3(h->N, c.Bp / c.plan.var_T), dim3(c.plan.var_T), c.plan.var_lds, c.s, 0, h->d_col_ptr,
+                               h->d_csc_edge, h->d_edge_h, h->d_var_q, h->d_var_off, h->d_llr, h->d_msg, h->W, c.Bp, c.batch, h->W, last,
+                               h->d_hard, dc, dm);
             break;
     }
 }

@@ -82,6 +82,7 @@ struct QaryPlan {
     int wave_fallback_nb = -1;    // SPECIAL_TREE / SPECIAL_DP: skip_nb of the k_q_special_check_wave launch that follows for the rows of
                                   // another degree; -1: no such launch (every row has that many coefficient edges, or another form)
     int T = 64;                   // threads (= codewords) per block of the LDS-staged lane kernels
+    int var_T = 64;               // threads (= codewords) per block of k_q_var: as many (<= 64) as keep its two W-row tables within 64 KB
     size_t check_lds = 0, wave_lds = 0, tree_lds = 0, var_lds = 0;  // dynamic LDS of LANE / SPECIAL_LANE, the wave kernels, the tree walk, k_q_var
     size_t dp_any_lds = 0;        // SPECIAL_DP_ANY: three tables of (Q - 1)(maxdc - 1) + 1 entries, 64 lanes each
 };
@@ -112,7 +113,9 @@ inline int qary_plan(const QaryShape &g, const QaryKnobs &kn, int batch, QaryPla
     const bool q_small = g.Q == 3 || g.Q == 5 || g.Q == 7 || g.Q == 15;  // (15: B = 7, the reference's criterion and unit-test decoders)
     if (!g.special && kn.var_small && g.maxdv <= 4 && q_small) p.var = QVar::SMALL;
     if (g.special && kn.var_small && g.maxdv <= 4 && g.Q == 5 && g.QS == 25) p.var = QVar::SMALL_SPECIAL;  // the Kyber SW6 classes (lib.rs:54-75)
-    p.var_lds = (size_t)2 * g.W * 64 * 4;
+    // k_q_var stages two rows of W floats per codeword: 64 codewords per block up to W = 128, 32 beyond (W <= 255: 65 280 B)
+    while (p.var_T > 8 && (size_t)2 * g.W * p.var_T * 4 > LDS) p.var_T >>= 1;
+    p.var_lds = (size_t)2 * g.W * p.var_T * 4;
     // check update.  Small batch: wave per (check, codeword), lanes share the assignment space
     // measured: wave mode 0.69 vs 3.2 ms at batch 64 (config-4 decoder), 24 vs 70 ms (Kyber SW6);
     // a tie at batch 1024, where one codeword per lane keeps global accesses coalesced

@@ -9,12 +9,14 @@ import warnings
 
 import pytest
 
+import qary_shape_cases as shapes
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CXX = os.environ.get("CXX", "g++")  # the C++ driver of oracle/Makefile's gcc
 
 # scaldpc_qary_last_timing's info[1] (include/scaldpc.h) = qary.CHECK_KERNELS
 CHECK = ("k_q_check_unrolled<3,7>", "k_q_check_unrolled<5,5>", "k_q_special_check_tree<5,6>", "k_q_special_check_wave", "k_q_check_wave",
-         "k_q_special_check", "k_q_check", "k_q_special_check_dp<5,6>", "k_q_check_dp<3,7>")
+         "k_q_special_check", "k_q_check", "k_q_special_check_dp<5,6>", "k_q_check_dp<3,7>", "k_q_special_check_dp_any")
 VAR = ("generic", "small", "small_special")
 LLR = ("fused_both", "fused_each", "unfused")
 
@@ -40,16 +42,32 @@ def plan(tmp_path_factory):
         warnings.warn("the host toolchain lacks the sanitizer runtimes: qary_plan_main is built without them")
         subprocess.check_call(cmd)
 
-    def run(shape, batch, **knobs):
-        args = [str(shape[k]) for k in ("special", "R", "N", "E", "Q", "QS", "W", "maxdc", "mindc", "maxdv")] + [str(batch)]
-        out = subprocess.run([exe] + args + [f"{k}={v}" for k, v in knobs.items()], capture_output=True, text=True, timeout=60)
-        assert out.returncode == 0 and not out.stderr, out.stderr  # (a sanitizer report lands here)
-        p = {k: int(v) for k, v in (kv.split("=") for kv in out.stdout.split())}
+    def words(shape, batch, knobs):
+        return [str(shape[k]) for k in ("special", "R", "N", "E", "Q", "QS", "W", "maxdc", "mindc", "maxdv")] + [str(batch)] + [
+            f"{k}={v}" for k, v in knobs.items()]
+
+    def parse(line):
+        p = {k: int(v) for k, v in (kv.split("=") for kv in line.split())}
         if not p["refused"]:
             p["check_name"] = CHECK[p["check"]] if p["check"] >= 0 else None
             p["var_name"], p["llr_name"] = VAR[p["var"]], LLR[p["llr"]]
         return p
 
+    def run(shape, batch, **knobs):
+        out = subprocess.run([exe] + words(shape, batch, knobs), capture_output=True, text=True, timeout=60)
+        assert out.returncode == 0 and not out.stderr, out.stderr  # (a sanitizer report lands here)
+        return parse(out.stdout)
+
+    def many(calls):
+        """The plans of a list of (shape, batch, knobs) out of ONE process (the program's `-` form)."""
+        text = "".join(" ".join(words(*c)) + "\n" for c in calls)
+        out = subprocess.run([exe, "-"], input=text, capture_output=True, text=True, timeout=300)
+        assert out.returncode == 0 and not out.stderr, out.stderr
+        lines = out.stdout.splitlines()
+        assert len(lines) == len(calls)
+        return [parse(ln) for ln in lines]
+
+    run.many = many
     return run
 
 
@@ -89,7 +107,8 @@ def test_generic_variable_and_conversion_knobs(plan):
     assert plan(generic(), 20, var_small=0)["var_name"] == "generic"
     p = plan(generic(), 20, llr_tiled=0)
     assert (p["llr_name"], p["llr_tiled_b"], p["init"]) == ("unfused", 0, 1)  # plain conversion, then k_q_init
-    assert plan(generic(), 20, var_small=0)["var_lds"] == 2 * 3 * 64 * 4
+    p = plan(generic(), 20, var_small=0)
+    assert p["var_T"] == 64 and p["var_lds"] == 2 * 3 * 64 * 4
 
 
 # ------------------------------------------------------------------------------------------------ generic decoder, other shapes
@@ -123,6 +142,91 @@ def test_the_plan_refuses_what_does_not_fit(plan):
 def test_columns_of_five_checks_take_the_generic_variable_form(plan):
     assert plan(generic(maxdv=5), 20)["var_name"] == "generic"
     assert plan(generic(maxdv=4), 20)["var_name"] == "small"
+
+
+# ------------------------------------------------------------------------------------------- every launch within 64 KB of LDS
+@pytest.mark.parametrize("W, var_T", [(3, 64), (127, 64), (129, 32), (255, 32)])
+def test_the_variable_kernel_block_size_fits_64_kb(plan, W, var_T):
+    """k_q_var stages two rows of W floats per codeword: 64 codewords per block while that fits 64 KB (W <= 128), halved
+    beyond.  Written from the rule (include/scaldpc.h): 2 * 4 * 128 * 64 = 65 536."""
+    want_lds = {3: 1536, 127: 65024, 129: 33024, 255: 65280}[W]
+    assert want_lds == 2 * W * var_T * 4 <= 64 * 1024 and (var_T == 64 or 2 * W * (2 * var_T) * 4 > 64 * 1024)
+    p = plan(generic(Q=W, maxdc=2, mindc=2), 20, var_small=0)
+    assert (p["var_name"], p["var_T"], p["var_lds"]) == ("generic", var_T, want_lds)
+    p = plan(dict(SPECIAL, Q=3, QS=W, W=W, maxdc=2, mindc=2), 20)  # DecoderSpecial: the row-sum alphabet sets the width
+    assert (p["var_name"], p["var_T"], p["var_lds"]) == ("generic", var_T, want_lds)
+
+
+def launched_lds(p):
+    """name -> dynamic LDS bytes of every kernel an accepted plan launches (csrc/scaldpc_qary.hip: launch_check, launch_var)."""
+    by_form = {"k_q_check_unrolled<3,7>": 0, "k_q_check_unrolled<5,5>": 0, "k_q_check_dp<3,7>": 0, "k_q_special_check_dp<5,6>": 0,
+               "k_q_special_check_tree<5,6>": p["tree_lds"], "k_q_special_check_wave": p["wave_lds"], "k_q_check_wave": p["wave_lds"],
+               "k_q_special_check": p["check_lds"], "k_q_check": p["check_lds"], "k_q_special_check_dp_any": p["dp_any_lds"]}
+    out = {}
+    if p["check_name"] is not None:
+        out[p["check_name"]] = by_form[p["check_name"]]
+    if p["wave_fallback_nb"] >= 0:
+        out["k_q_special_check_wave (fallback)"] = p["wave_lds"]
+    if p["var_name"] == "generic":
+        out["k_q_var"] = p["var_lds"]
+    return out
+
+
+def test_no_accepted_plan_asks_for_more_than_64_kb(plan):
+    """Odd Q from 3 to 255, rows of 1 .. 16 edges (with and without a shorter row), both decoder kinds (DecoderSpecial with
+    QS = Q, 2 Q + 1, 253, 255), columns of 1 and 5 checks, batches 1 and 300, default knobs and the lane form on demand: whatever
+    the plan accepts, no launch of it -- the check form, the wave kernel behind the tree walk or the recursion, k_q_var --
+    asks for more than 65 536 B of dynamic LDS.  Every form must have been seen, and refusals too."""
+    calls = []
+    for Q in range(3, 256, 2):
+        kinds = [(0, Q)] + [(1, QS) for QS in sorted({Q, 2 * Q + 1, 253, 255})]
+        for special_, QS in kinds:
+            for maxdc in range(1, 17):
+                for mindc in sorted({maxdc, max(1, maxdc - 1)} if special_ and Q == 5 else {maxdc}):  # (a shorter row: the fallback launch)
+                    g = dict(special=special_, R=12, N=40, E=12 * maxdc, Q=Q, QS=QS, W=max(Q, QS), maxdc=maxdc, mindc=mindc, maxdv=1)
+                    for maxdv in (1, 5):
+                        for batch in (1, 300):
+                            for knobs in (dict(), dict(wave=0, unroll=0, tree=0, dp=0)):
+                                calls.append((dict(g, maxdv=maxdv), batch, knobs))
+    plans = plan.many(calls)
+    seen, refused, worst = set(), 0, {}
+    for (g, batch, knobs), p in zip(calls, plans):
+        if p["refused"]:
+            refused += 1
+            continue
+        assert p["T"] in (8, 16, 32, 64) and p["var_T"] in (8, 16, 32, 64)
+        for name, lds in launched_lds(p).items():
+            assert lds <= 64 * 1024, (name, lds, g, batch, knobs)
+            seen.add(name)
+            worst[name] = max(worst.get(name, 0), lds)
+    print(f"{len(calls)} shapes, {refused} refused; largest dynamic LDS per launch: {worst}")
+    assert refused > 1000 and seen == set(CHECK) - {"k_q_check_unrolled<3,7>"} | {"k_q_special_check_wave (fallback)", "k_q_var"}
+
+
+@pytest.mark.parametrize("name", list(shapes.PLAIN) + list(shapes.SPECIAL))
+def test_the_shape_cases_take_the_branches_they_are_named_for(plan, name):
+    """tests/test_qary_shapes_gpu.py's cases (tests/qary_shape_cases.py), on the shapes qary_build works out of their graphs: at
+    every batch they run, each form is the named check kernel, with the block sizes, the conversion and the variable form of the
+    case's table row; the lane form's block size is the one the batches are ragged against."""
+    c = shapes.PLAIN.get(name) or shapes.SPECIAL[name]
+    g = shapes.shape_of(name)
+    per_codeword = 2 * ((g["maxdc"] - 1) * g["Q"] + g["QS"]) * 4 if g["special"] else g["maxdc"] * g["Q"] * 9
+    assert shapes.block_size(per_codeword) == c["T"]
+    for knobs, kernel in c["forms"]:
+        for batch in shapes.batches(c["T"]):
+            p = plan(g, batch, **knobs)
+            assert (p["check_name"], p["T"], p["llr_name"], p["var_name"]) == (kernel, c["T"], c["llr"], c.get("var", "generic")), (knobs, batch)
+            assert p["var_T"] == (64 if g["W"] <= 128 else 32) and p["init"] == (c["llr"] == "unfused")
+            assert p["check_words128"] == (kernel == "k_q_check" and g["maxdc"] > 8)
+    if name in shapes.FAMILY:
+        assert (plan(g, shapes.BATCH)["check_name"], plan(g, shapes.BIG)["check_name"]) == shapes.FAMILY[name]
+    # what the case is there for
+    want = {"q31": dict(llr_tiled_b=0), "q33": dict(llr_tiled_b=0, init=1), "SW3B7": dict(llr_tiled_b=1, llr_tiled_s=0, init=1),
+            "q63": dict(wave_lds=65792), "q63_wave": dict(wave_lds=49348), "q83": dict(wave_lds=65008), "q255": dict(var_lds=65280),
+            "SW2B63": dict(check_lds=64896, var_lds=2 * 253 * 32 * 4), "q15_dc8": dict(check_lds=8 * 15 * 9 * 32)}.get(name, {})
+    p = plan(g, shapes.BATCH, **c["forms"][-1][0])
+    assert {k: p[k] for k in want} == want
+    assert g["maxdv"] == {"q15_dc8_dv5": 5, "dv9_q3": 9, "dv9_q15": 9}.get(name, g["maxdv"]) and (c.get("var") != "small" or g["maxdv"] <= 4)
 
 
 # ------------------------------------------------------------------------------------------------- special decoder, Kyber SW6

@@ -147,6 +147,57 @@ def test_graphs_with_cycles_decide_as_the_oracle_does(oracle):
     assert unmet_seen == {False, True}
 
 
+def test_the_oracles_last_totals_are_the_restatements_bit_for_bit(oracle):
+    """oracle/qary_oracle.c hands out the totals of its last variable pass (qary_min_sum_soft_batch / qary_special_soft_batch:
+    the fast answer key of tests/test_qary_shapes_gpu.py).  On every case of this module -- the small and the large trees of both
+    decoders, the graphs with cycles at 1, 2 and 5 iterations -- they are the slow restatement's as uint32 bit patterns (any
+    NaN equal to any NaN), and so are its symbols; a good part of the totals is +inf (symbols of probability 0)."""
+    seen = {"finite": 0, "inf": 0, "nan": 0}
+
+    def tally(*tables):
+        for t in tables:
+            seen["finite"] += int(np.isfinite(t).sum())
+            seen["inf"] += int(np.isposinf(t).sum())
+            seen["nan"] += int(np.isnan(t).sum())
+
+    def plain(H, B, pmf, it):
+        with np.errstate(divide="ignore"):
+            r = ref.min_sum_soft(oracle, H, B, pmf, it)
+            sym, cost = oracle.qary_min_sum_soft_batch(S.TannerGraph.from_dense(H), 2 * B + 1, pmf, it, threads=2)
+        assert np.array_equal(sym, r["symbols"]) and cost.dtype == np.float32 and cost.shape == r["costs"].shape
+        assert ref.same_bits(cost, r["costs"]), (B, it)
+        tally(cost)
+
+    def special(H, B, BSUM, pb, ps, it):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            r = ref.special_min_sum_soft(oracle, H, B, BSUM, pb, ps, it)
+            sym, cb, cs = oracle.qary_special_soft_batch(S.TannerGraph.from_dense(H), B, BSUM, pb, ps, it, threads=2)
+        assert np.array_equal(sym, r["symbols"]) and cb.shape == r["costs"].shape and cs.shape == r["costs_sum"].shape
+        assert ref.same_bits(cb, r["costs"]) and ref.same_bits(cs, r["costs_sum"]), it
+        tally(cb, cs)
+
+    for B in (1, 2):
+        for seed in range(10):
+            H, pmf, _ = qary_tree_case(seed, B, batch=4)
+            plain(H, B, pmf, crossing_iterations(H))
+    for seed in range(12):
+        H, pb, ps, _ = special_tree_case(seed, batch=2)
+        special(H, 2, 12, pb, ps, crossing_iterations(H))
+    H, pmf, _, _ = large_qary_tree_case(250, 1, 2, seed=41)
+    plain(H, 1, pmf, 80)
+    H, pb, ps, _, _ = large_special_tree_case(16, 2, seed=70)
+    special(H, 2, 12, pb, ps, H.shape[0] + 1)
+    for H, B, pmf in (ref.q15_instance(4), ref.cyclic_instance(1, 6, seed=3), ref.cyclic_instance(2, 3, seed=5), ref.cyclic_instance(3, 2, seed=7)):
+        for it in (1, 2, 5):
+            plain(H, B, pmf, it)
+    print(f"totals compared: {seen}")
+    assert seen["finite"] > 3000 and seen["inf"] > 20, seen
+    # a variable no check holds: its totals are its channel LLRs (nothing is added), through the same copy
+    H, B, pmf = ref.cyclic_instance(2, 3, seed=11, R=4, N=9)
+    H[:, 4] = 0
+    plain(H, B, pmf, 2)
+
+
 def test_margin_rule_on_hand_made_rows():
     inf, nan = np.float32(np.inf), np.float32(np.nan)
     f = lambda *x: ref.margin_of(np.array(x, dtype=np.float32))  # noqa: E731
