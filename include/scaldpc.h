@@ -25,6 +25,11 @@
  *                                simulate/decode.py:36-40,165-175 (noise, syndrome, decode, compare)
  *   scaldpc_mc_hqc_run           hqc.decode() input assembly + success test for synthetic trials,
  *                                simulate/hqc.py:684-705,742-749
+ *   scaldpc_mc_hqc_run_soft      the same trials with the answers of the oracles the attack really asks: per check an outcome of
+ *                                wrapped_hqc_decoding_oracle / inner_hqc_decoding_oracle, simulate/hqc.py:782-871, drawn
+ *                                conditional on the check's true value -- the reported bit, its certainty (the check's own
+ *                                prior, hqc.py:689) and the oracle calls it spent -- on the device
+ *                                (entry point added under SCALDPC_VERSION 103: nothing that existed changed)
  *   scaldpc_qary_create          simulate_rs Decoder::new via PyO3 `#[new]`,
  *                                simulate_rs/src/pydecoder.rs:24-45 -> simulate_rs/src/decoder.rs:494-553
  *   scaldpc_qary_min_sum_batch   PyO3 `min_sum`, simulate_rs/src/pydecoder.rs:53-65
@@ -284,6 +289,50 @@ int scaldpc_mc_fer_run(scaldpc_bp *h, int64_t first_trial, int32_t batch, uint64
 int scaldpc_mc_hqc_run(scaldpc_bp *h, int32_t omega, double eps, int64_t first_trial, int32_t batch, uint64_t seed,
                        int32_t max_iter, int32_t method, float alpha, uint32_t flags, void *stream,
                        uint8_t *out_success, int32_t *out_iters, uint8_t *out_msg, int32_t *out_y);
+
+/*
+ * scaldpc_mc_hqc_run_soft = scaldpc_mc_hqc_run's trials under the law of the oracles of simulate/hqc.py:782-871: a check does
+ * not arrive with one shared error rate but with a certainty of its own, and the distribution of (answer wrong?, certainty,
+ * oracle calls spent) depends on the check's TRUE value.  The law is a table of K outcomes (HOST pointers whatever the flags):
+ *   weights double [2][K]  row b = the probabilities of the K outcomes when the true check bit is b
+ *   flips   uint8  [K]     1 = the reported bit is the complement of the true one
+ *   probs   float  [K]     the prior error probability the decoder is given with the outcome (1 - certainty, hqc.py:689)
+ *   costs   int32  [K]     the oracle calls the outcome spent; NULL = not counted
+ *
+ * Trial law (next to K6's above; a trial depends on (seed, first_trial + i) alone, not on batch, split or GPU count):
+ *   secret      y exactly as scaldpc_mc_hqc_run draws it (stream 1); the true bits are c = Hin y
+ *   generator   check r takes stream-0 word r of the trial: Philox counter (r >> 2, 0, trial_lo, trial_hi), word r & 3 -- the
+ *               word scaldpc_mc_hqc_run uses for the flip of check r
+ *   thresholds  T^b_k = thr(w[b][0] + ... + w[b][k]), the sum accumulated left to right in float64, thr(p) = floor(p 2^32), 0 for
+ *               p <= 0, 2^32 for p >= 1; T^b_k is forced to 2^32 from row b's last outcome of nonzero weight on, so that an
+ *               outcome of weight 0 is never drawn (the rule of scaldpc_mc_qary_run)
+ *   outcome     the smallest k with word < T^b_k, b = c_r
+ *   reported    c_r ^ flips[k]; column N + r of THAT trial carries the prior LLR logf((1.0f - probs[k]) / probs[k]), computed on
+ *               the host in float32 as scaldpc_bp_set_channel_probs computes the handle's (p = 0 / p = 1: +-inf); the columns
+ *               below N keep the handle's shared priors
+ *   decode      msg = [0]*N ++ reported in received-vector mode; success = (decoded[:N] == indicator(y))
+ *
+ * Defining property: for every trial, out_success and out_iters are what scaldpc_bp_decode_batch_soft gives on the exported
+ * out_msg with probs[out_outcome] as its last R columns (prob_cols = R) -- iterations bit for bit, for both methods and on every
+ * path (LDS-resident, 64-codeword tiles, row-parallel, compact passes): the same kernels run on the same planes.
+ * Reductions: K = 2, flips = (1, 0), probs = (eps, eps) and both weight rows (eps, 1 - eps) give scaldpc_mc_hqc_run(eps) exactly
+ * (outcome 0 is drawn where the word is below floor(eps 2^32); the handle's priors of the check columns being eps); K = 1,
+ * probs = (0) gives its eps = 0 case.
+ *
+ *   out_success / out_iters / out_msg / out_y   as scaldpc_mc_hqc_run's
+ *   out_outcome uint8 [batch][R]  optional: the outcome drawn for every check
+ *   out_flips   int32 [batch]     optional: checks reported wrong
+ *   out_cost    int32 [batch]     optional: the sum of costs[outcome] over the trial's checks; needs costs
+ * Validation (SCALDPC_EINVAL, nothing queued): 1 <= K <= 32; every weight finite and in [0, 1], each row summing to 1 +- 1e-6;
+ * probs in [0, 1]; flips 0 or 1; costs in [0, 65535] and R * max cost < 2^31; out_cost without costs; first_trial >= 0; omega and
+ * the [Hin | I] requirement as scaldpc_mc_hqc_run's.
+ * flags: SCALDPC_F_EARLY_EXIT, SCALDPC_F_DEVICE_IO (the seven outputs are device pointers); anything else is refused.
+ */
+int scaldpc_mc_hqc_run_soft(scaldpc_bp *h, int32_t omega, const double *weights, const uint8_t *flips, const float *probs,
+                            const int32_t *costs, int32_t K, int64_t first_trial, int32_t batch, uint64_t seed,
+                            int32_t max_iter, int32_t method, float alpha, uint32_t flags, void *stream,
+                            uint8_t *out_success, int32_t *out_iters, uint8_t *out_msg, int32_t *out_y, uint8_t *out_outcome,
+                            int32_t *out_flips, int32_t *out_cost);
 
 /* ------------------------------------------------------------ q-ary min-sum */
 typedef struct scaldpc_qary scaldpc_qary;

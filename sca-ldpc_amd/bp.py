@@ -310,6 +310,51 @@ class BpDecoder:
         )
         return {"success": succ, "iters": iters, "msg": msg, "y": y}
 
+    def mc_hqc_run_soft(self, runs, omega, table, seed, first_trial=0, max_iter=None, early_exit=True, want_inputs=False):
+        """`runs` synthetic hqc.decode() trials whose checks come from the oracles of simulate/hqc.py:782-871: every check
+        draws an OUTCOME conditional on its true value, and the outcome brings the reported bit, the certainty the decoder
+        is given with it (its own prior, hqc.py:689) and the oracle calls it spent -- all on the device
+        (scaldpc_mc_hqc_run_soft; the law is stated in include/scaldpc.h).
+
+          table  dict(weights [2, K], flips [K], probs [K], costs [K] or None), e.g. `trials.wrapped_oracle_table(...)`:
+                 weights[b] = probabilities of the K outcomes when the true check bit is b, flips = 1 where the reported bit
+                 is the complement, probs = the prior error probability given with the outcome (float32), costs = oracle calls
+        Returns dict(success uint8 [runs], iters int32 [runs], flips int32 [runs] (checks reported wrong), cost int32 [runs]
+        (oracle calls of the trial; None without costs in the table), and with want_inputs msg uint8 [runs, n],
+        y int32 [runs, omega], outcome uint8 [runs, R] (else None))."""
+        w = np.ascontiguousarray(table["weights"], dtype=np.float64)
+        if w.ndim != 2 or w.shape[0] != 2:
+            raise ValueError(f"table['weights'] must be [2, K], got shape {w.shape}")
+        K = w.shape[1]
+        fl = np.asarray(table["flips"])
+        pr = np.ascontiguousarray(table["probs"], dtype=np.float32)
+        costs = table.get("costs")
+        if fl.shape != (K,) or pr.shape != (K,) or (costs is not None and np.shape(costs) != (K,)):
+            raise ValueError(f"table: flips, probs and costs must hold one entry per outcome (K = {K})")
+        # (the library validates the values; here only what a conversion to its types would hide)
+        cs = None if costs is None else np.asarray(costs)
+        for name, a, t in (("flips", fl, np.uint8), ("costs", cs, np.int32)):
+            if a is not None and not np.array_equal(a.astype(t), a):
+                raise ValueError(f"table['{name}'] = {a.tolist()} does not fit {np.dtype(t).name}")
+        fl = np.ascontiguousarray(fl, dtype=np.uint8)
+        cs = None if cs is None else np.ascontiguousarray(cs, dtype=np.int32)
+        succ = np.empty(runs, dtype=np.uint8)
+        iters = np.empty(runs, dtype=np.int32)
+        flips = np.empty(runs, dtype=np.int32)
+        cost = np.empty(runs, dtype=np.int32) if costs is not None else None
+        msg = np.empty((runs, self.n), dtype=np.uint8) if want_inputs else None
+        y = np.empty((runs, omega), dtype=np.int32) if want_inputs else None
+        outcome = np.empty((runs, self.m), dtype=np.uint8) if want_inputs else None
+        _lib.check(
+            self._lib.scaldpc_mc_hqc_run_soft(
+                self._h, int(omega), _lib.ptr(w), _lib.ptr(fl), _lib.ptr(pr), _lib.ptr(cs), K,
+                int(first_trial), int(runs), int(seed), self.max_iter if max_iter is None else int(max_iter), self._method,
+                self.ms_scaling_factor, _lib.F_EARLY_EXIT if early_exit else 0, None, _lib.ptr(succ), _lib.ptr(iters),
+                _lib.ptr(msg), _lib.ptr(y), _lib.ptr(outcome), _lib.ptr(flips), _lib.ptr(cost),
+            )  # fmt: skip
+        )
+        return {"success": succ, "iters": iters, "flips": flips, "cost": cost, "msg": msg, "y": y, "outcome": outcome}
+
     def last_compacted(self):
         """Codewords the last early-exit call re-decoded in its compact second pass."""
         c = C.c_int64()

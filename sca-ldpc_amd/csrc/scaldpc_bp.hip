@@ -29,6 +29,7 @@
 //
 // No MFMA anywhere: this is a sparse gather/scatter stream, not a contraction.
 #include "scaldpc_common.h"
+#include "scaldpc_mc_law.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -156,6 +157,8 @@ struct scaldpc_bp : HandleStreams {
     Buf<int> d_ylist;
     Buf<uint8_t> d_succ;
     bool thr_valid = false;
+    Buf<int> d_mc_acc;            // scaldpc_mc_hqc_run_soft: [2][batch] checks reported wrong / oracle calls spent
+    Buf<uint8_t> d_mc_outcome;    // ... and the staging block of a host call's out_outcome
     // compact second pass over stragglers (early-exit runs)
     // (level k re-decodes the stragglers of level k-1 in dense tiles of their own; level 0 = the call's arrays)
     struct Level {
@@ -914,8 +917,8 @@ size_t small_lds(const scaldpc_bp *h)
 }
 
 // k_bp_small over `batch` codewords, one workgroup each.  PLANES: input syndromes and outputs are the tile path's bit
-// planes (Monte-Carlo entry points); else bytes per codeword in the caller's layout, and sp non-null = per-codeword priors
-// (scaldpc_bp_decode_batch_soft).
+// planes (Monte-Carlo entry points); else bytes per codeword in the caller's layout.  sp non-null = per-codeword priors
+// (scaldpc_bp_decode_batch_soft; with PLANES, scaldpc_mc_hqc_run_soft).
 template <bool PLANES>
 int launch_small(scaldpc_bp *h, size_t lds, int method, int batch, const void *in, int input_kind, int max_iter, float alpha,
                  bool early, void *bits, float *llr, int *iters, void *conv, hipStream_t s, const SoftPrior *sp = nullptr)
@@ -926,10 +929,7 @@ int launch_small(scaldpc_bp *h, size_t lds, int method, int batch, const void *i
                                h->d_col_ptr, h->d_csc_edge, prior, h->m, h->n, (int)h->E, in, input_kind, max_iter, alpha,
                                early ? 1 : 0, bits, llr, iters, conv);
         };
-        if constexpr (PLANES)  // (no <.., true, SoftPrior> instantiation)
-            launch(SharedPrior{}, (const float *)h->d_prior);
-        else
-            with_prior(h, sp, launch);
+        with_prior(h, sp, launch);
     });
     LAUNCH_CHECK();
     return 0;
@@ -1398,9 +1398,11 @@ int run_core(scaldpc_bp *h, int batch, int T, int G, int max_iter, int method, f
     h->stat_levels = 0;
 
     // small graph: the LDS-resident single-launch decoder, plane I/O (Monte-Carlo entry points)
-    if (const size_t lds = small_lds(h))
+    if (const size_t lds = small_lds(h)) {
+        const SoftPrior spv{h->d_prior, pprior, first_col, h->n - first_col};
         return launch_small<true>(h, lds, method, batch, h->d_synd, SCALDPC_IN_SYNDROME, max_iter, alpha, early, h->d_hard,
-                                  want_post ? h->d_post.get() : nullptr, h->d_iters, h->d_conv, s);
+                                  want_post ? h->d_post.get() : nullptr, h->d_iters, h->d_conv, s, pprior ? &spv : nullptr);
+    }
     const TileState st{h->d_synd, h->d_hard, h->d_done, h->d_conv, h->d_unsat, h->d_iters,
                        want_post ? h->d_post : nullptr, pprior, first_col};
     return decode_level(h, 0, st, batch, T, G, max_iter, method, alpha, early, want_post, s);
@@ -1980,6 +1982,25 @@ int scaldpc_bp_set_tile_group(scaldpc_bp *h, int32_t tiles)
     return 0;
 }
 
+// Tile group and workspace of a call on the tile path.  prob_cols > 0: the last prob_cols columns bring per-codeword priors
+// (scaldpc_bp_decode_batch_soft, scaldpc_mc_hqc_run_soft), whose plane h->d_pprior is sized here too.
+static int size_call(scaldpc_bp *h, const Call &c, int prob_cols, bool early, int method, bool want_post, int *G)
+{
+    *G = c.G;
+    if (prob_cols > 0 && h->tile_group <= 0) {
+        // the plane's rows share the cache with the group's messages where its passes keep reading them: every pass of an
+        // early-exit run and every message-form pass reads all of them, a record-form pass without output only the
+        // columns of degree >= 2 (launch_var: `light`)
+        int cols = prob_cols;
+        if (!early && rec_form(h, method)) {
+            cols = 0;
+            for (int v = h->n - prob_cols; v < h->n; v++) cols += h->hg_cdeg[v] > 1;
+        }
+        *G = auto_group(h, c.T, cols);
+    }
+    return ensure_workspace(h, c.T, *G, want_post, c.max_iter, prob_cols);
+}
+
 // Both decode entry points.  probs / prob_cols: a soft call's per-codeword probabilities of the last prob_cols columns
 // (float [batch][prob_cols], where `in` lives); prob_cols = 0: the handle's shared priors, the plain call.
 static int decode_batch_impl(scaldpc_bp *h, const uint8_t *in, int32_t input_kind, int32_t batch, const float *probs,
@@ -2069,19 +2090,8 @@ static int decode_batch_impl(scaldpc_bp *h, const uint8_t *in, int32_t input_kin
         if (!(flags & SCALDPC_F_ASYNC)) SC_HIP(hipStreamSynchronize(s));
         return settle.done();
     }
-    int G = c.G;
-    if (soft && h->tile_group <= 0) {
-        // the plane's rows share the cache with the group's messages where its passes keep reading them: every pass of an
-        // early-exit run and every message-form pass reads all of them, a record-form pass without output only the
-        // columns of degree >= 2 (launch_var: `light`)
-        int cols = prob_cols;
-        if (!early && rec_form(h, method)) {
-            cols = 0;
-            for (int v = first_col; v < h->n; v++) cols += h->hg_cdeg[v] > 1;
-        }
-        G = auto_group(h, T, cols);
-    }
-    SC_TRY(ensure_workspace(h, T, G, out_llr != nullptr, max_iter, prob_cols));
+    int G;
+    SC_TRY(size_call(h, c, prob_cols, early, method, out_llr != nullptr, &G));
     if (soft) SC_TRY(soft_convert());
     const float *const pprior = soft ? h->d_pprior.get() : nullptr;
 
@@ -2178,7 +2188,7 @@ int scaldpc_bp_decode_batch_soft(scaldpc_bp *h, const uint8_t *in, int32_t input
 // ---------------------------------------------------------------------------
 namespace {
 
-u64 bernoulli_threshold(double p) { return p >= 1.0 ? (1ull << 32) : p <= 0.0 ? 0ull : (u64)(p * 4294967296.0); }
+// (bernoulli_threshold: scaldpc_mc_law.h)
 
 int mc_common_args(scaldpc_bp *h, int32_t batch, int32_t method, float alpha, uint8_t *out_success)
 {
@@ -2320,6 +2330,89 @@ int scaldpc_mc_hqc_run(scaldpc_bp *h, int32_t omega, double eps, int64_t first_t
     if (out_y && !dev_io) {
         SC_HIP(hipMemcpyAsync(out_y, dy, sizeof(int) * (size_t)batch * omega, hipMemcpyDeviceToHost, s));
     }
+    // decoded[:N] = e[:N] XOR msg[:N] = e[:N] must equal the indicator of y (hqc.py:742-749)
+    SC_TRY(mc_finish(h, batch, T, N, dev_io, s, out_success, out_iters));
+    return settle.done();
+}
+
+// scaldpc_mc_hqc_run up to the syndrome; then every check draws an outcome of the oracle conditional on its true bit
+// (k_mc_hqc_outcome in the place of k_mc_bernoulli<true>), which also fills the prior plane of the check columns, and the
+// decode is the soft call's: run_core on h->d_pprior from column N on, sized by size_call as decode_batch_impl sizes it.
+int scaldpc_mc_hqc_run_soft(scaldpc_bp *h, int32_t omega, const double *weights, const uint8_t *flips, const float *probs,
+                            const int32_t *costs, int32_t K, int64_t first_trial, int32_t batch, uint64_t seed,
+                            int32_t max_iter_arg, int32_t method, float alpha, uint32_t flags, void *stream,
+                            uint8_t *out_success, int32_t *out_iters, uint8_t *out_msg, int32_t *out_y, uint8_t *out_outcome,
+                            int32_t *out_flips, int32_t *out_cost)
+{
+    SC_TRY(mc_common_args(h, batch, method, alpha, out_success));
+    if (flags & ~(SCALDPC_F_EARLY_EXIT | SCALDPC_F_DEVICE_IO))
+        return fail(SCALDPC_EINVAL, "flags: SCALDPC_F_EARLY_EXIT and SCALDPC_F_DEVICE_IO are taken");
+    if (first_trial < 0) return fail(SCALDPC_EINVAL, "first_trial must not be negative");
+    std::lock_guard<std::mutex> lk(h->mu);
+    SC_TRY(check_usable(h));
+    McHqcLaw law;
+    char why[160];
+    if (mc_hqc_law(weights, flips, probs, costs, K, h->m, out_cost != nullptr, &law, why, sizeof why))
+        return fail(SCALDPC_EINVAL, "%s", why);
+    DeviceGuard dg(h->device);
+    CacheBypass guard(h->async_used);
+    Call c;
+    SC_TRY(begin_call(h, batch, max_iter_arg, stream, &c));
+    const hipStream_t s = c.s;
+    SyncOnError settle{s};
+    SC_TRY(refresh_full(h));
+    if (h->identity_from < 0) return fail(SCALDPC_EINVAL, "parity-check matrix is not of the form [Hin | I] (hqc.py:680)");
+    const int N = h->identity_from, R = h->m;
+    if (omega < 0 || omega > N) return fail(SCALDPC_EINVAL, "omega must be in [0, N]");
+    if ((size_t)omega * 64 * 4 > 64 * 1024) return fail(SCALDPC_EDEGREE, "omega %d too large for the LDS-resident sampler", omega);
+    const bool dev_io = flags & SCALDPC_F_DEVICE_IO, early = flags & SCALDPC_F_EARLY_EXIT;
+    const int T = c.T, max_iter = c.max_iter;
+    int G;
+    SC_TRY(size_call(h, c, R, early, method, false, &G));
+    SC_TRY(grow(h->d_mc, (size_t)T * h->n));
+    SC_TRY(grow(h->d_mc_acc, (size_t)2 * batch));
+    int *dy = nullptr;
+    if (out_y) {
+        dy = out_y;
+        if (!dev_io) {
+            SC_TRY(grow(h->d_ylist, (size_t)batch * std::max(omega, 1)));
+            dy = h->d_ylist;
+        }
+    }
+    uint8_t *dout = nullptr;
+    if (out_outcome) {
+        dout = out_outcome;
+        if (!dev_io) {
+            SC_TRY(grow(h->d_mc_outcome, (size_t)batch * R));
+            dout = h->d_mc_outcome;
+        }
+    }
+    const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
+    // x = [y | 0]: omega distinct positions;  true bits c = Hin y = H x  (hqc.py:1253-1257)
+    SC_HIP(hipMemsetAsync(h->d_mc, 0, sizeof(u64) * (size_t)T * h->n, s));
+    if (omega) {
+        hipLaunchKernelGGL(k_mc_hqc_secret, dim3(T), dim3(64), (size_t)omega * 64 * sizeof(int), s, h->d_mc, h->n, N, omega,
+                           batch, (long)first_trial, k0, k1, dy);
+        LAUNCH_CHECK();
+    }
+    SC_TRY(launch_syndrome(h, h->d_mc, h->d_synd, T, s));
+    // each check: an outcome of the (wrapped) oracle given its true bit -> the reported bit and its certainty (hqc.py:782-871)
+    int *const acc_flips = h->d_mc_acc, *const acc_cost = costs ? acc_flips + batch : nullptr;
+    SC_HIP(hipMemsetAsync(acc_flips, 0, sizeof(int) * (size_t)2 * batch, s));
+    hipLaunchKernelGGL(k_mc_hqc_outcome, dim3((R + 63) / 64, T), dim3(256), 0, s, law, h->d_synd.get(), h->d_pprior.get(), R, batch,
+                       (long)first_trial, k0, k1, acc_flips, acc_cost, dout);
+    LAUNCH_CHECK();
+    // msg = [0]*N ++ reported (hqc.py:703-705); its syndrome under H = [Hin | I] is `reported` itself
+    SC_HIP(hipMemsetAsync(h->d_recv, 0, sizeof(u64) * (size_t)T * h->n, s));
+    SC_HIP(hipMemcpy2DAsync(h->d_recv + N, sizeof(u64) * h->n, h->d_synd, sizeof(u64) * h->m, sizeof(u64) * h->m, T,
+                            hipMemcpyDeviceToDevice, s));
+    if (out_msg) SC_TRY(mc_export_bits(h, h->d_recv, batch, T, dev_io, s, out_msg));
+    SC_TRY(run_core(h, batch, T, G, max_iter, method, alpha, early, false, s, h->d_pprior.get(), N));
+    const hipMemcpyKind back = dev_io ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (out_y && !dev_io) SC_HIP(hipMemcpyAsync(out_y, dy, sizeof(int) * (size_t)batch * omega, back, s));
+    if (out_outcome && !dev_io) SC_HIP(hipMemcpyAsync(out_outcome, dout, (size_t)batch * R, back, s));
+    if (out_flips) SC_HIP(hipMemcpyAsync(out_flips, acc_flips, sizeof(int) * (size_t)batch, back, s));
+    if (out_cost) SC_HIP(hipMemcpyAsync(out_cost, acc_cost, sizeof(int) * (size_t)batch, back, s));
     // decoded[:N] = e[:N] XOR msg[:N] = e[:N] must equal the indicator of y (hqc.py:742-749)
     SC_TRY(mc_finish(h, batch, T, N, dev_io, s, out_success, out_iters));
     return settle.done();

@@ -3,6 +3,7 @@
 // translation unit; the split is for reading, not for linking.
 #pragma once
 #include "scaldpc_logf.h"  // glibc's logf on the device (k_soft_convert)
+#include "scaldpc_mc_law.h"  // McHqcLaw: the outcome table k_mc_hqc_outcome takes by value
 #include "scaldpc_philox.h"
 #include <type_traits>
 
@@ -1007,7 +1008,8 @@ __global__ __launch_bounds__(256) void k_check_tanh(const int *__restrict__ list
 // PLANES = true : bit-plane I/O for the Monte-Carlo entry points (in = syndrome planes
 //                 u64 [tile][m]; out_bits = hard planes u64 [tile][n], zeroed by the caller;
 //                 out_conv = conv planes u64 [tile]; out_llr = posterior [tile][var][64]).
-// Per-codeword priors (P = SoftPrior) come with byte I/O only.
+// Per-codeword priors (P = SoftPrior) come with either: byte I/O for scaldpc_bp_decode_batch_soft, plane I/O for
+// scaldpc_mc_hqc_run_soft, whose plane the trial generator filled (a workgroup reads lane b & 63 of tile b >> 6 of it).
 template <int METHOD, bool PLANES, class P>  // METHOD: SCALDPC_BP_PRODUCT_SUM / SCALDPC_BP_MIN_SUM
 __device__ __forceinline__ void bp_small_body(const int *__restrict__ row_ptr, const int *__restrict__ col_idx,
                                               const int *__restrict__ col_ptr, const int *__restrict__ csc_edge,
@@ -1793,7 +1795,8 @@ __global__ __launch_bounds__(256) void k_apply_pairs(int *__restrict__ dst, cons
 // Random numbers: Philox4x32-10 (Salmon et al., SC'11), counter-based, keyed by the seed;
 // counter = (block, stream, trial_lo, trial_hi) with the GLOBAL trial index, so a trial's
 // inputs do not depend on batch size, tile position or the number of GPUs.
-//   stream 0 word x : Bernoulli(p_x) for position x      (flip iff word < floor(p_x * 2^32))
+//   stream 0 word x : Bernoulli(p_x) for position x      (flip iff word < floor(p_x * 2^32));
+//                     scaldpc_mc_hqc_run_soft: the outcome of check x (k_mc_hqc_outcome) -- the same word
 //   stream 1 word j : j-th candidate position of the HQC secret, pos = mulhi(word, N),
 //                     accepted if not chosen before, until omega are accepted
 // ---------------------------------------------------------------------------
@@ -1862,6 +1865,67 @@ __global__ __launch_bounds__(64) void k_mc_hqc_secret(u64 *__restrict__ planes, 
                 break;
             }
         }
+    }
+}
+
+// The oracle's answers of scaldpc_mc_hqc_run_soft: every check draws an OUTCOME conditional on its true bit, and the outcome
+// brings the reported bit and the prior the decoder is given with it (law: include/scaldpc.h; McHqcLaw, scaldpc_mc_law.h).
+//   synd   u64 [tile][R]       in: the true bits c = Hin y; out: the reported bits c ^ flips[outcome]
+//   plane  float [tile][R][64] out: the prior LLR of check column N + r per codeword -- the plane k_soft_convert writes and
+//                              SoftPrior reads; one 256-B store per (tile, check)
+//   acc_flips / acc_cost  int [batch], zeroed by the caller: checks reported wrong / oracle calls spent (acc_cost may be null)
+//   out_outcome  uint8 [batch][R] or null: the outcome drawn (an export path: strided byte stores)
+// The shape of k_mc_bernoulli: wave = (tile, 16 consecutive checks), lane = trial, one Philox call per four checks, the word
+// of check r = stream-0 word r -- the one k_mc_bernoulli<true> flips by.  The thresholds, LLRs and costs are uniform reads of
+// the kernel argument; the outcome is the number of thresholds of the true bit's row at or below the word, and since those
+// do not decrease, the LLR and cost of the last threshold passed are the outcome's.  The lanes of a ragged last tile get
+// bit 0 and LLR 0 and report nothing.  The wave that owns a syndrome word reads it before its lane 0 replaces it.
+// grid (ceil(R/64), T), block 256.
+__global__ __launch_bounds__(256) void k_mc_hqc_outcome(McHqcLaw law, u64 *synd, float *__restrict__ plane, int R, int batch,
+                                                        long first, unsigned k0, unsigned k1, int *__restrict__ acc_flips,
+                                                        int *__restrict__ acc_cost, uint8_t *__restrict__ out_outcome)
+{
+    const int lane = threadIdx.x & 63;
+    const int x0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 16;
+    const int t = blockIdx.y;
+    if (x0 >= R) return;
+    const long b = (long)t * TW + lane;
+    const bool live = b < batch;
+    const u64 trial = (u64)(first + b);
+    int nflips = 0, ncost = 0;
+    for (int q = 0; q < 4; q++) {
+        const int xb = x0 + 4 * q;
+        if (xb >= R) break;
+        const U4 r = philox4x32_10(U4{(unsigned)(xb >> 2), 0u, (unsigned)trial, (unsigned)(trial >> 32)}, k0, k1);
+        const unsigned w[4] = {r.x, r.y, r.z, r.w};
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const int x = xb + j;
+            if (x < R) {
+                const size_t row = (size_t)t * R + x;
+                const unsigned c = (unsigned)((synd[row] >> lane) & 1);
+                const u64 word = w[j];
+                int lv = 0, cost = law.cost[0];
+                float llr = law.llr[0];
+                for (int k = 0; k + 1 < law.K; k++) {
+                    const bool past = word >= (c ? law.t[1][k] : law.t[0][k]);
+                    lv += past;
+                    llr = past ? law.llr[k + 1] : llr;
+                    cost = past ? law.cost[k + 1] : cost;
+                }
+                const unsigned flip = live ? (law.flips >> lv) & 1u : 0u;
+                const u64 m = __ballot(live && (c ^ flip));
+                if (lane == 0) synd[row] = m;
+                plane[row * TW + lane] = live ? llr : 0.0f;
+                nflips += (int)flip;
+                ncost += live ? cost : 0;
+                if (out_outcome && live) out_outcome[(size_t)b * R + x] = (uint8_t)lv;
+            }
+        }
+    }
+    if (live) {
+        atomicAdd(acc_flips + b, nflips);
+        if (acc_cost) atomicAdd(acc_cost + b, ncost);
     }
 }
 

@@ -24,6 +24,7 @@
 // roofline claim is made for it.
 #include "scaldpc_common.h"
 #include "scaldpc_logf.h"
+#include "scaldpc_mc_law.h"
 #include "scaldpc_qary_plan.h"
 
 #include <cmath>
@@ -1190,10 +1191,8 @@ struct McOut {
     int8_t *symbols;
 };
 
-// floor(p 2^32), 0 for p <= 0, 2^32 for p >= 1: the rule of the binary helpers (bernoulli_threshold, scaldpc_bp.hip)
-u64 mc_threshold(double p) { return p >= 1.0 ? (1ull << 32) : p <= 0.0 ? 0ull : (u64)(p * 4294967296.0); }
-
-// Everything that can be refused about the tables, and their thresholds; nothing is queued, no handle state is touched.
+// Everything that can be refused about the tables, and their thresholds (mc_cumulative_thresholds, scaldpc_mc_law.h: the rule the
+// binary scaldpc_mc_hqc_run_soft draws its outcomes by); nothing is queued, no handle state is touched.
 int mc_law(const McTables &t, int ntab, McLaw *law)
 {
     static const char *const name[2] = {"levels_b", "levels_s"};
@@ -1201,17 +1200,8 @@ int mc_law(const McTables &t, int ntab, McLaw *law)
     for (int i = 0; i < ntab; i++) {
         const int K = t.K[i];
         if (K < 1 || K > MC_MAX_LEVELS) return fail(SCALDPC_EINVAL, "%s: %d levels, 1 .. %d are taken", name[i], K, MC_MAX_LEVELS);
-        double sum = 0.0;
-        int last = 0;  // the last level of nonzero weight: from there on the threshold is 2^32, so a level of weight 0 is never drawn
-        for (int k = 0; k < K; k++) {
-            const double w = t.weights[i][k];
-            if (!(w >= 0.0 && w <= 1.0)) return fail(SCALDPC_EINVAL, "%s: weight %d is %g, not a probability", name[i], k, w);
-            sum += w;
-            law->t[i][k] = mc_threshold(sum);
-            if (w > 0.0) last = k;
-        }
-        if (!(std::fabs(sum - 1.0) <= 1e-6)) return fail(SCALDPC_EINVAL, "%s: the weights sum to %.9g, not to 1 +- 1e-6", name[i], sum);
-        for (int k = last; k < K; k++) law->t[i][k] = 1ull << 32;
+        char why[160];
+        if (mc_cumulative_thresholds(name[i], t.weights[i], K, law->t[i], why, sizeof why)) return fail(SCALDPC_EINVAL, "%s", why);
         law->K[i] = K;
     }
     for (int i = 0; i < ntab; i++)

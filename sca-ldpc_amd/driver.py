@@ -9,6 +9,8 @@ decoder in ONE batched call.
   qary_fer_sweep                  the same loop, its trials drawn on the device (Philox, sharded by global trial index)
   hqc_decode                      simulate/hqc.py:661-759      (input assembly + 7 stats fields)
   hqc_decode_batch                the same for many trials with their own certainties, one soft call
+  hqc_oracle_sweep                such trials at a fixed number of checks, answered by the wrapped oracle's law
+                                  (simulate/hqc.py:782-871) on the device: successes, iterations, oracle calls spent
   regular_ldpc_code & co          main.py:189-276              (the four FER commands, as functions)
 
 The decoder classes are parameters (default: the HIP decoders) so that the host logic
@@ -205,6 +207,52 @@ def qary_fer_sweep(H, B, error_rate, runs, seed, chunk=4096, decoder_class=None)
     finally:
         if hasattr(decoder, "close"):
             decoder.close()
+    return res
+
+
+def hqc_oracle_sweep(Hin, N, omega, table, runs, seed, chunk=4096, bp_method="product_sum", max_iter=100, bp_decoder=None):
+    """A sweep of synthetic hqc.decode() trials at a FIXED number of checks (the rows of Hin) under the law of the attack's
+    oracle: every check is answered by an outcome of `table` (`trials.wrapped_oracle_table`: the repeated measurements of
+    wrapped_hqc_decoding_oracle, simulate/hqc.py:782-871), drawn on the device conditional on the check's true value, and
+    brings its own certainty into the decode (`BpDecoder.mc_hqc_run_soft`).  Global trial indices 0 .. runs - 1 are scanned
+    `chunk` at a time; the result does not depend on `chunk`.  Returns dict(
+      runs, successes,
+      iter_hist           int64 [max_iter + 1]: trials by the iteration count of their decode,
+      flips               checks reported wrong, over all trials,
+      oracle_calls, oracle_calls_mean                  total and per trial, over all trials,
+      oracle_calls_success, oracle_calls_success_mean  the same over the successful trials (mean None: none succeeded);
+    the four oracle-call fields are None when the table has no costs).  What the paper's plots report -- oracle calls per
+    recovered key -- is oracle_calls / successes."""
+    g = TannerGraph.coerce(Hin)
+    if g.n != N:
+        raise ValueError(f"Hin has {g.n} columns, N = {N}")
+    if runs < 0 or chunk < 1:
+        raise ValueError("runs must not be negative and chunk must be positive")
+    # the check columns' shared priors are replaced per trial: any probability does
+    shared = np.concatenate([np.full(N, omega / N, dtype=np.float64), np.full(g.m, 0.5, dtype=np.float64)])
+    bpd = (bp_decoder or _default_bp())(g.with_identity(), max_iter=max_iter, bp_method=bp_method, channel_probs=shared)
+    counted = table.get("costs") is not None
+    hist = np.zeros(max_iter + 1, dtype=np.int64)
+    successes = flips = calls = calls_ok = 0
+    try:
+        for first in range(0, runs, chunk):
+            out = bpd.mc_hqc_run_soft(min(chunk, runs - first), omega, table, seed, first_trial=first, max_iter=max_iter)
+            ok = np.asarray(out["success"]).astype(bool)
+            successes += int(ok.sum())
+            hist += np.bincount(np.asarray(out["iters"]), minlength=max_iter + 1)[: max_iter + 1]
+            flips += int(np.asarray(out["flips"], dtype=np.int64).sum())
+            if counted:
+                cost = np.asarray(out["cost"], dtype=np.int64)
+                calls += int(cost.sum())
+                calls_ok += int(cost[ok].sum())
+    finally:
+        if hasattr(bpd, "close"):
+            bpd.close()
+    res = dict(runs=int(runs), successes=successes, iter_hist=hist, flips=flips, oracle_calls=None, oracle_calls_mean=None,
+               oracle_calls_success=None, oracle_calls_success_mean=None)
+    if counted:
+        res.update(oracle_calls=calls, oracle_calls_mean=calls / runs if runs else None, oracle_calls_success=calls_ok,
+                   oracle_calls_success_mean=calls_ok / successes if successes else None)
     return res
 
 
