@@ -282,6 +282,11 @@ void scaldpc_bp_destroy(scaldpc_bp *h);
  *   out_msg (optional) uint8 [batch][n]; out_y (optional) int32 [batch][omega], in draw order.
  * out_success uint8 [batch] required; out_iters int32 [batch] optional.
  * flags: SCALDPC_F_EARLY_EXIT, SCALDPC_F_DEVICE_IO (outputs are device pointers).
+ * Refused with SCALDPC_EINVAL before anything is queued (as scaldpc_mc_qary_run and scaldpc_mc_hqc_run_soft refuse them):
+ * first_trial < 0, and any flag other than these two; so are batch <= 0, an unknown method, alpha that is negative or NaN and
+ * out_success = NULL.  scaldpc_mc_hqc_run also refuses omega outside [0, N], eps outside [0, 1] or NaN and a graph that does
+ * not end in an identity block (SCALDPC_EINVAL), and omega > 256 (SCALDPC_EDEGREE: the sampler keeps a trial's positions in
+ * LDS).  No refusal writes to an output, and the handle stays usable.
  */
 int scaldpc_mc_fer_run(scaldpc_bp *h, int64_t first_trial, int32_t batch, uint64_t seed, int32_t max_iter,
                        int32_t method, float alpha, uint32_t flags, void *stream, uint8_t *out_success,

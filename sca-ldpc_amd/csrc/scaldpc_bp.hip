@@ -2190,9 +2190,13 @@ namespace {
 
 // (bernoulli_threshold: scaldpc_mc_law.h)
 
-int mc_common_args(scaldpc_bp *h, int32_t batch, int32_t method, float alpha, uint8_t *out_success)
+int mc_common_args(scaldpc_bp *h, int64_t first_trial, int32_t batch, int32_t method, float alpha, uint32_t flags,
+                   uint8_t *out_success)
 {
     if (!h || !out_success) return fail(SCALDPC_EINVAL, "NULL argument");
+    if (flags & ~(SCALDPC_F_EARLY_EXIT | SCALDPC_F_DEVICE_IO))
+        return fail(SCALDPC_EINVAL, "flags: SCALDPC_F_EARLY_EXIT and SCALDPC_F_DEVICE_IO are taken");
+    if (first_trial < 0) return fail(SCALDPC_EINVAL, "first_trial must not be negative");
     if (batch <= 0) return fail(SCALDPC_EINVAL, "batch must be positive (got %d)", batch);
     if (method != SCALDPC_BP_PRODUCT_SUM && method != SCALDPC_BP_MIN_SUM)
         return fail(SCALDPC_EINVAL, "unknown bp method %d", method);
@@ -2243,7 +2247,7 @@ int scaldpc_mc_fer_run(scaldpc_bp *h, int64_t first_trial, int32_t batch, uint64
                        int32_t method, float alpha, uint32_t flags, void *stream, uint8_t *out_success,
                        int32_t *out_iters, uint8_t *out_error)
 {
-    SC_TRY(mc_common_args(h, batch, method, alpha, out_success));
+    SC_TRY(mc_common_args(h, first_trial, batch, method, alpha, flags, out_success));
     std::lock_guard<std::mutex> lk(h->mu);
     SC_TRY(check_usable(h));
     DeviceGuard dg(h->device);
@@ -2281,7 +2285,7 @@ int scaldpc_mc_hqc_run(scaldpc_bp *h, int32_t omega, double eps, int64_t first_t
                        int32_t max_iter_arg, int32_t method, float alpha, uint32_t flags, void *stream,
                        uint8_t *out_success, int32_t *out_iters, uint8_t *out_msg, int32_t *out_y)
 {
-    SC_TRY(mc_common_args(h, batch, method, alpha, out_success));
+    SC_TRY(mc_common_args(h, first_trial, batch, method, alpha, flags, out_success));
     std::lock_guard<std::mutex> lk(h->mu);
     SC_TRY(check_usable(h));
     DeviceGuard dg(h->device);
@@ -2344,10 +2348,7 @@ int scaldpc_mc_hqc_run_soft(scaldpc_bp *h, int32_t omega, const double *weights,
                             uint8_t *out_success, int32_t *out_iters, uint8_t *out_msg, int32_t *out_y, uint8_t *out_outcome,
                             int32_t *out_flips, int32_t *out_cost)
 {
-    SC_TRY(mc_common_args(h, batch, method, alpha, out_success));
-    if (flags & ~(SCALDPC_F_EARLY_EXIT | SCALDPC_F_DEVICE_IO))
-        return fail(SCALDPC_EINVAL, "flags: SCALDPC_F_EARLY_EXIT and SCALDPC_F_DEVICE_IO are taken");
-    if (first_trial < 0) return fail(SCALDPC_EINVAL, "first_trial must not be negative");
+    SC_TRY(mc_common_args(h, first_trial, batch, method, alpha, flags, out_success));
     std::lock_guard<std::mutex> lk(h->mu);
     SC_TRY(check_usable(h));
     McHqcLaw law;
