@@ -339,6 +339,41 @@ int scaldpc_mc_hqc_run_soft(scaldpc_bp *h, int32_t omega, const double *weights,
                             uint8_t *out_success, int32_t *out_iters, uint8_t *out_msg, int32_t *out_y, uint8_t *out_outcome,
                             int32_t *out_flips, int32_t *out_cost);
 
+/*
+ * scaldpc_mc_hqc_run_stats = scaldpc_mc_hqc_run_soft -- the same arguments, law, validation, refusals and flags -- that also
+ * returns, per trial, the counters tracking.add_decoder_stats records after every decode (simulate/hqc.py:709-758) and,
+ * optionally, the decoded word they are counted on.  Two more outputs follow scaldpc_mc_hqc_run_soft's:
+ *   out_stats int32 [batch][5]  required (NULL: SCALDPC_EINVAL, nothing queued), per trial in this order:
+ *               unsatisfied                   sum over checks r of reported_r
+ *               good_flips                    sum over v < N of hard_v & truth_v        (truth = indicator(y))
+ *               bad_flips                     sum over v < N of hard_v & ~truth_v
+ *               found_bad_satisfied_checks    sum over r of hard_{N+r} & ~reported_r
+ *               found_bad_unsatisfied_checks  sum over r of hard_{N+r} & reported_r
+ *             hard = the error estimate of the decode; the decoded check bit is hard_{N+r} ^ reported_r (received-vector mode),
+ *             so the last two are "reported 0, decoded 1" and "reported 1, decoded 0" (hqc.py:724-741).  `checks` is R and
+ *             `success` is out_success: with them the row is the reference's decoder_stats row.
+ *   out_bits  uint8 [batch][n]  optional: the decoded word, exactly what scaldpc_bp_decode_batch returns as out_bits for out_msg
+ * The counters are a column count over three bit planes the call holds anyway (k_mc_hqc_stats): one launch after the decode; no
+ * message, posterior or prior is read again.
+ *
+ * Defining property: for every trial i, out_stats[i] and out_success[i] are the counters and the success of the decoded word
+ * bits_i = scaldpc_bp_decode_batch_soft(out_msg, probs[out_outcome], prob_cols = R) of the same handle, counted on the host from
+ * (bits_i, the check part of out_msg_i, out_y_i) -- integer equality, for both methods and on every path (LDS-resident,
+ * 64-codeword tiles, row-parallel, compact passes: the counters are read after the stragglers' decisions are back in place) --
+ * and out_bits is bits.  Everything scaldpc_mc_hqc_run_soft returns is returned unchanged.
+ * Reduction: the K = 2 table weights = ((eps, 1 - eps), (eps, 1 - eps)), flips = (1, 0), probs = (eps, eps) IS
+ * scaldpc_mc_hqc_run(eps): this entry with that table returns the counters of scaldpc_mc_hqc_run's trials.
+ * Growing graphs: a trial's secret does not depend on R and check r always takes stream-0 word r, so the trials of a graph of R
+ * rows are the first R answers of the same trials on that graph with more rows appended (scaldpc_bp_append_rows): one seed, run
+ * again after every append, follows the same keys through the attack's loop (hqc.py:953-984).
+ * flags: SCALDPC_F_EARLY_EXIT, SCALDPC_F_DEVICE_IO (the nine outputs are device pointers, written on the caller's stream).
+ */
+int scaldpc_mc_hqc_run_stats(scaldpc_bp *h, int32_t omega, const double *weights, const uint8_t *flips, const float *probs,
+                             const int32_t *costs, int32_t K, int64_t first_trial, int32_t batch, uint64_t seed,
+                             int32_t max_iter, int32_t method, float alpha, uint32_t flags, void *stream,
+                             uint8_t *out_success, int32_t *out_iters, uint8_t *out_msg, int32_t *out_y, uint8_t *out_outcome,
+                             int32_t *out_flips, int32_t *out_cost, int32_t *out_stats, uint8_t *out_bits);
+
 /* ------------------------------------------------------------ q-ary min-sum */
 typedef struct scaldpc_qary scaldpc_qary;
 

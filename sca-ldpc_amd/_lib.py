@@ -86,10 +86,11 @@ def _declare(lib):
         vp, C.c_int32, vp, vp, vp, vp, C.c_int32, C.c_int64, C.c_int32, C.c_uint64, C.c_int32, C.c_int32, C.c_float, C.c_uint32,
         vp, vp, vp, vp, vp, vp, vp, vp,
     ]  # fmt: skip
+    lib.scaldpc_mc_hqc_run_stats.argtypes = lib.scaldpc_mc_hqc_run_soft.argtypes + [vp, vp]
     for name in (
         "scaldpc_device_count", "scaldpc_set_device", "scaldpc_bp_create", "scaldpc_bp_set_channel_probs",
         "scaldpc_bp_decode_batch", "scaldpc_bp_time_kernels", "scaldpc_bp_set_tile_group", "scaldpc_mc_fer_run",
-        "scaldpc_mc_hqc_run", "scaldpc_mc_hqc_run_soft",
+        "scaldpc_mc_hqc_run", "scaldpc_mc_hqc_run_soft", "scaldpc_mc_hqc_run_stats",
     ):  # fmt: skip
         getattr(lib, name).restype = C.c_int
     lib.scaldpc_qary_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, p(vp)]

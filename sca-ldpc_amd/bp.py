@@ -53,6 +53,10 @@ def _vector_type(t):
     raise ValueError(f"input_vector_type '{t}' is invalid. Choose 'syndrome', 'received_vector' or 'auto'.")
 
 
+# the five per-trial counters of scaldpc_mc_hqc_run_stats, in the order of its out_stats (= driver.STATS_COLUMNS[7:12])
+HQC_STATS_COLUMNS = ("unsatisfied", "good_flips", "bad_flips", "found_bad_satisfied_checks", "found_bad_unsatisfied_checks")
+
+
 class BpDecoder:
     def __init__(
         self,
@@ -293,10 +297,20 @@ class BpDecoder:
         )
         return {"success": succ, "iters": iters, "errors": err}
 
-    def mc_hqc_run(self, runs, omega, eps, seed, first_trial=0, max_iter=None, early_exit=True, want_inputs=False):
+    def mc_hqc_run(self, runs, omega, eps, seed, first_trial=0, max_iter=None, early_exit=True, want_inputs=False,
+                   want_stats=False, want_bits=False):
         """`runs` synthetic hqc.decode() trials (simulate/hqc.py:684-705,742-749) on H = [Hin | I]:
         secret y, noisy checks, msg = [0]*N ++ checks, decode, success = (decoded[:N] == y).
-        Returns dict(success, iters, msg uint8 [runs, n] or None, y int32 [runs, omega] or None)."""
+        Returns dict(success, iters, msg uint8 [runs, n] or None, y int32 [runs, omega] or None).
+        want_stats / want_bits: the same trials through scaldpc_mc_hqc_run_stats with the two-outcome table that IS this sweep
+        (include/scaldpc.h); the result gains `stats` and `bits` as `mc_hqc_run_soft`'s does."""
+        if want_stats or want_bits:
+            eps = float(eps)
+            table = dict(weights=np.array([[eps, 1.0 - eps]] * 2), flips=np.array([1, 0], dtype=np.uint8),
+                         probs=np.array([eps, eps]), costs=None)
+            r = self.mc_hqc_run_soft(runs, omega, table, seed, first_trial=first_trial, max_iter=max_iter, early_exit=early_exit,
+                                     want_inputs=want_inputs, want_stats=want_stats, want_bits=want_bits)
+            return {k: r[k] for k in ("success", "iters", "msg", "y", "stats", "bits")}
         succ = np.empty(runs, dtype=np.uint8)
         iters = np.empty(runs, dtype=np.int32)
         msg = np.empty((runs, self.n), dtype=np.uint8) if want_inputs else None
@@ -310,7 +324,8 @@ class BpDecoder:
         )
         return {"success": succ, "iters": iters, "msg": msg, "y": y}
 
-    def mc_hqc_run_soft(self, runs, omega, table, seed, first_trial=0, max_iter=None, early_exit=True, want_inputs=False):
+    def mc_hqc_run_soft(self, runs, omega, table, seed, first_trial=0, max_iter=None, early_exit=True, want_inputs=False,
+                        want_stats=False, want_bits=False):
         """`runs` synthetic hqc.decode() trials whose checks come from the oracles of simulate/hqc.py:782-871: every check
         draws an OUTCOME conditional on its true value, and the outcome brings the reported bit, the certainty the decoder
         is given with it (its own prior, hqc.py:689) and the oracle calls it spent -- all on the device
@@ -321,7 +336,12 @@ class BpDecoder:
                  is the complement, probs = the prior error probability given with the outcome (float32), costs = oracle calls
         Returns dict(success uint8 [runs], iters int32 [runs], flips int32 [runs] (checks reported wrong), cost int32 [runs]
         (oracle calls of the trial; None without costs in the table), and with want_inputs msg uint8 [runs, n],
-        y int32 [runs, omega], outcome uint8 [runs, R] (else None))."""
+        y int32 [runs, omega], outcome uint8 [runs, R] (else None)).
+        want_stats / want_bits: the call goes through scaldpc_mc_hqc_run_stats and the result gains
+          stats  int32 [runs, 5]: per trial the counters of tracking.add_decoder_stats (hqc.py:709-758) in the order of
+                 HQC_STATS_COLUMNS -- what `driver.hqc_stats` counts on the decoded word, counted on the device
+          bits   uint8 [runs, n] with want_bits (else None): the decoded word, `decode_batch`'s bits for `msg`
+        everything else is unchanged; without the two flags the call and its result are the plain sweep's."""
         w = np.ascontiguousarray(table["weights"], dtype=np.float64)
         if w.ndim != 2 or w.shape[0] != 2:
             raise ValueError(f"table['weights'] must be [2, K], got shape {w.shape}")
@@ -345,15 +365,20 @@ class BpDecoder:
         msg = np.empty((runs, self.n), dtype=np.uint8) if want_inputs else None
         y = np.empty((runs, omega), dtype=np.int32) if want_inputs else None
         outcome = np.empty((runs, self.m), dtype=np.uint8) if want_inputs else None
-        _lib.check(
-            self._lib.scaldpc_mc_hqc_run_soft(
-                self._h, int(omega), _lib.ptr(w), _lib.ptr(fl), _lib.ptr(pr), _lib.ptr(cs), K,
-                int(first_trial), int(runs), int(seed), self.max_iter if max_iter is None else int(max_iter), self._method,
-                self.ms_scaling_factor, _lib.F_EARLY_EXIT if early_exit else 0, None, _lib.ptr(succ), _lib.ptr(iters),
-                _lib.ptr(msg), _lib.ptr(y), _lib.ptr(outcome), _lib.ptr(flips), _lib.ptr(cost),
-            )  # fmt: skip
-        )
-        return {"success": succ, "iters": iters, "flips": flips, "cost": cost, "msg": msg, "y": y, "outcome": outcome}
+        args = (
+            self._h, int(omega), _lib.ptr(w), _lib.ptr(fl), _lib.ptr(pr), _lib.ptr(cs), K,
+            int(first_trial), int(runs), int(seed), self.max_iter if max_iter is None else int(max_iter), self._method,
+            self.ms_scaling_factor, _lib.F_EARLY_EXIT if early_exit else 0, None, _lib.ptr(succ), _lib.ptr(iters),
+            _lib.ptr(msg), _lib.ptr(y), _lib.ptr(outcome), _lib.ptr(flips), _lib.ptr(cost),
+        )  # fmt: skip
+        res = {"success": succ, "iters": iters, "flips": flips, "cost": cost, "msg": msg, "y": y, "outcome": outcome}
+        if want_stats or want_bits:
+            stats = np.empty((runs, len(HQC_STATS_COLUMNS)), dtype=np.int32)
+            bits = np.empty((runs, self.n), dtype=np.uint8) if want_bits else None
+            _lib.check(self._lib.scaldpc_mc_hqc_run_stats(*args, _lib.ptr(stats), _lib.ptr(bits)))
+            return dict(res, stats=stats, bits=bits)
+        _lib.check(self._lib.scaldpc_mc_hqc_run_soft(*args))
+        return res
 
     def last_compacted(self):
         """Codewords the last early-exit call re-decoded in its compact second pass."""

@@ -158,6 +158,7 @@ struct scaldpc_bp : HandleStreams {
     Buf<uint8_t> d_succ;
     bool thr_valid = false;
     Buf<int> d_mc_acc;            // scaldpc_mc_hqc_run_soft: [2][batch] checks reported wrong / oracle calls spent
+    Buf<int> d_mc_stats;          // scaldpc_mc_hqc_run_stats: [batch][5] counters of k_mc_hqc_stats (host callers)
     Buf<uint8_t> d_mc_outcome;    // ... and the staging block of a host call's out_outcome
     // compact second pass over stragglers (early-exit runs)
     // (level k re-decodes the stragglers of level k-1 in dense tiles of their own; level 0 = the call's arrays)
@@ -2342,11 +2343,13 @@ int scaldpc_mc_hqc_run(scaldpc_bp *h, int32_t omega, double eps, int64_t first_t
 // scaldpc_mc_hqc_run up to the syndrome; then every check draws an outcome of the oracle conditional on its true bit
 // (k_mc_hqc_outcome in the place of k_mc_bernoulli<true>), which also fills the prior plane of the check columns, and the
 // decode is the soft call's: run_core on h->d_pprior from column N on, sized by size_call as decode_batch_impl sizes it.
-int scaldpc_mc_hqc_run_soft(scaldpc_bp *h, int32_t omega, const double *weights, const uint8_t *flips, const float *probs,
-                            const int32_t *costs, int32_t K, int64_t first_trial, int32_t batch, uint64_t seed,
-                            int32_t max_iter_arg, int32_t method, float alpha, uint32_t flags, void *stream,
-                            uint8_t *out_success, int32_t *out_iters, uint8_t *out_msg, int32_t *out_y, uint8_t *out_outcome,
-                            int32_t *out_flips, int32_t *out_cost)
+// out_stats / out_bits: what scaldpc_mc_hqc_run_stats adds (k_mc_hqc_stats on the planes the decode leaves; the decoded word as
+// decode_batch_impl unpacks it).  Both null -- scaldpc_mc_hqc_run_soft -- and nothing is launched, cleared or allocated for them.
+static int mc_hqc_run_soft_body(scaldpc_bp *h, int32_t omega, const double *weights, const uint8_t *flips, const float *probs,
+                                const int32_t *costs, int32_t K, int64_t first_trial, int32_t batch, uint64_t seed,
+                                int32_t max_iter_arg, int32_t method, float alpha, uint32_t flags, void *stream,
+                                uint8_t *out_success, int32_t *out_iters, uint8_t *out_msg, int32_t *out_y, uint8_t *out_outcome,
+                                int32_t *out_flips, int32_t *out_cost, int32_t *out_stats, uint8_t *out_bits)
 {
     SC_TRY(mc_common_args(h, first_trial, batch, method, alpha, flags, out_success));
     std::lock_guard<std::mutex> lk(h->mu);
@@ -2388,6 +2391,11 @@ int scaldpc_mc_hqc_run_soft(scaldpc_bp *h, int32_t omega, const double *weights,
             dout = h->d_mc_outcome;
         }
     }
+    int *dstats = out_stats;
+    if (out_stats && !dev_io) {
+        SC_TRY(grow(h->d_mc_stats, (size_t)5 * batch));
+        dstats = h->d_mc_stats;
+    }
     const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
     // x = [y | 0]: omega distinct positions;  true bits c = Hin y = H x  (hqc.py:1253-1257)
     SC_HIP(hipMemsetAsync(h->d_mc, 0, sizeof(u64) * (size_t)T * h->n, s));
@@ -2414,9 +2422,49 @@ int scaldpc_mc_hqc_run_soft(scaldpc_bp *h, int32_t omega, const double *weights,
     if (out_outcome && !dev_io) SC_HIP(hipMemcpyAsync(out_outcome, dout, (size_t)batch * R, back, s));
     if (out_flips) SC_HIP(hipMemcpyAsync(out_flips, acc_flips, sizeof(int) * (size_t)batch, back, s));
     if (out_cost) SC_HIP(hipMemcpyAsync(out_cost, acc_cost, sizeof(int) * (size_t)batch, back, s));
+    if (out_stats) {
+        // the counters of hqc.py:709-758, from the decisions every path (compact passes included) has left in d_hard
+        SC_HIP(hipMemsetAsync(dstats, 0, sizeof(int) * (size_t)5 * batch, s));
+        hipLaunchKernelGGL(k_mc_hqc_stats, dim3((h->n + 4 * MC_STATS_RUN - 1) / (4 * MC_STATS_RUN), T), dim3(256), 0, s,
+                           h->d_hard.get(), h->d_mc.get(), h->d_recv.get(), h->n, N, batch, dstats);
+        LAUNCH_CHECK();
+        if (!dev_io) SC_HIP(hipMemcpyAsync(out_stats, dstats, sizeof(int) * (size_t)5 * batch, back, s));
+    }
+    if (out_bits) {  // decoded = e XOR msg, as scaldpc_bp_decode_batch returns it for out_msg
+        Outputs o, dev;
+        o.bits = out_bits;
+        SC_TRY(stage_outputs(h, o, batch, dev_io, false, &dev));
+        hipLaunchKernelGGL(k_unpack_bits, dim3((h->n + 255) / 256, T), dim3(256), 0, s, h->d_hard, h->d_recv, h->n, batch,
+                           dev.bits);
+        LAUNCH_CHECK();
+        SC_TRY(copy_outputs(h, o, dev, batch, dev_io, s));
+    }
     // decoded[:N] = e[:N] XOR msg[:N] = e[:N] must equal the indicator of y (hqc.py:742-749)
     SC_TRY(mc_finish(h, batch, T, N, dev_io, s, out_success, out_iters));
     return settle.done();
+}
+
+int scaldpc_mc_hqc_run_soft(scaldpc_bp *h, int32_t omega, const double *weights, const uint8_t *flips, const float *probs,
+                            const int32_t *costs, int32_t K, int64_t first_trial, int32_t batch, uint64_t seed,
+                            int32_t max_iter_arg, int32_t method, float alpha, uint32_t flags, void *stream,
+                            uint8_t *out_success, int32_t *out_iters, uint8_t *out_msg, int32_t *out_y, uint8_t *out_outcome,
+                            int32_t *out_flips, int32_t *out_cost)
+{
+    return mc_hqc_run_soft_body(h, omega, weights, flips, probs, costs, K, first_trial, batch, seed, max_iter_arg, method, alpha,
+                                flags, stream, out_success, out_iters, out_msg, out_y, out_outcome, out_flips, out_cost, nullptr,
+                                nullptr);
+}
+
+int scaldpc_mc_hqc_run_stats(scaldpc_bp *h, int32_t omega, const double *weights, const uint8_t *flips, const float *probs,
+                             const int32_t *costs, int32_t K, int64_t first_trial, int32_t batch, uint64_t seed,
+                             int32_t max_iter_arg, int32_t method, float alpha, uint32_t flags, void *stream,
+                             uint8_t *out_success, int32_t *out_iters, uint8_t *out_msg, int32_t *out_y, uint8_t *out_outcome,
+                             int32_t *out_flips, int32_t *out_cost, int32_t *out_stats, uint8_t *out_bits)
+{
+    if (!out_stats) return fail(SCALDPC_EINVAL, "out_stats is NULL");
+    return mc_hqc_run_soft_body(h, omega, weights, flips, probs, costs, K, first_trial, batch, seed, max_iter_arg, method, alpha,
+                                flags, stream, out_success, out_iters, out_msg, out_y, out_outcome, out_flips, out_cost, out_stats,
+                                out_bits);
 }
 
 int scaldpc_bp_configure(scaldpc_bp *h, const char *key, const char *value)

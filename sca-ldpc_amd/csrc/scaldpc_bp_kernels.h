@@ -2037,4 +2037,59 @@ __global__ __launch_bounds__(64) void k_scatter_post(float *__restrict__ post, i
     if (sl >= 0) post[((size_t)t * n + v) * TW + c] = post2[((size_t)(sl >> 6) * n + v) * TW + (sl & 63)];
 }
 
+// ---------------------------------------------------------------------------
+// K6, continued: the per-trial counters of scaldpc_mc_hqc_run_stats.  The kernel belongs with k_mc_compare; its definition
+// stands at the END of this header so that the kernels above keep their order in the code object.  Where a new kernel lands
+// there moves every other one, and the plain sweep (scaldpc_mc_hqc_run_soft, which never launches this kernel) measured
+// 0.2 - 0.9 ms per 161 ms call above the commit before with the definition up there, 0.4 ms with it here; the numbers, and
+// what is not understood about them, are in profiles/hqc_stats/hqc_stats_cost_mi355x.txt.
+// ---------------------------------------------------------------------------
+// The counters tracking.add_decoder_stats keeps per decode (simulate/hqc.py:709-758), for every trial of a sweep, from the three
+// bit planes a finished scaldpc_mc_hqc_run_stats call holds -- a column count of bit matrices, nothing else is read:
+//   hard   u64 [tile][n]  the error estimate            truth  u64 [tile][n]  the secret's indicator (columns < N)
+//   recv   u64 [tile][n]  the message: columns >= N carry the reported check bits
+//   stats  int [batch][5], zeroed by the caller: unsatisfied, good_flips, bad_flips, found_bad_satisfied_checks,
+//          found_bad_unsatisfied_checks.  The decoded check bit is hard ^ reported, so a check reported 0 and decoded 1 is
+//          hard & ~reported, and a check reported 1 and decoded 0 is hard & reported.
+// lane = trial (the shape of k_mc_hqc_outcome): a wave takes MC_STATS_RUN consecutive nodes of a tile, reads every plane word
+// once as a wave-uniform value, and lane c adds its bit.  The four waves of a block meet in LDS; one integer atomicAdd per
+// lane and nonzero counter leaves the block (integer sums: the result does not depend on the order).  The lanes of a ragged
+// last tile report nothing.  grid (ceil(n / (4 MC_STATS_RUN)), T), block 256.
+constexpr int MC_STATS_RUN = 256;
+__global__ __launch_bounds__(256) void k_mc_hqc_stats(const u64 *__restrict__ hard, const u64 *__restrict__ truth,
+                                                      const u64 *__restrict__ recv, int n, int N, int batch,
+                                                      int *__restrict__ stats)
+{
+    __shared__ int part[5][TW];
+    const int lane = threadIdx.x & 63, w = rfl(threadIdx.x >> 6), t = blockIdx.y;
+    for (int i = threadIdx.x; i < 5 * TW; i += 256) (&part[0][0])[i] = 0;
+    __syncthreads();
+    const int v0 = min((blockIdx.x * 4 + w) * MC_STATS_RUN, n), v1 = min(v0 + MC_STATS_RUN, n);
+    const size_t row = (size_t)t * n;
+    int unsat = 0, good = 0, bad = 0, bad_sat = 0, bad_unsat = 0;
+#pragma unroll 4
+    for (int v = v0; v < min(v1, N); v++) {  // the secret's columns
+        const u64 e = hard[row + v], y = truth[row + v];
+        good += (int)(((e & y) >> lane) & 1);
+        bad += (int)(((e & ~y) >> lane) & 1);
+    }
+#pragma unroll 4
+    for (int v = max(v0, N); v < v1; v++) {  // the check columns
+        const u64 e = hard[row + v], c = recv[row + v];
+        unsat += (int)((c >> lane) & 1);
+        bad_sat += (int)(((e & ~c) >> lane) & 1);
+        bad_unsat += (int)(((e & c) >> lane) & 1);
+    }
+    const int mine[5] = {unsat, good, bad, bad_sat, bad_unsat};
+#pragma unroll
+    for (int k = 0; k < 5; k++)
+        if (mine[k]) atomicAdd(&part[k][lane], mine[k]);
+    __syncthreads();
+    const long b = (long)t * TW + lane;
+    if (w != 0 || b >= batch) return;
+#pragma unroll
+    for (int k = 0; k < 5; k++)
+        if (part[k][lane]) atomicAdd(stats + (size_t)b * 5 + k, part[k][lane]);
+}
+
 }  // namespace

@@ -11,6 +11,8 @@ decoder in ONE batched call.
   hqc_decode_batch                the same for many trials with their own certainties, one soft call
   hqc_oracle_sweep                such trials at a fixed number of checks, answered by the wrapped oracle's law
                                   (simulate/hqc.py:782-871) on the device: successes, iterations, oracle calls spent
+  hqc_attack_curve                the same trials followed through the attack loop (simulate/hqc.py:953-984) on ONE growing
+                                  decoder: checks needed per key, and the reference's decoder_stats table, counted on the device
   regular_ldpc_code & co          main.py:189-276              (the four FER commands, as functions)
 
 The decoder classes are parameters (default: the HIP decoders) so that the host logic
@@ -210,7 +212,8 @@ def qary_fer_sweep(H, B, error_rate, runs, seed, chunk=4096, decoder_class=None)
     return res
 
 
-def hqc_oracle_sweep(Hin, N, omega, table, runs, seed, chunk=4096, bp_method="product_sum", max_iter=100, bp_decoder=None):
+def hqc_oracle_sweep(Hin, N, omega, table, runs, seed, chunk=4096, bp_method="product_sum", max_iter=100, bp_decoder=None,
+                     want_stats=False):
     """A sweep of synthetic hqc.decode() trials at a FIXED number of checks (the rows of Hin) under the law of the attack's
     oracle: every check is answered by an outcome of `table` (`trials.wrapped_oracle_table`: the repeated measurements of
     wrapped_hqc_decoding_oracle, simulate/hqc.py:782-871), drawn on the device conditional on the check's true value, and
@@ -222,7 +225,10 @@ def hqc_oracle_sweep(Hin, N, omega, table, runs, seed, chunk=4096, bp_method="pr
       oracle_calls, oracle_calls_mean                  total and per trial, over all trials,
       oracle_calls_success, oracle_calls_success_mean  the same over the successful trials (mean None: none succeeded);
     the four oracle-call fields are None when the table has no costs).  What the paper's plots report -- oracle calls per
-    recovered key -- is oracle_calls / successes."""
+    recovered key -- is oracle_calls / successes.
+    want_stats: the sweep also counts, on the device, what tracking.add_decoder_stats records per decode (hqc.py:709-758); the
+    result gains `stats` and `stats_success`: {counter: total} over all trials and over the successful ones, the counters
+    being HQC_STATS_COLUMNS."""
     g = TannerGraph.coerce(Hin)
     if g.n != N:
         raise ValueError(f"Hin has {g.n} columns, N = {N}")
@@ -234,10 +240,15 @@ def hqc_oracle_sweep(Hin, N, omega, table, runs, seed, chunk=4096, bp_method="pr
     counted = table.get("costs") is not None
     hist = np.zeros(max_iter + 1, dtype=np.int64)
     successes = flips = calls = calls_ok = 0
+    sums = np.zeros((2, len(HQC_STATS_COLUMNS)), dtype=np.int64)  # all trials / the successful ones
+    extra = dict(want_stats=True) if want_stats else {}
     try:
         for first in range(0, runs, chunk):
-            out = bpd.mc_hqc_run_soft(min(chunk, runs - first), omega, table, seed, first_trial=first, max_iter=max_iter)
+            out = bpd.mc_hqc_run_soft(min(chunk, runs - first), omega, table, seed, first_trial=first, max_iter=max_iter, **extra)
             ok = np.asarray(out["success"]).astype(bool)
+            if want_stats:
+                st = np.asarray(out["stats"], dtype=np.int64)
+                sums += [st.sum(axis=0), st[ok].sum(axis=0)]
             successes += int(ok.sum())
             hist += np.bincount(np.asarray(out["iters"]), minlength=max_iter + 1)[: max_iter + 1]
             flips += int(np.asarray(out["flips"], dtype=np.int64).sum())
@@ -253,7 +264,88 @@ def hqc_oracle_sweep(Hin, N, omega, table, runs, seed, chunk=4096, bp_method="pr
     if counted:
         res.update(oracle_calls=calls, oracle_calls_mean=calls / runs if runs else None, oracle_calls_success=calls_ok,
                    oracle_calls_success_mean=calls_ok / successes if successes else None)
+    if want_stats:
+        res.update(stats={k: int(v) for k, v in zip(HQC_STATS_COLUMNS, sums[0])},
+                   stats_success={k: int(v) for k, v in zip(HQC_STATS_COLUMNS, sums[1])})
     return res
+
+
+def hqc_attack_curve(first_row_support, N, rows, omega, table, runs, seed, decode_every, max_checks=None, chunk=4096,
+                     bp_method="product_sum", max_iter=100, bp_decoder=None):
+    """How many checks does a key need?  The reference's attack loop (`add_checks`, simulate/hqc.py:953-984: add rows, decode
+    every DECODE_EVERY, stop at the first success) for `runs` keys at once, every decode on the device.
+
+    A trial of `BpDecoder.mc_hqc_run_soft` depends on (seed, global trial index) alone: its secret does not depend on the
+    number of rows, and check r always takes the same random word.  So the trials of a graph of R rows are the first R answers
+    of the SAME trials on that graph with more rows appended, and re-running one sweep with one seed on a growing decoder
+    follows `runs` keys through the loop.  ONE live decoder is kept: it starts on the first `decode_every` rows of
+    circulant(first_row_support)[rows] (sparse, each row with its identity column, as `HqcCheckAccumulator` builds them), grows
+    by `decode_every` rows per step (`append_rows`) up to `max_checks` (default: all of `rows`; a last partial step is not
+    taken), and at every step decodes trials 0 .. runs - 1, `chunk` at a time, with the per-trial counters of
+    tracking.add_decoder_stats counted on the device (`want_stats`).  Trials that already succeeded are decoded again at
+    the later steps -- a call decodes a contiguous range of trial indices -- and converge within a few iterations; their
+    later results are not recorded.  The result does not depend on `chunk`.
+
+    Returns dict(
+      steps                int32 [S]: the numbers of checks R decoded at,
+      successes            int64 [S]: trials whose decode at that step succeeded (already-recovered keys included),
+      checks_needed        int32 [runs]: R at the trial's FIRST success, -1 if it never succeeded,
+      oracle_calls_needed  int64 [runs]: the oracle calls the trial had spent at that step (its `cost`), -1 where
+                           checks_needed is; None when the table has no costs,
+      decoder_stats        one row per (trial, step) up to and including the trial's first success -- the reference's attack
+                           stops there (hqc.py:980-982) -- ordered by trial, then step: dicts with the keys
+                           `write_decoder_stats_csv` takes (checks, oracle_calls (None without costs), HQC_STATS_COLUMNS,
+                           success) and `trial`)."""
+    k = np.sort(np.asarray(first_row_support, dtype=np.int64))
+    rows = np.asarray(rows, dtype=np.int64)
+    step = int(decode_every)
+    top = rows.size if max_checks is None else min(int(max_checks), rows.size)
+    if step < 1 or runs < 0 or chunk < 1:
+        raise ValueError("decode_every and chunk must be positive and runs must not be negative")
+    if top < step:
+        raise ValueError(f"{top} rows do not make one step of decode_every = {step}")
+    W = k.size
+    # row i: the sorted support of row rows[i] of the circulant, then its identity column N + i -- CSR as it stands
+    cols = np.concatenate([np.sort((rows[:top, None] - k[None, :]) % N, axis=1), N + np.arange(top)[:, None]], axis=1).astype(np.int32)
+    ptr = np.arange(step + 1, dtype=np.int32) * (W + 1)
+    steps = np.arange(step, top + 1, step, dtype=np.int32)
+    counted = table.get("costs") is not None
+    successes = np.zeros(steps.size, dtype=np.int64)
+    needed = np.full(runs, -1, dtype=np.int32)
+    calls = np.full(runs, -1, dtype=np.int64) if counted else None
+    per_trial = [[] for _ in range(runs)]
+    # the check columns' shared priors are replaced per trial: any probability does
+    shared = np.concatenate([np.full(N, omega / N, dtype=np.float64), np.full(step, 0.5, dtype=np.float64)])
+    with np.errstate(divide="ignore"):
+        bpd = (bp_decoder or _default_bp())(TannerGraph.from_csr(step, N + step, ptr, cols[:step].reshape(-1)), max_iter=max_iter,
+                                            bp_method=bp_method, channel_probs=shared)
+    try:
+        for s, R in enumerate(steps):
+            R = int(R)
+            if s:
+                bpd.append_rows(ptr, cols[R - step : R].reshape(-1), N + R, np.full(step, 0.5, dtype=np.float64))
+            for first in range(0, runs, chunk):
+                out = bpd.mc_hqc_run_soft(min(chunk, runs - first), omega, table, seed, first_trial=first, max_iter=max_iter,
+                                          want_stats=True)
+                ok = np.asarray(out["success"]).astype(bool)
+                st = np.asarray(out["stats"])
+                cost = np.asarray(out["cost"], dtype=np.int64) if counted else None
+                successes[s] += int(ok.sum())
+                for i in np.flatnonzero(needed[first : first + ok.size] < 0):
+                    t = first + int(i)
+                    row = {"trial": t, "checks": R, "oracle_calls": int(cost[i]) if counted else None}
+                    row.update(zip(HQC_STATS_COLUMNS, (int(v) for v in st[i])))
+                    row["success"] = bool(ok[i])
+                    per_trial[t].append(row)
+                    if ok[i]:
+                        needed[t] = R
+                        if counted:
+                            calls[t] = cost[i]
+    finally:
+        if hasattr(bpd, "close"):
+            bpd.close()
+    return dict(steps=steps, successes=successes, checks_needed=needed, oracle_calls_needed=calls,
+                decoder_stats=[row for rows_of in per_trial for row in rows_of])
 
 
 def hqc_decode(N, Hin, checks, y_sparse, bp_decoder=None, max_iter=100):
@@ -502,6 +594,8 @@ class HqcCheckAccumulator:
 
 STATS_COLUMNS = ["label", "alg", "weight", "epsilon0", "epsilon1", "checks", "oracle_calls", "unsatisfied", "good_flips",
                  "bad_flips", "found_bad_satisfied_checks", "found_bad_unsatisfied_checks", "success"]  # fmt: skip
+# the per-trial counters of `BpDecoder.mc_hqc_run_soft(want_stats=True)`, in the order of its `stats` columns (bp.HQC_STATS_COLUMNS)
+HQC_STATS_COLUMNS = tuple(STATS_COLUMNS[7:12])
 
 
 def write_decoder_stats_csv(path, decoder_stats, label, alg, weight, epsilon):
