@@ -1,7 +1,10 @@
 // The two row updates of the min-sum record form compared message for message: `row_old` below is the first version
 // (compare-select recurrences with per-lane state, ballots for the masks -- the recurrences of k_check_minsum_x word for
-// word), check_minsum_row_rec is the PRODUCT's (scaldpc_bp_kernels.h, included as it stands: scalar lane masks,
-// v_med3 / v_min on clamped magnitudes, v_writelane through the LLVM intrinsic).  Inputs full of ties, zeros, negative
+// word), check_minsum_row_rec is the PRODUCT's (scaldpc_bp_kernels.h, included as it stands: scalar parity mask,
+// v_med3 / v_min on clamped magnitudes, the arg-min as a byte per lane, and -- in its bootstrap form, the one run here --
+// the sign masks through v_writelane, the LLVM intrinsic).  The product's per-edge masks are rebuilt from what it
+// writes, as its variable pass does: negative = sign mask XOR the row's parity word, arg-min = (arg byte == edge).
+// Inputs full of ties, zeros, negative
 // zeros, NaN, +-inf and FLT_MAX, EVERY degree 1 .. 64.  A difference is a bug: in round 3 this program found the
 // VALU-writes-SGPR -> inline-asm v_writelane hazard on degree-1 rows.  It is a different translation unit from the
 // product's (other register pressure, other schedule): the product kernels themselves face the oracle on every row
@@ -57,14 +60,14 @@ __device__ __forceinline__ void row_old(const float *p, u64 synd_mask, float alp
 }
 
 template <int DEG>
-__global__ void k(const float *msg, const u64 *synd, float alpha, float *recA, float *rec2A, ulonglong2 *maskA, float *recB, float *rec2B, ulonglong2 *maskB,
-                  const int *iota)
+__global__ void k(const float *msg, const u64 *synd, float alpha, float *recA, float *rec2A, ulonglong2 *maskA, float *recB, float *rec2B, u64 *sgnB,
+                  unsigned char *argB, u64 *parB, const int *iota)
 {
     const int lane = threadIdx.x, r = blockIdx.x;
     const float *p = msg + (size_t)r * DEG * TW + lane;
     row_old<DEG, false>(p, synd[r], alpha, nullptr, nullptr, recA + r * TW, rec2A + r * TW, maskA + r * DEG, lane);
     // (the product lays its masks out by position in the variable pass's edge list; here edge k's position is k)
-    check_minsum_row_rec<DEG>(p, synd[r], alpha, recB + r * TW, rec2B + r * TW, maskB + r * DEG, lane, iota);
+    check_minsum_row_rec<DEG, true>(p, synd[r], alpha, recB + r * TW, rec2B + r * TW, argB + r * TW, parB + r, sgnB + r * DEG, lane, iota);
 }
 template <int DEG>
 int run(int rows, unsigned seed)
@@ -82,21 +85,31 @@ int run(int rows, unsigned seed)
     }
     std::vector<u64> sy(rows);
     for (auto &v : sy) v = ((u64)rand() << 40) ^ ((u64)rand() << 20) ^ rand();
-    float *d, *ra, *r2a, *rb, *r2b; u64 *ds; ulonglong2 *ma, *mb; int *iota;
+    float *d, *ra, *r2a, *rb, *r2b; u64 *ds, *sb, *pb; ulonglong2 *ma; unsigned char *ab; int *iota;
     int hi[64];
     for (int i = 0; i < 64; i++) hi[i] = i;
     hipMalloc(&iota, sizeof hi); hipMemcpy(iota, hi, sizeof hi, hipMemcpyHostToDevice);
     hipMalloc(&d, h.size() * 4); hipMalloc(&ds, rows * 8);
     hipMalloc(&ra, rows * TW * 4); hipMalloc(&r2a, rows * TW * 4); hipMalloc(&rb, rows * TW * 4); hipMalloc(&r2b, rows * TW * 4);
-    hipMalloc(&ma, rows * DEG * 16); hipMalloc(&mb, rows * DEG * 16);
+    hipMalloc(&ma, rows * DEG * 16); hipMalloc(&sb, rows * DEG * 8); hipMalloc(&ab, rows * TW); hipMalloc(&pb, rows * 8);
     hipMemcpy(d, h.data(), h.size() * 4, hipMemcpyHostToDevice); hipMemcpy(ds, sy.data(), rows * 8, hipMemcpyHostToDevice);
-    hipLaunchKernelGGL(k<DEG>, dim3(rows), dim3(64), 0, 0, d, ds, 0.75f, ra, r2a, ma, rb, r2b, mb, iota);
+    hipLaunchKernelGGL(k<DEG>, dim3(rows), dim3(64), 0, 0, d, ds, 0.75f, ra, r2a, ma, rb, r2b, sb, ab, pb, iota);
     hipDeviceSynchronize();
     std::vector<float> A(rows * TW), A2(rows * TW), B(rows * TW), B2(rows * TW);
-    std::vector<u64> MA(rows * DEG * 2), MB(rows * DEG * 2);
+    std::vector<u64> MA(rows * DEG * 2), MB(rows * DEG * 2), SB(rows * DEG), PB(rows);
+    std::vector<unsigned char> AB(rows * TW);
     hipMemcpy(A.data(), ra, A.size() * 4, hipMemcpyDeviceToHost); hipMemcpy(A2.data(), r2a, A.size() * 4, hipMemcpyDeviceToHost);
     hipMemcpy(B.data(), rb, A.size() * 4, hipMemcpyDeviceToHost); hipMemcpy(B2.data(), r2b, A.size() * 4, hipMemcpyDeviceToHost);
-    hipMemcpy(MA.data(), ma, MA.size() * 8, hipMemcpyDeviceToHost); hipMemcpy(MB.data(), mb, MB.size() * 8, hipMemcpyDeviceToHost);
+    hipMemcpy(MA.data(), ma, MA.size() * 8, hipMemcpyDeviceToHost); hipMemcpy(SB.data(), sb, SB.size() * 8, hipMemcpyDeviceToHost);
+    hipMemcpy(AB.data(), ab, AB.size(), hipMemcpyDeviceToHost); hipMemcpy(PB.data(), pb, PB.size() * 8, hipMemcpyDeviceToHost);
+    // the product's per-edge masks, rebuilt as k_var_rec rebuilds them
+    for (int r = 0; r < rows; r++)
+        for (int e = 0; e < DEG; e++) {
+            u64 am = 0;
+            for (int l = 0; l < TW; l++) am |= (u64)(AB[r * TW + l] == e) << l;
+            MB[(r * DEG + e) * 2] = SB[r * DEG + e] ^ PB[r];
+            MB[(r * DEG + e) * 2 + 1] = am;
+        }
     // compare the MESSAGES the variable pass would rebuild (an arg-min flag on another edge of the same magnitude is the same message)
     long bad = 0, badrec = 0, badneg = 0;
     for (int r = 0; r < rows; r++)
@@ -112,7 +125,7 @@ int run(int rows, unsigned seed)
             }
         }
     printf("DEG %2d: %ld of %d messages differ, %ld records, %ld signs\n", DEG, bad, rows * TW * DEG, badrec, badneg);
-    for (void *q : {(void *)d, (void *)ds, (void *)ra, (void *)r2a, (void *)rb, (void *)r2b, (void *)ma, (void *)mb, (void *)iota}) (void)hipFree(q);
+    for (void *q : {(void *)d, (void *)ds, (void *)ra, (void *)r2a, (void *)rb, (void *)r2b, (void *)ma, (void *)sb, (void *)ab, (void *)pb, (void *)iota}) (void)hipFree(q);
     return bad != 0 || badrec != 0;
 }
 template <int DEG>

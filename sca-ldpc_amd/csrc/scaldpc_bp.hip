@@ -204,10 +204,12 @@ struct scaldpc_bp : HandleStreams {
     // iteration 1 without its check pass: {first check-to-variable message of a zero-syndrome codeword, row} per position
     // of the re-laid edge list; valid for one (method, alpha of iteration 1) and the current priors / graph
     Buf<int2> d_first_tab;
-    // record form of min-sum on the tile kernels: per (tile, row) the two magnitudes, per (tile, edge) two lane masks;
-    // d_csc_row = row of every position of the re-laid edge list (inside d_tile_tab)
+    // record form of min-sum on the tile kernels: d_rec = per tile a block of rec_tile_floats(m) floats (per row the two
+    // magnitudes, the arg-min byte per codeword and the parity mask), d_mask = per (tile, position of the re-laid edge
+    // list) the lane mask "the variable pass's message on this edge is <= 0";
+    // d_csc_row = row word of every position of the re-laid edge list (inside d_tile_tab; scaldpc_rec_pack.h)
     Buf<float> d_rec;
-    Buf<ulonglong2> d_mask;
+    Buf<u64> d_mask;
     int cap_rec_group = 0;
     int *d_csc_row = nullptr, *d_var_rows = nullptr, *d_csr_pos = nullptr;  // views into d_tile_tab
     bool var_reversed = false;  // the column records are laid out heaviest first (column order 2): the degree-1 bucket is at the END
@@ -497,7 +499,10 @@ int ensure_tile_tables(scaldpc_bp *h)
             md[3] = hv.bk.maxd[b];
             for (int k = 0; k < d; k++) {
                 relaid[pos + k] = csc_edge[(size_t)col_ptr[v] + k];
-                relaid_row[pos + k] = edge_row[relaid[pos + k]];
+                const int e = relaid[pos + k], r = edge_row[e];
+                // (the row word of the record form: row | index in the row << 24; a graph it cannot hold never runs
+                // that form -- rec_form() -- and nothing else reads these tables)
+                relaid_row[pos + k] = rec_pack_row(rec_row_of(r), (e - row_ptr[r]) & (REC_MAX_ROW_DEG - 1));
                 host[o_csr_pos + relaid[pos + k]] = pos + k;
             }
             for (int k = 0; k < VAR_INLINE; k++) md[4 + k] = k < d ? relaid[pos + k] : 0;
@@ -618,8 +623,9 @@ int ensure_el_tables(scaldpc_bp *h)
 bool rec_form(const scaldpc_bp *h, int method)
 {
     // (columns of 33-64 edges: message form -- the exact-degree variable pass is compiled up to 32)
+    // (and the variable pass's row words hold 24 bits of row beside the edge's index in it: rec_rows_fit)
     return method == SCALDPC_BP_MIN_SUM && h->kn.minsum_rec && h->E > 0 && h->max_row_deg <= 64 && h->max_col_deg <= 32 &&
-           !h->hg_var.has_generic;
+           !h->hg_var.has_generic && rec_rows_fit(h->m, h->max_row_deg);
 }
 
 // message array of the tile path, G tiles (and the records of the min-sum record form)
@@ -629,7 +635,7 @@ int ensure_msg(scaldpc_bp *h, int G, int method)
     if (rec_form(h, method) && G > h->cap_rec_group) {  // (append_rows resets cap_rec_group too)
         h->d_rec.reset(); h->d_mask.reset();
         h->cap_rec_group = 0;
-        SC_TRY(h->d_rec.ensure((size_t)G * h->m * 2 * TW));
+        SC_TRY(h->d_rec.ensure((size_t)G * rec_tile_floats(h->m)));
         SC_TRY(h->d_mask.ensure((size_t)G * h->E));
         h->cap_rec_group = G;
     }
@@ -730,7 +736,8 @@ bool check_can_test(const scaldpc_bp *h, int method)
 // ft: non-null = this pass also runs the convergence test of the previous iteration (check_can_test(h, method), never `first`)
 // sp: non-null = a soft call; its FIRST check pass (the only one that reads priors) takes them per codeword
 int launch_check(scaldpc_bp *h, int method, float alpha, int G, const u64 *synd_g, const u64 *done_g, int skip_done,
-                 hipStream_t s, bool first = false, int tile0 = 0, const FusedTest *ft = nullptr, const SoftPrior *sp = nullptr)
+                 hipStream_t s, bool first = false, int tile0 = 0, const FusedTest *ft = nullptr, const SoftPrior *sp = nullptr,
+                 bool boot = false)
 {
     if (h->E == 0) return 0;
     float *const msg0 = h->d_msg + (size_t)tile0 * h->E * TW;  // tile0: first tile of a sub-group inside the group's array
@@ -752,13 +759,17 @@ int launch_check(scaldpc_bp *h, int method, float alpha, int G, const u64 *synd_
         // (a first check pass -- iteration 1 with first_fused off, or of a soft call -- reads the priors and writes
         // MESSAGES: the message form's kernel, followed by the message form's variable pass; the records start with
         // iteration 2)
-        float *const rec0 = h->d_rec + (size_t)tile0 * h->m * 2 * TW;
-        ulonglong2 *const mask0 = h->d_mask + (size_t)tile0 * h->E;
+        // boot: the first record-form pass of these tiles in a call -- the sign masks a k_var_rec would have left are
+        // not there yet (the messages come from k_var_first / k_var), so this pass writes them too
+        float *const rec0 = h->d_rec + (size_t)tile0 * rec_tile_floats(h->m);
+        u64 *const mask0 = h->d_mask + (size_t)tile0 * h->E;
         const FusedTest ft0 = test ? *ft : FusedTest{};
         with_cap<16, 32, 64>(h->max_row_deg, [&](auto cap) {
-            with_bool(test, [&](auto par) {
-                hipLaunchKernelGGL((k_check_minsum_rec<cap, par>), grid, block, 0, s, h->d_row_list, msg0, synd_g, done_g,
-                                   skip_done, h->m, h->E, alpha, h->d_col_idx, rec0, mask0, h->d_csr_pos, ft0);
+            with_bool(boot, [&](auto bt) {
+                with_bool(test, [&](auto par) {
+                    hipLaunchKernelGGL((k_check_minsum_rec<cap, bt, par>), grid, block, 0, s, h->d_row_list, msg0, synd_g, done_g,
+                                       skip_done, h->m, h->E, alpha, h->d_col_idx, rec0, mask0, h->d_csr_pos, ft0);
+                });
             });
         });
     } else if (h->max_row_deg <= ROW_CAP) {
@@ -839,8 +850,9 @@ int launch_var(scaldpc_bp *h, int G, float *post_g, u64 *hard_g, const u64 *done
         });
     } else if (rec) {  // the check pass left records, not messages (rec_form)
         // light: a pass without output after iteration 1.  A column of degree <= 1 always sends its prior; iteration 1
-        // has written that into the message array and the record check pass never overwrites it, so such a pass has
-        // nothing to do for the first bucket (the identity block of an HQC graph: 4000 of 21669 column waves per tile).
+        // has written that into the message array and the record check pass never overwrites it (its sign mask is the
+        // bootstrap check pass's, and stays true), so such a pass has nothing to do for the first bucket (the identity
+        // block of an HQC graph: 4000 of 21669 column waves per tile).
         const int n1 = (h->var_bk.nb > 0 && h->var_bk.maxd[0] == 1) ? h->var_bk.blk[1] : 0;
         const bool slim = light && !write_out && n1 > 0 && n1 < nblk;
         const int nb_launch = slim ? nblk - n1 : nblk;
@@ -851,7 +863,7 @@ int launch_var(scaldpc_bp *h, int G, float *post_g, u64 *hard_g, const u64 *done
         with_cap<16, 32>(h->max_col_deg, [&](auto cap) {  // (columns wider than 32 take the message form: rec_form)
             with_prior(h, sp, [&](auto P, auto prior) {
                 hipLaunchKernelGGL((k_var_rec<cap, decltype(P)>), gridr, dim3(256), 0, s, h->d_var_meta, h->d_var_rows, h->d_csc_list,
-                                   h->d_csc_row, prior, msg0, h->d_rec + (size_t)tile0 * h->m * 2 * TW,
+                                   h->d_csc_row, prior, msg0, h->d_rec + (size_t)tile0 * rec_tile_floats(h->m),
                                    h->d_mask + (size_t)tile0 * h->E, post_g, hard_g, done_g, skip_done, h->n, h->m, h->E, write_out,
                                    blk0, xmap);
             });
@@ -1162,6 +1174,8 @@ int iterate_tiles(scaldpc_bp *h, Lanes &lanes, const TileState &st, int g0, int 
     // sweep, profiles/r03/ab_test_overlap.log; so was the two-launch k_parity + k_finalize form in this loop.)
     const bool ride = early && h->kn.fuse_test && check_can_test(h, method) && pw >= FT_WORDS;
     bool verdict_pending[MAX_LANES] = {};  // lane k's last variable pass has not been tested yet: its next check pass will
+    const bool recf = rec_form(h, method);
+    bool rec_booted[MAX_LANES] = {};  // lane k has run its first record-form check pass (the one that also writes the sign masks)
     // (re-)establish the one-kernel offset between neighbouring lanes -- in a chained group too: carrying the offset over
     // instead measured +0.5 % on the config-5 sweep and -2 % on the fixed-iteration bench, profiles/r04/ab_chain_unseen_groups.log
     bool set_phase = true;
@@ -1179,8 +1193,10 @@ int iterate_tiles(scaldpc_bp *h, Lanes &lanes, const TileState &st, int g0, int 
                 verdict_pending[k] = false;
             }
             const SoftPrior spv = soft ? soft_prior(h, st, ta) : SoftPrior{};
+            const bool first = fused && it == 1, boot = recf && !first && !rec_booted[k];
+            if (boot) rec_booted[k] = true;
             SC_TRY(launch_check(h, method, alpha_for(alpha, it), gs[k], st.synd + (size_t)ta * h->m, st.done + ta, skip, lanes[k],
-                                fused && it == 1, t0[k], ft.hard ? &ft : nullptr, soft ? &spv : nullptr));
+                                first, t0[k], ft.hard ? &ft : nullptr, soft ? &spv : nullptr, boot));
             if (set_phase && k + 1 < nl) {
                 SC_HIP(hipEventRecord(h->ev_phase[k + 1], lanes[k]));
                 SC_HIP(hipStreamWaitEvent(lanes[k + 1], h->ev_phase[k + 1], 0));
@@ -1193,7 +1209,7 @@ int iterate_tiles(scaldpc_bp *h, Lanes &lanes, const TileState &st, int g0, int 
             const SoftPrior spv = soft ? soft_prior(h, st, ta) : SoftPrior{};
             SC_TRY(launch_var(h, gs[k], st.post ? st.post + (size_t)ta * h->n * TW : nullptr, st.hard + (size_t)ta * h->n,
                               st.done + ta, skip, (early || last) ? 1 : 0, lanes[k], t0[k],
-                              no_check ? st.synd + (size_t)ta * h->m : nullptr, it > 1 && rec_form(h, method), it > 1,
+                              no_check ? st.synd + (size_t)ta * h->m : nullptr, it > 1 && recf, it > 1,
                               soft ? &spv : nullptr));
             if (ride && !last && !poll) {
                 verdict_pending[k] = true;  // the next check pass of this lane carries the test

@@ -5,6 +5,7 @@
 #include "scaldpc_logf.h"  // glibc's logf on the device (k_soft_convert)
 #include "scaldpc_mc_law.h"  // McHqcLaw: the outcome table k_mc_hqc_outcome takes by value
 #include "scaldpc_philox.h"
+#include "scaldpc_rec_pack.h"  // row words of the record form's variable pass
 #include <type_traits>
 
 // v_writelane_b32 as an instruction the COMPILER emits: ROCm 7.2's clang has no __builtin_amdgcn_writelane, but the LLVM
@@ -26,9 +27,6 @@ constexpr int MAXB = 8;      // degree buckets per node kind
 constexpr int ROW_CAP = 64;  // largest register-resident row degree (also the sign-mask width)
 #ifndef REC_CHUNK
 #define REC_CHUNK 8
-#endif
-#ifndef REC_KEEP_AG
-#define REC_KEEP_AG 18
 #endif
 
 __device__ __forceinline__ int rfl(int x) { return __builtin_amdgcn_readfirstlane(x); }
@@ -723,39 +721,55 @@ __global__ __launch_bounds__(256) void k_check_minsum_x(const int *__restrict__ 
 // RECORD form of the min-sum check update (rows of degree <= 64).  A min-sum check sends only TWO magnitudes -- the
 // smallest incoming |x| to every edge but the arg-min, the second smallest to that one -- and a sign per edge.  Instead
 // of 4 B per edge and codeword (which the variable pass reads back as a gather), this pass leaves the message array
-// alone and writes, per (row, tile),
+// alone and writes, per (row, tile), NOTHING per edge:
 //     rec  [tile][2][row][64]  float : m1 * alpha | m2 * alpha         (8 B per row and codeword; two dense planes per
 //                                      tile: interleaved by row, the always-read first magnitudes would sit at a
 //                                      512-B stride, i.e. in half of the L2's sets and channels)
-//     mask [tile][edge]        2 x u64 : lane masks "message negative", "this edge is the codeword's arg-min"
-//                                                                      (0.25 B per edge and codeword)
-// and the variable pass (k_var_rec) rebuilds every message from them: c2v = +-(arg-min ? rec[1] : rec[0]).  Since
-// m * (-alpha) == -(m * alpha) in IEEE arithmetic, that is the float k_check_minsum_x would have stored, bit for bit;
-// the sums that follow run in the same order, so nothing about parity changes -- only the bytes: the check pass
-// reads 4 B per edge and writes next to nothing, and the 2 MB of records per tile (HQC-128) are L2-sized.
+//     arg  [tile][row][64]     u8    : index IN THE ROW of the codeword's arg-min edge -- the FIRST edge whose |x|
+//                                      equals m1; REC_NO_ARG where no edge attains it (all inputs NaN or infinite)
+//     par  [tile][row]         u64   : lane mask, syndrome bit XOR the XOR over the row's edges of (x <= 0)
+// (arg and par are further planes of a tile's block of d_rec: rec_tile_floats().)  The sign a check sends on edge e is
+// par XOR (x_e <= 0), and x_e is the message the VARIABLE pass itself stored on that edge one pass earlier, so that pass
+// keeps the second factor, per column and contiguously:
+//     sgn  [tile][position]    u64   : lane mask "the v2c message at this position of the variable pass's edge order
+//                                      is <= 0" (a float compare: +-0 count, NaN does not), written by k_var_rec from
+//                                      the very floats it stores
+// and rebuilds every message: c2v = +-(arg-min ? rec[1] : rec[0]).  Since m * (-alpha) == -(m * alpha) in IEEE
+// arithmetic, that is the float k_check_minsum_x would have stored, bit for bit; the sums that follow run in the same
+// order, so nothing about parity changes -- only the bytes: the check pass reads 4 B per edge and writes next to
+// nothing, and the 2 MB of records per tile (HQC-128) are L2-sized.
+// The FIRST record-form check pass of a group (BOOT) has no sgn from a k_var_rec before it -- its inputs were written
+// by k_var_first or k_var -- so it also writes sgn[pos[k]] = ballot(x_k <= 0) itself, scattered by position.
 // Measured before it was built: profiles/microbench/minsum_records.hip.
 // ---------------------------------------------------------------------------
 // The row update is written for VALU issue, which is what bounds the record-form kernels once the bytes are gone (a
-// wave64 instruction holds its SIMD for 4 cycles; the first version spent 25 instructions per edge here, 1274 per row
-// of the HQC-128 graph).  Per-lane state is only the two minima; everything that is one bit per codeword lives in
-// 64-bit SCALAR lane masks and is combined on the scalar unit:
+// wave64 instruction holds its SIMD for 4 cycles).  Per-lane state is the two minima and the arg-min index; the parity
+// is one bit per codeword and lives in a 64-bit SCALAR lane mask:
 //   sweep 1, per edge: negative? -> v_cmp into a mask, parity ^= mask (scalar); |x| clamped to FLT_MAX (v_min: a NaN
 //            or infinite input never wins a strict compare against minima that start at FLT_MAX, so the clamp changes
 //            nothing the loop form computes), m2 = med3(a, m1, m2), m1 = min(m1, a)  -- the compare-select recurrences
 //            of k_check_minsum_x, value for value (a < m1: m2 takes the old m1; m1 <= a < m2: m2 takes a; else nothing);
-//   sweep 2, per edge: negative? again (the inputs are still in registers), |x| == m1 -> mask; the arg-min is the FIRST
-//            edge that attains m1, as `ix` was: arg = eq & ~found, found |= eq (scalar); sign = negative ^ parity
-//            (scalar); the two masks go into lane k of the output registers with v_writelane.
-// 10 VALU instructions per edge.
-template <int DEG>
+//   sweep 2, per edge, LAST edge first: idx = (|x_k| == m1) ? k : idx, so the first edge that attains m1 wins, as
+//            `ix` did.  A compare and a select: 6 VALU instructions per edge in all.
+//   BOOT only, per edge: negative? again (the inputs are still in registers) -> lane k of two registers with v_writelane.
+constexpr unsigned REC_NO_ARG = 255;  // (no row has an edge 255: rows of the record form have at most 64)
+// floats of one tile's block of d_rec: [2][m][64] magnitudes, then arg (64 bytes per row), then par (8 bytes per row);
+// whole 256-B lines
+__host__ __device__ inline size_t rec_tile_floats(int m) { return ((size_t)m * (2 * TW + TW / 4 + 2) + 63) / 64 * 64; }
+__host__ __device__ inline size_t rec_arg_off(int m) { return (size_t)m * 2 * TW; }               // in floats, from the tile's block
+__host__ __device__ inline size_t rec_par_off(int m) { return (size_t)m * (2 * TW + TW / 4); }  // (a multiple of 2: 8-B aligned)
+
+template <int DEG, bool BOOT>
 __device__ __forceinline__ void check_minsum_row_rec(const float *p, u64 synd_mask, float alpha, float *__restrict__ rec,
-                                                     float *__restrict__ rec2, ulonglong2 *__restrict__ mask, int lane,
+                                                     float *__restrict__ rec2, unsigned char *__restrict__ arg,
+                                                     u64 *__restrict__ par_out, u64 *__restrict__ sgn, int lane,
                                                      const int *__restrict__ pos)
 {
-    // the masks are laid out in the variable pass's order (position of the edge in the re-laid edge list: a column's
-    // masks are contiguous there); lane k fetches edge k's position up front
+    // BOOT: the sign masks are laid out in the variable pass's order (position of the edge in the re-laid edge list: a
+    // column's masks are contiguous there); lane k fetches edge k's position up front
     int mp = 0;
-    if (lane < DEG) mp = pos[lane];
+    if constexpr (BOOT)
+        if (lane < DEG) mp = pos[lane];
     float x[DEG];
 #pragma unroll
     for (int k = 0; k < DEG; k++) x[k] = p[(size_t)k * TW];  // (plain loads: non-temporal ones cost 5-9 % and save no byte, profiles/r04/ab_rec_nontemporal.log)
@@ -764,6 +778,16 @@ __device__ __forceinline__ void check_minsum_row_rec(const float *p, u64 synd_ma
     u64 par = ((u64)(unsigned)rfl((int)(synd_mask >> 32)) << 32) | (unsigned)rfl((int)synd_mask);  // (uniform by construction: keep it on the scalar side)
 #pragma unroll
     for (int k = 0; k < DEG; k++) {
+        // the sweep runs in chunks of REC_CHUNK edges: the parity is pinned down after a chunk and the next chunk's inputs
+        // pass through an empty asm behind that point, so at most a chunk's sign masks are live in SGPRs.  Left alone
+        // the scheduler runs the compares of the whole row ahead of the XORs (nothing wants the parity before the row's
+        // end): 354 static SGPR spills in the 64-edge build, every one a v_writelane / v_readlane pair on the VALU this
+        // kernel is bound by.
+        if (k % REC_CHUNK == 0 && k > 0) {
+            asm volatile("" : "+s"(par));
+#pragma unroll
+            for (int j = k; j < DEG && j < k + REC_CHUNK; j++) asm volatile("" : "+v"(x[j]));
+        }
         par ^= __ballot(x[k] <= 0.0f);
         float a;
         asm("v_min_f32 %0, |%1|, %2" : "=v"(a) : "v"(x[k]), "v"(fmax));
@@ -772,44 +796,51 @@ __device__ __forceinline__ void check_minsum_row_rec(const float *p, u64 synd_ma
     }
     rec[lane] = m1 * alpha;
     rec2[lane] = m2 * alpha;
-    unsigned nlo = 0, nhi = 0, alo = 0, ahi = 0;  // lane k keeps edge k's two masks
-    // The v_writelanes below are the compiler's own instructions (writelane(), top of this file): a v_writelane reading an
-    // SGPR that a VALU instruction -- a v_cmp, or a v_readlane reloading a spilled mask -- wrote fewer than 2 wait states
-    // earlier gets the OLD value on gfx950, and inside an `asm` statement nobody pads (round 3 measured it on edge 0's
-    // arg-min mask of degree-1 rows; its work-around, masks routed through a scalar instruction, could not reach the
-    // register allocator's spill reloads: VERDICT r03 #1).
-    u64 found = 0;
+    if (lane == 0) *par_out = par;
+    unsigned idx = REC_NO_ARG;
 #pragma unroll
-    for (int k = 0; k < DEG; k++) {
-        // the sweep runs in chunks of REC_CHUNK edges: a chunk's compares wait (through an empty asm on their inputs) for
-        // the previous chunk's v_writelanes, so at most a chunk's masks are live in SGPRs.  Left alone the scheduler
-        // hoists the ballots of the whole row (and keeps sweep 1's sign masks for reuse): 128+ live SGPR pairs, 684 static
-        // SGPR spills in the 64-edge build, every one a v_writelane / v_readlane pair on the VALU this kernel is bound by.
-        if (k % REC_CHUNK == 0) {
-            asm volatile("" ::"v"(nlo), "v"(nhi), "v"(alo), "v"(ahi));
-#pragma unroll
-            for (int j = k; j < DEG && j < k + REC_CHUNK; j++) asm volatile("" : "+v"(x[j]));
-        }
-        const u64 ng = __ballot(x[k] <= 0.0f) ^ par;
-        const u64 eq = __ballot(fabsf(x[k]) == m1);
-        const u64 ag = eq & ~found;
-        found |= eq;
-        nlo = writelane((unsigned)ng, k, nlo);
-        nhi = writelane((unsigned)(ng >> 32), k, nhi);
-        alo = writelane((unsigned)ag, k, alo);
-        ahi = writelane((unsigned)(ag >> 32), k, ahi);
+    for (int k = DEG - 1; k >= 0; k--) {
+        // (edge k's compare waits for edge k + 1's select, through an empty asm: compare and select pair up through VCC
+        // instead of a run of compares ahead of the selects with a live SGPR pair each)
+        asm("" : "+v"(x[k]) : "v"(idx));
+        idx = (fabsf(x[k]) == m1) ? (unsigned)k : idx;
     }
-    if (lane < DEG) mask[mp] = make_ulonglong2(((u64)nhi << 32) | nlo, ((u64)ahi << 32) | alo);
+    arg[lane] = (unsigned char)idx;
+    if constexpr (BOOT) {
+        unsigned nlo = 0, nhi = 0;  // lane k keeps edge k's mask
+        // The v_writelanes below are the compiler's own instructions (writelane(), top of this file): a v_writelane reading
+        // an SGPR that a VALU instruction -- a v_cmp, or a v_readlane reloading a spilled mask -- wrote fewer than 2 wait
+        // states earlier gets the OLD value on gfx950, and inside an `asm` statement nobody pads (round 3 measured it on
+        // edge 0 of degree-1 rows: VERDICT r03 #1).
+#pragma unroll
+        for (int k = 0; k < DEG; k++) {
+            // the sweep runs in chunks of REC_CHUNK edges: a chunk's compares wait (through an empty asm on their inputs)
+            // for the previous chunk's v_writelanes, so at most a chunk's masks are live in SGPRs.  Left alone the
+            // scheduler keeps sweep 1's sign masks of the whole row for reuse: SGPR spills in the 64-edge build, every
+            // one a v_writelane / v_readlane pair.
+            if (k % REC_CHUNK == 0) {
+                asm volatile("" ::"v"(nlo), "v"(nhi));
+#pragma unroll
+                for (int j = k; j < DEG && j < k + REC_CHUNK; j++) asm volatile("" : "+v"(x[j]));
+            }
+            const u64 ng = __ballot(x[k] <= 0.0f);
+            nlo = writelane((unsigned)ng, k, nlo);
+            nhi = writelane((unsigned)(ng >> 32), k, nhi);
+        }
+        if (lane < DEG) sgn[mp] = ((u64)nhi << 32) | nlo;
+    }
 }
 
 // (Iteration 1 never comes here: it runs without a check pass -- k_var_first -- or, with first_fused off, in the message
 // form, whose check kernel reads the priors.)
-template <int CAP, bool PAR = false>
+// BOOT is the SECOND template parameter: a profile's per-kernel averages tell the one bootstrap launch of a group from
+// the steady-state ones by the instantiation's name.
+template <int CAP, bool BOOT, bool PAR = false>
 __global__ __launch_bounds__(256) void k_check_minsum_rec(const int *__restrict__ list, const float *msg,
                                                           const u64 *__restrict__ synd, const u64 *done,
                                                           int skip_done, int m, long E, float alpha,
                                                           const int *__restrict__ col_idx,
-                                                          float *__restrict__ rec, ulonglong2 *__restrict__ mask,
+                                                          float *__restrict__ rec, u64 *__restrict__ sgn,
                                                           const int *__restrict__ csr_pos, FusedTest ft = FusedTest{})
 {
     const int lane = threadIdx.x & 63;
@@ -830,15 +861,18 @@ __global__ __launch_bounds__(256) void k_check_minsum_rec(const int *__restrict_
         const int e0 = md[1];
         const int deg = md[2];
         const float *p = msg + ((size_t)tl * E + e0) * TW + lane;
-        float *rc = rec + ((size_t)tl * 2 * m + r) * TW, *rc2 = rc + (size_t)m * TW;  // two planes per tile: [m1 | m2][row][64]
-        ulonglong2 *mk = mask + (size_t)tl * E;  // (masks by position: the tile's base)
+        float *rt = rec + (size_t)tl * rec_tile_floats(m);  // the tile's block: [m1 | m2][row][64], arg, par
+        float *rc = rt + (size_t)r * TW, *rc2 = rc + (size_t)m * TW;
+        unsigned char *ar = (unsigned char *)(rt + rec_arg_off(m)) + (size_t)r * TW;
+        u64 *pa = (u64 *)(rt + rec_par_off(m)) + r;
+        u64 *sg = sgn + (size_t)tl * E;  // (masks by position: the tile's base)
         const int *ps = csr_pos + e0;
         const u64 sw = synd[(size_t)tl * m + r];  // (uniform: a scalar load; the row's syndrome bits ARE a lane mask)
         // (the ladder for_exact_degree spells, kept as a macro here and in k_var_rec: through the helper's lambda the
         // record-form kernels come out with other registers and an instruction more or less)
-#define MR(D)                                                                                 \
-    case D:                                                                                   \
-        if constexpr (D <= CAP) check_minsum_row_rec<D>(p, sw, alpha, rc, rc2, mk, lane, ps); \
+#define MR(D)                                                                                               \
+    case D:                                                                                                 \
+        if constexpr (D <= CAP) check_minsum_row_rec<D, BOOT>(p, sw, alpha, rc, rc2, ar, pa, sg, lane, ps); \
         break;
 #define MR8(D) MR(D) MR(D + 1) MR(D + 2) MR(D + 3) MR(D + 4) MR(D + 5) MR(D + 6) MR(D + 7)
         switch (deg) {
@@ -1452,25 +1486,41 @@ __global__ __launch_bounds__(256) void k_var_first(const int *__restrict__ list,
 
 // Variable pass of the min-sum RECORD form (see k_check_minsum_rec): the column's messages are rebuilt from the
 // records of its edges' rows.  The wave's column record carries the first VAR_INLINE edge ids, a parallel table the
-// rows of those edges (`var_rows`, VAR_INLINE ints per record), both through scalar loads: the first-magnitude
-// gathers (row on the scalar side) issue as soon as the masks are in.  Lane j fetches the two lane masks of the
-// column's j-th edge (its id put into the lane with v_writelane: no memory round trip); edge k's masks then reach
-// every lane through v_readlane as wave-uniform 64-bit words that go straight into the select / execute-mask
-// operands (__builtin_amdgcn_inverse_ballot_w64), and the second magnitude is fetched only for the lanes whose
-// arg-min this edge is (one in `row degree` on average).  All gathers of the column are in flight before the first one
-// is waited for.
-// Like the record-form check pass this kernel is bound by VALU issue (SQ counters: profiles/r03/sq_counters_*record*;
-// without its stores it took 58 us instead of 60, without the first-magnitude gathers 52), so it is straight-line code
-// for the column's EXACT degree, dispatched wave-uniformly: the bucketed form (unrolled to the bucket's bound,
-// predicated on `k < d`) spent more instructions on the predicates than on the column.
-//   csc_row: row of every position of the re-laid edge list (laid out like it), for edges beyond VAR_INLINE
+// row words of those edges (`var_rows`, VAR_INLINE ints per record: the row and, in the high bits, the edge's index IN
+// that row -- scaldpc_rec_pack.h), both through scalar loads.  Per edge and lane the pass reads the row's arg-min byte
+// (a 64-B row, row on the scalar side) and compares it with the edge's in-row index: that is "this edge is the
+// codeword's arg-min", and it SELECTS THE ADDRESS of the one magnitude gather that follows -- the lane's word of the
+// row's second-magnitude plane instead of the first (the planes lie m rows apart: one v_cndmask on the lane's byte
+// offset).  One gather per edge and lane, no execute-mask juggling, no mask kept in SGPRs between a load and a select.
+// All arg-min bytes of the column are in flight before the first is waited for, then all magnitudes.
+// The sign of edge k is par[row_k] XOR the column's own sign mask of that edge.  Lane j fetches the mask of the column's
+// j-th edge (contiguous) and the parity word of that edge's row (the row from csc_row, lane j's word) and XORs the
+// two: two VALU instructions for the whole column; edge k's word reaches the select through v_readlane.
+// The pass leaves the column's NEW sign masks behind: edge k's is the ballot of (stored float <= 0), taken from the
+// very value that is stored, put into lane k of two registers with v_writelane (the compiler's own: writelane()), and
+// lanes j < D store the words -- contiguous again.  They follow the messages for EVERY lane: the done bits freeze
+// outputs, not messages.
+// Like the record-form check pass this kernel is bound by VALU issue (SQ counters: profiles/r03/sq_counters_*record*),
+// so it is straight-line code for the column's EXACT degree, dispatched wave-uniformly: the bucketed form (unrolled to
+// the bucket's bound, predicated on `k < d`) spent more instructions on the predicates than on the column.
+//   csc_row: row word of every position of the re-laid edge list (laid out like it)
+//   rec2_off: bytes from a row's first magnitudes to its second ones (m * 256: below 2^32, rec_rows_fit)
+typedef __attribute__((address_space(1))) unsigned char gbyte;
+__device__ __forceinline__ gbyte *sbase_b(const unsigned char *p)
+{
+    gbyte *g = (gbyte *)p;
+    asm("" : "+s"(g));
+    return g;
+}
+
 template <int D>
-__device__ __forceinline__ float var_col_rec(float *tile_base, const float *__restrict__ rec_base,
-                                             const float *__restrict__ rec2_base, const ulonglong2 *__restrict__ mask_col,
-                                             unsigned lane, const int *__restrict__ rc, const int4 *__restrict__ row4,
+__device__ __forceinline__ float var_col_rec(float *tile_base, const float *__restrict__ rec_base, unsigned rec2_off,
+                                             const unsigned char *__restrict__ arg_base,
+                                             const u64 *__restrict__ par_base, u64 *sgn_col, unsigned lane,
+                                             const int *__restrict__ rc, const int4 *__restrict__ row4,
                                              const int *__restrict__ ce1, const int *__restrict__ cr1, float pr)
 {
-    int eid[D], rid[D];
+    int eid[D], rw[D];
     {
         const int4 *rec4 = (const int4 *)rc;
         const int4 a = rec4[1], b = rec4[2], c = rec4[3], e = rec4[4];
@@ -1480,40 +1530,30 @@ __device__ __forceinline__ float var_col_rec(float *tile_base, const float *__re
 #pragma unroll
         for (int k = 0; k < D && k < VAR_INLINE; k++) {
             eid[k] = in16[k];
-            rid[k] = rw16[k];
+            rw[k] = rw16[k];
         }
 #pragma unroll
-        for (int k = VAR_INLINE; k < D; k++) rid[k] = cr1[k];  // (their edge ids are wanted by the stores alone: fetched below)
+        for (int k = VAR_INLINE; k < D; k++) rw[k] = cr1[k];  // (their edge ids are wanted by the stores alone: fetched below)
     }
-    // lane j's two masks (mask_col = the masks of the column's first position: a column's masks are contiguous)
-    ulonglong2 mk = make_ulonglong2(0, 0);
-    if ((int)lane < D) mk = mask_col[lane];
-    const int nlo = (int)(unsigned)mk.x, nhi = (int)(unsigned)(mk.x >> 32), alo = (int)(unsigned)mk.y, ahi = (int)(unsigned)(mk.y >> 32);
-    float mm[D], pp[D], m2[D];
-    // The arg-min masks are wanted twice (execute mask of the second-magnitude load, select).  Up to REC_KEEP_AG edges they
-    // stay in SGPRs between the two; beyond, ids + rows + masks (4 SGPRs per edge) no longer fit the 102 and every excess
-    // mask became an SGPR spill, so the select of such a (rare) column re-reads them from the lane that holds them.
-    constexpr bool KEEP_AG = D <= REC_KEEP_AG;
-    u64 ag[KEEP_AG ? D : 1];
+    // lane j: "the check's message on the column's j-th edge is negative" = the edge's sign mask (sgn_col = the mask of the
+    // column's first position: a column's masks are contiguous) XOR the parity word of the edge's row
+    u64 sg = 0;
+    if ((int)lane < D) sg = sgn_col[lane] ^ par_base[rec_row_of(cr1[lane])];
+    const int slo = (int)(unsigned)sg, shi = (int)(unsigned)(sg >> 32);
+    float mm[D], pp[D];
+    unsigned ab[D];
 #pragma unroll
-    for (int k = 0; k < D; k++) mm[k] = sbase(rec_base + (size_t)rfl(rid[k]) * TW)[lane];
+    for (int k = 0; k < D; k++) ab[k] = sbase_b(arg_base + (size_t)rec_row_of(rfl(rw[k])) * TW)[lane];
+    const unsigned off1 = lane * 4u, off2 = off1 + rec2_off;
 #pragma unroll
     for (int k = 0; k < D; k++) {
-        const u64 agk = ((u64)(unsigned)__builtin_amdgcn_readlane(ahi, k) << 32) | (unsigned)__builtin_amdgcn_readlane(alo, k);
-        if constexpr (KEEP_AG) ag[k] = agk;
-        asm("" : "=v"(m2[k]));  // (any value: read only where the load below has written it)
-        if (__builtin_amdgcn_inverse_ballot_w64(agk)) m2[k] = sbase(rec2_base + (size_t)rfl(rid[k]) * TW)[lane];
+        const unsigned off = ab[k] == (unsigned)rec_index_of(rfl(rw[k])) ? off2 : off1;
+        mm[k] = *(const gfloat *)((const gbyte *)sbase(rec_base + (size_t)rec_row_of(rfl(rw[k])) * TW) + off);
     }
 #pragma unroll
     for (int k = 0; k < D; k++) {
-        const u64 ng = ((u64)(unsigned)__builtin_amdgcn_readlane(nhi, k) << 32) | (unsigned)__builtin_amdgcn_readlane(nlo, k);
-        u64 agk;
-        if constexpr (KEEP_AG)
-            agk = ag[k];
-        else
-            agk = ((u64)(unsigned)__builtin_amdgcn_readlane(ahi, k) << 32) | (unsigned)__builtin_amdgcn_readlane(alo, k);
-        const float a = __builtin_amdgcn_inverse_ballot_w64(agk) ? m2[k] : mm[k];
-        mm[k] = __builtin_amdgcn_inverse_ballot_w64(ng) ? -a : a;
+        const u64 ng = ((u64)(unsigned)__builtin_amdgcn_readlane(shi, k) << 32) | (unsigned)__builtin_amdgcn_readlane(slo, k);
+        mm[k] = __builtin_amdgcn_inverse_ballot_w64(ng) ? -mm[k] : mm[k];
     }
     float temp = pr;
 #pragma unroll
@@ -1522,18 +1562,24 @@ __device__ __forceinline__ float var_col_rec(float *tile_base, const float *__re
         temp += mm[k];
     }
     // the edge ids beyond the record's inline ones: held from the top they cost an SGPR per edge through the whole gather
-    // phase (with the rows and the masks: spills in the columns of 17+ edges)
+    // phase (with the row words and the masks: spills in the columns of 17+ edges)
 #pragma unroll
     for (int k = VAR_INLINE; k < D; k++) eid[k] = ce1[k];
     float suf = 0.0f;
+    unsigned nlo = 0, nhi = 0;  // lane k keeps edge k's new sign mask
 #pragma unroll
     for (int k = D - 1; k >= 0; k--) {
         gfloat *q = sbase(tile_base + (size_t)rfl(eid[k]) * TW) + lane;
+        const float out = pp[k] + suf;
         // sc1: the line does not stay in this XCD's L2 (it is read next by a check pass on whichever XCD), which keeps
         // the L2 for the records: 76.2 -> 74.3 ms per step on the HQC-128 bench (profiles/r03/ab_rec_l2.log)
-        __hip_atomic_store(q, pp[k] + suf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(q, out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const u64 nm = __ballot(out <= 0.0f);  // a float compare on the stored value: +-0 is "negative", NaN is not
+        nlo = writelane((unsigned)nm, k, nlo);
+        nhi = writelane((unsigned)(nm >> 32), k, nhi);
         suf += mm[k];
     }
+    if ((int)lane < D) sgn_col[lane] = ((u64)nhi << 32) | nlo;
     return temp;
 }
 
@@ -1543,7 +1589,7 @@ template <int CAP, class P>
 __global__ __launch_bounds__(256) void k_var_rec(const int *__restrict__ list, const int *__restrict__ var_rows,
                                                  const int *__restrict__ csc_edge, const int *__restrict__ csc_row,
                                                  typename P::Arg prior_arg, float *msg, const float *__restrict__ rec,
-                                                 const ulonglong2 *__restrict__ mask, float *__restrict__ post,
+                                                 u64 *sgn, float *__restrict__ post,
                                                  u64 *__restrict__ hard, const u64 *__restrict__ done, int skip_done, int n, int m,
                                                  long E, int write_out, int blk0, int xmap)
 {
@@ -1568,15 +1614,18 @@ __global__ __launch_bounds__(256) void k_var_rec(const int *__restrict__ list, c
     const int cb = rc[1];
     const int d = rc[2];
     float *tb = msg + (size_t)tl * E * TW;
-    const float *rb = rec + (size_t)tl * 2 * m * TW, *rb2 = rb + (size_t)m * TW;
-    const ulonglong2 *mt = mask + (size_t)tl * E;
+    const float *rb = rec + (size_t)tl * rec_tile_floats(m);  // the tile's block: [m1 | m2][row][64], arg, par
+    const unsigned r2 = (unsigned)m * (TW * (unsigned)sizeof(float));
+    const unsigned char *ab = (const unsigned char *)(rb + rec_arg_off(m));
+    const u64 *pb = (const u64 *)(rb + rec_par_off(m));
+    u64 *st = sgn + (size_t)tl * E;
     const int *ce = csc_edge + cb, *cr = csc_row + cb;
     const int4 *w4 = (const int4 *)(var_rows + (size_t)ri * VAR_INLINE);
     const float pr = prior(v, tl, (int)lane);
     float L = pr;
-#define VR(D)                                                                                       \
-    case D:                                                                                         \
-        if constexpr (D <= CAP) L = var_col_rec<D>(tb, rb, rb2, mt + cb, lane, rc, w4, ce, cr, pr); \
+#define VR(D)                                                                                               \
+    case D:                                                                                                 \
+        if constexpr (D <= CAP) L = var_col_rec<D>(tb, rb, r2, ab, pb, st + cb, lane, rc, w4, ce, cr, pr);  \
         break;
 #define VR8(D) VR(D) VR(D + 1) VR(D + 2) VR(D + 3) VR(D + 4) VR(D + 5) VR(D + 6) VR(D + 7)
     switch (d) {
