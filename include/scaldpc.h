@@ -49,6 +49,12 @@
  *                                every symbol of an all-zero word gets the "good" or the "bad" pmf row, min_sum, is the
  *                                decision all zero -- trials drawn on the device
  *                                (entry point added under SCALDPC_VERSION 103: nothing that existed changed)
+ *   scaldpc_mc_qary_run_secret   the trial the Kyber decoders exist for, simulate/kyber.py: a secret drawn from the centred
+ *                                binomial (kyber.py:60-64,95-105), the row sums that follow from it and H (compute_ssum,
+ *                                kyber.py:85-92), every variable measured by an oracle whose answer depends on the TRUE symbol,
+ *                                the posterior pmf of that answer handed to the decoder
+ *                                (max_likelihood.s_distribution_from_hard_y, kyber.py:362-376) -- is the key recovered?
+ *                                (entry point added under SCALDPC_VERSION 103: nothing that existed changed)
  *
  * Threading: calls on distinct handles are independent; calls on one handle are
  * serialised internally, so one decoder object may be shared by many host
@@ -502,6 +508,62 @@ int scaldpc_mc_qary_run(scaldpc_qary *h, const float *levels_b, const double *we
                         int64_t first_trial, int32_t batch, uint64_t seed, uint32_t flags, void *stream,
                         uint8_t *out_success, int32_t *out_errs, int32_t *out_wrong, uint8_t *out_levels,
                         int8_t *out_symbols);
+
+/* ------------------------------------------- Monte-Carlo trials of DecoderSpecial on drawn secrets under an oracle's law */
+/*
+ * `batch` trials of the Kyber attack's decode on the device (special handles only): a SECRET is drawn, every variable is
+ * answered by an oracle outcome drawn CONDITIONAL on the variable's true symbol, the outcome's pmf row goes to the decoder,
+ * and the decision is compared with the secret.  Tables and prior are HOST pointers whatever the flags say.
+ *   prior_b   double [Q]        Q = 2B+1: the law of a coefficient's true symbol, index q = value q - B
+ *   levels_b  float  [k_b][Q]   the pmf row outcome k hands the decoder (the posterior given that answer)
+ *   weights_b double [Q][k_b]   row s: the law of the outcome of a coefficient variable whose TRUE symbol is s
+ *   levels_s  float  [k_s][QS]  QS = 2BSUM+1: the same for the row-sum variables (index q = value q - BSUM)
+ *   weights_s double [QS][k_s]  row s: TRUE row-sum symbol s
+ *
+ * Trial law (next to the others; a trial depends on (seed, first_trial + i) alone, not on batch, split or GPU count):
+ *   generator   Philox4x32-10, key = seed, the GLOBAL trial index, as scaldpc_mc_qary_run
+ *   secret      coefficient variable v < N-R: stream 1 word v, i.e. counter (v >> 2, 1, trial_lo, trial_hi), word v & 3; the symbol
+ *               is the smallest q with word < T_q, T the cumulative thresholds of prior_b by the rule of scaldpc_mc_qary_run
+ *               (left-to-right float64 sum, thr, 2^32 from the last nonzero entry on)
+ *               row-sum variable N-R+r: the one value that makes check r hold over the integers,
+ *               t_r = -h_{r,id} * sum_j h_{r,j} s_j  (h_{r,id} = +-1 the row's identity entry, j over its coefficient edges);
+ *               creation guarantees (degree - 1) B <= BSUM, so t_r lies inside the alphabet: every drawn word is a valid word
+ *   outcome     variable x: stream 0 word x, the word scaldpc_mc_qary_run draws x's level from; the outcome is the
+ *               smallest k with word < T^s_k, s the index of the variable's TRUE symbol: row s of weights_b (x < N-R) or of weights_s, every
+ *               row through the threshold rule on its own -- an outcome of weight 0 in that row is never drawn under that symbol
+ *   decode      outcome k hands the decoder levels[k]; the rows are converted once per table by the conversion of
+ *               scaldpc_qary_into_llr (and kept over the chunks of a sweep, as scaldpc_mc_qary_run keeps them)
+ *
+ * Defining property: out_symbols is bit for bit what scaldpc_qary_special_min_sum_batch returns for
+ * pmf_b[i][v] = levels_b[out_levels[i][v]] and pmf_sum[i][r] = levels_s[out_levels[i][N-R+r]], in every kernel form and at any
+ * split of the trials into calls.
+ * Reduction: with prior_b a point mass on the value 0, all rows of weights_b equal and all rows of weights_s equal, the call draws
+ * the levels and the symbols of scaldpc_mc_qary_run with those weights, trial for trial; that call's out_wrong is
+ * out_wrong[i][0] + out_wrong[i][1] here, and its out_success says whether that sum is 0.
+ *
+ *   out_success       uint8 [batch]     required: out_wrong[i][0] == 0 -- the key is recovered
+ *   out_wrong         int32 [batch][2]  optional: decided != secret over the coefficient variables, over the row-sum variables
+ *   out_channel_wrong int32 [batch][2]  optional: variables whose drawn row ALONE decides wrong -- the first maximum of the pmf
+ *                                       row (the arg-min rule of decoder.rs:694-704 on its LLR row) is not the secret
+ *   out_secret        int8  [batch][N]  optional: the secret values (row-sum variables last)
+ *   out_levels        uint8 [batch][N]  optional: the outcome drawn for every variable
+ *   out_symbols       int8  [batch][N]  optional: the decisions
+ * Refused before anything is queued (the handle keeps working, no output is written):
+ *   SCALDPC_EINVAL   NULL prior_b, table or out_success; a plain (non-special) handle: without row-sum variables a drawn secret
+ *                    is no code word; k outside 1 .. 32 per table; the prior or a row of weights with an entry that is no
+ *                    probability or a sum outside 1 +- 1e-6 (the message names the table and the row); first_trial < 0;
+ *                    batch <= 0; SCALDPC_F_ASYNC
+ *   SCALDPC_EPMF     a level that fails the reference's pmf test (decoder.rs:683-684; the message names table and level)
+ *   SCALDPC_EDEGREE  a table of K levels over Q symbols with 4 (2 K Q + Q) > 65536: a launch keeps the table's LLR rows, its
+ *                    thresholds per true symbol and their counts in dynamic LDS, 64 KB at the most (k_s = 32 with QS >= 253)
+ * flags: SCALDPC_F_DEVICE_IO: the six outputs are device pointers.  SCALDPC_ENOCONF is reported as by the plain call.
+ */
+int scaldpc_mc_qary_run_secret(scaldpc_qary *h, const double *prior_b,
+                               const float *levels_b, const double *weights_b, int32_t k_b,
+                               const float *levels_s, const double *weights_s, int32_t k_s,
+                               int64_t first_trial, int32_t batch, uint64_t seed, uint32_t flags, void *stream,
+                               uint8_t *out_success, int32_t *out_wrong, int32_t *out_channel_wrong,
+                               int8_t *out_secret, uint8_t *out_levels, int8_t *out_symbols);
 
 #ifdef __cplusplus
 }

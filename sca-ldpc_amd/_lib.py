@@ -110,10 +110,13 @@ def _declare(lib):
     lib.scaldpc_mc_qary_run.argtypes = [
         vp, vp, vp, C.c_int32, vp, vp, C.c_int32, C.c_int64, C.c_int32, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp, vp,
     ]  # fmt: skip
+    lib.scaldpc_mc_qary_run_secret.argtypes = [
+        vp, vp, vp, vp, C.c_int32, vp, vp, C.c_int32, C.c_int64, C.c_int32, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp, vp, vp,
+    ]  # fmt: skip
     for name in (
         "scaldpc_qary_create", "scaldpc_qary_min_sum_batch", "scaldpc_qary_special_create",
         "scaldpc_qary_special_min_sum_batch", "scaldpc_qary_min_sum_batch_soft", "scaldpc_qary_special_min_sum_batch_soft",
-        "scaldpc_mc_qary_run",
+        "scaldpc_mc_qary_run", "scaldpc_mc_qary_run_secret",
     ):  # fmt: skip
         getattr(lib, name).restype = C.c_int
 

@@ -1,12 +1,15 @@
 // The trial laws of the Monte-Carlo entry points as the HOST builds them, before anything is queued: the cumulative thresholds of
 // a table of weights (one rule, shared by scaldpc_mc_qary_run and scaldpc_mc_hqc_run_soft) and the validated outcome table of
-// scaldpc_mc_hqc_run_soft in the form its kernel takes by value.  The laws themselves are stated in include/scaldpc.h.
+// scaldpc_mc_hqc_run_soft in the form its kernel takes by value, and the law of scaldpc_mc_qary_run_secret (a drawn secret, outcomes
+// conditional on every variable's true symbol).  The laws themselves are stated in include/scaldpc.h.
 // Plain C++17 with no HIP in it: tests/mc_law_main.cc drives this header from a host program under the sanitizers.
 #pragma once
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <cstdio>
+#include <string>
+#include <vector>
 
 // floor(p 2^32), 0 for p <= 0, 2^32 for p >= 1: a 32-bit word is below it with probability p (to 2^-32)
 static inline unsigned long long bernoulli_threshold(double p)
@@ -100,4 +103,114 @@ static inline int mc_hqc_law(const double *weights, const uint8_t *flips, const 
     }
     law->K = K;
     return 0;
+}
+
+// ------------------------------------------------------------------------------------------ scaldpc_mc_qary_run_secret
+
+constexpr int MC_SECRET_MAX_LEVELS = 32;
+// A launch keeps one table in dynamic LDS: its K LLR rows (K Q floats), the thresholds of every true symbol (Q K 32-bit words)
+// and the number of thresholds below 2^32 per true symbol (Q words).
+constexpr size_t MC_SECRET_MAX_LDS = 65536;
+static inline size_t mc_secret_lds_bytes(int K, int Q) { return 4 * ((size_t)2 * K * Q + (size_t)Q); }
+
+// One pmf row as decoder.rs:668-692 reads it (the rule of PmfScan in scaldpc_qary.hip, restated without HIP): the f32 sum, left
+// to right from 0.0, must lie within 1 +- 1e-3, and *best is the first strict maximum (a NaN is never chosen) -- the symbol whose
+// LLR is the row's first zero, i.e. what the arg-min rule of decoder.rs:694-704 decides from the row alone.
+// 0: fine, 1: the sum fails, 2: no maximum (all NaN).
+static inline int mc_pmf_row(const float *p, int Q, int *best)
+{
+    float sum = 0.0f, mx = 0.0f;
+    bool have = false;
+    *best = 0;
+    for (int q = 0; q < Q; q++) {
+        const float x = p[q];
+        sum += x;
+        if (x == x && (!have || x > mx)) {
+            mx = x;
+            have = true;
+            *best = q;
+        }
+    }
+    if (!have) return 2;
+    return !(sum < 1.0f + 0.001f) || !(sum > 1.0f - 0.001f);
+}
+
+// The law of scaldpc_mc_qary_run_secret as the host builds it (table 0: coefficient variables, 1: row-sum variables):
+//   prior    [Q[0]]        cumulative thresholds of prior_b: the secret symbol is the smallest q with word < prior[q]
+//   t[i]     [Q[i]][K[i]]  row s: the cumulative thresholds of weights_i[s], the outcomes of a variable whose TRUE symbol is s
+//   best[i]  [K[i]]        the VALUE (index - (Q[i] - 1) / 2) a variable decides from the pmf row of level k alone
+struct McSecretLaw {
+    int Q[2] = {0, 0}, K[2] = {0, 0};
+    std::vector<unsigned long long> prior, t[2];
+    std::vector<signed char> best[2];
+};
+
+enum { MC_SECRET_OK = 0, MC_SECRET_EINVAL = 1, MC_SECRET_EPMF = 2, MC_SECRET_EDEGREE = 3 };
+
+// Everything that can be refused about the tables and the trial range of scaldpc_mc_qary_run_secret (the kind of refusal, with
+// the reason in msg), and the law.  levels[i] float [K[i]][Q[i]], weights[i] double [Q[i]][K[i]], prior_b double [Q[0]].
+static inline int mc_qary_secret_law(const double *prior_b, const float *const levels[2], const double *const weights[2], const int K[2],
+                                     const int Q[2], long long first_trial, int batch, bool async, McSecretLaw *law, char *msg,
+                                     size_t len)
+{
+    static const char *const lname[2] = {"levels_b", "levels_s"}, *const wname[2] = {"weights_b", "weights_s"};
+    *law = McSecretLaw();
+    if (!prior_b || !levels[0] || !levels[1] || !weights[0] || !weights[1]) {
+        snprintf(msg, len, "NULL prior or table");
+        return MC_SECRET_EINVAL;
+    }
+    if (batch <= 0) {
+        snprintf(msg, len, "batch must be positive");
+        return MC_SECRET_EINVAL;
+    }
+    if (first_trial < 0) {
+        snprintf(msg, len, "first_trial must not be negative");
+        return MC_SECRET_EINVAL;
+    }
+    if (async) {
+        snprintf(msg, len, "SCALDPC_F_ASYNC: a q-ary Monte-Carlo call is synchronous");
+        return MC_SECRET_EINVAL;
+    }
+    for (int i = 0; i < 2; i++) {
+        if (Q[i] < 1 || Q[i] > 255 || !(Q[i] & 1)) {
+            snprintf(msg, len, "%s: an alphabet of %d symbols", lname[i], Q[i]);
+            return MC_SECRET_EINVAL;
+        }
+        if (K[i] < 1 || K[i] > MC_SECRET_MAX_LEVELS) {
+            snprintf(msg, len, "%s: %d levels, 1 .. %d are taken", lname[i], K[i], MC_SECRET_MAX_LEVELS);
+            return MC_SECRET_EINVAL;
+        }
+    }
+    for (int i = 0; i < 2; i++)
+        if (mc_secret_lds_bytes(K[i], Q[i]) > MC_SECRET_MAX_LDS) {
+            snprintf(msg, len, "%s: %d levels of %d symbols need %zu B of LDS in a launch (4 (2 K Q + Q)), %zu are there", lname[i],
+                     K[i], Q[i], mc_secret_lds_bytes(K[i], Q[i]), MC_SECRET_MAX_LDS);
+            return MC_SECRET_EDEGREE;
+        }
+    law->prior.resize(Q[0]);
+    if (mc_cumulative_thresholds("prior_b", prior_b, Q[0], law->prior.data(), msg, len)) return MC_SECRET_EINVAL;
+    for (int i = 0; i < 2; i++) {
+        law->t[i].resize((size_t)Q[i] * K[i]);
+        for (int s = 0; s < Q[i]; s++) {
+            const std::string name = std::string(wname[i]) + "[" + std::to_string(s) + "]";
+            if (mc_cumulative_thresholds(name.c_str(), weights[i] + (size_t)s * K[i], K[i], law->t[i].data() + (size_t)s * K[i], msg, len))
+                return MC_SECRET_EINVAL;
+        }
+    }
+    for (int i = 0; i < 2; i++) {
+        law->best[i].resize(K[i]);
+        for (int k = 0; k < K[i]; k++) {
+            int best = 0;
+            const int bad = mc_pmf_row(levels[i] + (size_t)k * Q[i], Q[i], &best);
+            if (bad) {
+                snprintf(msg, len, bad == 2 ? "%s: level %d: No maximum probability found" : "%s: level %d does not sum to 1 +- 1e-3 (decoder.rs:683-684)",
+                         lname[i], k);
+                return MC_SECRET_EPMF;
+            }
+            law->best[i][k] = (signed char)(best - (Q[i] - 1) / 2);
+        }
+        law->Q[i] = Q[i];
+        law->K[i] = K[i];
+    }
+    return MC_SECRET_OK;
 }

@@ -39,6 +39,7 @@ typedef unsigned long long u64;
 #include "scaldpc_qary_rows.h"
 #include "scaldpc_qary_soft.h"
 #include "scaldpc_qary_mc.h"
+#include "scaldpc_qary_secret.h"
 
 namespace {
 
@@ -707,6 +708,12 @@ struct scaldpc_qary : QaryStreams, QaryShape {
     std::vector<float> mc_tab;  // host side of d_mc_tab's pmf rows and of d_mc_res: alive until the call has drained its stream
     std::vector<int> mc_res;
     bool mc_tab_ok = false;  // d_mc_tab holds the LLR rows of mc_tab (a finished call put them there): a sweep converts its tables once
+    // scaldpc_mc_qary_run_secret only (allocated by the first such call): the secret values [N][Bp] and, for host callers, as
+    // [batch][N]; the law's device form (pack_secret_law) with its host side, kept like the tables
+    Buf<signed char> d_mc_sec, d_mc_sec_out;
+    Buf<unsigned> d_mc_law;
+    std::vector<unsigned> mc_law;
+    bool mc_law_ok = false;
     // one 16-byte status block per handle, zeroed by ONE fill and read back by ONE copy per call: [0] = the bitwise complement of
     // the smallest (codeword, variable) key whose pmf row fails the sum test (0: none; kept inverted so that "none" is zero
     // and the kernels lower the key with atomicMax), [1] = the call's error code (low word).  A third word behind the block is
@@ -1231,11 +1238,9 @@ int mc_ensure(scaldpc_qary *h, const QaryCall &c, const McTables &t, const McOut
     return 0;
 }
 
-// The first step of a Monte-Carlo call: the tables' rows -> LLR rows (k_q_into_llr_rows: the plain call's glibc_logf(max / p);
-// skipped when the tables are those of the handle's last finished call), then
-// k_q_mc_draw leaves in d_llr and d_msg what stage_and_convert leaves there for the materialised input (fused or not: k_q_init
-// copies the same numbers), and the drawn levels in d_mc_lvl.
-int mc_draw(scaldpc_qary *h, const QaryCall &c, const McTables &t, const McLaw &law, long first_trial, uint64_t seed)
+// The tables' rows -> LLR rows (k_q_into_llr_rows: the plain call's glibc_logf(max / p); skipped when the tables are those of
+// the handle's last finished call).  Returns the LLR rows on the device, [K[0]][Q[0]] then [K[1]][Q[1]].
+int mc_rows(scaldpc_qary *h, const QaryCall &c, const McTables &t, float **rows)
 {
     const int nt = t.floats(), nb = t.K[0] * t.Q[0];
     float *d_rows = h->d_mc_tab + nt;
@@ -1253,7 +1258,18 @@ int mc_draw(scaldpc_qary *h, const QaryCall &c, const McTables &t, const McLaw &
             SC_HIP(hipGetLastError());
         }
     }
-    hipLaunchKernelGGL(k_q_mc_draw, dim3((h->N + 3) / 4, c.Bp / 64), dim3(256), (size_t)nt * sizeof(float), c.s, law, d_rows, t.Q[0],
+    *rows = d_rows;
+    return 0;
+}
+
+// The first step of a Monte-Carlo call: the tables' LLR rows (mc_rows), then
+// k_q_mc_draw leaves in d_llr and d_msg what stage_and_convert leaves there for the materialised input (fused or not: k_q_init
+// copies the same numbers), and the drawn levels in d_mc_lvl.
+int mc_draw(scaldpc_qary *h, const QaryCall &c, const McTables &t, const McLaw &law, long first_trial, uint64_t seed)
+{
+    float *d_rows = nullptr;
+    SC_TRY(mc_rows(h, c, t, &d_rows));
+    hipLaunchKernelGGL(k_q_mc_draw, dim3((h->N + 3) / 4, c.Bp / 64), dim3(256), (size_t)t.floats() * sizeof(float), c.s, law, d_rows, t.Q[0],
                        t.Q[1], c.BV, h->N, c.batch, c.Bp, first_trial, (unsigned)seed, (unsigned)(seed >> 32), h->d_col_ptr,
                        h->d_csc_edge, h->d_edge_h, h->d_llr, h->d_msg, h->W, h->d_mc_lvl);
     SC_HIP(hipGetLastError());
@@ -1298,6 +1314,141 @@ int mc_emit(scaldpc_qary *h, const QaryCall &c, const McLaw &law, const McOut &o
         if (o.errs) memcpy(o.errs, res, (size_t)batch * sizeof(int));
         if (o.wrong) memcpy(o.wrong, res + batch, (size_t)batch * sizeof(int));
         memcpy(o.success, res + 2 * (size_t)batch, batch);
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------- scaldpc_mc_qary_run_secret
+struct McSecretOut {
+    uint8_t *success;
+    int32_t *wrong, *chan;
+    int8_t *secret;
+    uint8_t *levels;
+    int8_t *symbols;
+};
+
+// The law as the kernels of scaldpc_qary_secret.h read it, in 32-bit words: the prior's Q[0] thresholds (64 bits each), then per
+// table thr [K][Q] and cnt [Q] (SecretTab), then the best values, 32 bytes per table.
+struct SecretLawAt {
+    size_t tab[2], best, words;
+};
+SecretLawAt pack_secret_law(const McSecretLaw &law, std::vector<unsigned> *out)
+{
+    SecretLawAt at;
+    size_t n = (size_t)2 * law.Q[0];
+    for (int i = 0; i < 2; i++) {
+        at.tab[i] = n;
+        n += (size_t)law.K[i] * law.Q[i] + law.Q[i];
+    }
+    at.best = n;
+    at.words = n + 16;
+    out->assign(at.words, 0u);
+    memcpy(out->data(), law.prior.data(), (size_t)law.Q[0] * sizeof(u64));
+    for (int i = 0; i < 2; i++) {
+        const int K = law.K[i], Q = law.Q[i];
+        unsigned *thr = out->data() + at.tab[i], *cnt = thr + (size_t)K * Q;
+        for (int s = 0; s < Q; s++)
+            for (int k = 0; k < K; k++) {
+                const u64 t = law.t[i][(size_t)s * K + k];
+                thr[(size_t)k * Q + s] = t < (1ull << 32) ? (unsigned)t : 0xFFFFFFFFu;
+                cnt[s] += t < (1ull << 32);
+            }
+        memcpy((signed char *)(out->data() + at.best) + 32 * i, law.best[i].data(), K);
+    }
+    return at;
+}
+
+int secret_ensure(scaldpc_qary *h, const QaryCall &c, const McTables &t, const McSecretOut &o, size_t law_words)
+{
+    QaryCall work = c;
+    work.dev_io = true;
+    SC_TRY(ensure_buffers(h, work));
+    SC_TRY(h->d_mc_lvl.ensure((size_t)h->N * c.Bp));
+    SC_TRY(h->d_mc_sec.ensure((size_t)h->N * c.Bp));
+    if (h->d_mc_tab.cap() < (size_t)2 * t.floats()) h->mc_tab_ok = false;
+    SC_TRY(h->d_mc_tab.ensure((size_t)2 * t.floats()));
+    if (h->d_mc_law.cap() < law_words) h->mc_law_ok = false;
+    SC_TRY(h->d_mc_law.ensure(law_words));
+    if (c.dev_io) return 0;
+    SC_TRY(h->d_mc_res.ensure((size_t)4 * c.batch + ((size_t)c.batch + 3) / 4));
+    if (o.secret) SC_TRY(h->d_mc_sec_out.ensure((size_t)c.batch * h->N));
+    if (o.levels) SC_TRY(h->d_mc_lvl_out.ensure((size_t)c.batch * h->N));
+    if (o.symbols) SC_TRY(h->d_out.ensure((size_t)c.batch * h->N));
+    return 0;
+}
+
+// The first step: the tables' LLR rows (mc_rows) and the law (copied unless it is the last finished call's, word for word), then
+// the secret and the outcomes of the coefficient variables, then the row sums and theirs.
+int secret_draw(scaldpc_qary *h, const QaryCall &c, const McTables &t, const std::vector<unsigned> &law, const SecretLawAt &at,
+                long first_trial, uint64_t seed)
+{
+    float *d_rows = nullptr;
+    SC_TRY(mc_rows(h, c, t, &d_rows));
+    if (!(h->mc_law_ok && h->mc_law == law)) {
+        h->mc_law_ok = false;
+        h->mc_law = law;
+        SC_HIP(hipMemcpyAsync(h->d_mc_law, h->mc_law.data(), at.words * sizeof(unsigned), hipMemcpyHostToDevice, c.s));
+    }
+    const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
+    hipLaunchKernelGGL(k_q_mc_secret_draw, dim3((c.BV + 3) / 4, c.Bp / 64), dim3(256), mc_secret_lds_bytes(t.K[0], t.Q[0]), c.s,
+                       (const u64 *)h->d_mc_law.get(), h->d_mc_law + at.tab[0], d_rows, t.K[0], t.Q[0], c.BV, c.batch, c.Bp, first_trial, k0,
+                       k1, h->d_col_ptr, h->d_csc_edge, h->d_edge_h, h->d_llr, h->d_msg, h->W, h->d_mc_lvl, h->d_mc_sec);
+    SC_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_q_mc_secret_sums, dim3((h->R + 3) / 4, c.Bp / 64), dim3(256), mc_secret_lds_bytes(t.K[1], t.Q[1]), c.s,
+                       h->d_mc_law + at.tab[1], d_rows + t.K[0] * t.Q[0], t.K[1], t.Q[1], t.Q[0], c.BV, h->R, c.batch, c.Bp, first_trial, k0,
+                       k1, h->d_row_ptr, h->d_edge_var, h->d_edge_h, h->d_llr, h->d_msg, h->W, h->d_mc_lvl, h->d_mc_sec);
+    SC_HIP(hipGetLastError());
+    return 0;
+}
+
+// The last step: the per-trial results; the optional [batch][N] arrays through k_q_unpack.  Host callers get wrong, channel_wrong
+// and success through ONE block and one copy, as mc_emit's.  Returns with the stream drained.
+int secret_emit(scaldpc_qary *h, const QaryCall &c, const SecretLawAt &at, const McSecretOut &o, u64 (&status)[2])
+{
+    const hipStream_t s = c.s;
+    const int batch = c.batch;
+    const size_t n_sym = (size_t)batch * h->N;
+    int *d_wrong = c.dev_io ? o.wrong : h->d_mc_res.get(), *d_chan = c.dev_io ? o.chan : h->d_mc_res.get() + 2 * (size_t)batch;
+    unsigned char *d_success = c.dev_io ? o.success : (unsigned char *)(h->d_mc_res.get() + 4 * (size_t)batch);
+    signed char *d_secret = c.dev_io ? (signed char *)o.secret : h->d_mc_sec_out.get();
+    unsigned char *d_levels = c.dev_io ? o.levels : h->d_mc_lvl_out.get();
+    signed char *d_symbols = c.dev_io ? (signed char *)o.symbols : h->d_out.get();
+    hipLaunchKernelGGL(k_q_mc_secret_result, dim3(c.Bp / 64), dim3(1024), 0, s, h->d_hard, h->d_mc_lvl, h->d_mc_sec,
+                       (const signed char *)(h->d_mc_law + at.best), h->N, c.BV, batch, c.Bp, d_success, d_wrong, d_chan);
+    SC_HIP(hipGetLastError());
+    const dim3 ug((h->N + 255) / 256, batch);
+    const auto unpack = [&](const void *plane, void *out) {
+        hipLaunchKernelGGL(k_q_unpack, ug, dim3(256), 0, s, (const signed char *)plane, h->N, batch, c.Bp, (signed char *)out);
+    };
+    if (o.secret) {
+        unpack(h->d_mc_sec.get(), d_secret);
+        SC_HIP(hipGetLastError());
+    }
+    if (o.levels) {
+        unpack(h->d_mc_lvl.get(), d_levels);
+        SC_HIP(hipGetLastError());
+    }
+    if (o.symbols) {
+        unpack(h->d_hard.get(), d_symbols);
+        SC_HIP(hipGetLastError());
+    }
+    SC_HIP(hipMemcpyAsync(status, h->d_status, sizeof(status), hipMemcpyDeviceToHost, s));
+    const size_t n_res = (size_t)4 * batch + ((size_t)batch + 3) / 4;
+    if (!c.dev_io) {
+        h->mc_res.resize(n_res);
+        SC_HIP(hipMemcpyAsync(h->mc_res.data(), h->d_mc_res, n_res * sizeof(int), hipMemcpyDeviceToHost, s));
+        if (o.secret) SC_HIP(hipMemcpyAsync(o.secret, d_secret, n_sym, hipMemcpyDeviceToHost, s));
+        if (o.levels) SC_HIP(hipMemcpyAsync(o.levels, d_levels, n_sym, hipMemcpyDeviceToHost, s));
+        if (o.symbols) SC_HIP(hipMemcpyAsync(o.symbols, d_symbols, n_sym, hipMemcpyDeviceToHost, s));
+    }
+    SC_HIP(hipStreamSynchronize(s));
+    h->mc_tab_ok = true;
+    h->mc_law_ok = true;
+    if (!c.dev_io) {
+        const int *res = h->mc_res.data();
+        if (o.wrong) memcpy(o.wrong, res, (size_t)2 * batch * sizeof(int));
+        if (o.chan) memcpy(o.chan, res + 2 * (size_t)batch, (size_t)2 * batch * sizeof(int));
+        memcpy(o.success, res + 4 * (size_t)batch, batch);
     }
     return 0;
 }
@@ -1427,6 +1578,31 @@ int scaldpc_mc_qary_run(scaldpc_qary *h, const float *levels_b, const double *we
         h, batch, flags, stream, SoftOut(), [&](QaryCall &c) { return mc_ensure(h, c, t, o); },
         [&](QaryCall &c) { return mc_draw(h, c, t, law, (long)first_trial, seed); },
         [&](QaryCall &c, u64(&status)[2]) { return mc_emit(h, c, law, o, status); });
+}
+
+int scaldpc_mc_qary_run_secret(scaldpc_qary *h, const double *prior_b, const float *levels_b, const double *weights_b, int32_t k_b,
+                               const float *levels_s, const double *weights_s, int32_t k_s, int64_t first_trial, int32_t batch,
+                               uint64_t seed, uint32_t flags, void *stream, uint8_t *out_success, int32_t *out_wrong,
+                               int32_t *out_channel_wrong, int8_t *out_secret, uint8_t *out_levels, int8_t *out_symbols)
+{
+    if (!h || !out_success) return fail(SCALDPC_EINVAL, "NULL argument");
+    if (!h->special)
+        return fail(SCALDPC_EINVAL, "this handle is not a special decoder: without row-sum variables a drawn secret is no code word");
+    McTables t;
+    t.levels[0] = levels_b; t.weights[0] = weights_b; t.K[0] = k_b; t.Q[0] = h->Q;
+    t.levels[1] = levels_s; t.weights[1] = weights_s; t.K[1] = k_s; t.Q[1] = h->QS;
+    McSecretLaw law;
+    char why[200];
+    if (const int kind = mc_qary_secret_law(prior_b, t.levels, t.weights, t.K, t.Q, (long long)first_trial, batch, (flags & SCALDPC_F_ASYNC) != 0,
+                                            &law, why, sizeof why))
+        return fail(kind == MC_SECRET_EPMF ? SCALDPC_EPMF : kind == MC_SECRET_EDEGREE ? SCALDPC_EDEGREE : SCALDPC_EINVAL, "%s", why);
+    std::vector<unsigned> words;
+    const SecretLawAt at = pack_secret_law(law, &words);
+    const McSecretOut o = {out_success, out_wrong, out_channel_wrong, out_secret, out_levels, out_symbols};
+    return qary_steps(
+        h, batch, flags, stream, SoftOut(), [&](QaryCall &c) { return secret_ensure(h, c, t, o, at.words); },
+        [&](QaryCall &c) { return secret_draw(h, c, t, words, at, (long)first_trial, seed); },
+        [&](QaryCall &c, u64(&status)[2]) { return secret_emit(h, c, at, o, status); });
 }
 
 void scaldpc_qary_destroy(scaldpc_qary *h)

@@ -212,6 +212,42 @@ def qary_fer_sweep(H, B, error_rate, runs, seed, chunk=4096, decoder_class=None)
     return res
 
 
+def kyber_fer_sweep(H, name, iterations, prior, table_b, table_s, runs, seed, chunk=4096, decoder_class=None):
+    """A sweep of the Kyber attack's decode (simulate/kyber.py) on drawn secrets: per trial a secret from `prior`
+    (`trials.centered_binomial`), the row sums that follow from it and H, every variable answered by an outcome of its table
+    (`trials.oracle_posterior_table`: table_b for the coefficients, table_s -- built with reverse=True -- for the row sums)
+    drawn on the device conditional on the variable's true value (`QarySpecialDecoder.mc_run_secret`).  `name` is the decoder's
+    (e.g. "DecoderN1280R512SW6").  Global trial indices 0 .. runs - 1 are scanned `chunk` at a time; the result does not depend
+    on `chunk`.  Returns dict(
+      runs, successes       trials, and those whose every coefficient was decided as drawn (the key is recovered),
+      wrong_hist            int64 [N - R + 1]: trials by their number of wrong coefficients after decoding,
+      channel_wrong, wrong  wrong coefficients over all trials: from the drawn rows alone, and after decoding)."""
+    Hd = H.to_dense(np.int8) if isinstance(H, TannerGraph) else np.asarray(H)
+    r, n = Hd.shape
+    if runs < 0 or chunk < 1:
+        raise ValueError("runs must not be negative and chunk must be positive")
+    if decoder_class is None:
+        from .qary import decoder_class as _dc
+
+        decoder_class = _dc
+    decoder = decoder_class(name)(Hd.astype(np.int8), iterations)
+    hist = np.zeros(n - r + 1, dtype=np.int64)
+    successes = channel_wrong = wrong = 0
+    try:
+        for first in range(0, runs, chunk):
+            out = decoder.mc_run_secret(min(chunk, runs - first), seed, prior, table_b["levels"], table_b["weights"], table_s["levels"],
+                                        table_s["weights"], first_trial=first)
+            w = np.asarray(out["wrong"], dtype=np.int64)[:, 0]
+            successes += int(np.asarray(out["success"]).astype(bool).sum())
+            hist += np.bincount(w, minlength=n - r + 1)
+            wrong += int(w.sum())
+            channel_wrong += int(np.asarray(out["channel_wrong"], dtype=np.int64)[:, 0].sum())
+    finally:
+        if hasattr(decoder, "close"):
+            decoder.close()
+    return dict(runs=int(runs), successes=successes, wrong_hist=hist, channel_wrong=channel_wrong, wrong=wrong)
+
+
 def hqc_oracle_sweep(Hin, N, omega, table, runs, seed, chunk=4096, bp_method="product_sum", max_iter=100, bp_decoder=None,
                      want_stats=False):
     """A sweep of synthetic hqc.decode() trials at a FIXED number of checks (the rows of Hin) under the law of the attack's

@@ -11,6 +11,9 @@ compute beyond the symbols: the last variable update's per-symbol totals, the ma
 of checks the decided word leaves unmet (include/scaldpc.h, scaldpc_qary_min_sum_batch_soft).
 `mc_run` / `mc_run_device` run whole Monte-Carlo trials of the reference's q-ary sweep on the device: the symbols' pmf rows
 are drawn there from a small table of levels, and one flag per trial comes back (include/scaldpc.h, scaldpc_mc_qary_run).
+`QarySpecialDecoder.mc_run_secret` / `mc_run_secret_device` run the Kyber attack's trial instead: a secret drawn from a prior, the
+row sums that follow from it, every variable answered by an oracle outcome drawn conditional on its true symbol -- is the key
+recovered (include/scaldpc.h, scaldpc_mc_qary_run_secret; the tables: trials.oracle_posterior_table).
 
   DecoderN{N}R{R}V{DV}C{DC}B{B}(H: int8 [R, N], iterations)   .min_sum(pmf float32 [N, 2B+1]) -> list[int]
   DecoderN{N}R{R}SW{SW}(H: int8 [R, N], iterations)           .min_sum(pmf [N-R, 5], pmf_sum [R, 2*BSUM+1]) -> list[int]
@@ -288,6 +291,59 @@ class QarySpecialDecoder(_QaryBase):
         """Device-pointer variant (ints; 0 = not wanted); the tables stay host arrays."""
         tables = (self._mc_table(levels, weights, self.Q, "levels"), self._mc_table(levels_sum, weights_sum, self.QS, "levels_sum"))
         self._mc_device(tables, runs, seed, first_trial, stream, (d_success, d_errs, d_wrong, d_levels, d_symbols))
+
+    # -- trials on drawn secrets under an oracle's law (include/scaldpc.h, scaldpc_mc_qary_run_secret) --------------------------
+    @staticmethod
+    def _secret_table(levels, weights, Q, what):
+        """One table as the C entry point takes it: float32 [K, Q] pmf rows, float64 [Q, K] outcome laws (row = TRUE symbol)."""
+        lv = np.ascontiguousarray(levels, dtype=np.float32)
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if lv.ndim != 2 or lv.shape[1] != Q or w.shape != (Q, lv.shape[0]):
+            raise ValueError(f"{what}: levels {lv.shape} / weights {w.shape}, expected (K, {Q}) pmf rows and ({Q}, K) outcome laws")
+        return lv, w
+
+    def _secret_call(self, prior, levels, weights, levels_sum, weights_sum, first_trial, runs, seed, flags, stream, outs):
+        pr = np.ascontiguousarray(prior, dtype=np.float64)
+        if pr.shape != (self.Q,):
+            raise ValueError(f"prior has shape {pr.shape}, expected ({self.Q},)")
+        lb, wb = self._secret_table(levels, weights, self.Q, "levels")
+        ls, ws = self._secret_table(levels_sum, weights_sum, self.QS, "levels_sum")
+        _lib.check(self._lib.scaldpc_mc_qary_run_secret(
+            self._h, _lib.ptr(pr), _lib.ptr(lb), _lib.ptr(wb), lb.shape[0], _lib.ptr(ls), _lib.ptr(ws), ls.shape[0], int(first_trial),
+            int(runs), int(seed), flags, C.c_void_p(stream or None), *outs))
+
+    def mc_run_secret(self, runs, seed, prior, levels, weights, levels_sum, weights_sum, first_trial=0, want_secret=False,
+                      want_levels=False, want_symbols=False):
+        """`runs` trials of the Kyber attack's decode (simulate/kyber.py), drawn on the device and Philox-keyed by (seed,
+        first_trial + i): every coefficient draws its true symbol from `prior` (float64 [Q], index q = value q - B), every row-sum
+        variable takes the one value that makes its check hold, and every variable draws an oracle outcome k with probability
+        weights[s, k] (weights_sum[s, k]), s its TRUE symbol, which hands the decoder the pmf row levels[k] (levels_sum[k]) --
+        `trials.oracle_posterior_table` builds both.  Returns dict(success uint8 [runs] (every coefficient decided as drawn: the key
+        is recovered), wrong int32 [runs, 2] (decisions != secret over the coefficients, over the row sums), channel_wrong int32
+        [runs, 2] (variables whose drawn row alone decides wrong)), with want_secret / want_levels / want_symbols also secret int8
+        [runs, N], levels uint8 [runs, N], symbols int8 [runs, N]: the symbols are
+        `min_sum_batch(levels[lv[:, :N-R]], levels_sum[lv[:, N-R:]])`, bit for bit."""
+        runs = int(runs)
+        if runs <= 0:
+            raise ValueError("runs must be positive")
+        res = {"success": np.empty(runs, dtype=np.uint8), "wrong": np.empty((runs, 2), dtype=np.int32),
+               "channel_wrong": np.empty((runs, 2), dtype=np.int32)}
+        if want_secret:
+            res["secret"] = np.empty((runs, self.N), dtype=np.int8)
+        if want_levels:
+            res["levels"] = np.empty((runs, self.N), dtype=np.uint8)
+        if want_symbols:
+            res["symbols"] = np.empty((runs, self.N), dtype=np.int8)
+        outs = [_lib.ptr(res.get(k)) for k in ("success", "wrong", "channel_wrong", "secret", "levels", "symbols")]
+        self._secret_call(prior, levels, weights, levels_sum, weights_sum, first_trial, runs, seed, 0, 0, outs)
+        return res
+
+    def mc_run_secret_device(self, runs, seed, prior, levels, weights, levels_sum, weights_sum, d_success, d_wrong=0, d_channel_wrong=0,
+                             d_secret=0, d_levels=0, d_symbols=0, first_trial=0, stream=0):
+        """Device-pointer variant (ints; 0 = not wanted): the outputs of `mc_run_secret` into HBM; prior and tables stay host
+        arrays.  Returns after the stream work is complete."""
+        outs = [C.c_void_p(d or None) for d in (d_success, d_wrong, d_channel_wrong, d_secret, d_levels, d_symbols)]
+        self._secret_call(prior, levels, weights, levels_sum, weights_sum, first_trial, runs, seed, _lib.F_DEVICE_IO, stream, outs)
 
     def min_sum_soft(self, py_channel_output, py_channel_output_sum, costs=True, margins=True, unmet=True):
         p, ps = np.asarray(py_channel_output), np.asarray(py_channel_output_sum)

@@ -7,6 +7,10 @@ Trial i (global index, independent of how trials are sharded over GPUs):
     c     = Hin y mod 2, each bit flipped with probability eps   (noisy oracle answers)
     msg   = [0]*N ++ c                          (hqc.py:703-705)
     prior = [omega/N]*N ++ [eps]*R              (hqc.py:684-690 with certainty 1-eps)
+
+Kyber attack trials (simulate/kyber.py) are drawn on the device (`QarySpecialDecoder.mc_run_secret`); what the host builds for
+them is here: the secret's law (`centered_binomial`) and, per kind of variable, the table of an oracle's answers with the
+posterior each answer hands the decoder (`oracle_posterior_table`).
 """
 from __future__ import annotations
 
@@ -139,6 +143,90 @@ def levels_table(levels, weights):
     row = np.stack([w * (1.0 - levels), w * levels], axis=1).reshape(-1)
     return dict(weights=np.stack([row, row]), flips=np.tile(np.array([1, 0], dtype=np.uint8), levels.size),
                 probs=np.repeat(1.0 - levels, 2), costs=None)
+
+
+def centered_binomial(eta, sum_weight=1):
+    """kyber.secret_distribution (simulate/kyber.py:60-64): the law of a sum of `sum_weight` coefficients of the centred binomial
+    of parameter eta, float64 [2B+1] with B = sum_weight * eta, index q = value q - B."""
+    from math import comb
+
+    B = int(sum_weight) * int(eta)
+    if B < 1:
+        raise ValueError("eta and sum_weight must be positive")
+    n = 2 * B
+    den = 2**n
+    return np.array([comb(n, q) / den for q in range(n + 1)], dtype=np.float64)
+
+
+MAX_POSTERIOR_OUTCOMES = 32  # scaldpc_mc_qary_run_secret takes tables of up to 32 outcomes: five oracle bits
+
+
+def _oracle_bit_law(accuracy, P):
+    """pr[i][expected][actual] of oracle bit i: a scalar is max_likelihood.SimpleOracle (right with probability `accuracy`), P
+    (false-positive, false-negative) pairs are FalsePositiveNegativePositionalOracle (simulate/max_likelihood.py:9-38), the
+    same float64 expressions."""
+    if np.ndim(accuracy) == 0:
+        p = float(accuracy)
+        if not 0.0 <= p <= 1.0:
+            raise ValueError("accuracy is a probability")
+        return [((p, 1 - p), (1 - p, p))] * P
+    pairs = [(float(fp), float(fn)) for fp, fn in accuracy]
+    if len(pairs) != P or not all(0.0 <= x <= 1.0 for pair in pairs for x in pair):
+        raise ValueError(f"accuracy: one probability, or {P} (false-positive, false-negative) pairs of probabilities")
+    return [((1 - fp, fp), (fn, 1 - fn)) for fp, fn in pairs]
+
+
+def oracle_posterior_table(coding, prior, accuracy, reverse=False):
+    """The table of one kind of variable for `QarySpecialDecoder.mc_run_secret`, from the oracle's code:
+
+      coding[s]  the P oracle bits of symbol s (a tuple of 0 / 1, or a single 0 / 1), s = 0 .. Q-1 standing for the value s - B
+      prior      float64 [Q], the law of the symbol (`centered_binomial`)
+      accuracy   a scalar (SimpleOracle) or P (false-positive, false-negative) pairs (FalsePositiveNegativePositionalOracle)
+
+    An outcome is one of the 2^P answers y, in the order of itertools.product((0, 1), repeat=P):
+        weights[s][y] = prod_i Pr[y_i | coding[s][i]]                 (max_likelihood.pr_cond_yx)
+        levels[y][s]  = weights[s][y] * prior[s] / sum_s' prior[s'] * weights[s'][y]
+    the posterior max_likelihood.s_distribution_from_hard_y gives the decoder for the answer y, in the same order of float64
+    operations.  An answer whose probability is 0 under every symbol is dropped (its posterior is 0 / 0 and it is never drawn).
+    reverse: the table of the variable t = -s (kyber.get_channel_probabilities reverses the row sums' distributions,
+    kyber.py:374-375): the symbol axis of both arrays is reversed.
+    Returns dict(levels float64 [K, Q], weights float64 [Q, K], answers [K] tuples).  Raises ValueError beyond 32 outcomes."""
+    import itertools
+
+    code = [tuple(int(b) for b in (c if np.ndim(c) else (c,))) for c in coding]
+    pr = [float(x) for x in np.asarray(prior, dtype=np.float64).reshape(-1)]
+    Q = len(code)
+    if Q < 1 or len(pr) != Q:
+        raise ValueError("coding and prior: one entry per symbol")
+    P = len(code[0])
+    if P < 1 or any(len(c) != P or any(b not in (0, 1) for b in c) for c in code):
+        raise ValueError("coding: the same number of oracle bits, 0 or 1, for every symbol")
+    if 2**P > MAX_POSTERIOR_OUTCOMES:
+        raise ValueError(f"{2 ** P} outcomes: scaldpc_mc_qary_run_secret takes up to {MAX_POSTERIOR_OUTCOMES}")
+    law = _oracle_bit_law(accuracy, P)
+    answers, weights, levels = [], [], []
+    for y in itertools.product((0, 1), repeat=P):
+        cond = []
+        for s in range(Q):
+            res = 1
+            for i in range(P):
+                res *= law[i][code[s][i]][y[i]]
+            cond.append(res)
+        pr_y = 0
+        for s in range(Q):
+            pr_y += pr[s] * cond[s]
+        if pr_y == 0:
+            continue
+        answers.append(y)
+        weights.append(cond)
+        levels.append([cond[s] * pr[s] / pr_y for s in range(Q)])
+    if not answers:
+        raise ValueError("no answer has a positive probability")
+    weights = np.array(weights, dtype=np.float64).T
+    levels = np.array(levels, dtype=np.float64)
+    if reverse:
+        weights, levels = weights[::-1], levels[:, ::-1]
+    return dict(levels=np.ascontiguousarray(levels), weights=np.ascontiguousarray(weights), answers=answers)
 
 
 def hqc_priors(N, R, omega, eps):
