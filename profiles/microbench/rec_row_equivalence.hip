@@ -3,7 +3,8 @@
 // word), check_minsum_row_rec is the PRODUCT's (scaldpc_bp_kernels.h, included as it stands: scalar parity mask,
 // v_med3 / v_min on clamped magnitudes, the arg-min as a byte per lane, and -- in its bootstrap form, the one run here --
 // the sign masks through v_writelane, the LLVM intrinsic).  The product's per-edge masks are rebuilt from what it
-// writes, as its variable pass does: negative = sign mask XOR the row's parity word, arg-min = (arg byte == edge).
+// writes, as its variable pass does: negative = sign mask XOR the sign bit of the row's record (the row's parity),
+// magnitude = the record with that bit cleared, arg-min = (arg byte == edge).
 // Inputs full of ties, zeros, negative
 // zeros, NaN, +-inf and FLT_MAX, EVERY degree 1 .. 64.  A difference is a bug: in round 3 this program found the
 // VALU-writes-SGPR -> inline-asm v_writelane hazard on degree-1 rows.  It is a different translation unit from the
@@ -61,13 +62,13 @@ __device__ __forceinline__ void row_old(const float *p, u64 synd_mask, float alp
 
 template <int DEG>
 __global__ void k(const float *msg, const u64 *synd, float alpha, float *recA, float *rec2A, ulonglong2 *maskA, float *recB, float *rec2B, u64 *sgnB,
-                  unsigned char *argB, u64 *parB, const int *iota)
+                  unsigned char *argB, const int *iota)
 {
     const int lane = threadIdx.x, r = blockIdx.x;
     const float *p = msg + (size_t)r * DEG * TW + lane;
     row_old<DEG, false>(p, synd[r], alpha, nullptr, nullptr, recA + r * TW, rec2A + r * TW, maskA + r * DEG, lane);
     // (the product lays its masks out by position in the variable pass's edge list; here edge k's position is k)
-    check_minsum_row_rec<DEG, true>(p, synd[r], alpha, recB + r * TW, rec2B + r * TW, argB + r * TW, parB + r, sgnB + r * DEG, lane, iota);
+    check_minsum_row_rec<DEG, true>(p, synd[r], alpha, recB + r * TW, rec2B + r * TW, argB + r * TW, sgnB + r * DEG, lane, iota);
 }
 template <int DEG>
 int run(int rows, unsigned seed)
@@ -85,23 +86,38 @@ int run(int rows, unsigned seed)
     }
     std::vector<u64> sy(rows);
     for (auto &v : sy) v = ((u64)rand() << 40) ^ ((u64)rand() << 20) ^ rand();
-    float *d, *ra, *r2a, *rb, *r2b; u64 *ds, *sb, *pb; ulonglong2 *ma; unsigned char *ab; int *iota;
+    float *d, *ra, *r2a, *rb; u64 *ds, *sb; ulonglong2 *ma; unsigned char *ab; int *iota;
     int hi[64];
     for (int i = 0; i < 64; i++) hi[i] = i;
     hipMalloc(&iota, sizeof hi); hipMemcpy(iota, hi, sizeof hi, hipMemcpyHostToDevice);
     hipMalloc(&d, h.size() * 4); hipMalloc(&ds, rows * 8);
-    hipMalloc(&ra, rows * TW * 4); hipMalloc(&r2a, rows * TW * 4); hipMalloc(&rb, rows * TW * 4); hipMalloc(&r2b, rows * TW * 4);
-    hipMalloc(&ma, rows * DEG * 16); hipMalloc(&sb, rows * DEG * 8); hipMalloc(&ab, rows * TW); hipMalloc(&pb, rows * 8);
+    hipMalloc(&ra, rows * TW * 4); hipMalloc(&r2a, rows * TW * 4); hipMalloc(&rb, rows * TW * 8);
+    hipMalloc(&ma, rows * DEG * 16); hipMalloc(&sb, rows * DEG * 8); hipMalloc(&ab, rows * TW);
     hipMemcpy(d, h.data(), h.size() * 4, hipMemcpyHostToDevice); hipMemcpy(ds, sy.data(), rows * 8, hipMemcpyHostToDevice);
-    hipLaunchKernelGGL(k<DEG>, dim3(rows), dim3(64), 0, 0, d, ds, 0.75f, ra, r2a, ma, rb, r2b, sb, ab, pb, iota);
+    hipLaunchKernelGGL(k<DEG>, dim3(rows), dim3(64), 0, 0, d, ds, 0.75f, ra, r2a, ma, rb, rb + rows * TW, sb, ab, iota);
     hipDeviceSynchronize();
-    std::vector<float> A(rows * TW), A2(rows * TW), B(rows * TW), B2(rows * TW);
-    std::vector<u64> MA(rows * DEG * 2), MB(rows * DEG * 2), SB(rows * DEG), PB(rows);
+    std::vector<float> A(rows * TW), A2(rows * TW), B(rows * TW), B2(rows * TW), BB(rows * TW * 2);
+    std::vector<u64> MA(rows * DEG * 2), MB(rows * DEG * 2), SB(rows * DEG), PB(rows), PB2(rows);
     std::vector<unsigned char> AB(rows * TW);
     hipMemcpy(A.data(), ra, A.size() * 4, hipMemcpyDeviceToHost); hipMemcpy(A2.data(), r2a, A.size() * 4, hipMemcpyDeviceToHost);
-    hipMemcpy(B.data(), rb, A.size() * 4, hipMemcpyDeviceToHost); hipMemcpy(B2.data(), r2b, A.size() * 4, hipMemcpyDeviceToHost);
+    hipMemcpy(BB.data(), rb, BB.size() * 4, hipMemcpyDeviceToHost);
+    // both magnitude planes carry the row's parity in their sign bit: take it off (PB, PB2: the parity as lane masks)
+    for (int r = 0; r < rows; r++) {
+        PB[r] = PB2[r] = 0;
+        for (int l = 0; l < TW; l++) {
+            unsigned u[2];
+            memcpy(&u[0], &BB[(size_t)r * TW + l], 4);
+            memcpy(&u[1], &BB[(size_t)(rows + r) * TW + l], 4);
+            PB[r] |= (u64)(u[0] >> 31) << l;
+            PB2[r] |= (u64)(u[1] >> 31) << l;
+            u[0] &= 0x7fffffffu;
+            u[1] &= 0x7fffffffu;
+            memcpy(&B[r * TW + l], &u[0], 4);
+            memcpy(&B2[r * TW + l], &u[1], 4);
+        }
+    }
     hipMemcpy(MA.data(), ma, MA.size() * 8, hipMemcpyDeviceToHost); hipMemcpy(SB.data(), sb, SB.size() * 8, hipMemcpyDeviceToHost);
-    hipMemcpy(AB.data(), ab, AB.size(), hipMemcpyDeviceToHost); hipMemcpy(PB.data(), pb, PB.size() * 8, hipMemcpyDeviceToHost);
+    hipMemcpy(AB.data(), ab, AB.size(), hipMemcpyDeviceToHost);
     // the product's per-edge masks, rebuilt as k_var_rec rebuilds them
     for (int r = 0; r < rows; r++)
         for (int e = 0; e < DEG; e++) {
@@ -112,6 +128,7 @@ int run(int rows, unsigned seed)
         }
     // compare the MESSAGES the variable pass would rebuild (an arg-min flag on another edge of the same magnitude is the same message)
     long bad = 0, badrec = 0, badneg = 0;
+    for (int r = 0; r < rows; r++) badrec += PB[r] != PB2[r];  // both floats of a record carry the same parity
     for (int r = 0; r < rows; r++)
         for (int l = 0; l < TW; l++) {
             if (memcmp(&A[r * TW + l], &B[r * TW + l], 4) || memcmp(&A2[r * TW + l], &B2[r * TW + l], 4)) badrec++;
@@ -125,7 +142,7 @@ int run(int rows, unsigned seed)
             }
         }
     printf("DEG %2d: %ld of %d messages differ, %ld records, %ld signs\n", DEG, bad, rows * TW * DEG, badrec, badneg);
-    for (void *q : {(void *)d, (void *)ds, (void *)ra, (void *)r2a, (void *)rb, (void *)r2b, (void *)ma, (void *)sb, (void *)ab, (void *)pb, (void *)iota}) (void)hipFree(q);
+    for (void *q : {(void *)d, (void *)ds, (void *)ra, (void *)r2a, (void *)rb, (void *)ma, (void *)sb, (void *)ab, (void *)iota}) (void)hipFree(q);
     return bad != 0 || badrec != 0;
 }
 template <int DEG>

@@ -204,8 +204,8 @@ struct scaldpc_bp : HandleStreams {
     // iteration 1 without its check pass: {first check-to-variable message of a zero-syndrome codeword, row} per position
     // of the re-laid edge list; valid for one (method, alpha of iteration 1) and the current priors / graph
     Buf<int2> d_first_tab;
-    // record form of min-sum on the tile kernels: d_rec = per tile a block of rec_tile_floats(m) floats (per row the two
-    // magnitudes, the arg-min byte per codeword and the parity mask), d_mask = per (tile, position of the re-laid edge
+    // record form of min-sum on the tile kernels: d_rec = per tile a block of rec_tile_floats(m) floats (per row and
+    // codeword the two magnitudes with the row's parity in their sign bit, and the arg-min byte), d_mask = per (tile, position of the re-laid edge
     // list) the lane mask "the variable pass's message on this edge is <= 0";
     // d_csc_row = row word of every position of the re-laid edge list (inside d_tile_tab; scaldpc_rec_pack.h)
     Buf<float> d_rec;

@@ -722,22 +722,26 @@ __global__ __launch_bounds__(256) void k_check_minsum_x(const int *__restrict__ 
 // smallest incoming |x| to every edge but the arg-min, the second smallest to that one -- and a sign per edge.  Instead
 // of 4 B per edge and codeword (which the variable pass reads back as a gather), this pass leaves the message array
 // alone and writes, per (row, tile), NOTHING per edge:
-//     rec  [tile][2][row][64]  float : m1 * alpha | m2 * alpha         (8 B per row and codeword; two dense planes per
-//                                      tile: interleaved by row, the always-read first magnitudes would sit at a
-//                                      512-B stride, i.e. in half of the L2's sets and channels)
+//     rec  [tile][2][row][64]  float : m1 * alpha | m2 * alpha, each with the row's PARITY in its sign bit: negative
+//                                      where the syndrome bit XOR the XOR over the row's edges of (x <= 0) is 1.  The
+//                                      magnitudes are never negative (and never NaN: clamped to FLT_MAX), so the bit
+//                                      is free.  8 B per row and codeword; two dense planes per tile.  (One float2
+//                                      per row and codeword -- 512-B rows, either a 4-byte gather at an 8-byte stride
+//                                      or both floats in one 8-byte gather -- measured 7 % slower per step:
+//                                      profiles/minsum_signed_records/README.md)
 //     arg  [tile][row][64]     u8    : index IN THE ROW of the codeword's arg-min edge -- the FIRST edge whose |x|
 //                                      equals m1; REC_NO_ARG where no edge attains it (all inputs NaN or infinite)
-//     par  [tile][row]         u64   : lane mask, syndrome bit XOR the XOR over the row's edges of (x <= 0)
-// (arg and par are further planes of a tile's block of d_rec: rec_tile_floats().)  The sign a check sends on edge e is
-// par XOR (x_e <= 0), and x_e is the message the VARIABLE pass itself stored on that edge one pass earlier, so that pass
-// keeps the second factor, per column and contiguously:
+// (arg is a third plane of a tile's block of d_rec: rec_tile_floats(), scaldpc_rec_pack.h.)  The sign a check sends on
+// edge e is parity XOR (x_e <= 0), and x_e is the message the VARIABLE pass itself stored on that edge one pass earlier,
+// so that pass keeps the second factor, per column and contiguously:
 //     sgn  [tile][position]    u64   : lane mask "the v2c message at this position of the variable pass's edge order
 //                                      is <= 0" (a float compare: +-0 count, NaN does not), written by k_var_rec from
 //                                      the very floats it stores
-// and rebuilds every message: c2v = +-(arg-min ? rec[1] : rec[0]).  Since m * (-alpha) == -(m * alpha) in IEEE
-// arithmetic, that is the float k_check_minsum_x would have stored, bit for bit; the sums that follow run in the same
-// order, so nothing about parity changes -- only the bytes: the check pass reads 4 B per edge and writes next to
-// nothing, and the 2 MB of records per tile (HQC-128) are L2-sized.
+// and rebuilds every message: c2v bits = (arg-min ? rec[1] : rec[0]) bits XOR (own sgn bit << 31).  Negation is a flip of
+// the sign bit (of zeros and of FLT_MAX too) and m * (-alpha) == -(m * alpha) in IEEE arithmetic, so that is the float
+// k_check_minsum_x would have stored, bit for bit; the sums that follow run in the same order, so nothing about parity
+// changes -- only the bytes: the check pass reads 4 B per edge and writes next to nothing, and the 2.3 MB of records
+// and arg-min bytes per tile (HQC-128) are L2-sized.
 // The FIRST record-form check pass of a group (BOOT) has no sgn from a k_var_rec before it -- its inputs were written
 // by k_var_first or k_var -- so it also writes sgn[pos[k]] = ballot(x_k <= 0) itself, scattered by position.
 // Measured before it was built: profiles/microbench/minsum_records.hip.
@@ -753,17 +757,12 @@ __global__ __launch_bounds__(256) void k_check_minsum_x(const int *__restrict__ 
 //            `ix` did.  A compare and a select: 6 VALU instructions per edge in all.
 //   BOOT only, per edge: negative? again (the inputs are still in registers) -> lane k of two registers with v_writelane.
 constexpr unsigned REC_NO_ARG = 255;  // (no row has an edge 255: rows of the record form have at most 64)
-// floats of one tile's block of d_rec: [2][m][64] magnitudes, then arg (64 bytes per row), then par (8 bytes per row);
-// whole 256-B lines
-__host__ __device__ inline size_t rec_tile_floats(int m) { return ((size_t)m * (2 * TW + TW / 4 + 2) + 63) / 64 * 64; }
-__host__ __device__ inline size_t rec_arg_off(int m) { return (size_t)m * 2 * TW; }               // in floats, from the tile's block
-__host__ __device__ inline size_t rec_par_off(int m) { return (size_t)m * (2 * TW + TW / 4); }  // (a multiple of 2: 8-B aligned)
+static_assert(REC_TW == TW, "the record layout of scaldpc_rec_pack.h is laid out for the kernels' tile width");
 
 template <int DEG, bool BOOT>
 __device__ __forceinline__ void check_minsum_row_rec(const float *p, u64 synd_mask, float alpha, float *__restrict__ rec,
                                                      float *__restrict__ rec2, unsigned char *__restrict__ arg,
-                                                     u64 *__restrict__ par_out, u64 *__restrict__ sgn, int lane,
-                                                     const int *__restrict__ pos)
+                                                     u64 *__restrict__ sgn, int lane, const int *__restrict__ pos)
 {
     // BOOT: the sign masks are laid out in the variable pass's order (position of the edge in the re-laid edge list: a
     // column's masks are contiguous there); lane k fetches edge k's position up front
@@ -794,9 +793,13 @@ __device__ __forceinline__ void check_minsum_row_rec(const float *p, u64 synd_ma
         asm("v_med3_f32 %0, %1, %2, %0" : "+v"(m2) : "v"(a), "v"(m1));
         asm("v_min_f32 %0, %0, %1" : "+v"(m1) : "v"(a));
     }
-    rec[lane] = m1 * alpha;
-    rec2[lane] = m2 * alpha;
-    if (lane == 0) *par_out = par;
+    {
+        // the row's parity goes into the records' sign bit: one select with a negated source each, on the scalar mask
+        const bool odd = __builtin_amdgcn_inverse_ballot_w64(par);
+        const float r1 = m1 * alpha, r2 = m2 * alpha;
+        rec[lane] = odd ? -r1 : r1;
+        rec2[lane] = odd ? -r2 : r2;
+    }
     unsigned idx = REC_NO_ARG;
 #pragma unroll
     for (int k = DEG - 1; k >= 0; k--) {
@@ -861,10 +864,9 @@ __global__ __launch_bounds__(256) void k_check_minsum_rec(const int *__restrict_
         const int e0 = md[1];
         const int deg = md[2];
         const float *p = msg + ((size_t)tl * E + e0) * TW + lane;
-        float *rt = rec + (size_t)tl * rec_tile_floats(m);  // the tile's block: [m1 | m2][row][64], arg, par
-        float *rc = rt + (size_t)r * TW, *rc2 = rc + (size_t)m * TW;
+        float *rt = rec + (size_t)tl * rec_tile_floats(m);  // the tile's block: [m1 | m2][row][64], arg
+        float *rc = rt + rec_row_off(r), *rc2 = rc + rec_m2_off(m);
         unsigned char *ar = (unsigned char *)(rt + rec_arg_off(m)) + (size_t)r * TW;
-        u64 *pa = (u64 *)(rt + rec_par_off(m)) + r;
         u64 *sg = sgn + (size_t)tl * E;  // (masks by position: the tile's base)
         const int *ps = csr_pos + e0;
         const u64 sw = synd[(size_t)tl * m + r];  // (uniform: a scalar load; the row's syndrome bits ARE a lane mask)
@@ -872,7 +874,7 @@ __global__ __launch_bounds__(256) void k_check_minsum_rec(const int *__restrict_
         // record-form kernels come out with other registers and an instruction more or less)
 #define MR(D)                                                                                               \
     case D:                                                                                                 \
-        if constexpr (D <= CAP) check_minsum_row_rec<D, BOOT>(p, sw, alpha, rc, rc2, ar, pa, sg, lane, ps); \
+        if constexpr (D <= CAP) check_minsum_row_rec<D, BOOT>(p, sw, alpha, rc, rc2, ar, sg, lane, ps); \
         break;
 #define MR8(D) MR(D) MR(D + 1) MR(D + 2) MR(D + 3) MR(D + 4) MR(D + 5) MR(D + 6) MR(D + 7)
         switch (deg) {
@@ -1495,10 +1497,12 @@ __global__ __launch_bounds__(256) void k_var_first(const int *__restrict__ list,
 // codeword's arg-min", and it SELECTS THE ADDRESS of the one magnitude gather that follows -- the lane's word of the
 // row's second-magnitude plane instead of the first (the planes lie m rows apart: one v_cndmask on the lane's byte
 // offset).  One gather per edge and lane, no execute-mask juggling, no mask kept in SGPRs between a load and a select.
-// All arg-min bytes of the column are in flight before the first is waited for, then all magnitudes.
-// The sign of edge k is par[row_k] XOR the column's own sign mask of that edge.  Lane j fetches the mask of the column's
-// j-th edge (contiguous) and the parity word of that edge's row (the row from csc_row, lane j's word) and XORs the
-// two: two VALU instructions for the whole column; edge k's word reaches the select through v_readlane.
+// All arg-min bytes of the column are in flight before the first is waited for, then all magnitudes.  (Fetching both
+// magnitudes in one independent 8-byte gather, with the compare selecting a register, saves the second round trip and
+// measured 5.7 % SLOWER per step: twice the record bytes between L2 and the CUs.  profiles/minsum_signed_records/.)
+// The records carry their row's parity in the sign bit, so the sign of edge k is that bit XOR the column's own sign
+// mask of the edge: lane j fetches the mask of the column's j-th edge (contiguous), edge k's word reaches a
+// sign-flipping select through v_readlane.  No parity plane, no row word per lane, no per-column parity gather.
 // The pass leaves the column's NEW sign masks behind: edge k's is the ballot of (stored float <= 0), taken from the
 // very value that is stored, put into lane k of two registers with v_writelane (the compiler's own: writelane()), and
 // lanes j < D store the words -- contiguous again.  They follow the messages for EVERY lane: the done bits freeze
@@ -1506,7 +1510,7 @@ __global__ __launch_bounds__(256) void k_var_first(const int *__restrict__ list,
 // Like the record-form check pass this kernel is bound by VALU issue (SQ counters: profiles/r03/sq_counters_*record*),
 // so it is straight-line code for the column's EXACT degree, dispatched wave-uniformly: the bucketed form (unrolled to
 // the bucket's bound, predicated on `k < d`) spent more instructions on the predicates than on the column.
-//   csc_row: row word of every position of the re-laid edge list (laid out like it)
+//   csc_row: row word of every position of the re-laid edge list (laid out like it); read for edges beyond VAR_INLINE
 //   rec2_off: bytes from a row's first magnitudes to its second ones (m * 256: below 2^32, rec_rows_fit)
 typedef __attribute__((address_space(1))) unsigned char gbyte;
 __device__ __forceinline__ gbyte *sbase_b(const unsigned char *p)
@@ -1518,30 +1522,24 @@ __device__ __forceinline__ gbyte *sbase_b(const unsigned char *p)
 
 template <int D>
 __device__ __forceinline__ float var_col_rec(float *tile_base, const float *__restrict__ rec_base, unsigned rec2_off,
-                                             const unsigned char *__restrict__ arg_base,
-                                             const u64 *__restrict__ par_base, u64 *sgn_col, unsigned lane,
+                                             const unsigned char *__restrict__ arg_base, u64 *sgn_col, unsigned lane,
                                              const int *__restrict__ rc, const int4 *__restrict__ row4,
                                              const int *__restrict__ ce1, const int *__restrict__ cr1, float pr)
 {
     int eid[D], rw[D];
     {
-        const int4 *rec4 = (const int4 *)rc;
-        const int4 a = rec4[1], b = rec4[2], c = rec4[3], e = rec4[4];
-        const int in16[16] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w, e.x, e.y, e.z, e.w};
         const int4 ra = row4[0], rb = row4[1], rc4 = row4[2], re = row4[3];
         const int rw16[16] = {ra.x, ra.y, ra.z, ra.w, rb.x, rb.y, rb.z, rb.w, rc4.x, rc4.y, rc4.z, rc4.w, re.x, re.y, re.z, re.w};
 #pragma unroll
-        for (int k = 0; k < D && k < VAR_INLINE; k++) {
-            eid[k] = in16[k];
-            rw[k] = rw16[k];
-        }
+        for (int k = 0; k < D && k < VAR_INLINE; k++) rw[k] = rw16[k];
 #pragma unroll
-        for (int k = VAR_INLINE; k < D; k++) rw[k] = cr1[k];  // (their edge ids are wanted by the stores alone: fetched below)
+        for (int k = VAR_INLINE; k < D; k++) rw[k] = cr1[k];
+        // (the edge ids are wanted by the stores alone: fetched below)
     }
-    // lane j: "the check's message on the column's j-th edge is negative" = the edge's sign mask (sgn_col = the mask of the
-    // column's first position: a column's masks are contiguous) XOR the parity word of the edge's row
+    // lane j: the sign mask of the column's j-th edge (sgn_col = the mask of the column's first position: a column's
+    // masks are contiguous); the row's parity comes with the record
     u64 sg = 0;
-    if ((int)lane < D) sg = sgn_col[lane] ^ par_base[rec_row_of(cr1[lane])];
+    if ((int)lane < D) sg = sgn_col[lane];
     const int slo = (int)(unsigned)sg, shi = (int)(unsigned)(sg >> 32);
     float mm[D], pp[D];
     unsigned ab[D];
@@ -1558,14 +1556,21 @@ __device__ __forceinline__ float var_col_rec(float *tile_base, const float *__re
         const u64 ng = ((u64)(unsigned)__builtin_amdgcn_readlane(shi, k) << 32) | (unsigned)__builtin_amdgcn_readlane(slo, k);
         mm[k] = __builtin_amdgcn_inverse_ballot_w64(ng) ? -mm[k] : mm[k];
     }
+    // the record's inline edge ids (wanted by the stores alone)
+    {
+        const int4 *rec4 = (const int4 *)rc;
+        const int4 a = rec4[1], b = rec4[2], c = rec4[3], e = rec4[4];
+        const int in16[16] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w, e.x, e.y, e.z, e.w};
+#pragma unroll
+        for (int k = 0; k < D && k < VAR_INLINE; k++) eid[k] = in16[k];
+    }
     float temp = pr;
 #pragma unroll
     for (int k = 0; k < D; k++) {
         pp[k] = temp;
         temp += mm[k];
     }
-    // the edge ids beyond the record's inline ones: held from the top they cost an SGPR per edge through the whole gather
-    // phase (with the row words and the masks: spills in the columns of 17+ edges)
+    // (those beyond the record's inline ones come from the edge list)
 #pragma unroll
     for (int k = VAR_INLINE; k < D; k++) eid[k] = ce1[k];
     float suf = 0.0f;
@@ -1617,18 +1622,17 @@ __global__ __launch_bounds__(256) void k_var_rec(const int *__restrict__ list, c
     const int cb = rc[1];
     const int d = rc[2];
     float *tb = msg + (size_t)tl * E * TW;
-    const float *rb = rec + (size_t)tl * rec_tile_floats(m);  // the tile's block: [m1 | m2][row][64], arg, par
-    const unsigned r2 = (unsigned)m * (TW * (unsigned)sizeof(float));
+    const float *rb = rec + (size_t)tl * rec_tile_floats(m);  // the tile's block: [m1 | m2][row][64], arg
     const unsigned char *ab = (const unsigned char *)(rb + rec_arg_off(m));
-    const u64 *pb = (const u64 *)(rb + rec_par_off(m));
     u64 *st = sgn + (size_t)tl * E;
     const int *ce = csc_edge + cb, *cr = csc_row + cb;
     const int4 *w4 = (const int4 *)(var_rows + (size_t)ri * VAR_INLINE);
     const float pr = prior(v, tl, (int)lane);
     float L = pr;
-#define VR(D)                                                                                               \
-    case D:                                                                                                 \
-        if constexpr (D <= CAP) L = var_col_rec<D>(tb, rb, r2, ab, pb, st + cb, lane, rc, w4, ce, cr, pr);  \
+    const unsigned r2 = (unsigned)m * (TW * (unsigned)sizeof(float));  // rec_m2_off(m) in bytes
+#define VR(D)                                                                                           \
+    case D:                                                                                             \
+        if constexpr (D <= CAP) L = var_col_rec<D>(tb, rb, r2, ab, st + cb, lane, rc, w4, ce, cr, pr);  \
         break;
 #define VR8(D) VR(D) VR(D + 1) VR(D + 2) VR(D + 3) VR(D + 4) VR(D + 5) VR(D + 6) VR(D + 7)
     switch (d) {
