@@ -79,7 +79,7 @@
 extern "C" {
 #endif
 
-#define SCALDPC_VERSION 103
+#define SCALDPC_VERSION 104
 
 /* status codes */
 #define SCALDPC_OK 0
@@ -235,6 +235,25 @@ int scaldpc_bp_last_compacted(scaldpc_bp *h, int64_t *count);
  *            compacted again, up to 3 levels)
  *   out[3] = reserved (0) */
 int scaldpc_bp_last_stats(scaldpc_bp *h, int64_t *out);
+/* The schedule the last decode or Monte-Carlo call ran on the tile kernels, out[SCALDPC_SCHEDULE_WORDS]: counters kept
+ * on the host (no device work), reset when a call starts.  Results never depend on any of this; the words say which way
+ * the early-exit scheduler went (scaldpc_bp_sched.h holds its rules):
+ *   out[0..3]  tile groups run at compaction level 0 .. 3
+ *   out[4..6]  codewords handed down FROM level 0 .. 2 (out[4] = scaldpc_bp_last_compacted)
+ *   out[7]     host polls of the tile loop (a synchronise plus a read of a "still running" counter)
+ *   out[8]     groups that stopped at the hand-over point UNSEEN (no poll: as the groups before them did)
+ *   out[9]     early-exit groups that continued the stream lanes of the group before them (no fork)
+ *   out[10]    early-exit groups whose lanes were left un-joined for the group after them
+ *   out[11]    fixed-iteration groups that continued the lanes of the group before them
+ *   out[12]    clears of the ring of counter rows after the call's first (the ring wrapped)
+ *   out[13]    clears that met un-joined lanes (always 0: no group is left open into a clear)
+ *   out[14]    rows of the ring during the call
+ *   out[15]    host polls of the row-parallel loop
+ *   out[16]    rows of the ring handed out
+ *   further words reserved (0)
+ * (entry point added under SCALDPC_VERSION 104: nothing that existed changed) */
+#define SCALDPC_SCHEDULE_WORDS 24
+int scaldpc_bp_last_schedule(scaldpc_bp *h, int64_t *out);
 /* Tuning / test knobs of one handle.  A new handle takes its defaults from the environment ONCE, at
  * creation (SCALDPC_PATH, SCALDPC_SPLIT, SCALDPC_GROUP_MB, SCALDPC_EL_MAX, SCALDPC_COMPACT_AFTER,
  * SCALDPC_FIRST_FUSED, SCALDPC_FUSE_TEST, SCALDPC_MINSUM_REC); the decode entry points never read the environment.

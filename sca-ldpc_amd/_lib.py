@@ -65,6 +65,8 @@ def _declare(lib):
     lib.scaldpc_bp_last_compacted.restype = C.c_int
     lib.scaldpc_bp_last_stats.argtypes = [vp, p(C.c_int64)]
     lib.scaldpc_bp_last_stats.restype = C.c_int
+    lib.scaldpc_bp_last_schedule.argtypes = [vp, p(C.c_int64)]
+    lib.scaldpc_bp_last_schedule.restype = C.c_int
     lib.scaldpc_bp_append_rows.argtypes = [vp, C.c_int32, vp, vp, C.c_int32]
     lib.scaldpc_bp_append_rows.restype = C.c_int
     lib.scaldpc_bp_set_channel_probs_tail.argtypes = [vp, C.c_int32, C.c_int32, vp]

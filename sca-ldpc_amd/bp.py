@@ -393,6 +393,18 @@ class BpDecoder:
         _lib.check(self._lib.scaldpc_bp_last_stats(self._h, out))
         return {"compacted": int(out[0]), "row_parallel": int(out[1]), "levels": int(out[2])}
 
+    def last_schedule(self):
+        """The schedule the last call ran on the tile kernels (scaldpc_bp_last_schedule): host-side counters, reset when
+        a call starts.  groups / handed_down are per compaction level; the rest says where the early-exit scheduler
+        polled, which groups stopped at the hand-over point unseen, which were chained lane to lane, and how often the
+        ring of "still running" counter rows wrapped."""
+        out = (C.c_int64 * 24)()
+        _lib.check(self._lib.scaldpc_bp_last_schedule(self._h, out))
+        w = [int(x) for x in out]
+        return {"groups": w[0:4], "handed_down": w[4:7], "polls": w[7], "unseen": w[8], "continued": w[9],
+                "left_open": w[10], "fixed_chained": w[11], "clears": w[12], "open_at_clear": w[13], "ring_rows": w[14],
+                "row_parallel_polls": w[15], "ring_takes": w[16]}  # fmt: skip
+
     def last_row_parallel(self):
         return self.last_stats()["row_parallel"]
 

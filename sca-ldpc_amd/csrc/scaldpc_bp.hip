@@ -29,6 +29,7 @@
 //
 // No MFMA anywhere: this is a sparse gather/scatter stream, not a contraction.
 #include "scaldpc_common.h"
+#include "scaldpc_bp_sched.h"
 #include "scaldpc_mc_law.h"
 
 #include <algorithm>
@@ -136,12 +137,13 @@ struct scaldpc_bp : HandleStreams {
     Buf<float> d_pprior, d_probs_in;
     Buf<u64> d_soft_bad;
     int cap_remaining = 0;  // counters per row of d_remaining (and of h_remaining)
-    // d_remaining holds rem_rows rows of cap_remaining "codewords still running after iteration it" counters: every tile
+    // d_remaining holds rem.rows rows of cap_remaining "codewords still running after iteration it" counters: every tile
     // group of a call takes the next row (zeroed once per call, not once per group: a memset is a 5 us launch in the
-    // group's dependency chain); rem_slot = next free row, rem_rows = all used (the next taker zeroes the array).
-    // rem_rows follows the groups a call can run (at most REM_SLOTS): max_iter defaults to n, and 512 rows of n + 2
+    // group's dependency chain); rem.slot = next free row, rem.rows = all used (the next taker zeroes the array).
+    // rem.rows follows the groups a call can run (at most REM_SLOTS): max_iter defaults to n, and 512 rows of n + 2
     // counters were 44 MB -- allocated and cleared -- on an HQC-sized decoder that decodes ONE codeword.
-    int rem_slot = 0, rem_rows = 0;
+    RemRing rem;  // slot = next free row, rows = all (scaldpc_bp_sched.h)
+    SchedCounters sched;  // what the scheduler did in the last call (scaldpc_bp_last_schedule): host integers only
     // host-I/O staging
     Buf<uint8_t> d_in, d_out_bits, d_out_conv;
     Buf<float> d_out_llr;
@@ -168,7 +170,7 @@ struct scaldpc_bp : HandleStreams {
         Buf<int> iters, ids, slot_of;
         Buf<float> post, pprior;  // pprior: the stragglers' rows of a soft call's prior plane
     };
-    static constexpr int MAX_LEVELS = 3;
+    static constexpr int MAX_LEVELS = SCHED_MAX_LEVELS;
     Level lv[MAX_LEVELS + 1];  // [0] unused
     long stat_levels = 0;      // deepest compact level the last call reached
     long stat_deferred = 0;  // codewords re-decoded by the compact pass in the last call
@@ -334,8 +336,6 @@ int parity_blocks(int m) { return (m + 4 * ROWS_PER_WAVE - 1) / (4 * ROWS_PER_WA
 // waves per tile of such a launch = words per tile of the unsat arrays
 int parity_waves(const scaldpc_bp *h) { return 4 * parity_blocks(h->m); }
 
-constexpr int REM_SLOTS = 512;
-
 int ensure_workspace(scaldpc_bp *h, int T, int G, bool want_post, int max_iter, int prob_cols = 0)
 {
     if (prob_cols) SC_TRY(grow(h->d_pprior, (size_t)T * prob_cols * TW));
@@ -361,32 +361,33 @@ int ensure_workspace(scaldpc_bp *h, int T, int G, bool want_post, int max_iter, 
     if (want_post) SC_TRY(h->d_post.ensure((size_t)h->cap_tiles * h->ws_n * TW));  // (released above whenever the planes move)
     // (the message arrays are allocated by the path that uses them: ensure_msg / ensure_el)
     // rows of counters: one per tile group of the call, the compact levels' groups (fewer tiles each) included, + row 0
-    const int groups = (T + std::max(1, G) - 1) / std::max(1, G);
-    const int want_rows = std::min(REM_SLOTS, 2 * groups + 8);
-    if (max_iter + 2 > h->cap_remaining || want_rows > h->rem_rows) {
+    const int want_rows = ring_rows_wanted(T, G);
+    if (max_iter + 2 > h->cap_remaining || want_rows > h->rem.rows) {
         h->d_remaining.reset();
         h->h_remaining.reset();
         h->cap_remaining = 0;
-        h->rem_rows = 0;
+        h->rem.rows = 0;
         const int len = max_iter + 2;
         SC_TRY(h->d_remaining.ensure((size_t)want_rows * (size_t)len));
         SC_TRY(h->h_remaining.ensure((size_t)len));
         h->cap_remaining = len;
-        h->rem_rows = want_rows;
+        h->rem.rows = want_rows;
     }
-    h->rem_slot = h->rem_rows;  // a new call: the first tile group that needs counters zeroes the array
+    h->rem.slot = h->rem.rows;  // a new call: the first tile group that needs counters zeroes the array
+    h->sched.w[SCHED_RING_ROWS] = h->rem.rows;
     return 0;
 }
 
 // the next zeroed row of "still running" counters (the row-parallel and small-call paths keep using row 0 with a
 // memset of their own; they run between tile groups on the same stream)
-int next_remaining_row(scaldpc_bp *h, hipStream_t s, int **row)
+// lanes_open: the lanes of the group before are not joined into s yet (decode_level never lets that meet a clear)
+int next_remaining_row(scaldpc_bp *h, hipStream_t s, int **row, bool lanes_open)
 {
-    if (h->rem_slot >= h->rem_rows) {
-        SC_HIP(hipMemsetAsync(h->d_remaining, 0, sizeof(int) * (size_t)h->rem_rows * h->cap_remaining, s));
-        h->rem_slot = 1;  // (row 0 is the other paths')
-    }
-    *row = h->d_remaining + (size_t)h->rem_slot++ * h->cap_remaining;
+    bool clears = false;
+    const int slot = ring_take(h->rem, &clears);
+    h->sched.note_take(clears, lanes_open);
+    if (clears) SC_HIP(hipMemsetAsync(h->d_remaining, 0, sizeof(int) * (size_t)h->rem.rows * h->cap_remaining, s));
+    *row = h->d_remaining + (size_t)slot * h->cap_remaining;
     return 0;
 }
 
@@ -1017,7 +1018,8 @@ int iterate_el(scaldpc_bp *h, const TileState &st, int nb, int max_iter, int met
         // Graphs that come here are too large for LDS: a decode that converges does so in 3-5 iterations (the
         // attack loop once enough checks are in; measured 3-4 on the HQC-128 graph), one that does not runs to
         // max_iter.  Poll densely where convergence is likely, sparsely afterwards.
-        if (early && ((ip >= 3 && ip <= 6) || (ip > 6 && ip <= 16 && ip % 2 == 0) || (ip > 16 && ip % 16 == 0))) {
+        if (early && el_poll_point(ip)) {
+            h->sched.w[SCHED_EL_POLLS]++;
             SC_HIP(hipMemcpyAsync(h->h_remaining + ip, h->d_remaining + ip, sizeof(int), hipMemcpyDeviceToHost, s));
             SC_HIP(hipStreamSynchronize(s));
             if (h->h_remaining[ip] == 0) break;
@@ -1031,15 +1033,14 @@ int iterate_el(scaldpc_bp *h, const TileState &st, int nb, int max_iter, int met
 // depends only on the previous pass over the same tiles) run one kernel out of phase, so that
 // while one lane drains the tail of its kernel another lane's kernel fills the machine.  Same
 // kernels, same cache footprint, same results.  Early-exit runs join the lanes at every poll.
-constexpr int MAX_LANES = 4;
+constexpr int MAX_LANES = SCHED_MAX_LANES;
 // measured on the HQC-128 bench (4-tile groups, ms per 4096-codeword step): 1 lane 104.0,
 // 2 lanes 98.5, 3 lanes 101.3, 4 lanes 106.8 -- two kernels in flight fill each other's tails,
 // more only shrink the launches.  SCALDPC_SPLIT=n overrides (1 = single stream).
 int fixed_lanes(const scaldpc_bp *h, int g)
 {
-    const int nl = h->kn.split;
     if (h->E == 0) return 1;
-    return std::max(1, std::min(std::min(nl, g), MAX_LANES));
+    return lanes_of(h->kn.split, g);
 }
 int ensure_lanes(scaldpc_bp *h, int nl)
 {
@@ -1052,15 +1053,6 @@ int ensure_lanes(scaldpc_bp *h, int nl)
         }
     if (nl > 1 && !h->ev_join[0]) SC_HIP(hipEventCreateWithFlags(&h->ev_join[0], hipEventDisableTiming));  // [0]: the fork event
     return 0;
-}
-// a group of g tiles dealt to nl lanes: lane k takes the gs[k] tiles from t0[k] on, the first g % nl lanes one more
-void deal_tiles(int g, int nl, int *gs, int *t0)
-{
-    for (int k = 0, t = 0; k < nl; k++) {
-        gs[k] = g / nl + (k < g % nl ? 1 : 0);
-        t0[k] = t;
-        t += gs[k];
-    }
 }
 // The lanes of a call: lane 0 is the call's stream, lanes 1.. the handle's further streams.  fork() starts them behind
 // everything enqueued on the call's stream so far, join() orders everything enqueued on them before it.  Lanes left open
@@ -1096,39 +1088,8 @@ struct Lanes {
     }
 };
 
-// What the groups of one call learn from each other about polling (a poll drains the queue: the GPU idles
-// while the host turns around, ~4 % of a group's time on the config-5 sweep):
-//   hint   poll points before this iteration saw no codeword finish in earlier groups: skip them
-//   streak consecutive groups that handed a small remainder (<= 1/8) to the compact pass at `defer_after`:
-//          after two of them the next groups stop there WITHOUT polling (their stragglers are found from the
-//          done masks afterwards, as always), with a real poll every 16th group to keep the assumption honest.
-//          A group stopped on a wrong guess only sends more codewords to the compact pass, which decodes
-//          them from their inputs: results cannot change.
-constexpr int SPEC_PERIOD = 16;  // (64 and 4096 measured the same to 0.5 % on the config-5 sweep: the polls are not where its time goes)
-constexpr int POLL_EVERY = 4;
-struct PollState {
-    int hint = 1, streak = 0, since_poll = 0;
-};
-// Is iteration `it` a poll point of an early-exit tile group?  Every POLL_EVERY-th iteration, the first and the hand-over
-// point, from the hint on.  (Decided before anything of the iteration is enqueued: these are the host's own sync points.)
-bool poll_point(int it, int defer_after, const PollState &ps)
-{
-    return (it % POLL_EVERY == 0 || it == 1 || it == defer_after) && it >= ps.hint;
-}
-// Does a group stop at the hand-over point `defer_after` UNSEEN, as the last groups did?
-bool stops_unseen(int defer_after, int max_iter, const PollState &ps)
-{
-    return defer_after > 0 && 2 * defer_after < max_iter && ps.streak >= 2 && ps.since_poll < SPEC_PERIOD - 1 &&
-           poll_point(defer_after, defer_after, ps);
-}
-// ... and does it get there without the host: no poll point before it is live?  (decode_level chains such groups)
-bool runs_unseen(int defer_after, int max_iter, const PollState &ps)
-{
-    if (!stops_unseen(defer_after, max_iter, ps)) return false;
-    for (int it = 1; it < defer_after; it++)
-        if (poll_point(it, defer_after, ps)) return false;
-    return true;
-}
+// What the groups of one call learn from each other about polling -- PollState, poll_point, stops_unseen, runs_unseen --
+// and what the host decides after a poll (after_poll) are in scaldpc_bp_sched.h.
 
 // All iterations of the tile group [g0, g0+g) of `st`.  With defer_after > 0 the group stops at the first poll point from
 // that iteration on at which at most half of its codewords are still running, and reports *deferred = true: those go to
@@ -1160,7 +1121,7 @@ int iterate_tiles(scaldpc_bp *h, Lanes &lanes, const TileState &st, int g0, int 
         LAUNCH_CHECK();
     }
     int *rem = h->d_remaining;  // this group's row of "still running" counters
-    if (early) SC_TRY(next_remaining_row(h, s, &rem));
+    if (early) SC_TRY(next_remaining_row(h, s, &rem, lanes.open));
     // (the accumulators / block counters of k_parity_fin and fused_commit are zeroed once per level, in decode_level,
     // and every launch leaves them zero)
     if (!(chain & 1)) SC_TRY(lanes.fork(nl));  // the other lanes start after everything enqueued on `s` so far
@@ -1232,7 +1193,8 @@ int iterate_tiles(scaldpc_bp *h, Lanes &lanes, const TileState &st, int g0, int 
         // a poll drains the queue (the GPU idles while the host turns around): skip the poll
         // points at which the call's earlier groups saw no codeword finish yet (poll_point)
         if (it == defer_after && stops_unseen(defer_after, max_iter, ps)) {
-            ps.since_poll++;  // stop here unseen, as the last groups did
+            note_unseen(ps);  // stop here unseen, as the last groups did
+            h->sched.w[SCHED_UNSEEN]++;
             *deferred = true;
             if (chain & 2) return 0;  // (the next group stops unseen too and continues these lanes: no host in between)
             return lanes.join();
@@ -1241,21 +1203,14 @@ int iterate_tiles(scaldpc_bp *h, Lanes &lanes, const TileState &st, int g0, int 
         SC_HIP(hipMemcpyAsync(h->h_remaining + it, rem + it, sizeof(int), hipMemcpyDeviceToHost, s));
         SC_HIP(hipStreamSynchronize(s));
         set_phase = true;
-        const int left = h->h_remaining[it];
-        if (left == 0) return 0;
-        if (left >= real_codewords) ps.hint = std::max(ps.hint, it + 1);
-        // from `defer_after` on, any poll point may hand the stragglers over, provided the
-        // restart (it iterations redone) is cheap next to what is still ahead
-        // ... and the stragglers really get cheaper: fewer tiles, or few enough for the
-        // row-parallel kernels
-        const bool shrinks = (left + TW - 1) / TW < g || left <= el_limit(h, method);
-        if (defer_after > 0 && it >= defer_after && 2 * it < max_iter && 2 * left <= real_codewords && shrinks) {
-            ps.streak = (it == defer_after && 8 * left <= real_codewords) ? ps.streak + 1 : 0;
-            ps.since_poll = 0;
+        h->sched.w[SCHED_POLLS]++;
+        // nobody left: done.  From `defer_after` on, any poll point may hand the stragglers over (after_poll)
+        const PollVerdict v = after_poll(ps, it, defer_after, max_iter, h->h_remaining[it], real_codewords, g, el_limit(h, method));
+        if (v == POLL_DONE) return 0;
+        if (v == POLL_HAND_OVER) {
             *deferred = true;
             return 0;
         }
-        if (it >= defer_after) ps.streak = 0;
     }
     if (chain & 2) return 0;  // (the next group continues these lanes; the last one of the chain joins)
     return lanes.join();
@@ -1288,12 +1243,7 @@ int decode_level(scaldpc_bp *h, int lvl, const TileState &st, int batch, int T, 
         return iterate_el(h, st, el, max_iter, method, alpha, early, s);
     }
 
-    int defer_after = 0;
-    if (early && lvl < scaldpc_bp::MAX_LEVELS) {
-        defer_after = 4;  // measured on the config-5 sweep: 4-5 best (177k trials/s), 8: 156k, 12: 136k
-        if (h->kn.compact_after >= 0) defer_after = h->kn.compact_after;
-        if (max_iter <= 2 * defer_after) defer_after = 0;  // nothing to gain
-    }
+    const int defer_after = defer_after_of(early, lvl, h->kn.compact_after, max_iter);
     // accumulators and block counters of the convergence tests: zero once, every launch leaves them zero
     SC_HIP(hipMemsetAsync(st.unsat, 0, sizeof(u64) * (size_t)T * parity_waves(h), s));
     std::vector<char> deferred_tile(T, 0);
@@ -1307,24 +1257,15 @@ int decode_level(scaldpc_bp *h, int lvl, const TileState &st, int batch, int T, 
     // Early-exit runs chain too where the host stays out: a group that will stop at the hand-over point UNSEEN and polls
     // nowhere before (runs_unseen, from the same PollState and rules iterate_tiles decides by) enqueues its launches
     // without ever synchronising.
-    auto unseen = [&](const PollState &p) { return early && lanes2 && runs_unseen(defer_after, max_iter, p); };
     Lanes lanes(h, s);
     for (int g0 = 0; g0 < T; g0 += Gl) {
         const int g = std::min(Gl, T - g0);
         const int real = std::min(batch - g0 * TW, g * TW);
         bool d = false;
-        int chain = 0;
         const bool next_full = g0 + Gl < T && std::min(Gl, T - (g0 + Gl)) == Gl;
-        if (!early && lanes2 && g == Gl) {
-            if (g0 > 0) chain |= 1;       // (the group before it was a full one too)
-            if (next_full) chain |= 2;    // ... and so is the next
-        } else if (g == Gl && unseen(poll)) {
-            PollState nxt = poll;
-            nxt.since_poll++;
-            if (lanes.open) chain |= 1;  // (the group before it left them un-joined)
-            // (the next group takes the next row of "still running" counters: no chaining across the wrap, which clears them all)
-            if (next_full && unseen(nxt) && h->rem_slot + 2 < h->rem_rows) chain |= 2;
-        }
+        // (no chaining across the wrap of the "still running" counter rows, which clears them all: chain_bits)
+        const int chain = chain_bits(early, lanes2, g == Gl, g0 == 0, next_full, lanes.open, defer_after, max_iter, poll, h->rem);
+        h->sched.note_group(lvl, early, chain);
         SC_TRY(iterate_tiles(h, lanes, st, g0, g, max_iter, method, alpha, early, defer_after, &d, real, poll, chain));
         if (d) {
             any = true;
@@ -1351,6 +1292,7 @@ int decode_level(scaldpc_bp *h, int lvl, const TileState &st, int batch, int T, 
     const int batch2 = (int)ids.size();
     if (batch2 == 0) return 0;
     if (lvl == 0) h->stat_deferred = batch2;
+    h->sched.w[SCHED_HANDED + lvl] = batch2;
     const int T2 = (batch2 + TW - 1) / TW;
     ids.resize((size_t)T2 * TW, -1);
     scaldpc_bp::Level &L = h->lv[lvl + 1];
@@ -1614,6 +1556,7 @@ int begin_call(scaldpc_bp *h, int batch, int max_iter, void *stream, Call *c)
 {
     if (!h->have_prior || h->prior_n < h->n)
         return fail(SCALDPC_EINVAL, "channel probabilities not set (columns [%d, %d))", h->have_prior ? h->prior_n : 0, h->n);
+    h->sched.reset();
     c->max_iter = max_iter > 0 ? max_iter : h->n;
     c->s = stream ? (hipStream_t)stream : h->own_stream;
     c->T = (batch + TW - 1) / TW;
@@ -1988,6 +1931,15 @@ int scaldpc_bp_last_stats(scaldpc_bp *h, int64_t *out)
     out[1] = h->stat_el;
     out[2] = h->stat_levels;
     out[3] = 0;
+    return 0;
+}
+
+int scaldpc_bp_last_schedule(scaldpc_bp *h, int64_t *out)
+{
+    if (!h || !out) return fail(SCALDPC_EINVAL, "NULL argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    for (int i = 0; i < SCHED_WORDS; i++) out[i] = h->sched.w[i];
+    for (int i = SCHED_WORDS; i < SCALDPC_SCHEDULE_WORDS; i++) out[i] = 0;
     return 0;
 }
 

@@ -1,0 +1,200 @@
+// The decisions of the early-exit tile scheduler (decode_level / iterate_tiles in scaldpc_bp.hip), and the counters
+// scaldpc_bp_last_schedule reports about them.  Every function here is a pure function of integers: which iterations the
+// host polls at, when a tile group hands its stragglers one level down, when it stops at the hand-over point UNSEEN, when
+// such groups are chained lane to lane, and which row of "still running" counters a group takes.
+// Plain C++, no HIP: tests/bp_sched_main.cc walks these functions with a host compiler under the address and
+// undefined-behaviour sanitizers, and tests/test_bp_schedule.py holds them to tests/sched_model.py, a restatement of the
+// same rules in Python.
+#pragma once
+
+#include <cstdint>
+
+namespace scaldpc {
+
+constexpr int SCHED_TW = 64;          // codewords per tile (the kernels' TW)
+constexpr int SCHED_MAX_LANES = 4;    // stream lanes of a tile group
+constexpr int SCHED_MAX_LEVELS = 3;   // compaction levels below the call's own arrays
+constexpr int REM_SLOTS = 512;        // most rows of "still running" counters a handle keeps
+
+// What the groups of one call learn from each other about polling (a poll drains the queue: the GPU idles
+// while the host turns around, ~4 % of a group's time on the config-5 sweep):
+//   hint   poll points before this iteration saw no codeword finish in earlier groups: skip them
+//   streak consecutive groups that handed a small remainder (<= 1/8) to the compact pass at `defer_after`:
+//          after two of them the next groups stop there WITHOUT polling (their stragglers are found from the
+//          done masks afterwards, as always), with a real poll every 16th group to keep the assumption honest.
+//          A group stopped on a wrong guess only sends more codewords to the compact pass, which decodes
+//          them from their inputs: results cannot change.
+//   since_poll  groups stopped unseen since the last real hand-over poll
+constexpr int SPEC_PERIOD = 16;  // (64 and 4096 measured the same to 0.5 % on the config-5 sweep: the polls are not where its time goes)
+constexpr int POLL_EVERY = 4;
+struct PollState {
+    int hint = 1, streak = 0, since_poll = 0;
+};
+// Is iteration `it` a poll point of an early-exit tile group?  Every POLL_EVERY-th iteration, the first and the hand-over
+// point, from the hint on.  (Decided before anything of the iteration is enqueued: these are the host's own sync points.)
+inline bool poll_point(int it, int defer_after, const PollState &ps)
+{
+    return (it % POLL_EVERY == 0 || it == 1 || it == defer_after) && it >= ps.hint;
+}
+// Does a group stop at the hand-over point `defer_after` UNSEEN, as the last groups did?
+inline bool stops_unseen(int defer_after, int max_iter, const PollState &ps)
+{
+    return defer_after > 0 && 2 * defer_after < max_iter && ps.streak >= 2 && ps.since_poll < SPEC_PERIOD - 1 &&
+           poll_point(defer_after, defer_after, ps);
+}
+// ... and does it get there without the host: no poll point before it is live?  (decode_level chains such groups)
+inline bool runs_unseen(int defer_after, int max_iter, const PollState &ps)
+{
+    if (!stops_unseen(defer_after, max_iter, ps)) return false;
+    for (int it = 1; it < defer_after; it++)
+        if (poll_point(it, defer_after, ps)) return false;
+    return true;
+}
+// a group that stopped unseen: one more since the last real poll
+inline void note_unseen(PollState &ps) { ps.since_poll++; }
+
+// stream lanes of a group of g tiles under the `split` knob: at most one per tile, at most SCHED_MAX_LANES
+inline int lanes_of(int split, int g)
+{
+    const int nl = split < g ? split : g;
+    return nl < 1 ? 1 : nl > SCHED_MAX_LANES ? SCHED_MAX_LANES : nl;
+}
+// a group of g tiles dealt to nl lanes: lane k takes the gs[k] tiles from t0[k] on, the first g % nl lanes one more
+inline void deal_tiles(int g, int nl, int *gs, int *t0)
+{
+    for (int k = 0, t = 0; k < nl; k++) {
+        gs[k] = g / nl + (k < g % nl ? 1 : 0);
+        t0[k] = t;
+        t += gs[k];
+    }
+}
+
+// The hand-over point of compaction level lvl (0 = none: the level runs every group to its end).  compact_after < 0 = the
+// default.
+inline int defer_after_of(bool early, int lvl, int compact_after, int max_iter)
+{
+    int defer_after = 0;
+    if (early && lvl < SCHED_MAX_LEVELS) {
+        defer_after = 4;  // measured on the config-5 sweep: 4-5 best (177k trials/s), 8: 156k, 12: 136k
+        if (compact_after >= 0) defer_after = compact_after;
+        if (max_iter <= 2 * defer_after) defer_after = 0;  // nothing to gain
+    }
+    return defer_after;
+}
+
+// What the host does after it has read `left` = codewords of the group still running after iteration `it`, at a poll
+// point that is not the group's last iteration.  g = tiles of the group, real = its codewords, el_lim = codewords the
+// row-parallel kernels take (0 = none).
+enum PollVerdict { POLL_DONE = 0, POLL_HAND_OVER = 1, POLL_GO_ON = 2 };
+inline PollVerdict after_poll(PollState &ps, int it, int defer_after, int max_iter, int left, int real, int g, int el_lim)
+{
+    if (left == 0) return POLL_DONE;
+    if (left >= real) ps.hint = ps.hint > it + 1 ? ps.hint : it + 1;
+    // from `defer_after` on, any poll point may hand the stragglers over, provided the
+    // restart (it iterations redone) is cheap next to what is still ahead
+    // ... and the stragglers really get cheaper: fewer tiles, or few enough for the
+    // row-parallel kernels
+    const bool shrinks = (left + SCHED_TW - 1) / SCHED_TW < g || left <= el_lim;
+    if (defer_after > 0 && it >= defer_after && 2 * it < max_iter && 2 * left <= real && shrinks) {
+        ps.streak = (it == defer_after && 8 * left <= real) ? ps.streak + 1 : 0;
+        ps.since_poll = 0;
+        return POLL_HAND_OVER;
+    }
+    if (it >= defer_after) ps.streak = 0;
+    return POLL_GO_ON;
+}
+
+// The ring of "still running" counter rows: every early-exit tile group of a call takes the next row; row 0 belongs to
+// the row-parallel and small-call paths.  A call starts with slot = rows ("nothing zeroed yet"), and a taker that finds
+// the ring used up clears ALL rows and starts again at row 1.
+inline int ring_rows_wanted(int T, int G)
+{
+    const int gg = G > 1 ? G : 1;
+    const int groups = (T + gg - 1) / gg;
+    const int want = 2 * groups + 8;  // one per tile group of the call, the compact levels' groups (fewer tiles each) included, + row 0
+    return want < REM_SLOTS ? want : REM_SLOTS;
+}
+struct RemRing {
+    int slot = 0, rows = 0;
+};
+// the row the next group takes; *clears = the whole ring is zeroed first
+inline int ring_take(RemRing &r, bool *clears)
+{
+    *clears = r.slot >= r.rows;
+    if (*clears) r.slot = 1;  // (row 0 is the other paths')
+    return r.slot++;
+}
+
+// chain bits of a group (iterate_tiles): bit 0 = it CONTINUES the lanes of the group before it, bit 1 = it leaves them
+// un-joined for the group after it.
+//   early       the call runs with early exit
+//   lanes2      the level's groups run on more than one lane, without an initialisation pass
+//   full        this group has the level's full tile count; next_full: there is a next group and it has, too
+//   first       this is the level's first group
+//   lanes_open  the group before it left its lanes un-joined
+//   ps          the poll state BEFORE this group; ring: the counter rows BEFORE this group takes its own
+inline int chain_bits(bool early, bool lanes2, bool full, bool first, bool next_full, bool lanes_open, int defer_after,
+                      int max_iter, const PollState &ps, const RemRing &ring)
+{
+    int chain = 0;
+    if (!lanes2 || !full) return 0;
+    if (!early) {
+        // fixed-iteration runs chain consecutive groups of the same geometry lane by lane: no host interaction
+        if (!first) chain |= 1;     // (the group before it was a full one too)
+        if (next_full) chain |= 2;  // ... and so is the next
+    } else if (runs_unseen(defer_after, max_iter, ps)) {
+        // a group that will stop at the hand-over point UNSEEN and polls nowhere before enqueues its launches without
+        // ever synchronising
+        PollState nxt = ps;
+        note_unseen(nxt);
+        if (lanes_open) chain |= 1;  // (the group before it left them un-joined)
+        // (the next group takes the next row of "still running" counters: no chaining across the wrap, which clears them all)
+        if (next_full && runs_unseen(defer_after, max_iter, nxt) && ring.slot + 2 < ring.rows) chain |= 2;
+    }
+    return chain;
+}
+
+// Counters of the schedule a call ran (scaldpc_bp_last_schedule), host integers only.
+enum SchedWord {
+    SCHED_GROUPS = 0,         // [4] tile groups run at compaction level 0 .. 3
+    SCHED_HANDED = 4,         // [3] codewords handed down FROM level 0 .. 2
+    SCHED_POLLS = 7,          // host polls of the tile loop (a synchronise plus a read of a counter)
+    SCHED_UNSEEN = 8,         // groups that stopped at the hand-over point unseen
+    SCHED_CONTINUED = 9,      // early-exit groups that continued their predecessor's lanes (chain bit 0)
+    SCHED_LEFT_OPEN = 10,     // early-exit groups left un-joined for their successor (chain bit 1)
+    SCHED_FIXED_CHAINED = 11, // fixed-iteration groups that continued their predecessor's lanes
+    SCHED_CLEARS = 12,        // clears of the counter ring after the call's first
+    SCHED_OPEN_AT_CLEAR = 13, // clears that found the lanes of the group before un-joined (must stay 0)
+    SCHED_RING_ROWS = 14,     // rows of the counter ring during the call
+    SCHED_EL_POLLS = 15,      // host polls of the row-parallel loop
+    SCHED_RING_TAKES = 16,    // rows of the ring handed out
+    SCHED_WORDS = 17
+};
+struct SchedCounters {
+    int64_t w[SCHED_WORDS] = {};
+    bool ring_cleared = false;  // the call's first clear has happened
+    void reset() { *this = SchedCounters{}; }
+    void note_take(bool clears, bool lanes_open)
+    {
+        w[SCHED_RING_TAKES]++;
+        if (!clears) return;
+        if (ring_cleared) w[SCHED_CLEARS]++;
+        if (lanes_open) w[SCHED_OPEN_AT_CLEAR]++;
+        ring_cleared = true;
+    }
+    void note_group(int lvl, bool early, int chain)
+    {
+        w[SCHED_GROUPS + lvl]++;
+        if (early) {
+            if (chain & 1) w[SCHED_CONTINUED]++;
+            if (chain & 2) w[SCHED_LEFT_OPEN]++;
+        } else if (chain & 1)
+            w[SCHED_FIXED_CHAINED]++;
+    }
+};
+
+// Poll points of the row-parallel loop: `ip` = the iteration whose verdict the host may look at.  Poll densely where
+// convergence is likely, sparsely afterwards.
+inline bool el_poll_point(int ip) { return (ip >= 3 && ip <= 6) || (ip > 6 && ip <= 16 && ip % 2 == 0) || (ip > 16 && ip % 16 == 0); }
+
+}  // namespace scaldpc

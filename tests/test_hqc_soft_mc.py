@@ -28,7 +28,7 @@ S = importlib.import_module("sca-ldpc_amd")
 
 def test_the_boundary_has_the_entry_point():
     src = open(os.path.join(ROOT, "include", "scaldpc.h")).read()
-    assert "#define SCALDPC_VERSION 103" in src
+    assert "#define SCALDPC_VERSION 104" in src
     decl = re.search(r"\bint scaldpc_mc_hqc_run_soft\(([^;]*)\);", re.sub(r"/\*.*?\*/", "", src, flags=re.S))
     assert decl and len(decl.group(1).split(",")) == 22
     for word in ("r >> 2", "word r & 3", "smallest k with word < T^b_k", "never drawn", "Reductions", "Defining property"):

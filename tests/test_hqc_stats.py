@@ -73,7 +73,7 @@ def test_the_trials_of_a_prefix_graph_are_a_prefix_of_the_trials():
 # --------------------------------------------------------------------------------------------------------------- the boundary
 def test_the_boundary_has_the_entry_point():
     src = open(os.path.join(ROOT, "include", "scaldpc.h")).read()
-    assert "#define SCALDPC_VERSION 103" in src
+    assert "#define SCALDPC_VERSION 104" in src
     code = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     soft = re.search(r"\bint scaldpc_mc_hqc_run_soft\(([^;]*)\);", code)
     decl = re.search(r"\bint scaldpc_mc_hqc_run_stats\(([^;]*)\);", code)
@@ -85,7 +85,7 @@ def test_the_boundary_has_the_entry_point():
         assert word in src, word
     lib = L.load()
     fn = lib.scaldpc_mc_hqc_run_stats
-    assert lib.scaldpc_version() == 103
+    assert lib.scaldpc_version() == 104
     assert fn.argtypes == lib.scaldpc_mc_hqc_run_soft.argtypes + [ctypes.c_void_p] * 2 and fn.restype is ctypes.c_int
     # refused before anything touches a device: no handle, no out_stats
     assert fn(*[None if t is ctypes.c_void_p else 0 for t in fn.argtypes]) == L.EINVAL

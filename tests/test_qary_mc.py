@@ -19,13 +19,13 @@ L = importlib.import_module("sca-ldpc_amd._lib")
 
 def test_the_boundary_has_the_entry_point():
     src = open(os.path.join(ROOT, "include", "scaldpc.h")).read()
-    assert "#define SCALDPC_VERSION 103" in src
+    assert "#define SCALDPC_VERSION 104" in src
     decl = re.search(r"\bint scaldpc_mc_qary_run\(([^;]*)\);", re.sub(r"/\*.*?\*/", "", src, flags=re.S))
     assert decl and len(decl.group(1).split(",")) == 17
     for word in ("Philox4x32-10", "x >> 2", "floor(p 2^32)", "smallest k with word < T_k", "never drawn"):
         assert word in src, word  # the trial law is written down next to K6's
     lib = L.load()
-    assert lib.scaldpc_version() == 103
+    assert lib.scaldpc_version() == 104
     fn = lib.scaldpc_mc_qary_run
     assert len(fn.argtypes) == 17 and fn.restype is not None
     # refused before anything touches a device: no handle

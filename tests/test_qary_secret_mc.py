@@ -26,14 +26,14 @@ L = importlib.import_module("sca-ldpc_amd._lib")
 
 def test_the_boundary_has_the_entry_point():
     src = open(os.path.join(ROOT, "include", "scaldpc.h")).read()
-    assert "#define SCALDPC_VERSION 103" in src
+    assert "#define SCALDPC_VERSION 104" in src
     decl = re.search(r"\bint scaldpc_mc_qary_run_secret\(([^;]*)\);", re.sub(r"/\*.*?\*/", "", src, flags=re.S))
     assert decl and len(decl.group(1).split(",")) == 19
     for word in ("v >> 2, 1, trial_lo, trial_hi", "word v & 3", "t_r = -h_{r,id} * sum_j h_{r,j} s_j", "smallest k with word < T^s_k",
                  "never drawn under that symbol", "Defining property", "Reduction", "4 (2 K Q + Q) > 65536"):
         assert word in src, word  # the trial law is written down next to the others
     lib = L.load()
-    assert lib.scaldpc_version() == 103
+    assert lib.scaldpc_version() == 104
     fn = lib.scaldpc_mc_qary_run_secret
     assert len(fn.argtypes) == 19 and fn.restype is not None
     # refused before anything touches a device: no handle

@@ -211,7 +211,7 @@ def test_margin_rule_on_hand_made_rows():
 
 # ------------------------------------------------------------------------------------------------------------------------ (c)
 def test_the_interface_is_bound():
-    """Header, library, ctypes binding and Python surface of the two soft entry points; the version stays 103."""
+    """Header, library, ctypes binding and Python surface of the two soft entry points; the version is 104."""
     hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "scaldpc.h")).read(), flags=re.S)
     L = importlib.import_module("sca-ldpc_amd._lib")
     lib = L.load()
@@ -222,7 +222,7 @@ def test_the_interface_is_bound():
         assert hasattr(lib, name), f"{name} is not exported"
         fn = getattr(lib, name)
         assert fn.argtypes is not None and len(fn.argtypes) == nargs and fn.restype is ctypes.c_int
-    assert lib.scaldpc_version() == 103 and "#define SCALDPC_VERSION 103" in hdr
+    assert lib.scaldpc_version() == 104 and "#define SCALDPC_VERSION 104" in hdr
     # NULL handle: an error code with a message, not a crash
     assert lib.scaldpc_qary_min_sum_batch_soft(None, None, 1, 0, None, None, None, None, None) == L.EINVAL
     assert lib.scaldpc_qary_special_min_sum_batch_soft(None, None, None, 1, 0, None, None, None, None, None, None) == L.EINVAL
