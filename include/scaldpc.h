@@ -20,6 +20,10 @@
  *                                `channel_probs = [w/N]*N ++ [1 - certainty_i]`, simulate/hqc.py:684-699, whose check
  *                                certainties differ from trial to trial (hqc.py:782-806)
  *                                (entry point added under SCALDPC_VERSION 103: nothing that existed changed)
+ *   scaldpc_bp_decode_batch_f64  the same decode() in the package's OWN arithmetic: product-sum in the probability-ratio
+ *                                domain, float64 -- decisions, iteration counts and converged flags are
+ *                                the package's exactly, posteriors to the last ulps of one log()
+ *                                (entry point added under SCALDPC_VERSION 104: nothing that existed changed)
  *   scaldpc_bp_destroy           object lifetime
  *   scaldpc_mc_fer_run           the per-trial body of simulate_frame_error_rate,
  *                                simulate/decode.py:36-40,165-175 (noise, syndrome, decode, compare)
@@ -195,6 +199,38 @@ int scaldpc_bp_decode_batch_soft(scaldpc_bp *h, const uint8_t *in, int32_t input
                                  const float *probs, int32_t prob_cols,
                                  int32_t max_iter, int32_t method, float alpha, uint32_t flags, void *stream,
                                  uint8_t *out_bits, float *out_llr, int32_t *out_iters, uint8_t *out_conv);
+/*
+ * The reference's own arithmetic on the device: ldpc.bp_decoder(..., bp_method="product_sum") is the probability-ratio
+ * recursion in float64, and this entry point runs it operation for operation (no fused multiply-add, IEEE division):
+ *   init      every edge of column j carries r_j = p_j / (1 - p_j), formed in double (p = 0 -> 0, p = 1 -> inf)
+ *   check i   t = +-1 by the syndrome bit; forward over the row in ascending column: c[e] = t, t *= 2 / (1 + x[e]) - 1;
+ *             backward with s = 1: c[e] *= s, c[e] = (1 - c[e]) / (1 + c[e]), s *= 2 / (1 + x[e]) - 1
+ *   variable  t = r_j; forward over the column in ascending row: x[e] = t, t *= c[e], a NaN t becomes 1;
+ *             posterior L = log(1 / t), decision t >= 1; backward with s = 1: x[e] *= s, s *= c[e], a NaN s becomes 1
+ *   test      H e == s after every iteration; with SCALDPC_F_EARLY_EXIT a converged codeword's decision, posterior and
+ *             iteration count are latched
+ * out_bits, out_iters and out_conv equal the float64 CPU recursion's on EVERY codeword, settled or not; out_llr differs from
+ * it by the last log() alone (a few ulp; +-inf and NaN in the same places).  It is the form to ask for when the reference's
+ * numbers must be reproduced, and the full-batch float64 key the fp32 tanh kernels are audited against.  It is NOT the
+ * throughput path: 8-byte messages in two arrays, two to three IEEE divisions per edge and iteration, one stream, no
+ * compaction -- about a third of the fp32 tanh rule's rate.
+ *   in, input_kind, batch, max_iter (<= 0 -> n), out_bits, out_iters, out_conv, SCALDPC_F_EARLY_EXIT, SCALDPC_F_DEVICE_IO
+ *             mean what they mean in scaldpc_bp_decode_batch; SCALDPC_F_ASYNC is refused (SCALDPC_EINVAL)
+ *   out_llr   double [batch][n], optional (NULL): log(1 / T) of the posterior ratio T
+ *   probs     NULL with prob_cols = 0: the handle's shared priors (scaldpc_bp_set_channel_probs, taken from its float64
+ *             values).  Otherwise double [batch][prob_cols], 1 <= prob_cols <= n: prior error probabilities PER CODEWORD of
+ *             the last prob_cols columns (hqc.decode()'s `1 - certainty`, simulate/hqc.py:684-699), where `in` lives; the
+ *             ratios are formed on the device by the same IEEE division.  One without the other is SCALDPC_EINVAL.
+ * Validation as scaldpc_bp_decode_batch_soft's: a value outside [0, 1] or a NaN returns SCALDPC_EINVAL and names the codeword
+ * and the column -- host values before anything is enqueued, device values after the conversion kernel and before the
+ * decode starts.  No refusal writes to an output, and the handle stays usable.
+ * Works on a handle grown by scaldpc_bp_append_rows.  Tile groups follow the "group_mb" budget with 16 bytes per edge and
+ * codeword (scaldpc_bp_set_tile_group overrides); results never depend on the group size.
+ * (entry point added under SCALDPC_VERSION 104: nothing that existed changed)
+ */
+int scaldpc_bp_decode_batch_f64(scaldpc_bp *h, const uint8_t *in, int32_t input_kind, int32_t batch,
+                                const double *probs, int32_t prob_cols, int32_t max_iter, uint32_t flags, void *stream,
+                                uint8_t *out_bits, double *out_llr, int32_t *out_iters, uint8_t *out_conv);
 /*
  * Measurement aid for bench.py: on the message state left by the last (fixed-iteration)
  * decode, run `iters` back-to-back launches of the check kernel and of the variable kernel of

@@ -59,6 +59,10 @@ def _declare(lib):
         vp, vp, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_uint32, vp, vp, vp, vp, vp,
     ]  # fmt: skip
     lib.scaldpc_bp_decode_batch_soft.restype = C.c_int
+    lib.scaldpc_bp_decode_batch_f64.argtypes = [
+        vp, vp, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, C.c_uint32, vp, vp, vp, vp, vp,
+    ]  # fmt: skip
+    lib.scaldpc_bp_decode_batch_f64.restype = C.c_int
     lib.scaldpc_bp_time_kernels.argtypes = [vp, C.c_int32, C.c_int32, C.c_float, vp, p(C.c_float), p(C.c_int32)]
     lib.scaldpc_bp_set_tile_group.argtypes = [vp, C.c_int32]
     lib.scaldpc_bp_last_compacted.argtypes = [vp, p(C.c_int64)]

@@ -13,6 +13,10 @@ Differences from the reference package, all deliberate:
   * messages are fp32 (the package computes in float64);
   * "product_sum" runs the tanh rule in the LLR domain (the package's ratio-domain
     recursion is the same function of the messages, SURVEY.md App. A);
+    `precision="float64"` (or SCALDPC_PRECISION=float64 in the environment) asks for the
+    package's own arithmetic instead -- the ratio-domain recursion in float64, operation for
+    operation (scaldpc_bp_decode_batch_f64): its decisions, iteration counts and converged
+    flags exactly, at a fraction of the fp32 path's throughput;
   * H may be a dense array (as the reference passes), a scipy sparse matrix or a
     `TannerGraph`; it is never densified.
 There is no CPU fallback: constructing a decoder without libscaldpc.so raises.
@@ -20,6 +24,7 @@ There is no CPU fallback: constructing a decoder without libscaldpc.so raises.
 from __future__ import annotations
 
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -53,6 +58,19 @@ def _vector_type(t):
     raise ValueError(f"input_vector_type '{t}' is invalid. Choose 'syndrome', 'received_vector' or 'auto'.")
 
 
+_PRECISIONS = ("float32", "float64")
+
+
+def _precision(value, method, source="precision"):
+    """"float32" / "float64" from the keyword (or the environment's default); float64 exists for the product-sum rule only."""
+    key = str(value).lower()
+    if key not in _PRECISIONS:
+        raise ValueError(f"{source} '{value}' is invalid. Choose 'float32' or 'float64'.")
+    if key == "float64" and method != _lib.BP_PRODUCT_SUM:
+        raise ValueError(f"{source}='float64' is the reference's ratio-domain product-sum recursion: it has no min-sum form")
+    return key
+
+
 # the five per-trial counters of scaldpc_mc_hqc_run_stats, in the order of its out_stats (= driver.STATS_COLUMNS[7:12])
 HQC_STATS_COLUMNS = ("unsatisfied", "good_flips", "bad_flips", "found_bad_satisfied_checks", "found_bad_unsatisfied_checks")
 
@@ -67,8 +85,18 @@ class BpDecoder:
         ms_scaling_factor=1.0,
         channel_probs=[None],
         input_vector_type=-1,
+        precision=None,
     ):
+        """precision: "float32" (the fp32 kernels) or "float64" (the reference package's own ratio-domain float64 recursion,
+        product-sum only); None reads SCALDPC_PRECISION once, here, and defaults to "float32".  `decode()` follows it;
+        `decode_batch` / `decode_batch_device` take a `precision` of their own that overrides it per call."""
         self._h = None
+        # (before any library call: a float64 min-sum decoder is refused with nothing built)
+        if precision is None:
+            env = os.environ.get("SCALDPC_PRECISION")
+            self.precision = _precision(env, _method_id(bp_method), "SCALDPC_PRECISION") if env else "float32"
+        else:
+            self.precision = _precision(precision, _method_id(bp_method))
         self._lib = _lib.load()  # raises when the HIP extension is missing
         g = TannerGraph.coerce(parity_check_matrix)
         self.graph = g
@@ -187,21 +215,24 @@ class BpDecoder:
             v = v.reshape(-1)
         r = self.decode_batch(v[None, :], want_llr=True)
         self.bp_decoding = r["bits"][0].astype(int)
-        self.log_prob_ratios = r["llr"][0].astype(np.float64)
+        self.log_prob_ratios = r["llr"][0].astype(np.float64)  # (precision "float64": the reference's values as they are)
         self.converge = int(r["converged"][0])
         self.iter = int(r["iters"][0])
         return self.bp_decoding
 
     # -- batched API ------------------------------------------------------------
     def decode_batch(self, inputs, max_iter=None, early_exit=True, want_llr=False, input_vector_type=None,
-                     channel_probs=None):
+                     channel_probs=None, precision=None):
         """inputs: [batch, m] syndromes or [batch, n] received words (any integer dtype).
         channel_probs: None (the decoder's priors for every codeword), or a 2-D array [batch, k] of prior error
         probabilities PER CODEWORD for the last k columns (1 <= k <= n; the columns below keep the decoder's priors):
         hqc.decode()'s `1 - certainty` of every check with k = R on H = [Hin | I_R] (simulate/hqc.py:684-699).  Values are
         taken as float32.  The decoder's own priors are left as they are.
+        precision: None (the decoder's), "float32" or "float64".  With "float64" the call runs the reference's ratio-domain
+        float64 recursion (scaldpc_bp_decode_batch_f64): `llr` is float64 and `channel_probs` is taken as float64.
         Returns dict(bits uint8 [batch, n], llr float32 [batch, n] or None,
         iters int32 [batch], converged uint8 [batch])."""
+        f64 = (self.precision if precision is None else _precision(precision, self._method)) == "float64"
         x = np.asarray(inputs)
         if x.ndim != 2:
             raise ValueError("decode_batch expects a 2-D array [batch, length]")
@@ -211,16 +242,27 @@ class BpDecoder:
         if batch == 0:
             raise ValueError("empty batch")
         bits = np.empty((batch, self.n), dtype=np.uint8)
-        llr = np.empty((batch, self.n), dtype=np.float32) if want_llr else None
+        llr = np.empty((batch, self.n), dtype=np.float64 if f64 else np.float32) if want_llr else None
         iters = np.empty(batch, dtype=np.int32)
         conv = np.empty(batch, dtype=np.uint8)
         flags = _lib.F_EARLY_EXIT if early_exit else 0
+        cp = None
         if channel_probs is not None:
-            cp = np.ascontiguousarray(channel_probs, dtype=np.float32)
+            cp = np.ascontiguousarray(channel_probs, dtype=np.float64 if f64 else np.float32)
             if cp.ndim != 2 or cp.shape[0] != batch:
                 raise ValueError(f"channel_probs must be a 2-D array [batch = {batch}, k], got shape {cp.shape}")
             if not 1 <= cp.shape[1] <= self.n:
                 raise ValueError(f"channel_probs covers {cp.shape[1]} columns: expected 1 to n = {self.n}")
+        if f64:
+            _lib.check(
+                self._lib.scaldpc_bp_decode_batch_f64(
+                    self._h, _lib.ptr(x), kind, batch, _lib.ptr(cp), 0 if cp is None else cp.shape[1],
+                    self.max_iter if max_iter is None else int(max_iter), flags, None,
+                    _lib.ptr(bits), _lib.ptr(llr), _lib.ptr(iters), _lib.ptr(conv),
+                )  # fmt: skip
+            )
+            return {"bits": bits, "llr": llr, "iters": iters, "converged": conv}
+        if cp is not None:
             _lib.check(
                 self._lib.scaldpc_bp_decode_batch_soft(
                     self._h, _lib.ptr(x), kind, batch, _lib.ptr(cp), cp.shape[1],
@@ -239,12 +281,25 @@ class BpDecoder:
         return {"bits": bits, "llr": llr, "iters": iters, "converged": conv}
 
     def decode_batch_device(self, d_in, kind, batch, d_out_bits, max_iter=None, early_exit=False, stream=0,
-                            d_out_llr=0, d_out_iters=0, d_out_conv=0, asynchronous=False, d_channel_probs=0, prob_cols=0):
+                            d_out_llr=0, d_out_iters=0, d_out_conv=0, asynchronous=False, d_channel_probs=0, prob_cols=0,
+                            precision=None):
         """Device-pointer variant (ints, e.g. torch `tensor.data_ptr()`): nothing crosses PCIe.
         d_channel_probs / prob_cols: float32 [batch, prob_cols] per-codeword priors of the last prob_cols columns (see
         decode_batch); a value that is no probability raises ValueError when the call synchronises -- an asynchronous
-        call does not check."""
+        call does not check.
+        precision: None (the decoder's), "float32" or "float64"; with "float64" d_out_llr and d_channel_probs hold float64
+        and the call cannot be asynchronous (scaldpc_bp_decode_batch_f64)."""
         flags = _lib.F_DEVICE_IO | (_lib.F_EARLY_EXIT if early_exit else 0) | (_lib.F_ASYNC if asynchronous else 0)
+        if (self.precision if precision is None else _precision(precision, self._method)) == "float64":
+            _lib.check(
+                self._lib.scaldpc_bp_decode_batch_f64(
+                    self._h, C.c_void_p(d_in), kind, batch, C.c_void_p(d_channel_probs or None), int(prob_cols),
+                    self.max_iter if max_iter is None else int(max_iter), flags, C.c_void_p(stream or None),
+                    C.c_void_p(d_out_bits), C.c_void_p(d_out_llr or None), C.c_void_p(d_out_iters or None),
+                    C.c_void_p(d_out_conv or None),
+                )  # fmt: skip
+            )
+            return
         if d_channel_probs or prob_cols:
             _lib.check(
                 self._lib.scaldpc_bp_decode_batch_soft(

@@ -46,6 +46,7 @@ typedef unsigned long long u64;
 using namespace scaldpc;
 
 #include "scaldpc_bp_kernels.h"
+#include "scaldpc_bp_ref64.h"  // scaldpc_bp_decode_batch_f64: the ratio-domain float64 kernels
 
 namespace {
 
@@ -231,6 +232,15 @@ struct scaldpc_bp : HandleStreams {
     // disagree, so every later call on the handle returns an error instead of decoding on it (check_usable); destroy
     // still frees all.
     bool broken = false;
+    // scaldpc_bp_decode_batch_f64 (the reference's ratio-domain float64 arithmetic; kernels in scaldpc_bp_ref64.h):
+    // d_ratio = the shared priors as r = p / (1 - p) from h_probs, built on first use (ratio_valid); d_x64 / d_c64 = the two
+    // message arrays double [tile][edge][64] of one tile group; d_post64 = the posterior plane double [tile][n][64];
+    // d_pratio = a call's per-codeword ratio plane double [tile][prob_cols][64]; d_probs_in64 / d_out_llr64 stage host I/O;
+    // d_rem64 = the group's "still running" counters, one per iteration, read through h_rem64
+    Buf<double> d_ratio, d_x64, d_c64, d_post64, d_pratio, d_probs_in64, d_out_llr64;
+    Buf<int> d_rem64;
+    PinnedBuf<int> h_rem64;
+    bool ratio_valid = false;
     int last_group = 0;  // tiles of the last decoded group (for scaldpc_bp_time_kernels)
     bool last_early = false;  // ... and whether that decode ran with early exit (its variable passes then all write decisions)
     std::mutex mu;
@@ -1707,6 +1717,7 @@ int scaldpc_bp_set_channel_probs(scaldpc_bp *h, const double *probs)
     h->h_probs.assign(probs, probs + h->n);
     h->thr_valid = false;
     h->first_valid = false;
+    h->ratio_valid = false;
     h->have_prior = true;
     h->prior_n = h->n;
     return 0;
@@ -1730,6 +1741,7 @@ int scaldpc_bp_set_channel_probs_tail(scaldpc_bp *h, int32_t first, int32_t coun
     std::copy(probs, probs + count, h->h_probs.begin() + first);
     h->thr_valid = false;
     h->first_valid = false;
+    h->ratio_valid = false;
     h->prior_n = std::max(h->prior_n, first + count);
     h->have_prior = true;
     return 0;
@@ -1897,6 +1909,10 @@ int scaldpc_bp_append_rows(scaldpc_bp *h, int32_t nrows, const int32_t *row_ptr,
     h->h_probs.resize(new_n, 0.0);
     h->thr_valid = false;
     h->first_valid = false;
+    h->ratio_valid = false;
+    h->d_x64.reset();
+    h->d_c64.reset();
+    h->d_post64.reset();
     h->d_thr.reset();
     h->d_msg.reset();
     h->d_scratch.reset();
@@ -2150,6 +2166,193 @@ int scaldpc_bp_decode_batch_soft(scaldpc_bp *h, const uint8_t *in, int32_t input
     if (prob_cols < 1) return fail(SCALDPC_EINVAL, "prob_cols = %d: at least one column", prob_cols);
     return decode_batch_impl(h, in, input_kind, batch, probs, prob_cols, max_iter, method, alpha, flags, stream, out_bits, out_llr,
                              out_iters, out_conv);
+}
+
+// ---------------------------------------------------------------------------
+// The reference's own arithmetic: product-sum in the probability-ratio domain, float64 (kernels: scaldpc_bp_ref64.h)
+// ---------------------------------------------------------------------------
+// every REF64_POLL-th iteration of an early-exit tile group the host reads "codewords still running" and stops the group
+// at 0 (iterations enqueued for a group that has finished return at once: their tiles are frozen)
+static constexpr int REF64_POLL = 4;
+
+// tiles per group of the float64 loop: the handle's group_mb budget with 8-byte messages in two arrays, at least one tile
+static int ref64_group(const scaldpc_bp *h, int T)
+{
+    if (h->tile_group > 0) return std::min(h->tile_group, T);
+    const double per_tile = (double)h->E * TW * sizeof(double) * 2;
+    const int g = per_tile > 0 ? (int)(h->kn.group_mb * 1e6 / per_tile) : T;
+    return std::max(1, std::min(g, T));
+}
+
+// the shared priors as ratios r = p / (1 - p), in double from the handle's float64 mirror (p = 0 -> 0, p = 1 -> inf)
+static int ensure_ratio64(scaldpc_bp *h)
+{
+    if (h->ratio_valid && h->d_ratio) return 0;
+    h->ratio_valid = false;
+    pvec<double> r(h->n);
+    for (int j = 0; j < h->n; j++) {
+        const double p = h->h_probs[j];
+        r[j] = p / (1.0 - p);
+    }
+    SC_TRY(grow(h->d_ratio, (size_t)h->n));
+    SC_HIP(hipMemcpy(h->d_ratio, r.data(), sizeof(double) * h->n, hipMemcpyHostToDevice));
+    h->ratio_valid = true;
+    return 0;
+}
+
+int scaldpc_bp_decode_batch_f64(scaldpc_bp *h, const uint8_t *in, int32_t input_kind, int32_t batch, const double *probs,
+                                int32_t prob_cols, int32_t max_iter_arg, uint32_t flags, void *stream, uint8_t *out_bits,
+                                double *out_llr, int32_t *out_iters, uint8_t *out_conv)
+{
+    if (!h || !in || !out_bits) return fail(SCALDPC_EINVAL, "NULL argument");
+    if (batch <= 0) return fail(SCALDPC_EINVAL, "batch must be positive (got %d)", batch);
+    if (input_kind != SCALDPC_IN_SYNDROME && input_kind != SCALDPC_IN_RECEIVED)
+        return fail(SCALDPC_EINVAL, "unknown input kind %d", input_kind);
+    if (flags & SCALDPC_F_ASYNC) return fail(SCALDPC_EINVAL, "SCALDPC_F_ASYNC: the float64 decode is synchronous");
+    if (prob_cols < 0 || (probs != nullptr) != (prob_cols > 0))
+        return fail(SCALDPC_EINVAL, "probs and prob_cols = %d go together (NULL and 0: the handle's shared priors)", prob_cols);
+    std::lock_guard<std::mutex> lk(h->mu);
+    SC_TRY(check_usable(h));
+    if (prob_cols > h->n) return fail(SCALDPC_EINVAL, "prob_cols = %d exceeds the block length n = %d", prob_cols, h->n);
+    DeviceGuard dg(h->device);
+    Call c;
+    SC_TRY(begin_call(h, batch, max_iter_arg, stream, &c));
+    const bool dev_io = flags & SCALDPC_F_DEVICE_IO;
+    const bool early = flags & SCALDPC_F_EARLY_EXIT;
+    CacheBypass guard(h->async_used);
+    const hipStream_t s = c.s;
+    const int T = c.T, max_iter = c.max_iter, n = h->n, m = h->m;
+    const long E = h->E;
+    const int len = input_kind == SCALDPC_IN_SYNDROME ? m : n;
+    const int first_col = n - prob_cols;
+    // host probabilities are checked before anything is enqueued
+    if (prob_cols && !dev_io)
+        for (size_t i = 0, cnt = (size_t)batch * prob_cols; i < cnt; i++)
+            if (!(probs[i] >= 0.0 && probs[i] <= 1.0))
+                return fail(SCALDPC_EINVAL, "channel_probs[%zu][%zu] = %g is not a probability (codeword %zu, column %zu)",
+                            i / prob_cols, i % prob_cols, probs[i], i / prob_cols, first_col + i % prob_cols);
+    SyncOnError settle{s};
+    SC_TRY(refresh_full(h));  // rows were appended: the CSC arrays follow
+    SC_TRY(ensure_ratio64(h));
+    const int G = ref64_group(h, T);
+    SC_TRY(ensure_workspace(h, T, G, false, max_iter));
+    SC_TRY(h->d_x64.ensure((size_t)G * E * TW));
+    SC_TRY(h->d_c64.ensure((size_t)G * E * TW));
+    if (out_llr) SC_TRY(h->d_post64.ensure((size_t)T * n * TW));
+    SC_TRY(h->d_rem64.ensure((size_t)max_iter + 2));
+    SC_TRY(h->h_rem64.ensure(1));
+    if (prob_cols) SC_TRY(grow(h->d_pratio, (size_t)T * prob_cols * TW));
+    const Outputs out{out_bits, nullptr, out_iters, out_conv};
+    Outputs dev;
+    SC_TRY(stage_outputs(h, out, batch, dev_io, true, &dev));
+    double *dev_llr = out_llr;
+    if (out_llr && !dev_io) {
+        SC_TRY(grow(h->d_out_llr64, (size_t)batch * n));
+        dev_llr = h->d_out_llr64;
+    }
+
+    // ---- per-codeword priors -> the ratio plane; a value that is no probability is refused before the decode starts ----
+    if (prob_cols) {
+        const double *dp = probs;
+        const size_t cnt = (size_t)batch * prob_cols;
+        if (!dev_io) {
+            SC_TRY(grow(h->d_probs_in64, cnt));
+            SC_HIP(hipMemcpyAsync(h->d_probs_in64, probs, sizeof(double) * cnt, hipMemcpyHostToDevice, s));
+            dp = h->d_probs_in64;
+        }
+        SC_TRY(h->d_soft_bad.ensure(1));
+        SC_HIP(hipMemsetAsync(h->d_soft_bad, 0xff, sizeof(u64), s));
+        hipLaunchKernelGGL(k_ratio64_convert, dim3((prob_cols + 63) / 64, T), dim3(256), 0, s, dp, prob_cols, batch,
+                           h->d_pratio.get(), h->d_soft_bad.get());
+        LAUNCH_CHECK();
+        if (dev_io) {  // (host values were checked above)
+            u64 bad = ~0ull;
+            SC_HIP(hipMemcpyAsync(&bad, h->d_soft_bad, sizeof(u64), hipMemcpyDeviceToHost, s));
+            SC_HIP(hipStreamSynchronize(s));
+            if (bad != ~0ull)
+                return fail(SCALDPC_EINVAL, "channel_probs[%llu][%llu] is not a probability (codeword %llu, column %llu)",
+                            bad / prob_cols, bad % prob_cols, bad / prob_cols, first_col + bad % prob_cols);
+        }
+    }
+
+    // ---- input planes, state ----------------------------------------------------------------------------------------
+    const uint8_t *din = in;
+    SC_TRY(stage_input(h, in, (size_t)batch * len, dev_io, s, &din));
+    if (input_kind == SCALDPC_IN_SYNDROME) {
+        hipLaunchKernelGGL(k_pack_bits, dim3((m + 63) / 64, T), dim3(256), 0, s, din, m, batch, h->d_synd);
+        LAUNCH_CHECK();
+    } else {
+        hipLaunchKernelGGL(k_pack_bits, dim3((n + 63) / 64, T), dim3(256), 0, s, din, n, batch, h->d_recv);
+        LAUNCH_CHECK();
+        SC_TRY(launch_syndrome(h, h->d_recv, h->d_synd, T, s));
+    }
+    hipLaunchKernelGGL(k_init_state, dim3(T), dim3(64), 0, s, batch, max_iter, h->d_done, h->d_conv, h->d_iters);
+    LAUNCH_CHECK();
+    SC_HIP(hipMemsetAsync(h->d_hard, 0, sizeof(u64) * (size_t)T * n, s));
+    const int pw = parity_waves(h);
+    SC_HIP(hipMemsetAsync(h->d_unsat, 0, sizeof(u64) * (size_t)T * pw, s));  // k_parity_fin leaves its words zero
+    h->last_group = 0;
+    h->stat_deferred = 0;
+    h->stat_el = 0;
+    h->stat_levels = 0;
+
+    // ---- the loop: one tile group after the other; per iteration check pass, variable pass, test + latch --------------
+    for (int g0 = 0; g0 < T; g0 += G) {
+        const int g = std::min(G, T - g0);
+        const Ratio64 prior{h->d_ratio, prob_cols ? h->d_pratio + (size_t)g0 * prob_cols * TW : nullptr, first_col, prob_cols};
+        const u64 *synd = h->d_synd + (size_t)g0 * m, *done = h->d_done + g0;
+        u64 *hard = h->d_hard + (size_t)g0 * n;
+        double *post = out_llr ? h->d_post64 + (size_t)g0 * n * TW : nullptr;
+        if (E) {
+            hipLaunchKernelGGL(k_init_ratio64, dim3((unsigned)((E + 3) / 4), g), dim3(256), 0, s, h->d_col_idx, h->d_x64.get(), E,
+                               prior);
+            LAUNCH_CHECK();
+        }
+        if (early) SC_HIP(hipMemsetAsync(h->d_rem64, 0, sizeof(int) * ((size_t)max_iter + 2), s));
+        for (int it = 1; it <= max_iter; it++) {
+            const bool last = it == max_iter;
+            if (E) {
+                // (the register-resident width the launch is built for: the smallest that holds the widest row)
+                auto check = h->max_row_deg <= 16 ? k_check_ratio64<16> : h->max_row_deg <= 52 ? k_check_ratio64<52>
+                                                                                              : k_check_ratio64<REF64_ROW_CAP>;
+                hipLaunchKernelGGL(check, dim3((m + 3) / 4, g), dim3(256), 0, s, h->d_row_ptr, h->d_x64.get(), h->d_c64.get(), E, m,
+                                   synd, done);
+                LAUNCH_CHECK();
+            }
+            auto var = h->max_col_deg <= 16 ? k_var_ratio64<16> : k_var_ratio64<REF64_COL_CAP>;
+            hipLaunchKernelGGL(var, dim3((n + 3) / 4, g), dim3(256), 0, s, h->d_col_ptr, h->d_csc_edge, h->d_c64.get(),
+                               h->d_x64.get(), E, n, prior, done, (early || last) ? 1 : 0, hard, post);
+            LAUNCH_CHECK();
+            if (!early && !last) continue;
+            hipLaunchKernelGGL(k_parity_fin, dim3(parity_blocks(m), g), dim3(256), 0, s, h->d_row_ptr, h->d_col_idx, hard, m, n,
+                               synd, h->d_unsat + (size_t)g0 * pw, pw, it, early ? 1 : 0, h->d_done + g0, h->d_conv + g0,
+                               h->d_iters + (size_t)g0 * TW, h->d_rem64 + it);
+            LAUNCH_CHECK();
+            if (early && !last && it % REF64_POLL == 0) {
+                SC_HIP(hipMemcpyAsync(h->h_rem64, h->d_rem64 + it, sizeof(int), hipMemcpyDeviceToHost, s));
+                SC_HIP(hipStreamSynchronize(s));
+                if (h->h_rem64[0] == 0) break;
+            }
+        }
+    }
+
+    // ---- outputs ----------------------------------------------------------------------------------------------------
+    hipLaunchKernelGGL(k_unpack_bits, dim3((n + 255) / 256, T), dim3(256), 0, s, h->d_hard,
+                       input_kind == SCALDPC_IN_RECEIVED ? h->d_recv : (const u64 *)nullptr, n, batch, dev.bits);
+    LAUNCH_CHECK();
+    if (out_llr) {
+        hipLaunchKernelGGL(k_unpack_llr64, dim3((n + 63) / 64, T), dim3(256), 0, s, h->d_post64.get(), n, batch, dev_llr);
+        LAUNCH_CHECK();
+    }
+    if (dev.iters || dev.conv) {
+        hipLaunchKernelGGL(k_unpack_state, dim3(T), dim3(64), 0, s, h->d_conv, h->d_iters, batch, dev.iters, dev.conv);
+        LAUNCH_CHECK();
+    }
+    SC_TRY(copy_outputs(h, out, dev, batch, dev_io, s));
+    if (out_llr && !dev_io)
+        SC_HIP(hipMemcpyAsync(out_llr, dev_llr, sizeof(double) * (size_t)batch * n, hipMemcpyDeviceToHost, s));
+    SC_HIP(hipStreamSynchronize(s));
+    return settle.done();
 }
 
 // ---------------------------------------------------------------------------

@@ -384,10 +384,17 @@ def hqc_attack_curve(first_row_support, N, rows, omega, table, runs, seed, decod
                 decoder_stats=[row for rows_of in per_trial for row in rows_of])
 
 
-def hqc_decode(N, Hin, checks, y_sparse, bp_decoder=None, max_iter=100):
+def _precision_kw(precision):
+    # (only where asked for: a stand-in decoder class need not know the keyword)
+    return {} if precision is None else {"precision": precision}
+
+
+def hqc_decode(N, Hin, checks, y_sparse, bp_decoder=None, max_iter=100, precision=None):
     """simulate/hqc.py:661-759.  Hin: TannerGraph (R x N, one row per oracle answer) or a
     dense array; checks: [(value, certainty)]; returns (success, stats) with the seven
-    fields `tracking.add_decoder_stats` records (hqc.py:750-758)."""
+    fields `tracking.add_decoder_stats` records (hqc.py:750-758).
+    precision: None (the decoder's default), "float32" or "float64" (the reference's own float64 recursion), handed to the
+    decoder's constructor."""
     g = TannerGraph.coerce(Hin)
     R = g.m
     H = g.with_identity()
@@ -396,14 +403,15 @@ def hqc_decode(N, Hin, checks, y_sparse, bp_decoder=None, max_iter=100):
         [np.full(N, prob_for_one, dtype=np.float64), np.array([1 - p for (_, p) in checks], dtype=np.float64)]
     )
     with np.errstate(divide="ignore"):
-        bpd = (bp_decoder or _default_bp())(H, max_iter=max_iter, bp_method="product_sum", channel_probs=channel_probs)
+        bpd = (bp_decoder or _default_bp())(H, max_iter=max_iter, bp_method="product_sum", channel_probs=channel_probs,
+                                            **_precision_kw(precision))
     cvals = np.array([int(c) for (c, _) in checks], dtype=np.uint8)
     msg = np.concatenate([np.zeros(N, dtype=np.uint8), cvals])
     decoded = bpd.decode_batch(msg[None, :], early_exit=True, input_vector_type="received_vector")["bits"][0]
     return hqc_stats(N, decoded, cvals, y_sparse)
 
 
-def hqc_decode_batch(N, Hin, checks_per_trial, y_sparse_per_trial, bp_decoder=None, max_iter=100):
+def hqc_decode_batch(N, Hin, checks_per_trial, y_sparse_per_trial, bp_decoder=None, max_iter=100, precision=None):
     """The batched twin of `hqc_decode`: many trials over the SAME Hin, each with its own answers and its own
     certainties (the oracles of hqc.py:782-806 raise a check's certainty with every repeated measurement, so two trials
     differ on their R check columns).  ONE decoder, ONE call: the per-trial `1 - certainty` rows go in as per-codeword
@@ -412,6 +420,8 @@ def hqc_decode_batch(N, Hin, checks_per_trial, y_sparse_per_trial, bp_decoder=No
 
       checks_per_trial    one [(value, certainty)] list of length R per trial
       y_sparse_per_trial  the secrets' supports
+      precision           None (the decoder's default), "float32" or "float64": handed to the decoder's constructor; a float64
+                          decoder takes the per-trial priors as float64
     Returns [(success, stats)]: per trial what `hqc_decode` returns for it."""
     g = TannerGraph.coerce(Hin)
     R = g.m
@@ -426,7 +436,8 @@ def hqc_decode_batch(N, Hin, checks_per_trial, y_sparse_per_trial, bp_decoder=No
     weights = [len(y) for y in y_sparse_per_trial]
     shared = np.concatenate([np.full(N, weights[0] / N, dtype=np.float64), check_part[0]])
     with np.errstate(divide="ignore"):
-        bpd = (bp_decoder or _default_bp())(H, max_iter=max_iter, bp_method="product_sum", channel_probs=shared)
+        bpd = (bp_decoder or _default_bp())(H, max_iter=max_iter, bp_method="product_sum", channel_probs=shared,
+                                            **_precision_kw(precision))
     if len(set(weights)) == 1:
         soft = check_part
     else:
@@ -434,7 +445,8 @@ def hqc_decode_batch(N, Hin, checks_per_trial, y_sparse_per_trial, bp_decoder=No
     msg = np.concatenate([np.zeros((batch, N), dtype=np.uint8), cvals], axis=1)
     try:
         decoded = bpd.decode_batch(msg, early_exit=True, input_vector_type="received_vector",
-                                   channel_probs=soft.astype(np.float32))["bits"]
+                                   channel_probs=soft if getattr(bpd, "precision", "float32") == "float64"
+                                   else soft.astype(np.float32))["bits"]
     finally:
         if hasattr(bpd, "close"):
             bpd.close()
