@@ -34,6 +34,10 @@
  *                                conditional on the check's true value -- the reported bit, its certainty (the check's own
  *                                prior, hqc.py:689) and the oracle calls it spent -- on the device
  *                                (entry point added under SCALDPC_VERSION 103: nothing that existed changed)
+ *   scaldpc_mc_fer_run_f64 / scaldpc_mc_hqc_run_f64 / scaldpc_mc_hqc_run_stats_f64
+ *                                the same three sweeps decoded by scaldpc_bp_decode_batch_f64's recursion: the reference's
+ *                                success rates in its own arithmetic, trial for trial
+ *                                (entry points added under SCALDPC_VERSION 104: nothing that existed changed)
  *   scaldpc_qary_create          simulate_rs Decoder::new via PyO3 `#[new]`,
  *                                simulate_rs/src/pydecoder.rs:24-45 -> simulate_rs/src/decoder.rs:494-553
  *   scaldpc_qary_min_sum_batch   PyO3 `min_sum`, simulate_rs/src/pydecoder.rs:53-65
@@ -302,7 +306,8 @@ int scaldpc_bp_last_schedule(scaldpc_bp *h, int64_t *out);
  *   "split"         stream lanes per tile group (default 2)
  *   "group_mb"      budget of a cache-resident tile group in MB (default 215; large = stream from HBM)
  *   "el_max"        largest call the row-parallel kernels take (default 6 min-sum / 4 tanh)
- *   "compact_after" iteration from which stragglers may be handed to a compact pass (default 4, 0 = never)
+ *   "compact_after" iteration from which stragglers may be handed to a compact pass (default 4, 0 = never); for the
+ *                   float64 sweeps (scaldpc_mc_*_f64) it is the iteration AT which the one hand-over happens
  *   "fuse_test"     1 (default) = in the early-exit tile loop the convergence test of an iteration rides on the check
  *                   pass of the next one (except where the host polls or stops), with sharded accumulators;
  *                   0 = a stand-alone launch after every variable pass (what poll iterations use anyway).
@@ -434,6 +439,58 @@ int scaldpc_mc_hqc_run_stats(scaldpc_bp *h, int32_t omega, const double *weights
                              int32_t max_iter, int32_t method, float alpha, uint32_t flags, void *stream,
                              uint8_t *out_success, int32_t *out_iters, uint8_t *out_msg, int32_t *out_y, uint8_t *out_outcome,
                              int32_t *out_flips, int32_t *out_cost, int32_t *out_stats, uint8_t *out_bits);
+
+/*
+ * The three sweep families decoded in the reference's own arithmetic: scaldpc_bp_decode_batch_f64's ratio-domain float64
+ * recursion -- the same kernels, the same order of operations, the same test and latch -- on trials drawn on the device.  For
+ * reproducing a success rate of the reference over 10^5 .. 10^6 trials, and for counting the trials on which the fp32 sweeps and
+ * the reference's arithmetic disagree (driver.hqc_precision_audit), without moving a trial's inputs over PCIe.
+ *   scaldpc_mc_fer_run_f64        scaldpc_mc_fer_run's trials
+ *   scaldpc_mc_hqc_run_f64        scaldpc_mc_hqc_run's trials
+ *   scaldpc_mc_hqc_run_stats_f64  scaldpc_mc_hqc_run_stats's trials; with out_stats = NULL it is scaldpc_mc_hqc_run_soft's sweep
+ * There is no method and no alpha argument: the form is product-sum only.
+ *
+ * Trial law: that of the fp32 entries, word for word -- the same Philox words, thresholds, secret sampler and outcome rule.  For
+ * the same (seed, first_trial + i) every exported input (out_error, out_msg, out_y, out_outcome, out_flips, out_cost) equals the
+ * fp32 entry's bit for bit: precision is a property of the decode, not of the trial.
+ * Decode: scaldpc_mc_fer_run_f64 and scaldpc_mc_hqc_run_f64 use the handle's shared float64 priors as ratios p / (1 - p).  In
+ * scaldpc_mc_hqc_run_stats_f64 column N + r of each trial carries the ratio probs[k] / (1 - probs[k]) of its drawn outcome k, formed
+ * in double by the IEEE division the per-codeword priors of scaldpc_bp_decode_batch_f64 go through; probs is DOUBLE [K] here, not
+ * float: the table's certainties are taken as they are.
+ *
+ * Defining properties:
+ *   - for every trial, out_success and out_iters are what scaldpc_bp_decode_batch_f64 gives on the exported inputs of the same
+ *     handle with the same flags and max_iter (scaldpc_mc_hqc_run_stats_f64: with probs[out_outcome] as its last R columns,
+ *     prob_cols = R), and out_bits is that call's out_bits -- integer equality;
+ *   - out_stats is the five counters of scaldpc_mc_hqc_run_stats, counted on the decoded word of the float64 decode;
+ *   - reduction: weights = ((eps, 1 - eps), (eps, 1 - eps)), flips = (1, 0), probs = (eps, eps) is scaldpc_mc_hqc_run_f64(eps) on a
+ *     handle whose check columns carry eps -- exactly, because the table's probabilities are doubles.
+ *
+ * Stragglers: with SCALDPC_F_EARLY_EXIT, the knob "compact_after" = k > 0 and max_iter > k, every tile group stops after
+ * iteration k; all codewords not latched by then are gathered over the whole call into dense tiles (syndromes, and for
+ * scaldpc_mc_hqc_run_stats_f64 their rows of the ratio plane), decoded there from iteration 1 for max_iter iterations, and their
+ * decisions and state are put back: one level, bit-identical (codewords are independent).  scaldpc_bp_last_compacted returns the
+ * number handed over, scaldpc_bp_last_stats out[2] is 1 when any were; fixed-iteration calls never hand over.  Results never
+ * depend on k, on the tile group size or on how a sweep is cut into calls.
+ *
+ * Refused as the fp32 entries refuse (SCALDPC_EINVAL, nothing queued, no output written, the handle usable afterwards):
+ * first_trial < 0, batch <= 0, out_success = NULL, any flag other than SCALDPC_F_EARLY_EXIT | SCALDPC_F_DEVICE_IO; omega, eps and
+ * the [Hin | I] requirement as scaldpc_mc_hqc_run's (omega > 256: SCALDPC_EDEGREE); K, weights, flips and costs as
+ * scaldpc_mc_hqc_run_soft's, out_cost needing costs; probs outside [0, 1] or NaN.
+ * Outputs as the fp32 entries'; in scaldpc_mc_hqc_run_stats_f64 out_stats is optional.
+ * (entry points added under SCALDPC_VERSION 104: nothing that existed changed)
+ */
+int scaldpc_mc_fer_run_f64(scaldpc_bp *h, int64_t first_trial, int32_t batch, uint64_t seed, int32_t max_iter,
+                           uint32_t flags, void *stream, uint8_t *out_success, int32_t *out_iters, uint8_t *out_error);
+int scaldpc_mc_hqc_run_f64(scaldpc_bp *h, int32_t omega, double eps, int64_t first_trial, int32_t batch, uint64_t seed,
+                           int32_t max_iter, uint32_t flags, void *stream, uint8_t *out_success, int32_t *out_iters,
+                           uint8_t *out_msg, int32_t *out_y);
+int scaldpc_mc_hqc_run_stats_f64(scaldpc_bp *h, int32_t omega, const double *weights, const uint8_t *flips,
+                                 const double *probs, const int32_t *costs, int32_t K, int64_t first_trial,
+                                 int32_t batch, uint64_t seed, int32_t max_iter, uint32_t flags, void *stream,
+                                 uint8_t *out_success, int32_t *out_iters, uint8_t *out_msg, int32_t *out_y,
+                                 uint8_t *out_outcome, int32_t *out_flips, int32_t *out_cost,
+                                 int32_t *out_stats /* optional here */, uint8_t *out_bits);
 
 /* ------------------------------------------------------------ q-ary min-sum */
 typedef struct scaldpc_qary scaldpc_qary;

@@ -93,6 +93,17 @@ def _declare(lib):
         vp, vp, vp, vp, vp, vp, vp, vp,
     ]  # fmt: skip
     lib.scaldpc_mc_hqc_run_stats.argtypes = lib.scaldpc_mc_hqc_run_soft.argtypes + [vp, vp]
+    # the float64 sweeps: the fp32 entries' arguments without method and alpha
+    lib.scaldpc_mc_fer_run_f64.argtypes = [vp, C.c_int64, C.c_int32, C.c_uint64, C.c_int32, C.c_uint32, vp, vp, vp, vp]
+    lib.scaldpc_mc_hqc_run_f64.argtypes = [
+        vp, C.c_int32, C.c_double, C.c_int64, C.c_int32, C.c_uint64, C.c_int32, C.c_uint32, vp, vp, vp, vp, vp,
+    ]  # fmt: skip
+    lib.scaldpc_mc_hqc_run_stats_f64.argtypes = [
+        vp, C.c_int32, vp, vp, vp, vp, C.c_int32, C.c_int64, C.c_int32, C.c_uint64, C.c_int32, C.c_uint32,
+        vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+    ]  # fmt: skip
+    for name in ("scaldpc_mc_fer_run_f64", "scaldpc_mc_hqc_run_f64", "scaldpc_mc_hqc_run_stats_f64"):
+        getattr(lib, name).restype = C.c_int
     for name in (
         "scaldpc_device_count", "scaldpc_set_device", "scaldpc_bp_create", "scaldpc_bp_set_channel_probs",
         "scaldpc_bp_decode_batch", "scaldpc_bp_time_kernels", "scaldpc_bp_set_tile_group", "scaldpc_mc_fer_run",

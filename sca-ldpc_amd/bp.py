@@ -336,13 +336,24 @@ class BpDecoder:
                 "var_writes_out": bool(ln[5] & 2), "var_slim": bool(ln[5] & 4)}
 
     # -- Monte-Carlo helpers on the device (K6) --------------------------------------
-    def mc_fer_run(self, runs, seed, first_trial=0, max_iter=None, early_exit=True, want_errors=False):
+    def mc_fer_run(self, runs, seed, first_trial=0, max_iter=None, early_exit=True, want_errors=False, precision="float32"):
         """`runs` trials of the FER loop body (simulate/decode.py:165-175) entirely on the
         device: error ~ Bernoulli(channel_probs), syndrome, decode, compare.
+        precision: "float32" (the default WHATEVER the decoder's own `precision`: the sweeps have always run the fp32 kernels)
+        or "float64": the same trials decoded by the reference's float64 recursion (scaldpc_mc_fer_run_f64), product-sum only.
         Returns dict(success uint8 [runs], iters int32 [runs], errors uint8 [runs, n] or None)."""
+        f64 = _precision(precision, self._method) == "float64"
         succ = np.empty(runs, dtype=np.uint8)
         iters = np.empty(runs, dtype=np.int32)
         err = np.empty((runs, self.n), dtype=np.uint8) if want_errors else None
+        if f64:
+            _lib.check(
+                self._lib.scaldpc_mc_fer_run_f64(
+                    self._h, int(first_trial), int(runs), int(seed), self.max_iter if max_iter is None else int(max_iter),
+                    _lib.F_EARLY_EXIT if early_exit else 0, None, _lib.ptr(succ), _lib.ptr(iters), _lib.ptr(err),
+                )  # fmt: skip
+            )
+            return {"success": succ, "iters": iters, "errors": err}
         _lib.check(
             self._lib.scaldpc_mc_fer_run(
                 self._h, int(first_trial), int(runs), int(seed), self.max_iter if max_iter is None else int(max_iter),
@@ -353,23 +364,36 @@ class BpDecoder:
         return {"success": succ, "iters": iters, "errors": err}
 
     def mc_hqc_run(self, runs, omega, eps, seed, first_trial=0, max_iter=None, early_exit=True, want_inputs=False,
-                   want_stats=False, want_bits=False):
+                   want_stats=False, want_bits=False, precision="float32"):
         """`runs` synthetic hqc.decode() trials (simulate/hqc.py:684-705,742-749) on H = [Hin | I]:
         secret y, noisy checks, msg = [0]*N ++ checks, decode, success = (decoded[:N] == y).
         Returns dict(success, iters, msg uint8 [runs, n] or None, y int32 [runs, omega] or None).
         want_stats / want_bits: the same trials through scaldpc_mc_hqc_run_stats with the two-outcome table that IS this sweep
-        (include/scaldpc.h); the result gains `stats` and `bits` as `mc_hqc_run_soft`'s does."""
+        (include/scaldpc.h); the result gains `stats` and `bits` as `mc_hqc_run_soft`'s does.
+        precision: "float32" (the default WHATEVER the decoder's own `precision`) or "float64": the same trials decoded by the
+        reference's float64 recursion (scaldpc_mc_hqc_run_f64; with want_stats / want_bits the two-outcome table through
+        scaldpc_mc_hqc_run_stats_f64, its probabilities unrounded), product-sum only."""
+        f64 = _precision(precision, self._method) == "float64"
         if want_stats or want_bits:
             eps = float(eps)
             table = dict(weights=np.array([[eps, 1.0 - eps]] * 2), flips=np.array([1, 0], dtype=np.uint8),
                          probs=np.array([eps, eps]), costs=None)
             r = self.mc_hqc_run_soft(runs, omega, table, seed, first_trial=first_trial, max_iter=max_iter, early_exit=early_exit,
-                                     want_inputs=want_inputs, want_stats=want_stats, want_bits=want_bits)
+                                     want_inputs=want_inputs, want_stats=want_stats, want_bits=want_bits, precision=precision)
             return {k: r[k] for k in ("success", "iters", "msg", "y", "stats", "bits")}
         succ = np.empty(runs, dtype=np.uint8)
         iters = np.empty(runs, dtype=np.int32)
         msg = np.empty((runs, self.n), dtype=np.uint8) if want_inputs else None
         y = np.empty((runs, omega), dtype=np.int32) if want_inputs else None
+        if f64:
+            _lib.check(
+                self._lib.scaldpc_mc_hqc_run_f64(
+                    self._h, int(omega), float(eps), int(first_trial), int(runs), int(seed),
+                    self.max_iter if max_iter is None else int(max_iter), _lib.F_EARLY_EXIT if early_exit else 0, None,
+                    _lib.ptr(succ), _lib.ptr(iters), _lib.ptr(msg), _lib.ptr(y),
+                )  # fmt: skip
+            )
+            return {"success": succ, "iters": iters, "msg": msg, "y": y}
         _lib.check(
             self._lib.scaldpc_mc_hqc_run(
                 self._h, int(omega), float(eps), int(first_trial), int(runs), int(seed),
@@ -380,7 +404,7 @@ class BpDecoder:
         return {"success": succ, "iters": iters, "msg": msg, "y": y}
 
     def mc_hqc_run_soft(self, runs, omega, table, seed, first_trial=0, max_iter=None, early_exit=True, want_inputs=False,
-                        want_stats=False, want_bits=False):
+                        want_stats=False, want_bits=False, precision="float32"):
         """`runs` synthetic hqc.decode() trials whose checks come from the oracles of simulate/hqc.py:782-871: every check
         draws an OUTCOME conditional on its true value, and the outcome brings the reported bit, the certainty the decoder
         is given with it (its own prior, hqc.py:689) and the oracle calls it spent -- all on the device
@@ -396,13 +420,17 @@ class BpDecoder:
           stats  int32 [runs, 5]: per trial the counters of tracking.add_decoder_stats (hqc.py:709-758) in the order of
                  HQC_STATS_COLUMNS -- what `driver.hqc_stats` counts on the decoded word, counted on the device
           bits   uint8 [runs, n] with want_bits (else None): the decoded word, `decode_batch`'s bits for `msg`
-        everything else is unchanged; without the two flags the call and its result are the plain sweep's."""
+        everything else is unchanged; without the two flags the call and its result are the plain sweep's.
+        precision: "float32" (the default WHATEVER the decoder's own `precision`) or "float64": the same trials -- inputs,
+        outcomes, flips and costs bit for bit -- decoded by the reference's float64 recursion (scaldpc_mc_hqc_run_stats_f64),
+        product-sum only; the table's `probs` then go in as float64, unrounded."""
+        f64 = _precision(precision, self._method) == "float64"
         w = np.ascontiguousarray(table["weights"], dtype=np.float64)
         if w.ndim != 2 or w.shape[0] != 2:
             raise ValueError(f"table['weights'] must be [2, K], got shape {w.shape}")
         K = w.shape[1]
         fl = np.asarray(table["flips"])
-        pr = np.ascontiguousarray(table["probs"], dtype=np.float32)
+        pr = np.ascontiguousarray(table["probs"], dtype=np.float64 if f64 else np.float32)
         costs = table.get("costs")
         if fl.shape != (K,) or pr.shape != (K,) or (costs is not None and np.shape(costs) != (K,)):
             raise ValueError(f"table: flips, probs and costs must hold one entry per outcome (K = {K})")
@@ -422,11 +450,17 @@ class BpDecoder:
         outcome = np.empty((runs, self.m), dtype=np.uint8) if want_inputs else None
         args = (
             self._h, int(omega), _lib.ptr(w), _lib.ptr(fl), _lib.ptr(pr), _lib.ptr(cs), K,
-            int(first_trial), int(runs), int(seed), self.max_iter if max_iter is None else int(max_iter), self._method,
-            self.ms_scaling_factor, _lib.F_EARLY_EXIT if early_exit else 0, None, _lib.ptr(succ), _lib.ptr(iters),
+            int(first_trial), int(runs), int(seed), self.max_iter if max_iter is None else int(max_iter),
+            *(() if f64 else (self._method, self.ms_scaling_factor)),  # (no method, no alpha: product-sum only)
+            _lib.F_EARLY_EXIT if early_exit else 0, None, _lib.ptr(succ), _lib.ptr(iters),
             _lib.ptr(msg), _lib.ptr(y), _lib.ptr(outcome), _lib.ptr(flips), _lib.ptr(cost),
         )  # fmt: skip
         res = {"success": succ, "iters": iters, "flips": flips, "cost": cost, "msg": msg, "y": y, "outcome": outcome}
+        if f64:  # one entry: out_stats is optional there
+            stats = np.empty((runs, len(HQC_STATS_COLUMNS)), dtype=np.int32) if want_stats or want_bits else None
+            bits = np.empty((runs, self.n), dtype=np.uint8) if want_bits else None
+            _lib.check(self._lib.scaldpc_mc_hqc_run_stats_f64(*args, _lib.ptr(stats), _lib.ptr(bits)))
+            return dict(res, stats=stats, bits=bits) if want_stats or want_bits else res
         if want_stats or want_bits:
             stats = np.empty((runs, len(HQC_STATS_COLUMNS)), dtype=np.int32)
             bits = np.empty((runs, self.n), dtype=np.uint8) if want_bits else None

@@ -48,6 +48,13 @@ using namespace scaldpc;
 #include "scaldpc_bp_kernels.h"
 #include "scaldpc_bp_ref64.h"  // scaldpc_bp_decode_batch_f64: the ratio-domain float64 kernels
 
+// The two kernels the float64 sweeps add live in scaldpc_bp_mc64.hip, behind these launches (that file says why).
+namespace scaldpc {
+int launch_mc_hqc_outcome64(const McHqcLaw64 &law, unsigned long long *synd, double *plane, int R, int batch, int T, long first,
+                            unsigned k0, unsigned k1, int *acc_flips, int *acc_cost, uint8_t *out_outcome, hipStream_t s);
+int launch_gather_prior64(const double *src, int cols, const int *ids, double *dst, int T2, hipStream_t s);
+}  // namespace scaldpc
+
 namespace {
 
 // Degree buckets of one fused launch (a host-side notion: the kernels read per-wave descriptor lists built from it):
@@ -84,7 +91,7 @@ struct Knobs {
     int split = 2;            // stream lanes per tile group
     double group_mb = 215.0;  // cache-resident group budget (auto_group)
     int el_max = -1;          // row-parallel limit; -1 = per-method default (6 / 4)
-    int compact_after = -1;   // -1 = default (4); 0 = no compact pass
+    int compact_after = -1;   // -1 = default (4); 0 = no compact pass.  The fp32 scheduler: the iteration FROM which a hand-over may happen; the float64 sweeps: the iteration AT which the one hand-over happens (ref64_handover)
     int fuse_test = 1;        // early-exit tile loop: the convergence test of iteration it rides on the check pass of it + 1 wherever the host does not need the verdict in between
     int first_fused = 1;      // iteration 1 of the tile kernels without its check pass (k_var_first from the first-message table); 0 = check pass + plain variable pass
     int minsum_rec = 1;       // min-sum on the tile kernels: check pass writes per-row records + lane masks instead of messages (k_check_minsum_rec / k_var_rec); 0 = message form
@@ -170,6 +177,7 @@ struct scaldpc_bp : HandleStreams {
         Buf<u64> synd, hard, done, conv, unsat;
         Buf<int> iters, ids, slot_of;
         Buf<float> post, pprior;  // pprior: the stragglers' rows of a soft call's prior plane
+        Buf<double> pratio64;     // the same rows of a float64 soft sweep's ratio plane (level 1 only: ref64_handover)
     };
     static constexpr int MAX_LEVELS = SCHED_MAX_LEVELS;
     Level lv[MAX_LEVELS + 1];  // [0] unused
@@ -1226,6 +1234,24 @@ int iterate_tiles(scaldpc_bp *h, Lanes &lanes, const TileState &st, int g0, int 
     return lanes.join();
 }
 
+// the state planes of a compact level, for T2 dense tiles of stragglers
+int ensure_level(scaldpc_bp *h, scaldpc_bp::Level &L, int T2)
+{
+    if (T2 <= L.cap_tiles) return 0;
+    L.synd.reset(); L.hard.reset(); L.done.reset(); L.conv.reset(); L.unsat.reset();
+    L.iters.reset(); L.ids.reset();
+    L.cap_tiles = 0;
+    SC_TRY(L.synd.ensure((size_t)T2 * h->m));
+    SC_TRY(L.hard.ensure((size_t)T2 * h->n));
+    SC_TRY(L.done.ensure((size_t)T2));
+    SC_TRY(L.conv.ensure((size_t)T2));
+    SC_TRY(L.unsat.ensure((size_t)T2 * parity_waves(h)));
+    SC_TRY(L.iters.ensure((size_t)T2 * TW));
+    SC_TRY(L.ids.ensure((size_t)T2 * TW));
+    L.cap_tiles = T2;
+    return 0;
+}
+
 // One compaction level: the `batch` codewords of `st` (T tiles), all iterations of one
 // cache-resident tile group after the other.  In early-exit runs the stragglers of
 // mostly-converged groups are gathered into dense tiles of their own and re-decoded from their
@@ -1306,19 +1332,7 @@ int decode_level(scaldpc_bp *h, int lvl, const TileState &st, int batch, int T, 
     const int T2 = (batch2 + TW - 1) / TW;
     ids.resize((size_t)T2 * TW, -1);
     scaldpc_bp::Level &L = h->lv[lvl + 1];
-    if (T2 > L.cap_tiles) {
-        L.synd.reset(); L.hard.reset(); L.done.reset(); L.conv.reset(); L.unsat.reset();
-        L.iters.reset(); L.ids.reset();
-        L.cap_tiles = 0;
-        SC_TRY(L.synd.ensure((size_t)T2 * h->m));
-        SC_TRY(L.hard.ensure((size_t)T2 * h->n));
-        SC_TRY(L.done.ensure((size_t)T2));
-        SC_TRY(L.conv.ensure((size_t)T2));
-        SC_TRY(L.unsat.ensure((size_t)T2 * parity_waves(h)));
-        SC_TRY(L.iters.ensure((size_t)T2 * TW));
-        SC_TRY(L.ids.ensure((size_t)T2 * TW));
-        L.cap_tiles = T2;
-    }
+    SC_TRY(ensure_level(h, L, T2));
     SC_TRY(grow(L.slot_of, (size_t)T * TW));
     if (want_post) SC_TRY(grow(L.post, (size_t)T2 * h->n * TW));
     const int pcols = st.pprior ? h->n - st.first_col : 0;
@@ -1922,7 +1936,7 @@ int scaldpc_bp_append_rows(scaldpc_bp *h, int32_t nrows, const int32_t *row_ptr,
     h->cap_rec_group = 0;
     for (auto &L : h->lv) {
         L.synd.reset(); L.hard.reset(); L.done.reset(); L.conv.reset(); L.unsat.reset();
-        L.iters.reset(); L.ids.reset(); L.post.reset(); L.pprior.reset();
+        L.iters.reset(); L.ids.reset(); L.post.reset(); L.pprior.reset(); L.pratio64.reset();
         L.cap_tiles = 0;
     }
     h->last_group = 0;
@@ -2200,6 +2214,156 @@ static int ensure_ratio64(scaldpc_bp *h)
     return 0;
 }
 
+// What the float64 loop needs on the device for a call of T tiles in groups of G: the shared ratios, the state planes, both
+// message arrays, the "still running" counters, and on request the posterior plane and the per-codeword ratio plane.
+static int ref64_ensure(scaldpc_bp *h, int T, int G, int max_iter, bool want_post, int prob_cols)
+{
+    SC_TRY(ensure_ratio64(h));
+    SC_TRY(ensure_workspace(h, T, G, false, max_iter));
+    SC_TRY(h->d_x64.ensure((size_t)G * h->E * TW));
+    SC_TRY(h->d_c64.ensure((size_t)G * h->E * TW));
+    if (want_post) SC_TRY(h->d_post64.ensure((size_t)T * h->n * TW));
+    SC_TRY(h->d_rem64.ensure((size_t)max_iter + 2));
+    SC_TRY(h->h_rem64.ensure(1));
+    if (prob_cols) SC_TRY(grow(h->d_pratio, (size_t)T * prob_cols * TW));
+    return 0;
+}
+
+// The planes a float64 loop runs on: the call's own (h->d_synd ...), or the dense tiles of its stragglers (h->lv[1]).
+//   synd [tile][m], hard [tile][n], done / conv [tile], unsat [tile][parity_waves], iters [tile][64]
+//   post    double [tile][n][64] or null
+//   pratio  double [tile][prob_cols][64]: the per-codeword ratios of the last prob_cols columns; null = the shared priors
+struct Ref64Planes {
+    const u64 *synd;
+    u64 *hard, *done, *conv, *unsat;
+    int *iters;
+    double *post;
+    const double *pratio;
+    int prob_cols;
+};
+
+// T tiles, one tile group after the other; per iteration check pass, variable pass, test + latch.  Every group runs the
+// iterations 1 .. stop_at of a decode of max_iter (stop_at = max_iter: the whole decode; less: an early-exit call that hands its
+// stragglers over after stop_at, ref64_handover).
+static int ref64_iterate(scaldpc_bp *h, const Ref64Planes &p, int T, int G, int max_iter, int stop_at, bool early, hipStream_t s)
+{
+    const int n = h->n, m = h->m, pw = parity_waves(h), first_col = n - p.prob_cols;
+    const long E = h->E;
+    for (int g0 = 0; g0 < T; g0 += G) {
+        const int g = std::min(G, T - g0);
+        const Ratio64 prior{h->d_ratio, p.pratio ? p.pratio + (size_t)g0 * p.prob_cols * TW : nullptr, first_col,
+                            p.pratio ? p.prob_cols : 0};
+        const u64 *synd = p.synd + (size_t)g0 * m, *done = p.done + g0;
+        u64 *hard = p.hard + (size_t)g0 * n;
+        double *post = p.post ? p.post + (size_t)g0 * n * TW : nullptr;
+        if (E) {
+            hipLaunchKernelGGL(k_init_ratio64, dim3((unsigned)((E + 3) / 4), g), dim3(256), 0, s, h->d_col_idx, h->d_x64.get(), E,
+                               prior);
+            LAUNCH_CHECK();
+        }
+        if (early) SC_HIP(hipMemsetAsync(h->d_rem64, 0, sizeof(int) * ((size_t)max_iter + 2), s));
+        for (int it = 1; it <= stop_at; it++) {
+            const bool last = it == max_iter;
+            if (E) {
+                // (the register-resident width the launch is built for: the smallest that holds the widest row)
+                auto check = h->max_row_deg <= 16 ? k_check_ratio64<16> : h->max_row_deg <= 52 ? k_check_ratio64<52>
+                                                                                              : k_check_ratio64<REF64_ROW_CAP>;
+                hipLaunchKernelGGL(check, dim3((m + 3) / 4, g), dim3(256), 0, s, h->d_row_ptr, h->d_x64.get(), h->d_c64.get(), E, m,
+                                   synd, done);
+                LAUNCH_CHECK();
+            }
+            auto var = h->max_col_deg <= 16 ? k_var_ratio64<16> : k_var_ratio64<REF64_COL_CAP>;
+            hipLaunchKernelGGL(var, dim3((n + 3) / 4, g), dim3(256), 0, s, h->d_col_ptr, h->d_csc_edge, h->d_c64.get(),
+                               h->d_x64.get(), E, n, prior, done, (early || last) ? 1 : 0, hard, post);
+            LAUNCH_CHECK();
+            if (!early && !last) continue;
+            hipLaunchKernelGGL(k_parity_fin, dim3(parity_blocks(m), g), dim3(256), 0, s, h->d_row_ptr, h->d_col_idx, hard, m, n,
+                               synd, p.unsat + (size_t)g0 * pw, pw, it, early ? 1 : 0, p.done + g0, p.conv + g0,
+                               p.iters + (size_t)g0 * TW, h->d_rem64 + it);
+            LAUNCH_CHECK();
+            if (early && it < stop_at && it % REF64_POLL == 0) {
+                SC_HIP(hipMemcpyAsync(h->h_rem64, h->d_rem64 + it, sizeof(int), hipMemcpyDeviceToHost, s));
+                SC_HIP(hipStreamSynchronize(s));
+                if (h->h_rem64[0] == 0) break;
+            }
+        }
+    }
+    return 0;
+}
+
+// state of `batch` codewords in T tiles before their first iteration
+static int ref64_reset(scaldpc_bp *h, const Ref64Planes &p, int batch, int T, int max_iter, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_init_state, dim3(T), dim3(64), 0, s, batch, max_iter, p.done, p.conv, p.iters);
+    LAUNCH_CHECK();
+    SC_HIP(hipMemsetAsync(p.hard, 0, sizeof(u64) * (size_t)T * h->n, s));
+    SC_HIP(hipMemsetAsync(p.unsat, 0, sizeof(u64) * (size_t)T * parity_waves(h), s));  // k_parity_fin leaves its words zero
+    return 0;
+}
+
+// The hand-over of the float64 sweeps, ONE level and one rule: every group of the call has stopped after iteration k; all
+// codewords not latched by then are gathered, over the whole call, into dense tiles of their own (h->lv[1]: syndromes, and the
+// rows of the ratio plane that go with them), decoded there from iteration 1 for max_iter iterations by the same loop on the
+// same message arrays, and their decisions, iteration counts and converged bits are scattered back.  Codewords are independent
+// and the recursion is deterministic: the results are those of the loop without hand-over, bit for bit.
+static int ref64_handover(scaldpc_bp *h, const Ref64Planes &p, int batch, int T, int G, int max_iter, hipStream_t s)
+{
+    std::vector<u64> done_h(T);
+    SC_HIP(hipMemcpyAsync(done_h.data(), p.done, sizeof(u64) * T, hipMemcpyDeviceToHost, s));
+    SC_HIP(hipStreamSynchronize(s));
+    pvec<int> ids, slot_of((size_t)T * TW, -1);
+    for (long b = 0; b < batch; b++)
+        if (!((done_h[b >> 6] >> (b & 63)) & 1)) {
+            slot_of[b] = (int)ids.size();
+            ids.push_back((int)b);
+        }
+    const int batch2 = (int)ids.size();
+    if (batch2 == 0) return 0;
+    h->stat_deferred = batch2;
+    h->stat_levels = 1;
+    const int T2 = (batch2 + TW - 1) / TW;
+    ids.resize((size_t)T2 * TW, -1);
+    scaldpc_bp::Level &L = h->lv[1];
+    SC_TRY(ensure_level(h, L, T2));
+    SC_TRY(grow(L.slot_of, (size_t)T * TW));
+    if (p.pratio) SC_TRY(grow(L.pratio64, (size_t)T2 * p.prob_cols * TW));
+    SC_HIP(hipMemcpyAsync(L.ids, ids.data(), sizeof(int) * ids.size(), hipMemcpyHostToDevice, s));
+    SC_HIP(hipMemcpyAsync(L.slot_of, slot_of.data(), sizeof(int) * slot_of.size(), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_gather_planes, dim3((h->m + 63) / 64, T2), dim3(256), 0, s, p.synd, h->m, L.ids, L.synd);
+    LAUNCH_CHECK();
+    if (p.pratio) {  // the stragglers' ratios go with them
+        SC_TRY(launch_gather_prior64(p.pratio, p.prob_cols, L.ids, L.pratio64, T2, s));
+    }
+    const Ref64Planes p2{L.synd, L.hard, L.done, L.conv, L.unsat, L.iters, nullptr, p.pratio ? L.pratio64.get() : nullptr,
+                         p.prob_cols};
+    SC_TRY(ref64_reset(h, p2, batch2, T2, max_iter, s));
+    SC_HIP(hipStreamSynchronize(s));  // ids / slot_of are locals
+    SC_TRY(ref64_iterate(h, p2, T2, std::min(G, T2), max_iter, max_iter, true, s));
+    hipLaunchKernelGGL(k_scatter_planes, dim3((h->n + 63) / 64, T), dim3(256), 0, s, p.hard, h->n, L.slot_of, L.hard);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_scatter_state, dim3(T), dim3(64), 0, s, p.iters, p.conv, L.slot_of, L.iters, L.conv);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// The float64 decode proper, on inputs already staged as planes (p.synd, p.pratio): state reset, then the loop.  Results stay on
+// the device (p.hard / post / conv / iters).  handover_at = k > 0 (the sweeps, early exit, max_iter > k): every group stops after
+// iteration k and the stragglers are re-decoded in dense tiles; 0: every group runs to its end (scaldpc_bp_decode_batch_f64
+// always; fixed-iteration sweeps; the knob "compact_after" = 0).
+static int ref64_run(scaldpc_bp *h, const Ref64Planes &p, int batch, int T, int G, int max_iter, bool early, int handover_at,
+                     hipStream_t s)
+{
+    SC_TRY(ref64_reset(h, p, batch, T, max_iter, s));
+    h->last_group = 0;
+    h->stat_deferred = 0;
+    h->stat_el = 0;
+    h->stat_levels = 0;
+    const bool hand = early && handover_at > 0 && max_iter > handover_at && !p.post;
+    SC_TRY(ref64_iterate(h, p, T, G, max_iter, hand ? handover_at : max_iter, early, s));
+    if (hand) SC_TRY(ref64_handover(h, p, batch, T, G, max_iter, s));
+    return 0;
+}
+
 int scaldpc_bp_decode_batch_f64(scaldpc_bp *h, const uint8_t *in, int32_t input_kind, int32_t batch, const double *probs,
                                 int32_t prob_cols, int32_t max_iter_arg, uint32_t flags, void *stream, uint8_t *out_bits,
                                 double *out_llr, int32_t *out_iters, uint8_t *out_conv)
@@ -2222,7 +2386,6 @@ int scaldpc_bp_decode_batch_f64(scaldpc_bp *h, const uint8_t *in, int32_t input_
     CacheBypass guard(h->async_used);
     const hipStream_t s = c.s;
     const int T = c.T, max_iter = c.max_iter, n = h->n, m = h->m;
-    const long E = h->E;
     const int len = input_kind == SCALDPC_IN_SYNDROME ? m : n;
     const int first_col = n - prob_cols;
     // host probabilities are checked before anything is enqueued
@@ -2233,15 +2396,8 @@ int scaldpc_bp_decode_batch_f64(scaldpc_bp *h, const uint8_t *in, int32_t input_
                             i / prob_cols, i % prob_cols, probs[i], i / prob_cols, first_col + i % prob_cols);
     SyncOnError settle{s};
     SC_TRY(refresh_full(h));  // rows were appended: the CSC arrays follow
-    SC_TRY(ensure_ratio64(h));
     const int G = ref64_group(h, T);
-    SC_TRY(ensure_workspace(h, T, G, false, max_iter));
-    SC_TRY(h->d_x64.ensure((size_t)G * E * TW));
-    SC_TRY(h->d_c64.ensure((size_t)G * E * TW));
-    if (out_llr) SC_TRY(h->d_post64.ensure((size_t)T * n * TW));
-    SC_TRY(h->d_rem64.ensure((size_t)max_iter + 2));
-    SC_TRY(h->h_rem64.ensure(1));
-    if (prob_cols) SC_TRY(grow(h->d_pratio, (size_t)T * prob_cols * TW));
+    SC_TRY(ref64_ensure(h, T, G, max_iter, out_llr != nullptr, prob_cols));
     const Outputs out{out_bits, nullptr, out_iters, out_conv};
     Outputs dev;
     SC_TRY(stage_outputs(h, out, batch, dev_io, true, &dev));
@@ -2286,55 +2442,10 @@ int scaldpc_bp_decode_batch_f64(scaldpc_bp *h, const uint8_t *in, int32_t input_
         LAUNCH_CHECK();
         SC_TRY(launch_syndrome(h, h->d_recv, h->d_synd, T, s));
     }
-    hipLaunchKernelGGL(k_init_state, dim3(T), dim3(64), 0, s, batch, max_iter, h->d_done, h->d_conv, h->d_iters);
-    LAUNCH_CHECK();
-    SC_HIP(hipMemsetAsync(h->d_hard, 0, sizeof(u64) * (size_t)T * n, s));
-    const int pw = parity_waves(h);
-    SC_HIP(hipMemsetAsync(h->d_unsat, 0, sizeof(u64) * (size_t)T * pw, s));  // k_parity_fin leaves its words zero
-    h->last_group = 0;
-    h->stat_deferred = 0;
-    h->stat_el = 0;
-    h->stat_levels = 0;
-
-    // ---- the loop: one tile group after the other; per iteration check pass, variable pass, test + latch --------------
-    for (int g0 = 0; g0 < T; g0 += G) {
-        const int g = std::min(G, T - g0);
-        const Ratio64 prior{h->d_ratio, prob_cols ? h->d_pratio + (size_t)g0 * prob_cols * TW : nullptr, first_col, prob_cols};
-        const u64 *synd = h->d_synd + (size_t)g0 * m, *done = h->d_done + g0;
-        u64 *hard = h->d_hard + (size_t)g0 * n;
-        double *post = out_llr ? h->d_post64 + (size_t)g0 * n * TW : nullptr;
-        if (E) {
-            hipLaunchKernelGGL(k_init_ratio64, dim3((unsigned)((E + 3) / 4), g), dim3(256), 0, s, h->d_col_idx, h->d_x64.get(), E,
-                               prior);
-            LAUNCH_CHECK();
-        }
-        if (early) SC_HIP(hipMemsetAsync(h->d_rem64, 0, sizeof(int) * ((size_t)max_iter + 2), s));
-        for (int it = 1; it <= max_iter; it++) {
-            const bool last = it == max_iter;
-            if (E) {
-                // (the register-resident width the launch is built for: the smallest that holds the widest row)
-                auto check = h->max_row_deg <= 16 ? k_check_ratio64<16> : h->max_row_deg <= 52 ? k_check_ratio64<52>
-                                                                                              : k_check_ratio64<REF64_ROW_CAP>;
-                hipLaunchKernelGGL(check, dim3((m + 3) / 4, g), dim3(256), 0, s, h->d_row_ptr, h->d_x64.get(), h->d_c64.get(), E, m,
-                                   synd, done);
-                LAUNCH_CHECK();
-            }
-            auto var = h->max_col_deg <= 16 ? k_var_ratio64<16> : k_var_ratio64<REF64_COL_CAP>;
-            hipLaunchKernelGGL(var, dim3((n + 3) / 4, g), dim3(256), 0, s, h->d_col_ptr, h->d_csc_edge, h->d_c64.get(),
-                               h->d_x64.get(), E, n, prior, done, (early || last) ? 1 : 0, hard, post);
-            LAUNCH_CHECK();
-            if (!early && !last) continue;
-            hipLaunchKernelGGL(k_parity_fin, dim3(parity_blocks(m), g), dim3(256), 0, s, h->d_row_ptr, h->d_col_idx, hard, m, n,
-                               synd, h->d_unsat + (size_t)g0 * pw, pw, it, early ? 1 : 0, h->d_done + g0, h->d_conv + g0,
-                               h->d_iters + (size_t)g0 * TW, h->d_rem64 + it);
-            LAUNCH_CHECK();
-            if (early && !last && it % REF64_POLL == 0) {
-                SC_HIP(hipMemcpyAsync(h->h_rem64, h->d_rem64 + it, sizeof(int), hipMemcpyDeviceToHost, s));
-                SC_HIP(hipStreamSynchronize(s));
-                if (h->h_rem64[0] == 0) break;
-            }
-        }
-    }
+    // ---- the loop: every tile group through all its iterations (no hand-over: the launches are the call's own) ----------
+    const Ref64Planes pl{h->d_synd, h->d_hard, h->d_done, h->d_conv, h->d_unsat, h->d_iters, out_llr ? h->d_post64.get() : nullptr,
+                         prob_cols ? h->d_pratio.get() : nullptr, prob_cols};
+    SC_TRY(ref64_run(h, pl, batch, T, G, max_iter, early, 0, s));
 
     // ---- outputs ----------------------------------------------------------------------------------------------------
     hipLaunchKernelGGL(k_unpack_bits, dim3((n + 255) / 256, T), dim3(256), 0, s, h->d_hard,
@@ -2373,6 +2484,18 @@ int mc_common_args(scaldpc_bp *h, int64_t first_trial, int32_t batch, int32_t me
     if (method != SCALDPC_BP_PRODUCT_SUM && method != SCALDPC_BP_MIN_SUM)
         return fail(SCALDPC_EINVAL, "unknown bp method %d", method);
     if (!(alpha >= 0.0f)) return fail(SCALDPC_EINVAL, "ms_scaling_factor must be >= 0");
+    return 0;
+}
+
+// the Bernoulli thresholds of the shared priors (the FER sweeps' noise), built on first use
+int ensure_thresholds(scaldpc_bp *h)
+{
+    if (h->thr_valid) return 0;
+    if (!h->d_thr) SC_TRY(h->d_thr.ensure((size_t)h->n));
+    pvec<u64> thr(h->n);
+    for (int j = 0; j < h->n; j++) thr[j] = bernoulli_threshold(h->h_probs[j]);
+    SC_HIP(hipMemcpy(h->d_thr, thr.data(), sizeof(u64) * h->n, hipMemcpyHostToDevice));
+    h->thr_valid = true;
     return 0;
 }
 
@@ -2433,13 +2556,7 @@ int scaldpc_mc_fer_run(scaldpc_bp *h, int64_t first_trial, int32_t batch, uint64
     const int T = c.T, G = c.G, max_iter = c.max_iter;
     SC_TRY(ensure_workspace(h, T, G, false, max_iter));
     SC_TRY(grow(h->d_mc, (size_t)T * h->n));
-    if (!h->thr_valid) {
-        if (!h->d_thr) SC_TRY(h->d_thr.ensure((size_t)h->n));
-        pvec<u64> thr(h->n);
-        for (int j = 0; j < h->n; j++) thr[j] = bernoulli_threshold(h->h_probs[j]);
-        SC_HIP(hipMemcpy(h->d_thr, thr.data(), sizeof(u64) * h->n, hipMemcpyHostToDevice));
-        h->thr_valid = true;
-    }
+    SC_TRY(ensure_thresholds(h));
     const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
     // error ~ Bernoulli(p_i) per position (decode.py:166-167), syndrome = H error (decode.py:168)
     hipLaunchKernelGGL(k_mc_bernoulli<false>, dim3((h->n + 63) / 64, T), dim3(256), 0, s, h->d_mc, h->n, batch,
@@ -2636,6 +2753,189 @@ int scaldpc_mc_hqc_run_stats(scaldpc_bp *h, int32_t omega, const double *weights
     return mc_hqc_run_soft_body(h, omega, weights, flips, probs, costs, K, first_trial, batch, seed, max_iter_arg, method, alpha,
                                 flags, stream, out_success, out_iters, out_msg, out_y, out_outcome, out_flips, out_cost, out_stats,
                                 out_bits);
+}
+
+// ---------------------------------------------------------------------------
+// The same sweeps decoded in the reference's own arithmetic (float64 ratio domain): the trials are drawn by the kernels above --
+// precision is a property of the decode, not of the trial -- and decoded by scaldpc_bp_decode_batch_f64's loop (ref64_run), whose
+// stragglers are handed over to dense tiles once, after iteration "compact_after" (ref64_handover).
+// ---------------------------------------------------------------------------
+namespace {
+
+// The refusals the float64 sweeps share with the fp32 entries (there is no method and no alpha: the form is product-sum only).
+// The handle is looked at last, so that every one of them can be seen without a device.
+int mc_f64_args(const scaldpc_bp *h, int64_t first_trial, int32_t batch, uint32_t flags, const uint8_t *out_success)
+{
+    if (flags & ~(SCALDPC_F_EARLY_EXIT | SCALDPC_F_DEVICE_IO))
+        return fail(SCALDPC_EINVAL, "flags: SCALDPC_F_EARLY_EXIT and SCALDPC_F_DEVICE_IO are taken");
+    if (first_trial < 0) return fail(SCALDPC_EINVAL, "first_trial must not be negative");
+    if (batch <= 0) return fail(SCALDPC_EINVAL, "batch must be positive (got %d)", batch);
+    if (!h || !out_success) return fail(SCALDPC_EINVAL, "NULL argument");
+    return 0;
+}
+
+// the iteration after which an early-exit float64 sweep hands its stragglers over (0: never)
+int mc_f64_handover_at(const scaldpc_bp *h) { return h->kn.compact_after < 0 ? 4 : h->kn.compact_after; }
+
+// the decode of a float64 sweep on the planes its trial kernels have staged (h->d_synd; pratio = h->d_pratio or null)
+int mc_run_f64(scaldpc_bp *h, int batch, int T, int G, int max_iter, bool early, const double *pratio, int prob_cols, hipStream_t s)
+{
+    const Ref64Planes pl{h->d_synd, h->d_hard, h->d_done, h->d_conv, h->d_unsat, h->d_iters, nullptr, pratio, prob_cols};
+    return ref64_run(h, pl, batch, T, G, max_iter, early, mc_f64_handover_at(h), s);
+}
+
+// Both float64 HQC sweeps.  law = null: scaldpc_mc_hqc_run_f64 -- every check flipped with probability eps, the handle's shared
+// float64 priors.  Otherwise scaldpc_mc_hqc_run_stats_f64: every check draws an outcome of the table, which brings its ratio
+// into the plane h->d_pratio (k_mc_hqc_outcome64), and the five outputs from out_outcome on may be asked for.
+int mc_hqc_run_f64_body(scaldpc_bp *h, int32_t omega, const McHqcLaw64 *law, double eps, bool counted, int64_t first_trial,
+                        int32_t batch, uint64_t seed, int32_t max_iter_arg, uint32_t flags, void *stream, uint8_t *out_success,
+                        int32_t *out_iters, uint8_t *out_msg, int32_t *out_y, uint8_t *out_outcome, int32_t *out_flips,
+                        int32_t *out_cost, int32_t *out_stats, uint8_t *out_bits)
+{
+    DeviceGuard dg(h->device);
+    CacheBypass guard(h->async_used);
+    Call c;
+    SC_TRY(begin_call(h, batch, max_iter_arg, stream, &c));
+    const hipStream_t s = c.s;
+    SyncOnError settle{s};
+    SC_TRY(refresh_full(h));
+    if (h->identity_from < 0) return fail(SCALDPC_EINVAL, "parity-check matrix is not of the form [Hin | I] (hqc.py:680)");
+    const int N = h->identity_from, R = h->m;
+    if (omega < 0 || omega > N) return fail(SCALDPC_EINVAL, "omega must be in [0, N]");
+    if (!law && !(eps >= 0.0 && eps <= 1.0)) return fail(SCALDPC_EINVAL, "eps must be a probability");
+    if ((size_t)omega * 64 * 4 > 64 * 1024) return fail(SCALDPC_EDEGREE, "omega %d too large for the LDS-resident sampler", omega);
+    const bool dev_io = flags & SCALDPC_F_DEVICE_IO, early = flags & SCALDPC_F_EARLY_EXIT;
+    const int T = c.T, max_iter = c.max_iter, G = ref64_group(h, T);
+    SC_TRY(ref64_ensure(h, T, G, max_iter, false, law ? R : 0));
+    SC_TRY(grow(h->d_mc, (size_t)T * h->n));
+    if (law) SC_TRY(grow(h->d_mc_acc, (size_t)2 * batch));
+    int *dy = nullptr;
+    if (out_y) {
+        dy = out_y;
+        if (!dev_io) {
+            SC_TRY(grow(h->d_ylist, (size_t)batch * std::max(omega, 1)));
+            dy = h->d_ylist;
+        }
+    }
+    uint8_t *dout = out_outcome;
+    if (out_outcome && !dev_io) {
+        SC_TRY(grow(h->d_mc_outcome, (size_t)batch * R));
+        dout = h->d_mc_outcome;
+    }
+    int *dstats = out_stats;
+    if (out_stats && !dev_io) {
+        SC_TRY(grow(h->d_mc_stats, (size_t)5 * batch));
+        dstats = h->d_mc_stats;
+    }
+    const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
+    // x = [y | 0]: omega distinct positions;  true bits c = Hin y = H x  (hqc.py:1253-1257)
+    SC_HIP(hipMemsetAsync(h->d_mc, 0, sizeof(u64) * (size_t)T * h->n, s));
+    if (omega) {
+        hipLaunchKernelGGL(k_mc_hqc_secret, dim3(T), dim3(64), (size_t)omega * 64 * sizeof(int), s, h->d_mc, h->n, N, omega,
+                           batch, (long)first_trial, k0, k1, dy);
+        LAUNCH_CHECK();
+    }
+    SC_TRY(launch_syndrome(h, h->d_mc, h->d_synd, T, s));
+    int *const acc_flips = h->d_mc_acc, *const acc_cost = counted ? acc_flips + batch : nullptr;
+    if (law) {  // an outcome per check: the reported bit and the ratio of its certainty
+        SC_HIP(hipMemsetAsync(acc_flips, 0, sizeof(int) * (size_t)2 * batch, s));
+        SC_TRY(launch_mc_hqc_outcome64(*law, h->d_synd, h->d_pratio, R, batch, T, (long)first_trial, k0, k1, acc_flips, acc_cost, dout, s));
+    } else {  // each oracle answer wrong with probability eps
+        hipLaunchKernelGGL(k_mc_bernoulli<true>, dim3((R + 63) / 64, T), dim3(256), 0, s, h->d_synd, R, batch, (long)first_trial,
+                           0u, k0, k1, (const u64 *)nullptr, bernoulli_threshold(eps));
+        LAUNCH_CHECK();
+    }
+    // msg = [0]*N ++ reported (hqc.py:703-705); its syndrome under H = [Hin | I] is `reported` itself
+    SC_HIP(hipMemsetAsync(h->d_recv, 0, sizeof(u64) * (size_t)T * h->n, s));
+    SC_HIP(hipMemcpy2DAsync(h->d_recv + N, sizeof(u64) * h->n, h->d_synd, sizeof(u64) * h->m, sizeof(u64) * h->m, T,
+                            hipMemcpyDeviceToDevice, s));
+    if (out_msg) SC_TRY(mc_export_bits(h, h->d_recv, batch, T, dev_io, s, out_msg));
+    SC_TRY(mc_run_f64(h, batch, T, G, max_iter, early, law ? h->d_pratio.get() : nullptr, law ? R : 0, s));
+    const hipMemcpyKind back = dev_io ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (out_y && !dev_io) SC_HIP(hipMemcpyAsync(out_y, dy, sizeof(int) * (size_t)batch * omega, back, s));
+    if (out_outcome && !dev_io) SC_HIP(hipMemcpyAsync(out_outcome, dout, (size_t)batch * R, back, s));
+    if (out_flips) SC_HIP(hipMemcpyAsync(out_flips, acc_flips, sizeof(int) * (size_t)batch, back, s));
+    if (out_cost) SC_HIP(hipMemcpyAsync(out_cost, acc_cost, sizeof(int) * (size_t)batch, back, s));
+    if (out_stats) {  // the counters of hqc.py:709-758, from the decisions the loop and the hand-over have left in d_hard
+        SC_HIP(hipMemsetAsync(dstats, 0, sizeof(int) * (size_t)5 * batch, s));
+        hipLaunchKernelGGL(k_mc_hqc_stats, dim3((h->n + 4 * MC_STATS_RUN - 1) / (4 * MC_STATS_RUN), T), dim3(256), 0, s,
+                           h->d_hard.get(), h->d_mc.get(), h->d_recv.get(), h->n, N, batch, dstats);
+        LAUNCH_CHECK();
+        if (!dev_io) SC_HIP(hipMemcpyAsync(out_stats, dstats, sizeof(int) * (size_t)5 * batch, back, s));
+    }
+    if (out_bits) {  // decoded = e XOR msg, as scaldpc_bp_decode_batch_f64 returns it for out_msg
+        Outputs o, dev;
+        o.bits = out_bits;
+        SC_TRY(stage_outputs(h, o, batch, dev_io, false, &dev));
+        hipLaunchKernelGGL(k_unpack_bits, dim3((h->n + 255) / 256, T), dim3(256), 0, s, h->d_hard, h->d_recv, h->n, batch,
+                           dev.bits);
+        LAUNCH_CHECK();
+        SC_TRY(copy_outputs(h, o, dev, batch, dev_io, s));
+    }
+    // decoded[:N] = e[:N] XOR msg[:N] = e[:N] must equal the indicator of y (hqc.py:742-749)
+    SC_TRY(mc_finish(h, batch, T, N, dev_io, s, out_success, out_iters));
+    return settle.done();
+}
+
+}  // namespace
+
+int scaldpc_mc_fer_run_f64(scaldpc_bp *h, int64_t first_trial, int32_t batch, uint64_t seed, int32_t max_iter_arg, uint32_t flags,
+                           void *stream, uint8_t *out_success, int32_t *out_iters, uint8_t *out_error)
+{
+    SC_TRY(mc_f64_args(h, first_trial, batch, flags, out_success));
+    std::lock_guard<std::mutex> lk(h->mu);
+    SC_TRY(check_usable(h));
+    DeviceGuard dg(h->device);
+    CacheBypass guard(h->async_used);
+    Call c;
+    SC_TRY(begin_call(h, batch, max_iter_arg, stream, &c));
+    const hipStream_t s = c.s;
+    SyncOnError settle{s};
+    SC_TRY(refresh_full(h));
+    const bool dev_io = flags & SCALDPC_F_DEVICE_IO, early = flags & SCALDPC_F_EARLY_EXIT;
+    const int T = c.T, max_iter = c.max_iter, G = ref64_group(h, T);
+    SC_TRY(ref64_ensure(h, T, G, max_iter, false, 0));
+    SC_TRY(grow(h->d_mc, (size_t)T * h->n));
+    SC_TRY(ensure_thresholds(h));
+    const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
+    // error ~ Bernoulli(p_i) per position (decode.py:166-167), syndrome = H error (decode.py:168)
+    hipLaunchKernelGGL(k_mc_bernoulli<false>, dim3((h->n + 63) / 64, T), dim3(256), 0, s, h->d_mc, h->n, batch,
+                       (long)first_trial, 0u, k0, k1, (const u64 *)h->d_thr, 0ull);
+    LAUNCH_CHECK();
+    SC_TRY(launch_syndrome(h, h->d_mc, h->d_synd, T, s));
+    if (out_error) SC_TRY(mc_export_bits(h, h->d_mc, batch, T, dev_io, s, out_error));
+    SC_TRY(mc_run_f64(h, batch, T, G, max_iter, early, nullptr, 0, s));
+    // success iff decoding == error everywhere (decode.py:173-175)
+    SC_TRY(mc_finish(h, batch, T, h->n, dev_io, s, out_success, out_iters));
+    return settle.done();
+}
+
+int scaldpc_mc_hqc_run_f64(scaldpc_bp *h, int32_t omega, double eps, int64_t first_trial, int32_t batch, uint64_t seed,
+                           int32_t max_iter_arg, uint32_t flags, void *stream, uint8_t *out_success, int32_t *out_iters,
+                           uint8_t *out_msg, int32_t *out_y)
+{
+    SC_TRY(mc_f64_args(h, first_trial, batch, flags, out_success));
+    std::lock_guard<std::mutex> lk(h->mu);
+    SC_TRY(check_usable(h));
+    return mc_hqc_run_f64_body(h, omega, nullptr, eps, false, first_trial, batch, seed, max_iter_arg, flags, stream, out_success,
+                               out_iters, out_msg, out_y, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+int scaldpc_mc_hqc_run_stats_f64(scaldpc_bp *h, int32_t omega, const double *weights, const uint8_t *flips, const double *probs,
+                                 const int32_t *costs, int32_t K, int64_t first_trial, int32_t batch, uint64_t seed,
+                                 int32_t max_iter_arg, uint32_t flags, void *stream, uint8_t *out_success, int32_t *out_iters,
+                                 uint8_t *out_msg, int32_t *out_y, uint8_t *out_outcome, int32_t *out_flips, int32_t *out_cost,
+                                 int32_t *out_stats, uint8_t *out_bits)
+{
+    SC_TRY(mc_f64_args(h, first_trial, batch, flags, out_success));
+    std::lock_guard<std::mutex> lk(h->mu);
+    SC_TRY(check_usable(h));
+    McHqcLaw64 law;
+    char why[160];
+    if (mc_hqc_law64(weights, flips, probs, costs, K, h->m, out_cost != nullptr, &law, why, sizeof why))
+        return fail(SCALDPC_EINVAL, "%s", why);
+    return mc_hqc_run_f64_body(h, omega, &law, 0.0, costs != nullptr, first_trial, batch, seed, max_iter_arg, flags, stream,
+                               out_success, out_iters, out_msg, out_y, out_outcome, out_flips, out_cost, out_stats, out_bits);
 }
 
 int scaldpc_bp_configure(scaldpc_bp *h, const char *key, const char *value)

@@ -4,7 +4,8 @@
 // alone.  Included by scaldpc_bp.hip after scaldpc_bp_kernels.h (same anonymous namespace, same bit planes and state).
 //
 // What it is for: reproducing the reference's numbers, and a full-batch float64 key for the fp32 tanh kernels.  What it is
-// not: the throughput path -- no record form, no fused first iteration, no row-parallel or LDS variant, no compaction.
+// not: the throughput path -- no record form, no fused first iteration, no row-parallel or LDS variant; no compaction in
+// scaldpc_bp_decode_batch_f64, one level of it in the float64 Monte-Carlo sweeps (ref64_handover; scaldpc_bp_mc64.hip).
 //
 // Layout: TWO message arrays, as the oracle keeps them,
 //     x : double [tile][edge][64]   bit-to-check ratios     (written by the variable pass, read by the check pass)
@@ -305,5 +306,8 @@ __global__ __launch_bounds__(256) void k_var_ratio64(const int *__restrict__ col
         var_ratio64_loop_bwd(ce, ct, xt, d, live);
     }
 }
+
+// (The two kernels the float64 Monte-Carlo sweeps add -- the outcome draw that writes the ratio plane and the double twin of
+// k_gather_prior -- are a translation unit of their own, scaldpc_bp_mc64.hip: this unit's code object stays what it was.)
 
 }  // namespace

@@ -105,6 +105,46 @@ static inline int mc_hqc_law(const double *weights, const uint8_t *flips, const 
     return 0;
 }
 
+// The same table for the float64 sweeps (scaldpc_mc_hqc_run_stats_f64), as k_mc_hqc_outcome64 takes it by value (904 B): the
+// thresholds, flips and costs are McHqcLaw's -- the trial law does not know the decode's precision -- and an outcome brings the
+// RATIO r = p / (1 - p) of its prior, formed here in double by the division the float64 decode's own priors go through
+// (p = 0 -> 0, p = 1 -> inf).
+struct McHqcLaw64 {
+    unsigned long long t[2][MC_HQC_MAX_OUTCOMES];
+    double ratio[MC_HQC_MAX_OUTCOMES];
+    int cost[MC_HQC_MAX_OUTCOMES];
+    unsigned flips;
+    int K;
+};
+
+// mc_hqc_law with probs double [K], taken as they are: the values are checked in double (a value that only rounds into [0, 1]
+// is refused), everything else is mc_hqc_law's on the rounded values, whose thresholds, flips and costs are copied.
+static inline int mc_hqc_law64(const double *weights, const uint8_t *flips, const double *probs, const int32_t *costs, int K, int R,
+                               bool want_cost, McHqcLaw64 *law, char *msg, size_t len)
+{
+    *law = McHqcLaw64();
+    float rounded[MC_HQC_MAX_OUTCOMES] = {};
+    if (probs && K >= 1 && K <= MC_HQC_MAX_OUTCOMES)
+        for (int k = 0; k < K; k++) {
+            if (!(probs[k] >= 0.0 && probs[k] <= 1.0)) {
+                snprintf(msg, len, "probs[%d] = %g is not a probability", k, probs[k]);
+                return 1;
+            }
+            rounded[k] = (float)probs[k];
+        }
+    McHqcLaw law32;
+    if (mc_hqc_law(weights, flips, probs ? rounded : nullptr, costs, K, R, want_cost, &law32, msg, len)) return 1;
+    for (int b = 0; b < 2; b++)
+        for (int k = 0; k < MC_HQC_MAX_OUTCOMES; k++) law->t[b][k] = law32.t[b][k];
+    for (int k = 0; k < K; k++) {
+        law->ratio[k] = probs[k] / (1.0 - probs[k]);
+        law->cost[k] = law32.cost[k];
+    }
+    law->flips = law32.flips;
+    law->K = K;
+    return 0;
+}
+
 // ------------------------------------------------------------------------------------------ scaldpc_mc_qary_run_secret
 
 constexpr int MC_SECRET_MAX_LEVELS = 32;

@@ -249,7 +249,7 @@ def kyber_fer_sweep(H, name, iterations, prior, table_b, table_s, runs, seed, ch
 
 
 def hqc_oracle_sweep(Hin, N, omega, table, runs, seed, chunk=4096, bp_method="product_sum", max_iter=100, bp_decoder=None,
-                     want_stats=False):
+                     want_stats=False, precision=None):
     """A sweep of synthetic hqc.decode() trials at a FIXED number of checks (the rows of Hin) under the law of the attack's
     oracle: every check is answered by an outcome of `table` (`trials.wrapped_oracle_table`: the repeated measurements of
     wrapped_hqc_decoding_oracle, simulate/hqc.py:782-871), drawn on the device conditional on the check's true value, and
@@ -264,7 +264,9 @@ def hqc_oracle_sweep(Hin, N, omega, table, runs, seed, chunk=4096, bp_method="pr
     recovered key -- is oracle_calls / successes.
     want_stats: the sweep also counts, on the device, what tracking.add_decoder_stats records per decode (hqc.py:709-758); the
     result gains `stats` and `stats_success`: {counter: total} over all trials and over the successful ones, the counters
-    being HQC_STATS_COLUMNS."""
+    being HQC_STATS_COLUMNS.
+    precision: None (the call as it always was: the fp32 kernels), "float32" or "float64" -- handed to
+    `BpDecoder.mc_hqc_run_soft`: the same trials decoded by the reference's float64 recursion, product-sum only."""
     g = TannerGraph.coerce(Hin)
     if g.n != N:
         raise ValueError(f"Hin has {g.n} columns, N = {N}")
@@ -277,7 +279,7 @@ def hqc_oracle_sweep(Hin, N, omega, table, runs, seed, chunk=4096, bp_method="pr
     hist = np.zeros(max_iter + 1, dtype=np.int64)
     successes = flips = calls = calls_ok = 0
     sums = np.zeros((2, len(HQC_STATS_COLUMNS)), dtype=np.int64)  # all trials / the successful ones
-    extra = dict(want_stats=True) if want_stats else {}
+    extra = dict(dict(want_stats=True) if want_stats else {}, **_precision_kw(precision))
     try:
         for first in range(0, runs, chunk):
             out = bpd.mc_hqc_run_soft(min(chunk, runs - first), omega, table, seed, first_trial=first, max_iter=max_iter, **extra)
@@ -321,6 +323,8 @@ def hqc_attack_curve(first_row_support, N, rows, omega, table, runs, seed, decod
     tracking.add_decoder_stats counted on the device (`want_stats`).  Trials that already succeeded are decoded again at
     the later steps -- a call decodes a contiguous range of trial indices -- and converge within a few iterations; their
     later results are not recorded.  The result does not depend on `chunk`.
+    The curve in the reference's own arithmetic: `bp_decoder=sweeps_in("float64")` -- a decoder class whose sweeps decode in
+    float64 (the float64 form works on a decoder grown by `append_rows`); this function's own parameters are what they were.
 
     Returns dict(
       steps                int32 [S]: the numbers of checks R decoded at,
@@ -387,6 +391,72 @@ def hqc_attack_curve(first_row_support, N, rows, omega, table, runs, seed, decod
 def _precision_kw(precision):
     # (only where asked for: a stand-in decoder class need not know the keyword)
     return {} if precision is None else {"precision": precision}
+
+
+def sweeps_in(precision, bp_decoder=None):
+    """A decoder class whose Monte-Carlo sweeps (`mc_fer_run`, `mc_hqc_run`, `mc_hqc_run_soft`) decode in `precision` unless a
+    call says otherwise: `bp_decoder` (default: the HIP class) with that one default changed, for the drivers that take a
+    decoder class and no `precision` of their own -- `hqc_attack_curve(..., bp_decoder=sweeps_in("float64"))` is the
+    checks-needed curve in the reference's float64 arithmetic.  `decode` / `decode_batch` are untouched.  "float64" on a min-sum
+    decoder raises the `ValueError` of the methods themselves, at the first sweep."""
+    if str(precision).lower() not in ("float32", "float64"):
+        raise ValueError(f"precision '{precision}' is invalid. Choose 'float32' or 'float64'.")
+    base = bp_decoder or _default_bp()
+
+    class Sweeps(base):
+        def mc_fer_run(self, *args, **kw):
+            return super().mc_fer_run(*args, **dict({"precision": precision}, **kw))
+
+        def mc_hqc_run(self, *args, **kw):
+            return super().mc_hqc_run(*args, **dict({"precision": precision}, **kw))
+
+        def mc_hqc_run_soft(self, *args, **kw):
+            return super().mc_hqc_run_soft(*args, **dict({"precision": precision}, **kw))
+
+    Sweeps.__name__ = Sweeps.__qualname__ = f"{base.__name__}Sweeps{str(precision).capitalize()}"
+    return Sweeps
+
+
+def hqc_precision_audit(Hin, N, omega, table, runs, seed, chunk=4096, max_iter=100, bp_decoder=None):
+    """On how many trials do the fp32 tanh kernels and the reference's float64 arithmetic decide differently?  The sweep of
+    `hqc_oracle_sweep` (product-sum), every chunk of trial indices run twice on ONE decoder: `mc_hqc_run_soft` with
+    precision="float32" and with precision="float64".  The trials are the same whatever the precision -- inputs, outcomes and
+    certainties bit for bit (the float64 decode takes the table's certainties unrounded) -- so every difference is the decode's.
+    Global trial indices 0 .. runs - 1 are scanned `chunk` at a time; the result does not depend on `chunk`.  Returns dict(
+      runs, successes32, successes64,
+      success_differs         int64 array: the trial indices whose success differs, ascending,
+      iters_differ            the number of trials whose iteration count differs,
+      iter_hist32, iter_hist64  int64 [max_iter + 1]: trials by the iteration count of their decode)."""
+    g = TannerGraph.coerce(Hin)
+    if g.n != N:
+        raise ValueError(f"Hin has {g.n} columns, N = {N}")
+    if runs < 0 or chunk < 1:
+        raise ValueError("runs must not be negative and chunk must be positive")
+    # the check columns' shared priors are replaced per trial: any probability does
+    shared = np.concatenate([np.full(N, omega / N, dtype=np.float64), np.full(g.m, 0.5, dtype=np.float64)])
+    bpd = (bp_decoder or _default_bp())(g.with_identity(), max_iter=max_iter, bp_method="product_sum", channel_probs=shared)
+    hist = np.zeros((2, max_iter + 1), dtype=np.int64)
+    successes = [0, 0]
+    differs = []
+    iters_differ = 0
+    try:
+        for first in range(0, runs, chunk):
+            ok, its = [], []
+            for k, precision in enumerate(("float32", "float64")):
+                out = bpd.mc_hqc_run_soft(min(chunk, runs - first), omega, table, seed, first_trial=first, max_iter=max_iter,
+                                          precision=precision)
+                ok.append(np.asarray(out["success"]).astype(bool))
+                its.append(np.asarray(out["iters"]))
+                successes[k] += int(ok[k].sum())
+                hist[k] += np.bincount(its[k], minlength=max_iter + 1)[: max_iter + 1]
+            differs.append(first + np.flatnonzero(ok[0] != ok[1]))
+            iters_differ += int((its[0] != its[1]).sum())
+    finally:
+        if hasattr(bpd, "close"):
+            bpd.close()
+    return dict(runs=int(runs), successes32=successes[0], successes64=successes[1],
+                success_differs=np.concatenate(differs).astype(np.int64) if differs else np.zeros(0, dtype=np.int64),
+                iters_differ=iters_differ, iter_hist32=hist[0], iter_hist64=hist[1])
 
 
 def hqc_decode(N, Hin, checks, y_sparse, bp_decoder=None, max_iter=100, precision=None):
