@@ -237,7 +237,8 @@ int scaldpc_bp_decode_batch_f64(scaldpc_bp *h, const uint8_t *in, int32_t input_
                                 uint8_t *out_bits, double *out_llr, int32_t *out_iters, uint8_t *out_conv);
 /*
  * Measurement aid for bench.py: on the message state left by the last (fixed-iteration)
- * decode, run `iters` back-to-back launches of the check kernel and of the variable kernel of
+ * decode -- in the min-sum record form the messages and sign masks of the pass BEFORE the decode's last one, which stores
+ * neither: a consistent pair, one iteration behind the decisions -- run `iters` back-to-back launches of the check kernel and of the variable kernel of
  * `method`, each series bracketed by HIP events on its launch stream.
  *   ms[0] / ms[1]   total ms of the check / variable series          (float[2])
  *   launches[0..1]  launches in each series                           (int32[6])

@@ -457,6 +457,10 @@ int ensure_tile_tables(scaldpc_bp *h)
     const size_t o_var_rows = reserve((size_t)4 * VAR_INLINE * hv.bk.blk[hv.bk.nb] + 4);  // rows of the records' inline edges
     int *host = stage_buffer(total);
     if (!host) return fail(SCALDPC_ENOMEM, "out of host memory");
+    // rows whose last edge goes into a column of degree 1 (scaldpc_rec_trim.h): rebuilt with the tables, so a column
+    // that appended rows gave a second edge has lost its row's mark by the next decode
+    pvec<int> const_last((size_t)h->m);
+    rec_mark_const_last(h->m, h->n, row_ptr, col_ptr, csc_edge, const_last.data());
     for (int b = 0; b < hr.bk.nb; b++) {
         const int blocks = hr.bk.blk[b + 1] - hr.bk.blk[b];
         for (int sl = 0; sl < blocks * 4; sl++) {
@@ -466,7 +470,7 @@ int ensure_tile_tables(scaldpc_bp *h)
             md[0] = r;
             md[1] = pad ? 0 : row_ptr[r];
             md[2] = pad ? 0 : row_ptr[r + 1] - row_ptr[r];
-            md[3] = hr.bk.maxd[b];
+            md[3] = rec_desc_word(hr.bk.maxd[b], pad ? 0 : const_last[r]);  // (k_check_tanh asks "== 0": any-degree rows stay 0)
         }
     }
     int *meta = host + o_var_meta, *relaid = host + o_csc_list, *relaid_row = host + o_csc_row;
@@ -783,11 +787,14 @@ int launch_check(scaldpc_bp *h, int method, float alpha, int G, const u64 *synd_
         float *const rec0 = h->d_rec + (size_t)tile0 * rec_tile_floats(h->m);
         u64 *const mask0 = h->d_mask + (size_t)tile0 * h->E;
         const FusedTest ft0 = test ? *ft : FusedTest{};
+        // the constant last edge of a marked row is read from the shared priors as they are NOW (set_channel_probs on a live
+        // decoder needs no rebuild); a soft call's columns of degree 1 may carry per-codeword priors: no constant there
+        const float *const cprior = sp ? nullptr : h->d_prior;
         with_cap<16, 32, 64>(h->max_row_deg, [&](auto cap) {
             with_bool(boot, [&](auto bt) {
                 with_bool(test, [&](auto par) {
                     hipLaunchKernelGGL((k_check_minsum_rec<cap, bt, par>), grid, block, 0, s, h->d_row_list, msg0, synd_g, done_g,
-                                       skip_done, h->m, h->E, alpha, h->d_col_idx, rec0, mask0, h->d_csr_pos, ft0);
+                                       skip_done, h->m, h->E, alpha, h->d_col_idx, rec0, mask0, h->d_csr_pos, cprior, ft0);
                 });
             });
         });
@@ -853,9 +860,12 @@ int ensure_first_table(scaldpc_bp *h, int method, float alpha1, hipStream_t s)
 
 // first_synd: non-null = iteration 1 without its check pass (the group's syndrome planes; ensure_first_table first)
 // sp: non-null = a soft call (never with first_synd: the first-message table is a function of shared priors)
+// final_pass: no check pass follows this one on these tiles (the last iteration of a decode, always with write_out): the
+//             record form then runs its store-free instantiation, which leaves messages and sign masks as the pass before
+//             left them
 int launch_var(scaldpc_bp *h, int G, float *post_g, u64 *hard_g, const u64 *done_g, int skip_done, int write_out,
                hipStream_t s, int tile0 = 0, const u64 *first_synd = nullptr, bool rec = false, bool light = false,
-               const SoftPrior *sp = nullptr)
+               const SoftPrior *sp = nullptr, bool final_pass = false)
 {
     float *const msg0 = h->d_msg + (size_t)tile0 * h->E * TW;
     float *const scr0 = h->d_scratch ? h->d_scratch + (size_t)tile0 * h->E * TW : nullptr;
@@ -881,10 +891,12 @@ int launch_var(scaldpc_bp *h, int G, float *post_g, u64 *hard_g, const u64 *done
         const int blk0 = slim && !h->var_reversed ? n1 : 0, xmap = xm ? nb_launch : 0;
         with_cap<16, 32>(h->max_col_deg, [&](auto cap) {  // (columns wider than 32 take the message form: rec_form)
             with_prior(h, sp, [&](auto P, auto prior) {
-                hipLaunchKernelGGL((k_var_rec<cap, decltype(P)>), gridr, dim3(256), 0, s, h->d_var_meta, h->d_var_rows, h->d_csc_list,
-                                   h->d_csc_row, prior, msg0, h->d_rec + (size_t)tile0 * rec_tile_floats(h->m),
-                                   h->d_mask + (size_t)tile0 * h->E, post_g, hard_g, done_g, skip_done, h->n, h->m, h->E, write_out,
-                                   blk0, xmap);
+                with_bool(final_pass && write_out, [&](auto fin) {
+                    hipLaunchKernelGGL((k_var_rec<cap, decltype(P), fin>), gridr, dim3(256), 0, s, h->d_var_meta, h->d_var_rows,
+                                       h->d_csc_list, h->d_csc_row, prior, msg0, h->d_rec + (size_t)tile0 * rec_tile_floats(h->m),
+                                       h->d_mask + (size_t)tile0 * h->E, post_g, hard_g, done_g, skip_done, h->n, h->m, h->E,
+                                       write_out, blk0, xmap);
+                });
             });
         });
     } else {
@@ -1189,7 +1201,7 @@ int iterate_tiles(scaldpc_bp *h, Lanes &lanes, const TileState &st, int g0, int 
             SC_TRY(launch_var(h, gs[k], st.post ? st.post + (size_t)ta * h->n * TW : nullptr, st.hard + (size_t)ta * h->n,
                               st.done + ta, skip, (early || last) ? 1 : 0, lanes[k], t0[k],
                               no_check ? st.synd + (size_t)ta * h->m : nullptr, it > 1 && recf, it > 1,
-                              soft ? &spv : nullptr));
+                              soft ? &spv : nullptr, last));
             if (ride && !last && !poll) {
                 verdict_pending[k] = true;  // the next check pass of this lane carries the test
             } else if (early || last) {  // convergence test + latch, one launch

@@ -6,6 +6,7 @@
 #include "scaldpc_mc_law.h"  // McHqcLaw: the outcome table k_mc_hqc_outcome takes by value
 #include "scaldpc_philox.h"
 #include "scaldpc_rec_pack.h"  // row words of the record form's variable pass
+#include "scaldpc_rec_trim.h"  // rows of the record form's check pass that end in a constant edge
 #include <type_traits>
 
 // v_writelane_b32 as an instruction the COMPILER emits: ROCm 7.2's clang has no __builtin_amdgcn_writelane, but the LLVM
@@ -762,7 +763,8 @@ static_assert(REC_TW == TW, "the record layout of scaldpc_rec_pack.h is laid out
 template <int DEG, bool BOOT>
 __device__ __forceinline__ void check_minsum_row_rec(const float *p, u64 synd_mask, float alpha, float *__restrict__ rec,
                                                      float *__restrict__ rec2, unsigned char *__restrict__ arg,
-                                                     u64 *__restrict__ sgn, int lane, const int *__restrict__ pos)
+                                                     u64 *__restrict__ sgn, int lane, const int *__restrict__ pos,
+                                                     bool const_last = false, float x_last = 0.0f)
 {
     // BOOT: the sign masks are laid out in the variable pass's order (position of the edge in the re-laid edge list: a
     // column's masks are contiguous there); lane k fetches edge k's position up front
@@ -771,7 +773,16 @@ __device__ __forceinline__ void check_minsum_row_rec(const float *p, u64 synd_ma
         if (lane < DEG) mp = pos[lane];
     float x[DEG];
 #pragma unroll
-    for (int k = 0; k < DEG; k++) x[k] = p[(size_t)k * TW];  // (plain loads: non-temporal ones cost 5-9 % and save no byte, profiles/r04/ab_rec_nontemporal.log)
+    for (int k = 0; k < DEG - 1; k++) x[k] = p[(size_t)k * TW];  // (plain loads: non-temporal ones cost 5-9 % and save no byte, profiles/r04/ab_rec_nontemporal.log)
+    // const_last (wave-uniform: REC_CONST_LAST in the row's descriptor, shared priors): the row's LAST edge goes into a
+    // column of degree 1, whose message is its prior in every pass -- iteration 1 stored prior + 0.0f there and nothing
+    // has written the edge since.  x_last is that prior from a scalar load; the 256-B row of 64 equal floats stays
+    // unread.  (The pass uses x through x <= 0, |x| and |x| == m1 alone: a zero's sign cannot matter.)  One uniform
+    // branch, after the other edges' loads have been issued; every compare still comes behind every load.
+    if (const_last)
+        x[DEG - 1] = x_last;
+    else
+        x[DEG - 1] = p[(size_t)(DEG - 1) * TW];
     float m1 = FLT_MAX, m2 = FLT_MAX;
     const float fmax = FLT_MAX;
     u64 par = ((u64)(unsigned)rfl((int)(synd_mask >> 32)) << 32) | (unsigned)rfl((int)synd_mask);  // (uniform by construction: keep it on the scalar side)
@@ -844,7 +855,8 @@ __global__ __launch_bounds__(256) void k_check_minsum_rec(const int *__restrict_
                                                           int skip_done, int m, long E, float alpha,
                                                           const int *__restrict__ col_idx,
                                                           float *__restrict__ rec, u64 *__restrict__ sgn,
-                                                          const int *__restrict__ csr_pos, FusedTest ft = FusedTest{})
+                                                          const int *__restrict__ csr_pos,
+                                                          const float *__restrict__ const_prior, FusedTest ft = FusedTest{})
 {
     const int lane = threadIdx.x & 63;
     const int tl = blockIdx.y;
@@ -870,11 +882,16 @@ __global__ __launch_bounds__(256) void k_check_minsum_rec(const int *__restrict_
         u64 *sg = sgn + (size_t)tl * E;  // (masks by position: the tile's base)
         const int *ps = csr_pos + e0;
         const u64 sw = synd[(size_t)tl * m + r];  // (uniform: a scalar load; the row's syndrome bits ARE a lane mask)
+        // the constant last edge (check_minsum_row_rec): const_prior = the handle's shared priors, null in a soft call,
+        // whose columns of degree 1 may carry a prior per codeword -- its rows run with all their loads
+        const bool cl = const_prior != nullptr && (md[3] & REC_CONST_LAST) != 0;
+        float xl = 0.0f;
+        if (cl) xl = const_prior[rec_desc_col(md[3])];
         // (the ladder for_exact_degree spells, kept as a macro here and in k_var_rec: through the helper's lambda the
         // record-form kernels come out with other registers and an instruction more or less)
-#define MR(D)                                                                                               \
-    case D:                                                                                                 \
-        if constexpr (D <= CAP) check_minsum_row_rec<D, BOOT>(p, sw, alpha, rc, rc2, ar, sg, lane, ps); \
+#define MR(D)                                                                                                   \
+    case D:                                                                                                     \
+        if constexpr (D <= CAP) check_minsum_row_rec<D, BOOT>(p, sw, alpha, rc, rc2, ar, sg, lane, ps, cl, xl); \
         break;
 #define MR8(D) MR(D) MR(D + 1) MR(D + 2) MR(D + 3) MR(D + 4) MR(D + 5) MR(D + 6) MR(D + 7)
         switch (deg) {
@@ -1520,7 +1537,15 @@ __device__ __forceinline__ gbyte *sbase_b(const unsigned char *p)
     return g;
 }
 
-template <int D>
+// LAST: the pass after which no check pass follows (the last iteration of a decode).  Nothing reads the messages or the
+// sign masks it would leave -- the next call starts over at iteration 1 -- so it only sums: the same gathers and sign
+// flips, then prior + mm[0] + mm[1] + ... in the same order, which is the posterior.  No stores, no prefix array, no
+// suffix sums, no ballots, no edge ids.
+// (Forming the store addresses from the row words -- edge id = row * the rows' common degree + index in the row -- and
+// leaving the record's 64 B of inline ids unread was built and measured: 4.5 MB less fetched per launch and 5-7 % MORE
+// time per step, the scalar arithmetic in front of every store being issue slots this pass does not have.
+// profiles/minsum_trim/README.md.)
+template <int D, bool LAST>
 __device__ __forceinline__ float var_col_rec(float *tile_base, const float *__restrict__ rec_base, unsigned rec2_off,
                                              const unsigned char *__restrict__ arg_base, u64 *sgn_col, unsigned lane,
                                              const int *__restrict__ rc, const int4 *__restrict__ row4,
@@ -1555,6 +1580,12 @@ __device__ __forceinline__ float var_col_rec(float *tile_base, const float *__re
     for (int k = 0; k < D; k++) {
         const u64 ng = ((u64)(unsigned)__builtin_amdgcn_readlane(shi, k) << 32) | (unsigned)__builtin_amdgcn_readlane(slo, k);
         mm[k] = __builtin_amdgcn_inverse_ballot_w64(ng) ? -mm[k] : mm[k];
+    }
+    if constexpr (LAST) {
+        float sum = pr;
+#pragma unroll
+        for (int k = 0; k < D; k++) sum += mm[k];
+        return sum;
     }
     // the record's inline edge ids (wanted by the stores alone)
     {
@@ -1593,7 +1624,8 @@ __device__ __forceinline__ float var_col_rec(float *tile_base, const float *__re
 
 // grid (column records / 4, G), block 256 = 4 column records (k_var's launch shape and records).
 // (P = SoftPrior: tl is the tile the XCD map chose, the plane row follows it like the records do)
-template <int CAP, class P>
+// LAST: the store-free form of a decode's last pass (var_col_rec); it always comes with write_out.
+template <int CAP, class P, bool LAST = false>
 __global__ __launch_bounds__(256) void k_var_rec(const int *__restrict__ list, const int *__restrict__ var_rows,
                                                  const int *__restrict__ csc_edge, const int *__restrict__ csc_row,
                                                  typename P::Arg prior_arg, float *msg, const float *__restrict__ rec,
@@ -1630,9 +1662,9 @@ __global__ __launch_bounds__(256) void k_var_rec(const int *__restrict__ list, c
     const float pr = prior(v, tl, (int)lane);
     float L = pr;
     const unsigned r2 = (unsigned)m * (TW * (unsigned)sizeof(float));  // rec_m2_off(m) in bytes
-#define VR(D)                                                                                           \
-    case D:                                                                                             \
-        if constexpr (D <= CAP) L = var_col_rec<D>(tb, rb, r2, ab, st + cb, lane, rc, w4, ce, cr, pr);  \
+#define VR(D)                                                                                                \
+    case D:                                                                                                  \
+        if constexpr (D <= CAP) L = var_col_rec<D, LAST>(tb, rb, r2, ab, st + cb, lane, rc, w4, ce, cr, pr); \
         break;
 #define VR8(D) VR(D) VR(D + 1) VR(D + 2) VR(D + 3) VR(D + 4) VR(D + 5) VR(D + 6) VR(D + 7)
     switch (d) {
