@@ -38,6 +38,12 @@
  *                                the same three sweeps decoded by scaldpc_bp_decode_batch_f64's recursion: the reference's
  *                                success rates in its own arithmetic, trial for trial
  *                                (entry points added under SCALDPC_VERSION 104: nothing that existed changed)
+ *   scaldpc_mc_fer_run_at / scaldpc_mc_hqc_run_stats_at / scaldpc_mc_fer_run_at_f64 / scaldpc_mc_hqc_run_stats_at_f64 /
+ *   scaldpc_mc_qary_run_at / scaldpc_mc_qary_run_secret_at
+ *                                the sweeps above on CHOSEN trials: a list of global trial indices where the sibling takes a
+ *                                contiguous range -- the post-mortem of a sweep's failures, the attack loop that stops at a
+ *                                key's first success (simulate/hqc.py:980-982), a subset picked on the host
+ *                                (entry points added under SCALDPC_VERSION 104: nothing that existed changed)
  *   scaldpc_qary_create          simulate_rs Decoder::new via PyO3 `#[new]`,
  *                                simulate_rs/src/pydecoder.rs:24-45 -> simulate_rs/src/decoder.rs:494-553
  *   scaldpc_qary_min_sum_batch   PyO3 `min_sum`, simulate_rs/src/pydecoder.rs:53-65
@@ -493,6 +499,52 @@ int scaldpc_mc_hqc_run_stats_f64(scaldpc_bp *h, int32_t omega, const double *wei
                                  uint8_t *out_outcome, int32_t *out_flips, int32_t *out_cost,
                                  int32_t *out_stats /* optional here */, uint8_t *out_bits);
 
+/* Monte-Carlo sweeps on chosen trials: any list of global trial indices.
+ *
+ * Every sweep above draws trial i from (seed, first_trial + i) alone, so a trial is a pure function of its global index.  Each
+ * entry below is its sibling -- the entry of the same name without "_at" -- with `const int64_t *trial_ids, int32_t batch` where
+ * the sibling takes `int64_t first_trial, int32_t batch`; every other argument, the trial law, the validation, the flags and the
+ * outputs are word for word the sibling's.  One difference: in scaldpc_mc_hqc_run_stats_at out_stats is OPTIONAL (as in the float64
+ * entry), so that with the K = 2 table of scaldpc_mc_hqc_run_soft's reduction it covers scaldpc_mc_hqc_run(eps), and with
+ * out_stats = NULL scaldpc_mc_hqc_run_soft.
+ *
+ * Law: slot i of the call is trial trial_ids[i] -- its Philox counter carries trial_ids[i] where the sibling's carries
+ * first_trial + i.  Nothing else in any trial law changes.
+ *
+ * trial_ids: int64 [batch], a HOST pointer whatever the flags say (as the tables are); the call copies it to a device block the
+ * handle owns (released by destroy, counted by scaldpc_debug_live_blocks).  Any order is legal; duplicates are legal (two slots
+ * with the same index give the same row); indices up to 2^63 - 1 are legal.
+ *
+ * Defining property: for every i, every output row i of an _at call equals row trial_ids[i] - f of the sibling called with
+ * first_trial = f on any range that contains the index, with the same handle, flags, max_iter, method and tables: out_success and
+ * out_iters, out_flips and out_cost, out_stats, every exported input (out_error, out_msg, out_y, out_outcome, levels, secrets) and
+ * out_bits / out_symbols -- integer equality, on every path (LDS-resident, 64-codeword tiles, row-parallel, every compaction
+ * level, the float64 hand-over) and in every q-ary kernel form.  Only the generator kernels know trial indices; the decode,
+ * compaction, compare and statistics kernels work on the slots of the call.
+ *
+ * Refused with SCALDPC_EINVAL before anything is queued (no output is written, the handle stays usable): trial_ids = NULL; a
+ * negative index (the message names its position and its value); everything the sibling refuses.  The f64 entries (as all binary
+ * sweeps) and the q-ary entries refuse SCALDPC_F_ASYNC.
+ * (entry points added under SCALDPC_VERSION 104: nothing that existed changed)
+ */
+int scaldpc_mc_fer_run_at(scaldpc_bp *h, const int64_t *trial_ids, int32_t batch, uint64_t seed, int32_t max_iter,
+                          int32_t method, float alpha, uint32_t flags, void *stream, uint8_t *out_success,
+                          int32_t *out_iters, uint8_t *out_error);
+int scaldpc_mc_hqc_run_stats_at(scaldpc_bp *h, int32_t omega, const double *weights, const uint8_t *flips, const float *probs,
+                                const int32_t *costs, int32_t K, const int64_t *trial_ids, int32_t batch, uint64_t seed,
+                                int32_t max_iter, int32_t method, float alpha, uint32_t flags, void *stream,
+                                uint8_t *out_success, int32_t *out_iters, uint8_t *out_msg, int32_t *out_y,
+                                uint8_t *out_outcome, int32_t *out_flips, int32_t *out_cost,
+                                int32_t *out_stats /* optional here */, uint8_t *out_bits);
+int scaldpc_mc_fer_run_at_f64(scaldpc_bp *h, const int64_t *trial_ids, int32_t batch, uint64_t seed, int32_t max_iter,
+                              uint32_t flags, void *stream, uint8_t *out_success, int32_t *out_iters, uint8_t *out_error);
+int scaldpc_mc_hqc_run_stats_at_f64(scaldpc_bp *h, int32_t omega, const double *weights, const uint8_t *flips,
+                                    const double *probs, const int32_t *costs, int32_t K, const int64_t *trial_ids,
+                                    int32_t batch, uint64_t seed, int32_t max_iter, uint32_t flags, void *stream,
+                                    uint8_t *out_success, int32_t *out_iters, uint8_t *out_msg, int32_t *out_y,
+                                    uint8_t *out_outcome, int32_t *out_flips, int32_t *out_cost,
+                                    int32_t *out_stats /* optional */, uint8_t *out_bits);
+
 /* ------------------------------------------------------------ q-ary min-sum */
 typedef struct scaldpc_qary scaldpc_qary;
 
@@ -677,6 +729,29 @@ int scaldpc_mc_qary_run_secret(scaldpc_qary *h, const double *prior_b,
                                int64_t first_trial, int32_t batch, uint64_t seed, uint32_t flags, void *stream,
                                uint8_t *out_success, int32_t *out_wrong, int32_t *out_channel_wrong,
                                int8_t *out_secret, uint8_t *out_levels, int8_t *out_symbols);
+
+/* The two q-ary sweeps on chosen trials: scaldpc_mc_qary_run and scaldpc_mc_qary_run_secret with `const int64_t *trial_ids`
+ * (int64 [batch], a HOST pointer whatever the flags say, copied to a device block the handle owns) where they take
+ * `int64_t first_trial`; everything else is word for word the sibling's.  Slot i of the call is trial trial_ids[i]: its Philox
+ * counters carry trial_ids[i] where the sibling's carry first_trial + i.  Any order, duplicates and indices up to 2^63 - 1 are legal.
+ * Defining property: for every i, every output row i (success, errs / wrong / channel_wrong, levels, secret, symbols) equals row
+ * trial_ids[i] - f of the sibling called with first_trial = f on any range that contains the index, with the same handle, flags
+ * and tables, in every kernel form -- integer equality.
+ * Refused with SCALDPC_EINVAL before anything is queued (no output written, the handle usable): trial_ids = NULL, a negative index
+ * (the message names its position and its value), and everything the sibling refuses, SCALDPC_F_ASYNC included.
+ * (entry points added under SCALDPC_VERSION 104: nothing that existed changed)
+ */
+int scaldpc_mc_qary_run_at(scaldpc_qary *h, const float *levels_b, const double *weights_b, int32_t k_b,
+                           const float *levels_s, const double *weights_s, int32_t k_s,
+                           const int64_t *trial_ids, int32_t batch, uint64_t seed, uint32_t flags, void *stream,
+                           uint8_t *out_success, int32_t *out_errs, int32_t *out_wrong, uint8_t *out_levels,
+                           int8_t *out_symbols);
+int scaldpc_mc_qary_run_secret_at(scaldpc_qary *h, const double *prior_b,
+                                  const float *levels_b, const double *weights_b, int32_t k_b,
+                                  const float *levels_s, const double *weights_s, int32_t k_s,
+                                  const int64_t *trial_ids, int32_t batch, uint64_t seed, uint32_t flags, void *stream,
+                                  uint8_t *out_success, int32_t *out_wrong, int32_t *out_channel_wrong,
+                                  int8_t *out_secret, uint8_t *out_levels, int8_t *out_symbols);
 
 #ifdef __cplusplus
 }

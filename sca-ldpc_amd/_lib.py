@@ -104,6 +104,16 @@ def _declare(lib):
     ]  # fmt: skip
     for name in ("scaldpc_mc_fer_run_f64", "scaldpc_mc_hqc_run_f64", "scaldpc_mc_hqc_run_stats_f64"):
         getattr(lib, name).restype = C.c_int
+    # the sweeps on chosen trials: the sibling's arguments with `const int64_t *trial_ids` (a host array) for `first_trial`
+    for name, sibling, at in (("scaldpc_mc_fer_run_at", "scaldpc_mc_fer_run", 1),
+                              ("scaldpc_mc_hqc_run_stats_at", "scaldpc_mc_hqc_run_stats", 7),
+                              ("scaldpc_mc_fer_run_at_f64", "scaldpc_mc_fer_run_f64", 1),
+                              ("scaldpc_mc_hqc_run_stats_at_f64", "scaldpc_mc_hqc_run_stats_f64", 7)):
+        a = list(getattr(lib, sibling).argtypes)
+        assert a[at] is C.c_int64
+        a[at] = vp
+        getattr(lib, name).argtypes = a
+        getattr(lib, name).restype = C.c_int
     for name in (
         "scaldpc_device_count", "scaldpc_set_device", "scaldpc_bp_create", "scaldpc_bp_set_channel_probs",
         "scaldpc_bp_decode_batch", "scaldpc_bp_time_kernels", "scaldpc_bp_set_tile_group", "scaldpc_mc_fer_run",
@@ -130,6 +140,13 @@ def _declare(lib):
     lib.scaldpc_mc_qary_run_secret.argtypes = [
         vp, vp, vp, vp, C.c_int32, vp, vp, C.c_int32, C.c_int64, C.c_int32, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp, vp, vp,
     ]  # fmt: skip
+    lib.scaldpc_mc_qary_run_at.argtypes = [
+        vp, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp, vp,
+    ]  # fmt: skip
+    lib.scaldpc_mc_qary_run_secret_at.argtypes = [
+        vp, vp, vp, vp, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp, vp, vp,
+    ]  # fmt: skip
+    lib.scaldpc_mc_qary_run_at.restype = lib.scaldpc_mc_qary_run_secret_at.restype = C.c_int
     for name in (
         "scaldpc_qary_create", "scaldpc_qary_min_sum_batch", "scaldpc_qary_special_create",
         "scaldpc_qary_special_min_sum_batch", "scaldpc_qary_min_sum_batch_soft", "scaldpc_qary_special_min_sum_batch_soft",
@@ -193,6 +210,28 @@ def measure_rmw_stream(nbytes, rows_per_wave=51, reps=50):
     out = C.c_double(0.0)
     check(load().scaldpc_measure_rmw_stream(int(nbytes), int(rows_per_wave), int(reps), C.byref(out)))
     return float(out.value)
+
+
+def trial_ids(ids):
+    """The trial list of an `_at` sweep as the library takes it: a contiguous int64 array.  Checked here, before any library
+    call: one-dimensional, not empty, of integer dtype (a float array is refused, not rounded), non-negative, within int64."""
+    import numpy as np
+
+    a = np.asarray(ids)
+    if a.ndim != 1:
+        raise ValueError(f"trial_ids must be one-dimensional, got shape {a.shape}")
+    if a.size == 0:
+        raise ValueError("trial_ids is empty")
+    if a.dtype == object and all(isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_)) for x in a):
+        pass  # Python integers beyond 64 bits: the range checks below name them
+    elif a.dtype.kind not in "iu":
+        raise ValueError(f"trial_ids must be of integer dtype, got {a.dtype} (trial indices are not rounded)")
+    # vectorised: the first offender, if any, is named (object arrays of Python integers compare element by element in C too)
+    for bad, why in ((a < 0, "is negative"), (a > 2**63 - 1, "does not fit int64")):
+        if bad.any():
+            i = int(np.argmax(bad))
+            raise ValueError(f"trial_ids[{i}] = {a[i]} {why}")
+    return np.ascontiguousarray(a, dtype=np.int64)
 
 
 def ptr(a):

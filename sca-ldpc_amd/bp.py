@@ -342,26 +342,16 @@ class BpDecoder:
         precision: "float32" (the default WHATEVER the decoder's own `precision`: the sweeps have always run the fp32 kernels)
         or "float64": the same trials decoded by the reference's float64 recursion (scaldpc_mc_fer_run_f64), product-sum only.
         Returns dict(success uint8 [runs], iters int32 [runs], errors uint8 [runs, n] or None)."""
-        f64 = _precision(precision, self._method) == "float64"
-        succ = np.empty(runs, dtype=np.uint8)
-        iters = np.empty(runs, dtype=np.int32)
-        err = np.empty((runs, self.n), dtype=np.uint8) if want_errors else None
-        if f64:
-            _lib.check(
-                self._lib.scaldpc_mc_fer_run_f64(
-                    self._h, int(first_trial), int(runs), int(seed), self.max_iter if max_iter is None else int(max_iter),
-                    _lib.F_EARLY_EXIT if early_exit else 0, None, _lib.ptr(succ), _lib.ptr(iters), _lib.ptr(err),
-                )  # fmt: skip
-            )
-            return {"success": succ, "iters": iters, "errors": err}
-        _lib.check(
-            self._lib.scaldpc_mc_fer_run(
-                self._h, int(first_trial), int(runs), int(seed), self.max_iter if max_iter is None else int(max_iter),
-                self._method, self.ms_scaling_factor, _lib.F_EARLY_EXIT if early_exit else 0, None, _lib.ptr(succ),
-                _lib.ptr(iters), _lib.ptr(err),
-            )  # fmt: skip
-        )
-        return {"success": succ, "iters": iters, "errors": err}
+        return _mc_fer(self, int(first_trial), int(runs), "", seed, max_iter, early_exit, want_errors, precision)
+
+    def mc_fer_run_at(self, trial_ids, seed, max_iter=None, early_exit=True, want_errors=False, precision="float32"):
+        """`mc_fer_run` on CHOSEN trials: slot i of the result is global trial `trial_ids[i]` (any order, duplicates allowed,
+        indices up to 2^63 - 1), row for row what `mc_fer_run` returns for that index on any range that contains it
+        (scaldpc_mc_fer_run_at / _at_f64).  trial_ids: a one-dimensional array of non-negative integers (ValueError
+        otherwise, before any library call; a float array is refused, not rounded).  Returns `mc_fer_run`'s dict with
+        len(trial_ids) rows."""
+        ids = _lib.trial_ids(trial_ids)
+        return _mc_fer(self, _lib.ptr(ids), len(ids), "_at", seed, max_iter, early_exit, want_errors, precision)
 
     def mc_hqc_run(self, runs, omega, eps, seed, first_trial=0, max_iter=None, early_exit=True, want_inputs=False,
                    want_stats=False, want_bits=False, precision="float32"):
@@ -403,6 +393,32 @@ class BpDecoder:
         )
         return {"success": succ, "iters": iters, "msg": msg, "y": y}
 
+    def mc_hqc_run_at(self, trial_ids, omega, eps, seed, max_iter=None, early_exit=True, want_inputs=False, want_stats=False,
+                      want_bits=False, precision="float32"):
+        """`mc_hqc_run` on CHOSEN trials: slot i of the result is global trial `trial_ids[i]`, row for row what `mc_hqc_run`
+        returns for that index on any range that contains it.  Always through the two-outcome table that IS this sweep
+        (scaldpc_mc_hqc_run_stats_at), as `mc_hqc_run(want_stats=True)` goes.  trial_ids: as `mc_fer_run_at`'s.  Returns
+        `mc_hqc_run`'s dict with len(trial_ids) rows (`stats` / `bits` with want_stats / want_bits)."""
+        ids = _lib.trial_ids(trial_ids)
+        _precision(precision, self._method)
+        eps = float(eps)
+        table = dict(weights=np.array([[eps, 1.0 - eps]] * 2), flips=np.array([1, 0], dtype=np.uint8),
+                     probs=np.array([eps, eps]), costs=None)
+        r = self.mc_hqc_run_soft_at(ids, omega, table, seed, max_iter=max_iter, early_exit=early_exit, want_inputs=want_inputs,
+                                    want_stats=want_stats, want_bits=want_bits, precision=precision)
+        return {k: r[k] for k in ("success", "iters", "msg", "y") + (("stats", "bits") if want_stats or want_bits else ())}
+
+    def mc_hqc_run_soft_at(self, trial_ids, omega, table, seed, max_iter=None, early_exit=True, want_inputs=False,
+                           want_stats=False, want_bits=False, precision="float32"):
+        """`mc_hqc_run_soft` on CHOSEN trials: slot i of the result is global trial `trial_ids[i]` (any order, duplicates
+        allowed, indices up to 2^63 - 1), row for row -- success, iters, flips, cost, msg, y, outcome, stats, bits -- what
+        `mc_hqc_run_soft` returns for that index on any range that contains it (scaldpc_mc_hqc_run_stats_at / _at_f64, whose
+        out_stats is optional).  trial_ids: a one-dimensional array of non-negative integers (ValueError otherwise, before
+        any library call; a float array is refused, not rounded).  Returns `mc_hqc_run_soft`'s dict with len(trial_ids) rows."""
+        ids = _lib.trial_ids(trial_ids)
+        return _mc_hqc_soft(self, _lib.ptr(ids), len(ids), True, omega, table, seed, max_iter, early_exit, want_inputs, want_stats,
+                                 want_bits, precision)
+
     def mc_hqc_run_soft(self, runs, omega, table, seed, first_trial=0, max_iter=None, early_exit=True, want_inputs=False,
                         want_stats=False, want_bits=False, precision="float32"):
         """`runs` synthetic hqc.decode() trials whose checks come from the oracles of simulate/hqc.py:782-871: every check
@@ -424,50 +440,8 @@ class BpDecoder:
         precision: "float32" (the default WHATEVER the decoder's own `precision`) or "float64": the same trials -- inputs,
         outcomes, flips and costs bit for bit -- decoded by the reference's float64 recursion (scaldpc_mc_hqc_run_stats_f64),
         product-sum only; the table's `probs` then go in as float64, unrounded."""
-        f64 = _precision(precision, self._method) == "float64"
-        w = np.ascontiguousarray(table["weights"], dtype=np.float64)
-        if w.ndim != 2 or w.shape[0] != 2:
-            raise ValueError(f"table['weights'] must be [2, K], got shape {w.shape}")
-        K = w.shape[1]
-        fl = np.asarray(table["flips"])
-        pr = np.ascontiguousarray(table["probs"], dtype=np.float64 if f64 else np.float32)
-        costs = table.get("costs")
-        if fl.shape != (K,) or pr.shape != (K,) or (costs is not None and np.shape(costs) != (K,)):
-            raise ValueError(f"table: flips, probs and costs must hold one entry per outcome (K = {K})")
-        # (the library validates the values; here only what a conversion to its types would hide)
-        cs = None if costs is None else np.asarray(costs)
-        for name, a, t in (("flips", fl, np.uint8), ("costs", cs, np.int32)):
-            if a is not None and not np.array_equal(a.astype(t), a):
-                raise ValueError(f"table['{name}'] = {a.tolist()} does not fit {np.dtype(t).name}")
-        fl = np.ascontiguousarray(fl, dtype=np.uint8)
-        cs = None if cs is None else np.ascontiguousarray(cs, dtype=np.int32)
-        succ = np.empty(runs, dtype=np.uint8)
-        iters = np.empty(runs, dtype=np.int32)
-        flips = np.empty(runs, dtype=np.int32)
-        cost = np.empty(runs, dtype=np.int32) if costs is not None else None
-        msg = np.empty((runs, self.n), dtype=np.uint8) if want_inputs else None
-        y = np.empty((runs, omega), dtype=np.int32) if want_inputs else None
-        outcome = np.empty((runs, self.m), dtype=np.uint8) if want_inputs else None
-        args = (
-            self._h, int(omega), _lib.ptr(w), _lib.ptr(fl), _lib.ptr(pr), _lib.ptr(cs), K,
-            int(first_trial), int(runs), int(seed), self.max_iter if max_iter is None else int(max_iter),
-            *(() if f64 else (self._method, self.ms_scaling_factor)),  # (no method, no alpha: product-sum only)
-            _lib.F_EARLY_EXIT if early_exit else 0, None, _lib.ptr(succ), _lib.ptr(iters),
-            _lib.ptr(msg), _lib.ptr(y), _lib.ptr(outcome), _lib.ptr(flips), _lib.ptr(cost),
-        )  # fmt: skip
-        res = {"success": succ, "iters": iters, "flips": flips, "cost": cost, "msg": msg, "y": y, "outcome": outcome}
-        if f64:  # one entry: out_stats is optional there
-            stats = np.empty((runs, len(HQC_STATS_COLUMNS)), dtype=np.int32) if want_stats or want_bits else None
-            bits = np.empty((runs, self.n), dtype=np.uint8) if want_bits else None
-            _lib.check(self._lib.scaldpc_mc_hqc_run_stats_f64(*args, _lib.ptr(stats), _lib.ptr(bits)))
-            return dict(res, stats=stats, bits=bits) if want_stats or want_bits else res
-        if want_stats or want_bits:
-            stats = np.empty((runs, len(HQC_STATS_COLUMNS)), dtype=np.int32)
-            bits = np.empty((runs, self.n), dtype=np.uint8) if want_bits else None
-            _lib.check(self._lib.scaldpc_mc_hqc_run_stats(*args, _lib.ptr(stats), _lib.ptr(bits)))
-            return dict(res, stats=stats, bits=bits)
-        _lib.check(self._lib.scaldpc_mc_hqc_run_soft(*args))
-        return res
+        return _mc_hqc_soft(self, int(first_trial), int(runs), False, omega, table, seed, max_iter, early_exit, want_inputs,
+                                 want_stats, want_bits, precision)
 
     def last_compacted(self):
         """Codewords the last early-exit call re-decoded in its compact second pass."""
@@ -530,6 +504,81 @@ class BpDecoder:
             self.close()
         except Exception:
             pass
+
+
+# The bodies the contiguous sweeps share with their `_at` forms (dec: the decoder).
+def _mc_fer(dec, trials, runs, at, seed, max_iter, early_exit, want_errors, precision):
+    # trials: the first index ("" = the contiguous entries) or the pointer to an int64 list ("_at" = the list entries).
+    f64 = _precision(precision, dec._method) == "float64"
+    succ = np.empty(runs, dtype=np.uint8)
+    iters = np.empty(runs, dtype=np.int32)
+    err = np.empty((runs, dec.n), dtype=np.uint8) if want_errors else None
+    if f64:
+        _lib.check(
+            getattr(dec._lib, f"scaldpc_mc_fer_run{at}_f64")(
+                dec._h, trials, runs, int(seed), dec.max_iter if max_iter is None else int(max_iter),
+                _lib.F_EARLY_EXIT if early_exit else 0, None, _lib.ptr(succ), _lib.ptr(iters), _lib.ptr(err),
+            )  # fmt: skip
+        )
+        return {"success": succ, "iters": iters, "errors": err}
+    _lib.check(
+        getattr(dec._lib, f"scaldpc_mc_fer_run{at}")(
+            dec._h, trials, runs, int(seed), dec.max_iter if max_iter is None else int(max_iter),
+            dec._method, dec.ms_scaling_factor, _lib.F_EARLY_EXIT if early_exit else 0, None, _lib.ptr(succ),
+            _lib.ptr(iters), _lib.ptr(err),
+        )  # fmt: skip
+    )
+    return {"success": succ, "iters": iters, "errors": err}
+
+
+def _mc_hqc_soft(dec, trials, runs, listed, omega, table, seed, max_iter, early_exit, want_inputs, want_stats, want_bits,
+                 precision):
+    # trials: the first index of a contiguous call, or (listed) the pointer to the int64 list of an _at call
+    f64 = _precision(precision, dec._method) == "float64"
+    w = np.ascontiguousarray(table["weights"], dtype=np.float64)
+    if w.ndim != 2 or w.shape[0] != 2:
+        raise ValueError(f"table['weights'] must be [2, K], got shape {w.shape}")
+    K = w.shape[1]
+    fl = np.asarray(table["flips"])
+    pr = np.ascontiguousarray(table["probs"], dtype=np.float64 if f64 else np.float32)
+    costs = table.get("costs")
+    if fl.shape != (K,) or pr.shape != (K,) or (costs is not None and np.shape(costs) != (K,)):
+        raise ValueError(f"table: flips, probs and costs must hold one entry per outcome (K = {K})")
+    # (the library validates the values; here only what a conversion to its types would hide)
+    cs = None if costs is None else np.asarray(costs)
+    for name, a, t in (("flips", fl, np.uint8), ("costs", cs, np.int32)):
+        if a is not None and not np.array_equal(a.astype(t), a):
+            raise ValueError(f"table['{name}'] = {a.tolist()} does not fit {np.dtype(t).name}")
+    fl = np.ascontiguousarray(fl, dtype=np.uint8)
+    cs = None if cs is None else np.ascontiguousarray(cs, dtype=np.int32)
+    succ = np.empty(runs, dtype=np.uint8)
+    iters = np.empty(runs, dtype=np.int32)
+    flips = np.empty(runs, dtype=np.int32)
+    cost = np.empty(runs, dtype=np.int32) if costs is not None else None
+    msg = np.empty((runs, dec.n), dtype=np.uint8) if want_inputs else None
+    y = np.empty((runs, omega), dtype=np.int32) if want_inputs else None
+    outcome = np.empty((runs, dec.m), dtype=np.uint8) if want_inputs else None
+    args = (
+        dec._h, int(omega), _lib.ptr(w), _lib.ptr(fl), _lib.ptr(pr), _lib.ptr(cs), K,
+        trials, runs, int(seed), dec.max_iter if max_iter is None else int(max_iter),
+        *(() if f64 else (dec._method, dec.ms_scaling_factor)),  # (no method, no alpha: product-sum only)
+        _lib.F_EARLY_EXIT if early_exit else 0, None, _lib.ptr(succ), _lib.ptr(iters),
+        _lib.ptr(msg), _lib.ptr(y), _lib.ptr(outcome), _lib.ptr(flips), _lib.ptr(cost),
+    )  # fmt: skip
+    res = {"success": succ, "iters": iters, "flips": flips, "cost": cost, "msg": msg, "y": y, "outcome": outcome}
+    if f64 or listed:  # one entry: out_stats is optional there
+        stats = np.empty((runs, len(HQC_STATS_COLUMNS)), dtype=np.int32) if want_stats or want_bits else None
+        bits = np.empty((runs, dec.n), dtype=np.uint8) if want_bits else None
+        entry = getattr(dec._lib, "scaldpc_mc_hqc_run_stats" + ("_at" if listed else "") + ("_f64" if f64 else ""))
+        _lib.check(entry(*args, _lib.ptr(stats), _lib.ptr(bits)))
+        return dict(res, stats=stats, bits=bits) if want_stats or want_bits else res
+    if want_stats or want_bits:
+        stats = np.empty((runs, len(HQC_STATS_COLUMNS)), dtype=np.int32)
+        bits = np.empty((runs, dec.n), dtype=np.uint8) if want_bits else None
+        _lib.check(dec._lib.scaldpc_mc_hqc_run_stats(*args, _lib.ptr(stats), _lib.ptr(bits)))
+        return dict(res, stats=stats, bits=bits)
+    _lib.check(dec._lib.scaldpc_mc_hqc_run_soft(*args))
+    return res
 
 
 bp_decoder = BpDecoder

@@ -31,6 +31,7 @@
 #include "scaldpc_common.h"
 #include "scaldpc_bp_sched.h"
 #include "scaldpc_mc_law.h"
+#include "scaldpc_trials.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -53,6 +54,16 @@ namespace scaldpc {
 int launch_mc_hqc_outcome64(const McHqcLaw64 &law, unsigned long long *synd, double *plane, int R, int batch, int T, long first,
                             unsigned k0, unsigned k1, int *acc_flips, int *acc_cost, uint8_t *out_outcome, hipStream_t s);
 int launch_gather_prior64(const double *src, int cols, const int *ids, double *dst, int T2, hipStream_t s);
+// the list forms of the Monte-Carlo generators (scaldpc_bp_mc_at.hip): slot b = trial ids[b], ids on the device
+int launch_mc_bernoulli_at(bool xor_into, unsigned long long *planes, int len, int batch, int T, const long long *ids, unsigned stream,
+                           unsigned k0, unsigned k1, const unsigned long long *thr, unsigned long long thr0, hipStream_t s);
+int launch_mc_hqc_secret_at(unsigned long long *planes, int n, int N, int omega, int batch, int T, const long long *ids, unsigned k0,
+                            unsigned k1, int *out_y, hipStream_t s);
+int launch_mc_hqc_outcome_at(const McHqcLaw &law, unsigned long long *synd, float *plane, int R, int batch, int T, const long long *ids,
+                             unsigned k0, unsigned k1, int *acc_flips, int *acc_cost, uint8_t *out_outcome, hipStream_t s);
+int launch_mc_hqc_outcome64_at(const McHqcLaw64 &law, unsigned long long *synd, double *plane, int R, int batch, int T,
+                               const long long *ids, unsigned k0, unsigned k1, int *acc_flips, int *acc_cost, uint8_t *out_outcome,
+                               hipStream_t s);
 }  // namespace scaldpc
 
 namespace {
@@ -170,6 +181,7 @@ struct scaldpc_bp : HandleStreams {
     Buf<int> d_mc_acc;            // scaldpc_mc_hqc_run_soft: [2][batch] checks reported wrong / oracle calls spent
     Buf<int> d_mc_stats;          // scaldpc_mc_hqc_run_stats: [batch][5] counters of k_mc_hqc_stats (host callers)
     Buf<uint8_t> d_mc_outcome;    // ... and the staging block of a host call's out_outcome
+    Buf<long long> d_trial_ids;   // the _at entries: the device copy of the call's trial list, [batch]
     // compact second pass over stragglers (early-exit runs)
     // (level k re-decodes the stragglers of level k-1 in dense tiles of their own; level 0 = the call's arrays)
     struct Level {
@@ -2485,14 +2497,23 @@ namespace {
 
 // (bernoulli_threshold: scaldpc_mc_law.h)
 
-int mc_common_args(scaldpc_bp *h, int64_t first_trial, int32_t batch, int32_t method, float alpha, uint32_t flags,
+// the trial source's own refusals (scaldpc_trials.h); a list is looked at once batch is known to be positive
+int mc_trials_arg(const TrialSrc &ts, int32_t batch)
+{
+    char why[96];
+    if (!trials_ok(ts, batch, why, sizeof why)) return fail(SCALDPC_EINVAL, "%s", why);
+    return 0;
+}
+
+int mc_common_args(scaldpc_bp *h, const TrialSrc &ts, int32_t batch, int32_t method, float alpha, uint32_t flags,
                    uint8_t *out_success)
 {
     if (!h || !out_success) return fail(SCALDPC_EINVAL, "NULL argument");
     if (flags & ~(SCALDPC_F_EARLY_EXIT | SCALDPC_F_DEVICE_IO))
         return fail(SCALDPC_EINVAL, "flags: SCALDPC_F_EARLY_EXIT and SCALDPC_F_DEVICE_IO are taken");
-    if (first_trial < 0) return fail(SCALDPC_EINVAL, "first_trial must not be negative");
+    if (!ts.listed) SC_TRY(mc_trials_arg(ts, batch));
     if (batch <= 0) return fail(SCALDPC_EINVAL, "batch must be positive (got %d)", batch);
+    if (ts.listed) SC_TRY(mc_trials_arg(ts, batch));
     if (method != SCALDPC_BP_PRODUCT_SUM && method != SCALDPC_BP_MIN_SUM)
         return fail(SCALDPC_EINVAL, "unknown bp method %d", method);
     if (!(alpha >= 0.0f)) return fail(SCALDPC_EINVAL, "ms_scaling_factor must be >= 0");
@@ -2548,13 +2569,37 @@ int mc_export_bits(scaldpc_bp *h, const u64 *planes, int batch, int T, bool dev_
     return 0;
 }
 
+// The generators, from either source of trials (DeviceTrials, stage_trials: scaldpc_trials.h): a contiguous call enqueues the
+// launch it always did.
+int draw_bernoulli(bool xor_into, u64 *planes, int len, int batch, int T, const DeviceTrials &tr, unsigned k0, unsigned k1, const u64 *thr,
+                   u64 thr0, hipStream_t s)
+{
+    if (tr.ids) return launch_mc_bernoulli_at(xor_into, planes, len, batch, T, tr.ids, 0u, k0, k1, thr, thr0, s);
+    const dim3 grid((len + 63) / 64, T);
+    if (xor_into)
+        hipLaunchKernelGGL(k_mc_bernoulli<true>, grid, dim3(256), 0, s, planes, len, batch, tr.first, 0u, k0, k1, thr, thr0);
+    else
+        hipLaunchKernelGGL(k_mc_bernoulli<false>, grid, dim3(256), 0, s, planes, len, batch, tr.first, 0u, k0, k1, thr, thr0);
+    LAUNCH_CHECK();
+    return 0;
+}
+int draw_hqc_secret(scaldpc_bp *h, int N, int omega, int batch, int T, const DeviceTrials &tr, unsigned k0, unsigned k1, int *dy,
+                    hipStream_t s)
+{
+    if (tr.ids) return launch_mc_hqc_secret_at(h->d_mc, h->n, N, omega, batch, T, tr.ids, k0, k1, dy, s);
+    hipLaunchKernelGGL(k_mc_hqc_secret, dim3(T), dim3(64), (size_t)omega * 64 * sizeof(int), s, h->d_mc, h->n, N, omega, batch,
+                       tr.first, k0, k1, dy);
+    LAUNCH_CHECK();
+    return 0;
+}
+
 }  // namespace
 
-int scaldpc_mc_fer_run(scaldpc_bp *h, int64_t first_trial, int32_t batch, uint64_t seed, int32_t max_iter_arg,
-                       int32_t method, float alpha, uint32_t flags, void *stream, uint8_t *out_success,
-                       int32_t *out_iters, uint8_t *out_error)
+// scaldpc_mc_fer_run and scaldpc_mc_fer_run_at: one body, the trials from either source
+static int mc_fer_run_body(scaldpc_bp *h, const TrialSrc &ts, int32_t batch, uint64_t seed, int32_t max_iter_arg, int32_t method,
+                           float alpha, uint32_t flags, void *stream, uint8_t *out_success, int32_t *out_iters, uint8_t *out_error)
 {
-    SC_TRY(mc_common_args(h, first_trial, batch, method, alpha, flags, out_success));
+    SC_TRY(mc_common_args(h, ts, batch, method, alpha, flags, out_success));
     std::lock_guard<std::mutex> lk(h->mu);
     SC_TRY(check_usable(h));
     DeviceGuard dg(h->device);
@@ -2569,11 +2614,11 @@ int scaldpc_mc_fer_run(scaldpc_bp *h, int64_t first_trial, int32_t batch, uint64
     SC_TRY(ensure_workspace(h, T, G, false, max_iter));
     SC_TRY(grow(h->d_mc, (size_t)T * h->n));
     SC_TRY(ensure_thresholds(h));
+    DeviceTrials tr;
+    SC_TRY(stage_trials(h->d_trial_ids, ts, batch, s, &tr));
     const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
     // error ~ Bernoulli(p_i) per position (decode.py:166-167), syndrome = H error (decode.py:168)
-    hipLaunchKernelGGL(k_mc_bernoulli<false>, dim3((h->n + 63) / 64, T), dim3(256), 0, s, h->d_mc, h->n, batch,
-                       (long)first_trial, 0u, k0, k1, (const u64 *)h->d_thr, 0ull);
-    LAUNCH_CHECK();
+    SC_TRY(draw_bernoulli(false, h->d_mc, h->n, batch, T, tr, k0, k1, (const u64 *)h->d_thr, 0ull, s));
     SC_TRY(launch_syndrome(h, h->d_mc, h->d_synd, T, s));
     if (out_error) SC_TRY(mc_export_bits(h, h->d_mc, batch, T, dev_io, s, out_error));
     SC_TRY(run_core(h, batch, T, G, max_iter, method, alpha, early, false, s));
@@ -2582,11 +2627,27 @@ int scaldpc_mc_fer_run(scaldpc_bp *h, int64_t first_trial, int32_t batch, uint64
     return settle.done();
 }
 
+int scaldpc_mc_fer_run(scaldpc_bp *h, int64_t first_trial, int32_t batch, uint64_t seed, int32_t max_iter_arg,
+                       int32_t method, float alpha, uint32_t flags, void *stream, uint8_t *out_success,
+                       int32_t *out_iters, uint8_t *out_error)
+{
+    return mc_fer_run_body(h, TrialSrc::range(first_trial), batch, seed, max_iter_arg, method, alpha, flags, stream, out_success,
+                           out_iters, out_error);
+}
+
+int scaldpc_mc_fer_run_at(scaldpc_bp *h, const int64_t *trial_ids, int32_t batch, uint64_t seed, int32_t max_iter_arg,
+                          int32_t method, float alpha, uint32_t flags, void *stream, uint8_t *out_success, int32_t *out_iters,
+                          uint8_t *out_error)
+{
+    return mc_fer_run_body(h, TrialSrc::list(trial_ids), batch, seed, max_iter_arg, method, alpha, flags, stream, out_success,
+                           out_iters, out_error);
+}
+
 int scaldpc_mc_hqc_run(scaldpc_bp *h, int32_t omega, double eps, int64_t first_trial, int32_t batch, uint64_t seed,
                        int32_t max_iter_arg, int32_t method, float alpha, uint32_t flags, void *stream,
                        uint8_t *out_success, int32_t *out_iters, uint8_t *out_msg, int32_t *out_y)
 {
-    SC_TRY(mc_common_args(h, first_trial, batch, method, alpha, flags, out_success));
+    SC_TRY(mc_common_args(h, TrialSrc::range(first_trial), batch, method, alpha, flags, out_success));
     std::lock_guard<std::mutex> lk(h->mu);
     SC_TRY(check_usable(h));
     DeviceGuard dg(h->device);
@@ -2646,12 +2707,12 @@ int scaldpc_mc_hqc_run(scaldpc_bp *h, int32_t omega, double eps, int64_t first_t
 // out_stats / out_bits: what scaldpc_mc_hqc_run_stats adds (k_mc_hqc_stats on the planes the decode leaves; the decoded word as
 // decode_batch_impl unpacks it).  Both null -- scaldpc_mc_hqc_run_soft -- and nothing is launched, cleared or allocated for them.
 static int mc_hqc_run_soft_body(scaldpc_bp *h, int32_t omega, const double *weights, const uint8_t *flips, const float *probs,
-                                const int32_t *costs, int32_t K, int64_t first_trial, int32_t batch, uint64_t seed,
+                                const int32_t *costs, int32_t K, const TrialSrc &ts, int32_t batch, uint64_t seed,
                                 int32_t max_iter_arg, int32_t method, float alpha, uint32_t flags, void *stream,
                                 uint8_t *out_success, int32_t *out_iters, uint8_t *out_msg, int32_t *out_y, uint8_t *out_outcome,
                                 int32_t *out_flips, int32_t *out_cost, int32_t *out_stats, uint8_t *out_bits)
 {
-    SC_TRY(mc_common_args(h, first_trial, batch, method, alpha, flags, out_success));
+    SC_TRY(mc_common_args(h, ts, batch, method, alpha, flags, out_success));
     std::lock_guard<std::mutex> lk(h->mu);
     SC_TRY(check_usable(h));
     McHqcLaw law;
@@ -2696,21 +2757,23 @@ static int mc_hqc_run_soft_body(scaldpc_bp *h, int32_t omega, const double *weig
         SC_TRY(grow(h->d_mc_stats, (size_t)5 * batch));
         dstats = h->d_mc_stats;
     }
+    DeviceTrials tr;
+    SC_TRY(stage_trials(h->d_trial_ids, ts, batch, s, &tr));
     const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
     // x = [y | 0]: omega distinct positions;  true bits c = Hin y = H x  (hqc.py:1253-1257)
     SC_HIP(hipMemsetAsync(h->d_mc, 0, sizeof(u64) * (size_t)T * h->n, s));
-    if (omega) {
-        hipLaunchKernelGGL(k_mc_hqc_secret, dim3(T), dim3(64), (size_t)omega * 64 * sizeof(int), s, h->d_mc, h->n, N, omega,
-                           batch, (long)first_trial, k0, k1, dy);
-        LAUNCH_CHECK();
-    }
+    if (omega) SC_TRY(draw_hqc_secret(h, N, omega, batch, T, tr, k0, k1, dy, s));
     SC_TRY(launch_syndrome(h, h->d_mc, h->d_synd, T, s));
     // each check: an outcome of the (wrapped) oracle given its true bit -> the reported bit and its certainty (hqc.py:782-871)
     int *const acc_flips = h->d_mc_acc, *const acc_cost = costs ? acc_flips + batch : nullptr;
     SC_HIP(hipMemsetAsync(acc_flips, 0, sizeof(int) * (size_t)2 * batch, s));
-    hipLaunchKernelGGL(k_mc_hqc_outcome, dim3((R + 63) / 64, T), dim3(256), 0, s, law, h->d_synd.get(), h->d_pprior.get(), R, batch,
-                       (long)first_trial, k0, k1, acc_flips, acc_cost, dout);
-    LAUNCH_CHECK();
+    if (tr.ids) {
+        SC_TRY(launch_mc_hqc_outcome_at(law, h->d_synd, h->d_pprior, R, batch, T, tr.ids, k0, k1, acc_flips, acc_cost, dout, s));
+    } else {
+        hipLaunchKernelGGL(k_mc_hqc_outcome, dim3((R + 63) / 64, T), dim3(256), 0, s, law, h->d_synd.get(), h->d_pprior.get(), R, batch,
+                           tr.first, k0, k1, acc_flips, acc_cost, dout);
+        LAUNCH_CHECK();
+    }
     // msg = [0]*N ++ reported (hqc.py:703-705); its syndrome under H = [Hin | I] is `reported` itself
     SC_HIP(hipMemsetAsync(h->d_recv, 0, sizeof(u64) * (size_t)T * h->n, s));
     SC_HIP(hipMemcpy2DAsync(h->d_recv + N, sizeof(u64) * h->n, h->d_synd, sizeof(u64) * h->m, sizeof(u64) * h->m, T,
@@ -2750,9 +2813,9 @@ int scaldpc_mc_hqc_run_soft(scaldpc_bp *h, int32_t omega, const double *weights,
                             uint8_t *out_success, int32_t *out_iters, uint8_t *out_msg, int32_t *out_y, uint8_t *out_outcome,
                             int32_t *out_flips, int32_t *out_cost)
 {
-    return mc_hqc_run_soft_body(h, omega, weights, flips, probs, costs, K, first_trial, batch, seed, max_iter_arg, method, alpha,
-                                flags, stream, out_success, out_iters, out_msg, out_y, out_outcome, out_flips, out_cost, nullptr,
-                                nullptr);
+    return mc_hqc_run_soft_body(h, omega, weights, flips, probs, costs, K, TrialSrc::range(first_trial), batch, seed, max_iter_arg,
+                                method, alpha, flags, stream, out_success, out_iters, out_msg, out_y, out_outcome, out_flips, out_cost,
+                                nullptr, nullptr);
 }
 
 int scaldpc_mc_hqc_run_stats(scaldpc_bp *h, int32_t omega, const double *weights, const uint8_t *flips, const float *probs,
@@ -2762,9 +2825,21 @@ int scaldpc_mc_hqc_run_stats(scaldpc_bp *h, int32_t omega, const double *weights
                              int32_t *out_flips, int32_t *out_cost, int32_t *out_stats, uint8_t *out_bits)
 {
     if (!out_stats) return fail(SCALDPC_EINVAL, "out_stats is NULL");
-    return mc_hqc_run_soft_body(h, omega, weights, flips, probs, costs, K, first_trial, batch, seed, max_iter_arg, method, alpha,
-                                flags, stream, out_success, out_iters, out_msg, out_y, out_outcome, out_flips, out_cost, out_stats,
-                                out_bits);
+    return mc_hqc_run_soft_body(h, omega, weights, flips, probs, costs, K, TrialSrc::range(first_trial), batch, seed, max_iter_arg,
+                                method, alpha, flags, stream, out_success, out_iters, out_msg, out_y, out_outcome, out_flips, out_cost,
+                                out_stats, out_bits);
+}
+
+// (out_stats may be NULL here, as in the float64 entry: with it NULL this is scaldpc_mc_hqc_run_soft on chosen trials)
+int scaldpc_mc_hqc_run_stats_at(scaldpc_bp *h, int32_t omega, const double *weights, const uint8_t *flips, const float *probs,
+                                const int32_t *costs, int32_t K, const int64_t *trial_ids, int32_t batch, uint64_t seed,
+                                int32_t max_iter_arg, int32_t method, float alpha, uint32_t flags, void *stream,
+                                uint8_t *out_success, int32_t *out_iters, uint8_t *out_msg, int32_t *out_y, uint8_t *out_outcome,
+                                int32_t *out_flips, int32_t *out_cost, int32_t *out_stats, uint8_t *out_bits)
+{
+    return mc_hqc_run_soft_body(h, omega, weights, flips, probs, costs, K, TrialSrc::list(trial_ids), batch, seed, max_iter_arg,
+                                method, alpha, flags, stream, out_success, out_iters, out_msg, out_y, out_outcome, out_flips, out_cost,
+                                out_stats, out_bits);
 }
 
 // ---------------------------------------------------------------------------
@@ -2776,12 +2851,13 @@ namespace {
 
 // The refusals the float64 sweeps share with the fp32 entries (there is no method and no alpha: the form is product-sum only).
 // The handle is looked at last, so that every one of them can be seen without a device.
-int mc_f64_args(const scaldpc_bp *h, int64_t first_trial, int32_t batch, uint32_t flags, const uint8_t *out_success)
+int mc_f64_args(const scaldpc_bp *h, const TrialSrc &ts, int32_t batch, uint32_t flags, const uint8_t *out_success)
 {
     if (flags & ~(SCALDPC_F_EARLY_EXIT | SCALDPC_F_DEVICE_IO))
         return fail(SCALDPC_EINVAL, "flags: SCALDPC_F_EARLY_EXIT and SCALDPC_F_DEVICE_IO are taken");
-    if (first_trial < 0) return fail(SCALDPC_EINVAL, "first_trial must not be negative");
+    if (!ts.listed) SC_TRY(mc_trials_arg(ts, batch));
     if (batch <= 0) return fail(SCALDPC_EINVAL, "batch must be positive (got %d)", batch);
+    if (ts.listed) SC_TRY(mc_trials_arg(ts, batch));
     if (!h || !out_success) return fail(SCALDPC_EINVAL, "NULL argument");
     return 0;
 }
@@ -2799,7 +2875,7 @@ int mc_run_f64(scaldpc_bp *h, int batch, int T, int G, int max_iter, bool early,
 // Both float64 HQC sweeps.  law = null: scaldpc_mc_hqc_run_f64 -- every check flipped with probability eps, the handle's shared
 // float64 priors.  Otherwise scaldpc_mc_hqc_run_stats_f64: every check draws an outcome of the table, which brings its ratio
 // into the plane h->d_pratio (k_mc_hqc_outcome64), and the five outputs from out_outcome on may be asked for.
-int mc_hqc_run_f64_body(scaldpc_bp *h, int32_t omega, const McHqcLaw64 *law, double eps, bool counted, int64_t first_trial,
+int mc_hqc_run_f64_body(scaldpc_bp *h, int32_t omega, const McHqcLaw64 *law, double eps, bool counted, const TrialSrc &ts,
                         int32_t batch, uint64_t seed, int32_t max_iter_arg, uint32_t flags, void *stream, uint8_t *out_success,
                         int32_t *out_iters, uint8_t *out_msg, int32_t *out_y, uint8_t *out_outcome, int32_t *out_flips,
                         int32_t *out_cost, int32_t *out_stats, uint8_t *out_bits)
@@ -2839,23 +2915,22 @@ int mc_hqc_run_f64_body(scaldpc_bp *h, int32_t omega, const McHqcLaw64 *law, dou
         SC_TRY(grow(h->d_mc_stats, (size_t)5 * batch));
         dstats = h->d_mc_stats;
     }
+    DeviceTrials tr;
+    SC_TRY(stage_trials(h->d_trial_ids, ts, batch, s, &tr));
     const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
     // x = [y | 0]: omega distinct positions;  true bits c = Hin y = H x  (hqc.py:1253-1257)
     SC_HIP(hipMemsetAsync(h->d_mc, 0, sizeof(u64) * (size_t)T * h->n, s));
-    if (omega) {
-        hipLaunchKernelGGL(k_mc_hqc_secret, dim3(T), dim3(64), (size_t)omega * 64 * sizeof(int), s, h->d_mc, h->n, N, omega,
-                           batch, (long)first_trial, k0, k1, dy);
-        LAUNCH_CHECK();
-    }
+    if (omega) SC_TRY(draw_hqc_secret(h, N, omega, batch, T, tr, k0, k1, dy, s));
     SC_TRY(launch_syndrome(h, h->d_mc, h->d_synd, T, s));
     int *const acc_flips = h->d_mc_acc, *const acc_cost = counted ? acc_flips + batch : nullptr;
     if (law) {  // an outcome per check: the reported bit and the ratio of its certainty
         SC_HIP(hipMemsetAsync(acc_flips, 0, sizeof(int) * (size_t)2 * batch, s));
-        SC_TRY(launch_mc_hqc_outcome64(*law, h->d_synd, h->d_pratio, R, batch, T, (long)first_trial, k0, k1, acc_flips, acc_cost, dout, s));
+        if (tr.ids)
+            SC_TRY(launch_mc_hqc_outcome64_at(*law, h->d_synd, h->d_pratio, R, batch, T, tr.ids, k0, k1, acc_flips, acc_cost, dout, s));
+        else
+            SC_TRY(launch_mc_hqc_outcome64(*law, h->d_synd, h->d_pratio, R, batch, T, tr.first, k0, k1, acc_flips, acc_cost, dout, s));
     } else {  // each oracle answer wrong with probability eps
-        hipLaunchKernelGGL(k_mc_bernoulli<true>, dim3((R + 63) / 64, T), dim3(256), 0, s, h->d_synd, R, batch, (long)first_trial,
-                           0u, k0, k1, (const u64 *)nullptr, bernoulli_threshold(eps));
-        LAUNCH_CHECK();
+        SC_TRY(draw_bernoulli(true, h->d_synd, R, batch, T, tr, k0, k1, (const u64 *)nullptr, bernoulli_threshold(eps), s));
     }
     // msg = [0]*N ++ reported (hqc.py:703-705); its syndrome under H = [Hin | I] is `reported` itself
     SC_HIP(hipMemsetAsync(h->d_recv, 0, sizeof(u64) * (size_t)T * h->n, s));
@@ -2891,10 +2966,11 @@ int mc_hqc_run_f64_body(scaldpc_bp *h, int32_t omega, const McHqcLaw64 *law, dou
 
 }  // namespace
 
-int scaldpc_mc_fer_run_f64(scaldpc_bp *h, int64_t first_trial, int32_t batch, uint64_t seed, int32_t max_iter_arg, uint32_t flags,
-                           void *stream, uint8_t *out_success, int32_t *out_iters, uint8_t *out_error)
+// scaldpc_mc_fer_run_f64 and scaldpc_mc_fer_run_at_f64: one body, the trials from either source
+static int mc_fer_run_f64_body(scaldpc_bp *h, const TrialSrc &ts, int32_t batch, uint64_t seed, int32_t max_iter_arg, uint32_t flags,
+                               void *stream, uint8_t *out_success, int32_t *out_iters, uint8_t *out_error)
 {
-    SC_TRY(mc_f64_args(h, first_trial, batch, flags, out_success));
+    SC_TRY(mc_f64_args(h, ts, batch, flags, out_success));
     std::lock_guard<std::mutex> lk(h->mu);
     SC_TRY(check_usable(h));
     DeviceGuard dg(h->device);
@@ -2909,11 +2985,11 @@ int scaldpc_mc_fer_run_f64(scaldpc_bp *h, int64_t first_trial, int32_t batch, ui
     SC_TRY(ref64_ensure(h, T, G, max_iter, false, 0));
     SC_TRY(grow(h->d_mc, (size_t)T * h->n));
     SC_TRY(ensure_thresholds(h));
+    DeviceTrials tr;
+    SC_TRY(stage_trials(h->d_trial_ids, ts, batch, s, &tr));
     const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
     // error ~ Bernoulli(p_i) per position (decode.py:166-167), syndrome = H error (decode.py:168)
-    hipLaunchKernelGGL(k_mc_bernoulli<false>, dim3((h->n + 63) / 64, T), dim3(256), 0, s, h->d_mc, h->n, batch,
-                       (long)first_trial, 0u, k0, k1, (const u64 *)h->d_thr, 0ull);
-    LAUNCH_CHECK();
+    SC_TRY(draw_bernoulli(false, h->d_mc, h->n, batch, T, tr, k0, k1, (const u64 *)h->d_thr, 0ull, s));
     SC_TRY(launch_syndrome(h, h->d_mc, h->d_synd, T, s));
     if (out_error) SC_TRY(mc_export_bits(h, h->d_mc, batch, T, dev_io, s, out_error));
     SC_TRY(mc_run_f64(h, batch, T, G, max_iter, early, nullptr, 0, s));
@@ -2922,15 +2998,47 @@ int scaldpc_mc_fer_run_f64(scaldpc_bp *h, int64_t first_trial, int32_t batch, ui
     return settle.done();
 }
 
+int scaldpc_mc_fer_run_f64(scaldpc_bp *h, int64_t first_trial, int32_t batch, uint64_t seed, int32_t max_iter_arg, uint32_t flags,
+                           void *stream, uint8_t *out_success, int32_t *out_iters, uint8_t *out_error)
+{
+    return mc_fer_run_f64_body(h, TrialSrc::range(first_trial), batch, seed, max_iter_arg, flags, stream, out_success, out_iters,
+                               out_error);
+}
+
+int scaldpc_mc_fer_run_at_f64(scaldpc_bp *h, const int64_t *trial_ids, int32_t batch, uint64_t seed, int32_t max_iter_arg,
+                              uint32_t flags, void *stream, uint8_t *out_success, int32_t *out_iters, uint8_t *out_error)
+{
+    return mc_fer_run_f64_body(h, TrialSrc::list(trial_ids), batch, seed, max_iter_arg, flags, stream, out_success, out_iters,
+                               out_error);
+}
+
 int scaldpc_mc_hqc_run_f64(scaldpc_bp *h, int32_t omega, double eps, int64_t first_trial, int32_t batch, uint64_t seed,
                            int32_t max_iter_arg, uint32_t flags, void *stream, uint8_t *out_success, int32_t *out_iters,
                            uint8_t *out_msg, int32_t *out_y)
 {
-    SC_TRY(mc_f64_args(h, first_trial, batch, flags, out_success));
+    SC_TRY(mc_f64_args(h, TrialSrc::range(first_trial), batch, flags, out_success));
     std::lock_guard<std::mutex> lk(h->mu);
     SC_TRY(check_usable(h));
-    return mc_hqc_run_f64_body(h, omega, nullptr, eps, false, first_trial, batch, seed, max_iter_arg, flags, stream, out_success,
+    return mc_hqc_run_f64_body(h, omega, nullptr, eps, false, TrialSrc::range(first_trial), batch, seed, max_iter_arg, flags, stream, out_success,
                                out_iters, out_msg, out_y, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+// scaldpc_mc_hqc_run_stats_f64 and scaldpc_mc_hqc_run_stats_at_f64: one body, the trials from either source
+static int mc_hqc_run_stats_f64_body(scaldpc_bp *h, int32_t omega, const double *weights, const uint8_t *flips, const double *probs,
+                                     const int32_t *costs, int32_t K, const TrialSrc &ts, int32_t batch, uint64_t seed,
+                                     int32_t max_iter_arg, uint32_t flags, void *stream, uint8_t *out_success, int32_t *out_iters,
+                                     uint8_t *out_msg, int32_t *out_y, uint8_t *out_outcome, int32_t *out_flips, int32_t *out_cost,
+                                     int32_t *out_stats, uint8_t *out_bits)
+{
+    SC_TRY(mc_f64_args(h, ts, batch, flags, out_success));
+    std::lock_guard<std::mutex> lk(h->mu);
+    SC_TRY(check_usable(h));
+    McHqcLaw64 law;
+    char why[160];
+    if (mc_hqc_law64(weights, flips, probs, costs, K, h->m, out_cost != nullptr, &law, why, sizeof why))
+        return fail(SCALDPC_EINVAL, "%s", why);
+    return mc_hqc_run_f64_body(h, omega, &law, 0.0, costs != nullptr, ts, batch, seed, max_iter_arg, flags, stream,
+                               out_success, out_iters, out_msg, out_y, out_outcome, out_flips, out_cost, out_stats, out_bits);
 }
 
 int scaldpc_mc_hqc_run_stats_f64(scaldpc_bp *h, int32_t omega, const double *weights, const uint8_t *flips, const double *probs,
@@ -2939,15 +3047,20 @@ int scaldpc_mc_hqc_run_stats_f64(scaldpc_bp *h, int32_t omega, const double *wei
                                  uint8_t *out_msg, int32_t *out_y, uint8_t *out_outcome, int32_t *out_flips, int32_t *out_cost,
                                  int32_t *out_stats, uint8_t *out_bits)
 {
-    SC_TRY(mc_f64_args(h, first_trial, batch, flags, out_success));
-    std::lock_guard<std::mutex> lk(h->mu);
-    SC_TRY(check_usable(h));
-    McHqcLaw64 law;
-    char why[160];
-    if (mc_hqc_law64(weights, flips, probs, costs, K, h->m, out_cost != nullptr, &law, why, sizeof why))
-        return fail(SCALDPC_EINVAL, "%s", why);
-    return mc_hqc_run_f64_body(h, omega, &law, 0.0, costs != nullptr, first_trial, batch, seed, max_iter_arg, flags, stream,
-                               out_success, out_iters, out_msg, out_y, out_outcome, out_flips, out_cost, out_stats, out_bits);
+    return mc_hqc_run_stats_f64_body(h, omega, weights, flips, probs, costs, K, TrialSrc::range(first_trial), batch, seed, max_iter_arg,
+                                     flags, stream, out_success, out_iters, out_msg, out_y, out_outcome, out_flips, out_cost, out_stats,
+                                     out_bits);
+}
+
+int scaldpc_mc_hqc_run_stats_at_f64(scaldpc_bp *h, int32_t omega, const double *weights, const uint8_t *flips, const double *probs,
+                                    const int32_t *costs, int32_t K, const int64_t *trial_ids, int32_t batch, uint64_t seed,
+                                    int32_t max_iter_arg, uint32_t flags, void *stream, uint8_t *out_success, int32_t *out_iters,
+                                    uint8_t *out_msg, int32_t *out_y, uint8_t *out_outcome, int32_t *out_flips, int32_t *out_cost,
+                                    int32_t *out_stats, uint8_t *out_bits)
+{
+    return mc_hqc_run_stats_f64_body(h, omega, weights, flips, probs, costs, K, TrialSrc::list(trial_ids), batch, seed, max_iter_arg,
+                                     flags, stream, out_success, out_iters, out_msg, out_y, out_outcome, out_flips, out_cost, out_stats,
+                                     out_bits);
 }
 
 int scaldpc_bp_configure(scaldpc_bp *h, const char *key, const char *value)

@@ -5,6 +5,7 @@
 #include "scaldpc_logf.h"  // glibc's logf on the device (k_soft_convert)
 #include "scaldpc_mc_law.h"  // McHqcLaw: the outcome table k_mc_hqc_outcome takes by value
 #include "scaldpc_philox.h"
+#include "scaldpc_mc_draw.h"  // the bodies of the K6 generators, over the source of the trial index
 #include "scaldpc_rec_pack.h"  // row words of the record form's variable pass
 #include "scaldpc_rec_trim.h"  // rows of the record form's check pass that end in a constant edge
 #include <type_traits>
@@ -1889,6 +1890,8 @@ __global__ __launch_bounds__(256) void k_apply_pairs(int *__restrict__ dst, cons
 //                     accepted if not chosen before, until omega are accepted
 // ---------------------------------------------------------------------------
 // (U4, philox4x32_10: scaldpc_philox.h, shared with the q-ary trial generator)
+// The three generators below are written once, over the source of the trial index (scaldpc_mc_draw.h): these kernels are the
+// contiguous form, slot b = trial first + b; the list form of the _at entries (slot b = trial ids[b]) is scaldpc_bp_mc_at.hip's.
 
 // planes[t][x] (bit c) = [stream-`stream` word x of trial first + 64 t + c  <  thr_x]; XOR_INTO flips
 // an existing plane instead.  wave = (tile, 16 consecutive x).  grid (ceil(len/64), T), block 256.
@@ -1897,32 +1900,7 @@ __global__ __launch_bounds__(256) void k_mc_bernoulli(u64 *__restrict__ planes, 
                                                       unsigned stream, unsigned k0, unsigned k1,
                                                       const u64 *__restrict__ thr, u64 thr0)
 {
-    const int lane = threadIdx.x & 63;
-    const int x0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 16;
-    const int t = blockIdx.y;
-    if (x0 >= len) return;
-    const long b = (long)t * TW + lane;
-    const u64 trial = (u64)(first + b);
-    for (int q = 0; q < 4; q++) {
-        const int xb = x0 + 4 * q;
-        if (xb >= len) break;
-        const U4 r = philox4x32_10(U4{(unsigned)(xb >> 2), stream, (unsigned)trial, (unsigned)(trial >> 32)}, k0, k1);
-        const unsigned w[4] = {r.x, r.y, r.z, r.w};
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int x = xb + j;
-            if (x < len) {
-                const u64 th = thr ? thr[x] : thr0;
-                const u64 m = __ballot(b < batch && (u64)w[j] < th);
-                if (lane == 0) {
-                    if (XOR_INTO)
-                        planes[(size_t)t * len + x] ^= m;
-                    else
-                        planes[(size_t)t * len + x] = m;
-                }
-            }
-        }
-    }
+    mc_bernoulli_body<XOR_INTO>(planes, len, batch, TrialRange{first}, stream, k0, k1, thr, thr0);
 }
 
 // HQC secret: omega distinct positions per trial, set as bits of planes[t][pos] (pos < N; the
@@ -1932,28 +1910,7 @@ __global__ __launch_bounds__(64) void k_mc_hqc_secret(u64 *__restrict__ planes, 
                                                       long first, unsigned k0, unsigned k1, int *__restrict__ out_y)
 {
     extern __shared__ int chosen[];  // [omega][64]
-    const int lane = threadIdx.x, t = blockIdx.x;
-    const long b = (long)t * TW + lane;
-    if (b >= batch) return;
-    const u64 trial = (u64)(first + b);
-    unsigned j = 0;
-    U4 r{};
-    for (int i = 0; i < omega; i++) {
-        for (;;) {
-            if ((j & 3) == 0) r = philox4x32_10(U4{j >> 2, 1u, (unsigned)trial, (unsigned)(trial >> 32)}, k0, k1);
-            const unsigned w = (j & 3) == 0 ? r.x : (j & 3) == 1 ? r.y : (j & 3) == 2 ? r.z : r.w;
-            j++;
-            const int pos = (int)__umulhi(w, (unsigned)N);
-            bool dup = false;
-            for (int q = 0; q < i; q++) dup |= chosen[q * 64 + lane] == pos;
-            if (!dup) {
-                chosen[i * 64 + lane] = pos;
-                atomicOr(planes + (size_t)t * n + pos, 1ull << lane);
-                if (out_y) out_y[(size_t)b * omega + i] = pos;
-                break;
-            }
-        }
-    }
+    mc_hqc_secret_body(chosen, planes, n, N, omega, batch, TrialRange{first}, k0, k1, out_y);
 }
 
 // The oracle's answers of scaldpc_mc_hqc_run_soft: every check draws an OUTCOME conditional on its true bit, and the outcome
@@ -1973,48 +1930,7 @@ __global__ __launch_bounds__(256) void k_mc_hqc_outcome(McHqcLaw law, u64 *synd,
                                                         long first, unsigned k0, unsigned k1, int *__restrict__ acc_flips,
                                                         int *__restrict__ acc_cost, uint8_t *__restrict__ out_outcome)
 {
-    const int lane = threadIdx.x & 63;
-    const int x0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 16;
-    const int t = blockIdx.y;
-    if (x0 >= R) return;
-    const long b = (long)t * TW + lane;
-    const bool live = b < batch;
-    const u64 trial = (u64)(first + b);
-    int nflips = 0, ncost = 0;
-    for (int q = 0; q < 4; q++) {
-        const int xb = x0 + 4 * q;
-        if (xb >= R) break;
-        const U4 r = philox4x32_10(U4{(unsigned)(xb >> 2), 0u, (unsigned)trial, (unsigned)(trial >> 32)}, k0, k1);
-        const unsigned w[4] = {r.x, r.y, r.z, r.w};
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int x = xb + j;
-            if (x < R) {
-                const size_t row = (size_t)t * R + x;
-                const unsigned c = (unsigned)((synd[row] >> lane) & 1);
-                const u64 word = w[j];
-                int lv = 0, cost = law.cost[0];
-                float llr = law.llr[0];
-                for (int k = 0; k + 1 < law.K; k++) {
-                    const bool past = word >= (c ? law.t[1][k] : law.t[0][k]);
-                    lv += past;
-                    llr = past ? law.llr[k + 1] : llr;
-                    cost = past ? law.cost[k + 1] : cost;
-                }
-                const unsigned flip = live ? (law.flips >> lv) & 1u : 0u;
-                const u64 m = __ballot(live && (c ^ flip));
-                if (lane == 0) synd[row] = m;
-                plane[row * TW + lane] = live ? llr : 0.0f;
-                nflips += (int)flip;
-                ncost += live ? cost : 0;
-                if (out_outcome && live) out_outcome[(size_t)b * R + x] = (uint8_t)lv;
-            }
-        }
-    }
-    if (live) {
-        atomicAdd(acc_flips + b, nflips);
-        if (acc_cost) atomicAdd(acc_cost + b, ncost);
-    }
+    mc_hqc_outcome_body(law, synd, plane, R, batch, TrialRange{first}, k0, k1, acc_flips, acc_cost, out_outcome);
 }
 
 // diff[t] |= OR_v (a[t][v] ^ b[t][v]) over v < nv (plane rows of stride n).  grid (ceil(nv/256), T).

@@ -9,6 +9,7 @@
 #include "scaldpc_common.h"
 #include "scaldpc_mc_law.h"  // McHqcLaw64: the outcome table k_mc_hqc_outcome64 takes by value
 #include "scaldpc_philox.h"
+#include "scaldpc_mc_draw.h"  // mc_hqc_outcome_body: one text for k_mc_hqc_outcome, this kernel and their list forms
 
 typedef unsigned long long u64;
 
@@ -22,53 +23,13 @@ constexpr int TW = 64;  // codewords per tile = one wavefront of lanes (scaldpc_
 // double).  The lanes of a ragged last tile get bit 0 and ratio 0, as k_ratio64_convert leaves them, and report nothing.
 //   synd   u64 [tile][R]  in: the true bits c = Hin y; out: the reported bits c ^ flips[outcome]
 //   acc_flips / acc_cost  int [batch], zeroed by the caller (acc_cost may be null); out_outcome  uint8 [batch][R] or null
-// grid (ceil(R/64), T), block 256: wave = (tile, 16 consecutive checks), lane = trial.
+// grid (ceil(R/64), T), block 256: wave = (tile, 16 consecutive checks), lane = trial.  (The contiguous form, slot b = trial
+// first + b; the list form of scaldpc_mc_hqc_run_stats_at_f64 is scaldpc_bp_mc_at.hip's.)
 __global__ __launch_bounds__(256) void k_mc_hqc_outcome64(McHqcLaw64 law, u64 *synd, double *__restrict__ plane, int R, int batch,
                                                           long first, unsigned k0, unsigned k1, int *__restrict__ acc_flips,
                                                           int *__restrict__ acc_cost, uint8_t *__restrict__ out_outcome)
 {
-    const int lane = threadIdx.x & 63;
-    const int x0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 16;
-    const int t = blockIdx.y;
-    if (x0 >= R) return;
-    const long b = (long)t * TW + lane;
-    const bool live = b < batch;
-    const u64 trial = (u64)(first + b);
-    int nflips = 0, ncost = 0;
-    for (int q = 0; q < 4; q++) {
-        const int xb = x0 + 4 * q;
-        if (xb >= R) break;
-        const U4 r = philox4x32_10(U4{(unsigned)(xb >> 2), 0u, (unsigned)trial, (unsigned)(trial >> 32)}, k0, k1);
-        const unsigned w[4] = {r.x, r.y, r.z, r.w};
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int x = xb + j;
-            if (x < R) {
-                const size_t row = (size_t)t * R + x;
-                const unsigned c = (unsigned)((synd[row] >> lane) & 1);
-                const u64 word = w[j];
-                int lv = 0, cost = law.cost[0];
-                double ratio = law.ratio[0];
-                for (int k = 0; k + 1 < law.K; k++) {
-                    const bool past = word >= (c ? law.t[1][k] : law.t[0][k]);
-                    lv += past;
-                    ratio = past ? law.ratio[k + 1] : ratio;
-                    cost = past ? law.cost[k + 1] : cost;
-                }
-                const unsigned flip = live ? (law.flips >> lv) & 1u : 0u;
-                const u64 m = __ballot(live && (c ^ flip));
-                if (lane == 0) synd[row] = m;
-                plane[row * TW + lane] = live ? ratio : 0.0;
-                nflips += (int)flip;
-                ncost += live ? cost : 0;
-                if (out_outcome && live) out_outcome[(size_t)b * R + x] = (uint8_t)lv;
-            }
-        }
-    }
-    if (live) {
-        atomicAdd(acc_flips + b, nflips);
-        if (acc_cost) atomicAdd(acc_cost + b, ncost);
-    }
+    mc_hqc_outcome_body(law, synd, plane, R, batch, scaldpc::TrialRange{first}, k0, k1, acc_flips, acc_cost, out_outcome);
 }
 
 // k_gather_prior for the ratio plane (double [tile][cols][64]): dst[t2][j][c2] = src[id>>6][j][id&63], id = ids[64 t2 + c2];

@@ -26,6 +26,7 @@
 #include "scaldpc_logf.h"
 #include "scaldpc_mc_law.h"
 #include "scaldpc_qary_plan.h"
+#include "scaldpc_trials.h"
 
 #include <cmath>
 #include <cstring>
@@ -40,6 +41,7 @@ typedef unsigned long long u64;
 #include "scaldpc_qary_soft.h"
 #include "scaldpc_qary_mc.h"
 #include "scaldpc_qary_secret.h"
+#include "scaldpc_qary_mc_at.h"  // last: the list forms of the three generators
 
 namespace {
 
@@ -712,6 +714,7 @@ struct scaldpc_qary : QaryStreams, QaryShape {
     // [batch][N]; the law's device form (pack_secret_law) with its host side, kept like the tables
     Buf<signed char> d_mc_sec, d_mc_sec_out;
     Buf<unsigned> d_mc_law;
+    Buf<long long> d_trial_ids;  // the _at entries: the device copy of the call's trial list, [batch]
     std::vector<unsigned> mc_law;
     bool mc_law_ok = false;
     // one 16-byte status block per handle, zeroed by ONE fill and read back by ONE copy per call: [0] = the bitwise complement of
@@ -1265,13 +1268,23 @@ int mc_rows(scaldpc_qary *h, const QaryCall &c, const McTables &t, float **rows)
 // The first step of a Monte-Carlo call: the tables' LLR rows (mc_rows), then
 // k_q_mc_draw leaves in d_llr and d_msg what stage_and_convert leaves there for the materialised input (fused or not: k_q_init
 // copies the same numbers), and the drawn levels in d_mc_lvl.
-int mc_draw(scaldpc_qary *h, const QaryCall &c, const McTables &t, const McLaw &law, long first_trial, uint64_t seed)
+int mc_draw(scaldpc_qary *h, const QaryCall &c, const McTables &t, const McLaw &law, const TrialSrc &ts, uint64_t seed)
 {
     float *d_rows = nullptr;
     SC_TRY(mc_rows(h, c, t, &d_rows));
-    hipLaunchKernelGGL(k_q_mc_draw, dim3((h->N + 3) / 4, c.Bp / 64), dim3(256), (size_t)t.floats() * sizeof(float), c.s, law, d_rows, t.Q[0],
-                       t.Q[1], c.BV, h->N, c.batch, c.Bp, first_trial, (unsigned)seed, (unsigned)(seed >> 32), h->d_col_ptr,
-                       h->d_csc_edge, h->d_edge_h, h->d_llr, h->d_msg, h->W, h->d_mc_lvl);
+    DeviceTrials tr;  // (scaldpc_trials.h)
+    SC_TRY(stage_trials(h->d_trial_ids, ts, c.batch, c.s, &tr));
+    const long long *const ids = tr.ids;
+    const dim3 grid((h->N + 3) / 4, c.Bp / 64);
+    const size_t lds = (size_t)t.floats() * sizeof(float);
+    if (ids)
+        hipLaunchKernelGGL(k_q_mc_draw_at, grid, dim3(256), lds, c.s, law, d_rows, t.Q[0], t.Q[1], c.BV, h->N, c.batch, c.Bp, ids,
+                           (unsigned)seed, (unsigned)(seed >> 32), h->d_col_ptr, h->d_csc_edge, h->d_edge_h, h->d_llr, h->d_msg, h->W,
+                           h->d_mc_lvl);
+    else
+        hipLaunchKernelGGL(k_q_mc_draw, grid, dim3(256), lds, c.s, law, d_rows, t.Q[0], t.Q[1], c.BV, h->N, c.batch, c.Bp, tr.first,
+                           (unsigned)seed, (unsigned)(seed >> 32), h->d_col_ptr, h->d_csc_edge, h->d_edge_h, h->d_llr, h->d_msg, h->W,
+                           h->d_mc_lvl);
     SC_HIP(hipGetLastError());
     return 0;
 }
@@ -1380,16 +1393,31 @@ int secret_ensure(scaldpc_qary *h, const QaryCall &c, const McTables &t, const M
 // The first step: the tables' LLR rows (mc_rows) and the law (copied unless it is the last finished call's, word for word), then
 // the secret and the outcomes of the coefficient variables, then the row sums and theirs.
 int secret_draw(scaldpc_qary *h, const QaryCall &c, const McTables &t, const std::vector<unsigned> &law, const SecretLawAt &at,
-                long first_trial, uint64_t seed)
+                const TrialSrc &ts, uint64_t seed)
 {
     float *d_rows = nullptr;
     SC_TRY(mc_rows(h, c, t, &d_rows));
+    DeviceTrials tr;
+    SC_TRY(stage_trials(h->d_trial_ids, ts, c.batch, c.s, &tr));
+    const long long *const ids = tr.ids;
+    const long first_trial = tr.first;
     if (!(h->mc_law_ok && h->mc_law == law)) {
         h->mc_law_ok = false;
         h->mc_law = law;
         SC_HIP(hipMemcpyAsync(h->d_mc_law, h->mc_law.data(), at.words * sizeof(unsigned), hipMemcpyHostToDevice, c.s));
     }
     const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
+    if (ids) {
+        hipLaunchKernelGGL(k_q_mc_secret_draw_at, dim3((c.BV + 3) / 4, c.Bp / 64), dim3(256), mc_secret_lds_bytes(t.K[0], t.Q[0]), c.s,
+                           (const u64 *)h->d_mc_law.get(), h->d_mc_law + at.tab[0], d_rows, t.K[0], t.Q[0], c.BV, c.batch, c.Bp, ids, k0,
+                           k1, h->d_col_ptr, h->d_csc_edge, h->d_edge_h, h->d_llr, h->d_msg, h->W, h->d_mc_lvl, h->d_mc_sec);
+        SC_HIP(hipGetLastError());
+        hipLaunchKernelGGL(k_q_mc_secret_sums_at, dim3((h->R + 3) / 4, c.Bp / 64), dim3(256), mc_secret_lds_bytes(t.K[1], t.Q[1]), c.s,
+                           h->d_mc_law + at.tab[1], d_rows + t.K[0] * t.Q[0], t.K[1], t.Q[1], t.Q[0], c.BV, h->R, c.batch, c.Bp, ids, k0,
+                           k1, h->d_row_ptr, h->d_edge_var, h->d_edge_h, h->d_llr, h->d_msg, h->W, h->d_mc_lvl, h->d_mc_sec);
+        SC_HIP(hipGetLastError());
+        return 0;
+    }
     hipLaunchKernelGGL(k_q_mc_secret_draw, dim3((c.BV + 3) / 4, c.Bp / 64), dim3(256), mc_secret_lds_bytes(t.K[0], t.Q[0]), c.s,
                        (const u64 *)h->d_mc_law.get(), h->d_mc_law + at.tab[0], d_rows, t.K[0], t.Q[0], c.BV, c.batch, c.Bp, first_trial, k0,
                        k1, h->d_col_ptr, h->d_csc_edge, h->d_edge_h, h->d_llr, h->d_msg, h->W, h->d_mc_lvl, h->d_mc_sec);
@@ -1557,16 +1585,18 @@ int scaldpc_qary_special_min_sum_batch_soft(scaldpc_qary *h, const float *pmf_b,
     return qary_run(h, pmf_b, pmf_sum, batch, flags, stream, out, SoftOut{out_cost_b, out_cost_sum, out_margin, out_unmet});
 }
 
-int scaldpc_mc_qary_run(scaldpc_qary *h, const float *levels_b, const double *weights_b, int32_t k_b, const float *levels_s,
-                        const double *weights_s, int32_t k_s, int64_t first_trial, int32_t batch, uint64_t seed, uint32_t flags,
-                        void *stream, uint8_t *out_success, int32_t *out_errs, int32_t *out_wrong, uint8_t *out_levels,
-                        int8_t *out_symbols)
+// scaldpc_mc_qary_run and scaldpc_mc_qary_run_at: one body, the trials from either source
+static int mc_qary_run_body(scaldpc_qary *h, const float *levels_b, const double *weights_b, int32_t k_b, const float *levels_s,
+                            const double *weights_s, int32_t k_s, const TrialSrc &ts, int32_t batch, uint64_t seed, uint32_t flags,
+                            void *stream, uint8_t *out_success, int32_t *out_errs, int32_t *out_wrong, uint8_t *out_levels,
+                            int8_t *out_symbols)
 {
     if (!h || !levels_b || !weights_b || !out_success) return fail(SCALDPC_EINVAL, "NULL argument");
     if (h->special && (!levels_s || !weights_s)) return fail(SCALDPC_EINVAL, "a special decoder needs levels_s and weights_s");
     if (!h->special && (levels_s || weights_s || k_s)) return fail(SCALDPC_EINVAL, "levels_s / weights_s / k_s: this handle is not a special decoder");
     if (batch <= 0) return fail(SCALDPC_EINVAL, "batch must be positive");
-    if (first_trial < 0) return fail(SCALDPC_EINVAL, "first_trial must not be negative");
+    char why[96];
+    if (!trials_ok(ts, batch, why, sizeof why)) return fail(SCALDPC_EINVAL, "%s", why);
     if (flags & SCALDPC_F_ASYNC) return fail(SCALDPC_EINVAL, "SCALDPC_F_ASYNC: a q-ary Monte-Carlo call is synchronous");
     McTables t;
     t.levels[0] = levels_b; t.weights[0] = weights_b; t.K[0] = k_b; t.Q[0] = h->Q;
@@ -1576,14 +1606,33 @@ int scaldpc_mc_qary_run(scaldpc_qary *h, const float *levels_b, const double *we
     const McOut o = {out_success, out_errs, out_wrong, out_levels, out_symbols};
     return qary_steps(
         h, batch, flags, stream, SoftOut(), [&](QaryCall &c) { return mc_ensure(h, c, t, o); },
-        [&](QaryCall &c) { return mc_draw(h, c, t, law, (long)first_trial, seed); },
+        [&](QaryCall &c) { return mc_draw(h, c, t, law, ts, seed); },
         [&](QaryCall &c, u64(&status)[2]) { return mc_emit(h, c, law, o, status); });
 }
 
-int scaldpc_mc_qary_run_secret(scaldpc_qary *h, const double *prior_b, const float *levels_b, const double *weights_b, int32_t k_b,
-                               const float *levels_s, const double *weights_s, int32_t k_s, int64_t first_trial, int32_t batch,
-                               uint64_t seed, uint32_t flags, void *stream, uint8_t *out_success, int32_t *out_wrong,
-                               int32_t *out_channel_wrong, int8_t *out_secret, uint8_t *out_levels, int8_t *out_symbols)
+int scaldpc_mc_qary_run(scaldpc_qary *h, const float *levels_b, const double *weights_b, int32_t k_b, const float *levels_s,
+                        const double *weights_s, int32_t k_s, int64_t first_trial, int32_t batch, uint64_t seed, uint32_t flags,
+                        void *stream, uint8_t *out_success, int32_t *out_errs, int32_t *out_wrong, uint8_t *out_levels,
+                        int8_t *out_symbols)
+{
+    return mc_qary_run_body(h, levels_b, weights_b, k_b, levels_s, weights_s, k_s, TrialSrc::range(first_trial), batch, seed, flags, stream,
+                            out_success, out_errs, out_wrong, out_levels, out_symbols);
+}
+
+int scaldpc_mc_qary_run_at(scaldpc_qary *h, const float *levels_b, const double *weights_b, int32_t k_b, const float *levels_s,
+                           const double *weights_s, int32_t k_s, const int64_t *trial_ids, int32_t batch, uint64_t seed, uint32_t flags,
+                           void *stream, uint8_t *out_success, int32_t *out_errs, int32_t *out_wrong, uint8_t *out_levels,
+                           int8_t *out_symbols)
+{
+    return mc_qary_run_body(h, levels_b, weights_b, k_b, levels_s, weights_s, k_s, TrialSrc::list(trial_ids), batch, seed, flags, stream,
+                            out_success, out_errs, out_wrong, out_levels, out_symbols);
+}
+
+// scaldpc_mc_qary_run_secret and scaldpc_mc_qary_run_secret_at: one body, the trials from either source
+static int mc_qary_run_secret_body(scaldpc_qary *h, const double *prior_b, const float *levels_b, const double *weights_b, int32_t k_b,
+                                   const float *levels_s, const double *weights_s, int32_t k_s, const TrialSrc &ts, int32_t batch,
+                                   uint64_t seed, uint32_t flags, void *stream, uint8_t *out_success, int32_t *out_wrong,
+                                   int32_t *out_channel_wrong, int8_t *out_secret, uint8_t *out_levels, int8_t *out_symbols)
 {
     if (!h || !out_success) return fail(SCALDPC_EINVAL, "NULL argument");
     if (!h->special)
@@ -1593,7 +1642,9 @@ int scaldpc_mc_qary_run_secret(scaldpc_qary *h, const double *prior_b, const flo
     t.levels[1] = levels_s; t.weights[1] = weights_s; t.K[1] = k_s; t.Q[1] = h->QS;
     McSecretLaw law;
     char why[200];
-    if (const int kind = mc_qary_secret_law(prior_b, t.levels, t.weights, t.K, t.Q, (long long)first_trial, batch, (flags & SCALDPC_F_ASYNC) != 0,
+    // (a list's own refusals come first: mc_qary_secret_law knows a first index only, and is given a legal one)
+    if (ts.listed && !trials_ok(ts, batch, why, sizeof why)) return fail(SCALDPC_EINVAL, "%s", why);
+    if (const int kind = mc_qary_secret_law(prior_b, t.levels, t.weights, t.K, t.Q, (long long)ts.first, batch, (flags & SCALDPC_F_ASYNC) != 0,
                                             &law, why, sizeof why))
         return fail(kind == MC_SECRET_EPMF ? SCALDPC_EPMF : kind == MC_SECRET_EDEGREE ? SCALDPC_EDEGREE : SCALDPC_EINVAL, "%s", why);
     std::vector<unsigned> words;
@@ -1601,8 +1652,26 @@ int scaldpc_mc_qary_run_secret(scaldpc_qary *h, const double *prior_b, const flo
     const McSecretOut o = {out_success, out_wrong, out_channel_wrong, out_secret, out_levels, out_symbols};
     return qary_steps(
         h, batch, flags, stream, SoftOut(), [&](QaryCall &c) { return secret_ensure(h, c, t, o, at.words); },
-        [&](QaryCall &c) { return secret_draw(h, c, t, words, at, (long)first_trial, seed); },
+        [&](QaryCall &c) { return secret_draw(h, c, t, words, at, ts, seed); },
         [&](QaryCall &c, u64(&status)[2]) { return secret_emit(h, c, at, o, status); });
+}
+
+int scaldpc_mc_qary_run_secret(scaldpc_qary *h, const double *prior_b, const float *levels_b, const double *weights_b, int32_t k_b,
+                               const float *levels_s, const double *weights_s, int32_t k_s, int64_t first_trial, int32_t batch,
+                               uint64_t seed, uint32_t flags, void *stream, uint8_t *out_success, int32_t *out_wrong,
+                               int32_t *out_channel_wrong, int8_t *out_secret, uint8_t *out_levels, int8_t *out_symbols)
+{
+    return mc_qary_run_secret_body(h, prior_b, levels_b, weights_b, k_b, levels_s, weights_s, k_s, TrialSrc::range(first_trial), batch, seed,
+                                   flags, stream, out_success, out_wrong, out_channel_wrong, out_secret, out_levels, out_symbols);
+}
+
+int scaldpc_mc_qary_run_secret_at(scaldpc_qary *h, const double *prior_b, const float *levels_b, const double *weights_b, int32_t k_b,
+                                  const float *levels_s, const double *weights_s, int32_t k_s, const int64_t *trial_ids, int32_t batch,
+                                  uint64_t seed, uint32_t flags, void *stream, uint8_t *out_success, int32_t *out_wrong,
+                                  int32_t *out_channel_wrong, int8_t *out_secret, uint8_t *out_levels, int8_t *out_symbols)
+{
+    return mc_qary_run_secret_body(h, prior_b, levels_b, weights_b, k_b, levels_s, weights_s, k_s, TrialSrc::list(trial_ids), batch, seed,
+                                   flags, stream, out_success, out_wrong, out_channel_wrong, out_secret, out_levels, out_symbols);
 }
 
 void scaldpc_qary_destroy(scaldpc_qary *h)

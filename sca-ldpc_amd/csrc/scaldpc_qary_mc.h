@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 
 #include "scaldpc_philox.h"
+#include "scaldpc_trials.h"
 
 namespace {
 
@@ -30,13 +31,15 @@ struct McLaw {
 // tab: the tables' LLR rows, [K[0]][Qb] then [K[1]][Qs].  The variable index is uniform in a wave: its table, its edges and the
 // mirroring where h < 0 are scalar; only the level differs from lane to lane (an LDS read).  Every store is 64 codewords wide.
 // Padding lanes (b >= batch) get the all-zero rows the conversion kernels give them.
-__global__ __launch_bounds__(256) void k_q_mc_draw(McLaw law, const float *__restrict__ tab, int Qb, int Qs, int BV, int N, int batch,
-                                                   long Bp, long first, unsigned k0, unsigned k1, const int *__restrict__ col_ptr,
-                                                   const int *__restrict__ csc_edge, const int *__restrict__ edge_h,
-                                                   float *__restrict__ llr, float *__restrict__ msg, int W,
-                                                   unsigned char *__restrict__ lvl)
+// The body is written over the source of the trial index (TR: scaldpc_trials.h); k_q_mc_draw is the contiguous form, slot b =
+// trial first + b, and the list form of scaldpc_mc_qary_run_at is scaldpc_qary_mc_at.h's.
+template <class TR>
+__device__ __forceinline__ void q_mc_draw_body(float *rows, const McLaw &law, const float *__restrict__ tab, int Qb, int Qs, int BV, int N,
+                                               int batch, long Bp, TR tr, unsigned k0, unsigned k1, const int *__restrict__ col_ptr,
+                                               const int *__restrict__ csc_edge, const int *__restrict__ edge_h,
+                                               float *__restrict__ llr, float *__restrict__ msg, int W,
+                                               unsigned char *__restrict__ lvl)
 {
-    extern __shared__ float rows[];
     const int nb = law.K[0] * Qb, nt = nb + law.K[1] * Qs;
     for (int i = threadIdx.x; i < nt; i += 256) rows[i] = tab[i];
     __syncthreads();
@@ -45,7 +48,7 @@ __global__ __launch_bounds__(256) void k_q_mc_draw(McLaw law, const float *__res
     if (x >= N) return;
     const long b = (long)blockIdx.y * 64 + lane;
     const bool live = b < batch;
-    const unsigned long long trial = (unsigned long long)(first + b);
+    const unsigned long long trial = tr.trial(b, live);
     const U4 r = philox4x32_10(U4{blockIdx.x, 0u, (unsigned)trial, (unsigned)(trial >> 32)}, k0, k1);
     const unsigned long long word = j == 0 ? r.x : j == 1 ? r.y : j == 2 ? r.z : r.w;
     const int tb = x >= BV, Q = tb ? Qs : Qb, K = law.K[tb];
@@ -60,6 +63,16 @@ __global__ __launch_bounds__(256) void k_q_mc_draw(McLaw law, const float *__res
         const bool rev = edge_h[e] < 0;
         for (int q = 0; q < Q; q++) msg[((size_t)e * W + q) * Bp + b] = live ? row[rev ? Q - 1 - q : q] : 0.0f;
     }
+}
+
+__global__ __launch_bounds__(256) void k_q_mc_draw(McLaw law, const float *__restrict__ tab, int Qb, int Qs, int BV, int N, int batch,
+                                                   long Bp, long first, unsigned k0, unsigned k1, const int *__restrict__ col_ptr,
+                                                   const int *__restrict__ csc_edge, const int *__restrict__ edge_h,
+                                                   float *__restrict__ llr, float *__restrict__ msg, int W,
+                                                   unsigned char *__restrict__ lvl)
+{
+    extern __shared__ float rows[];
+    q_mc_draw_body(rows, law, tab, Qb, Qs, BV, N, batch, Bp, scaldpc::TrialRange{first}, k0, k1, col_ptr, csc_edge, edge_h, llr, msg, W, lvl);
 }
 
 // hard: the staged symbols [N][Bp]; lvl: the drawn levels [N][Bp] (bytes both).  grid Bp / 64, block 1024 = the block's 64

@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include "scaldpc_philox.h"
+#include "scaldpc_trials.h"
 
 namespace {
 
@@ -54,21 +55,23 @@ __device__ __forceinline__ unsigned word_of(const U4 &r, int j) { return j == 0 
 // Philox block blockIdx.x -- of stream 1 (the secret) and of stream 0 (the outcome, the word scaldpc_mc_qary_run draws x's level
 // from): two generator calls per wave.  prior: Q cumulative thresholds (uniform: scalar loads).  sec [N][Bp]: the secret VALUES.
 // Padding lanes (b >= batch): all-zero rows, secret 0, the last level.  Every store is 64 codewords wide.
-__global__ __launch_bounds__(256) void k_q_mc_secret_draw(const unsigned long long *__restrict__ prior, const unsigned *__restrict__ law,
-                                                          const float *__restrict__ tab, int K, int Q, int BV, int batch, long Bp,
-                                                          long first, unsigned k0, unsigned k1, const int *__restrict__ col_ptr,
-                                                          const int *__restrict__ csc_edge, const int *__restrict__ edge_h,
-                                                          float *__restrict__ llr, float *__restrict__ msg, int W,
-                                                          unsigned char *__restrict__ lvl, signed char *__restrict__ sec)
+// Both drawing kernels' bodies are written over the source of the trial index (TR: scaldpc_trials.h); the kernels here are the
+// contiguous form, slot b = trial first + b, and the list forms of scaldpc_mc_qary_run_secret_at are scaldpc_qary_mc_at.h's.
+template <class TR>
+__device__ __forceinline__ void q_mc_secret_draw_body(float *secret_lds, const unsigned long long *__restrict__ prior,
+                                                      const unsigned *__restrict__ law, const float *__restrict__ tab, int K, int Q, int BV,
+                                                      int batch, long Bp, TR tr, unsigned k0, unsigned k1,
+                                                      const int *__restrict__ col_ptr, const int *__restrict__ csc_edge,
+                                                      const int *__restrict__ edge_h, float *__restrict__ llr, float *__restrict__ msg,
+                                                      int W, unsigned char *__restrict__ lvl, signed char *__restrict__ sec)
 {
-    extern __shared__ float secret_lds[];
     const SecretTab t = secret_stage(secret_lds, tab, law, K, Q);
     const int lane = threadIdx.x & 63, j = threadIdx.x >> 6;
     const int x = (int)blockIdx.x * 4 + j;
     if (x >= BV) return;
     const long b = (long)blockIdx.y * 64 + lane;
     const bool live = b < batch;
-    const unsigned long long trial = (unsigned long long)(first + b);
+    const unsigned long long trial = tr.trial(b, live);
     const unsigned lo = (unsigned)trial, hi = (unsigned)(trial >> 32);
     const unsigned long long ws = word_of(philox4x32_10(U4{blockIdx.x, 1u, lo, hi}, k0, k1), j);
     const unsigned wo = word_of(philox4x32_10(U4{blockIdx.x, 0u, lo, hi}, k0, k1), j);
@@ -87,19 +90,31 @@ __global__ __launch_bounds__(256) void k_q_mc_secret_draw(const unsigned long lo
     }
 }
 
+__global__ __launch_bounds__(256) void k_q_mc_secret_draw(const unsigned long long *__restrict__ prior, const unsigned *__restrict__ law,
+                                                          const float *__restrict__ tab, int K, int Q, int BV, int batch, long Bp,
+                                                          long first, unsigned k0, unsigned k1, const int *__restrict__ col_ptr,
+                                                          const int *__restrict__ csc_edge, const int *__restrict__ edge_h,
+                                                          float *__restrict__ llr, float *__restrict__ msg, int W,
+                                                          unsigned char *__restrict__ lvl, signed char *__restrict__ sec)
+{
+    extern __shared__ float secret_lds[];
+    q_mc_secret_draw_body(secret_lds, prior, law, tab, K, Q, BV, batch, Bp, scaldpc::TrialRange{first}, k0, k1, col_ptr, csc_edge, edge_h,
+                          llr, msg, W, lvl, sec);
+}
+
 // grid (ceil(R / 4), Bp / 64), block 256, after k_q_mc_secret_draw on the same stream: wave j takes row r = 4 blockIdx.x + j and
 // its row-sum variable x = BV + r.  The row's edges are its coefficient edges and then the identity entry (creation holds H to
 // [H' | I]): a scalar walk over edge_var / edge_h, 64 secret bytes per edge.  (degree - 1) B <= BSUM (creation), so t_r lies inside
 // the alphabet; the clamp only keeps a broken plane from indexing past the table.  x's word is word x & 3 of stream-0 block
 // x >> 2, whatever r is: the first rows share their block with the last coefficient variables.
-__global__ __launch_bounds__(256) void k_q_mc_secret_sums(const unsigned *__restrict__ law, const float *__restrict__ tab, int K, int QS,
-                                                          int Qb, int BV, int R, int batch, long Bp, long first, unsigned k0,
-                                                          unsigned k1, const int *__restrict__ row_ptr, const int *__restrict__ edge_var,
-                                                          const int *__restrict__ edge_h, float *__restrict__ llr,
-                                                          float *__restrict__ msg, int W, unsigned char *__restrict__ lvl,
-                                                          signed char *__restrict__ sec)
+template <class TR>
+__device__ __forceinline__ void q_mc_secret_sums_body(float *secret_lds, const unsigned *__restrict__ law, const float *__restrict__ tab,
+                                                      int K, int QS, int Qb, int BV, int R, int batch, long Bp, TR trials, unsigned k0,
+                                                      unsigned k1, const int *__restrict__ row_ptr, const int *__restrict__ edge_var,
+                                                      const int *__restrict__ edge_h, float *__restrict__ llr,
+                                                      float *__restrict__ msg, int W, unsigned char *__restrict__ lvl,
+                                                      signed char *__restrict__ sec)
 {
-    extern __shared__ float secret_lds[];
     const SecretTab t = secret_stage(secret_lds, tab, law, K, QS);
     const int lane = threadIdx.x & 63, j = threadIdx.x >> 6;
     const int r = (int)blockIdx.x * 4 + j;
@@ -113,7 +128,7 @@ __global__ __launch_bounds__(256) void k_q_mc_secret_sums(const unsigned *__rest
     const bool rev = edge_h[e_id] < 0;
     const int BSUM = (QS - 1) / 2;
     const int tr = live ? min(max(rev ? sum : -sum, -BSUM), BSUM) : 0;
-    const unsigned long long trial = (unsigned long long)(first + b);
+    const unsigned long long trial = trials.trial(b, live);
     const unsigned wo = word_of(philox4x32_10(U4{(unsigned)(x >> 2), 0u, (unsigned)trial, (unsigned)(trial >> 32)}, k0, k1), x & 3);
     const int lv = t.outcome(wo, tr + BSUM, K, QS);
     const float *row = t.rows + lv * QS;
@@ -122,6 +137,18 @@ __global__ __launch_bounds__(256) void k_q_mc_secret_sums(const unsigned *__rest
     lvl[(size_t)x * Bp + b] = (unsigned char)(live ? lv : K - 1);
     sec[(size_t)x * Bp + b] = (signed char)tr;
     for (int q = 0; q < QS; q++) msg[((size_t)e_id * W + q) * Bp + b] = live ? row[rev ? QS - 1 - q : q] : 0.0f;
+}
+
+__global__ __launch_bounds__(256) void k_q_mc_secret_sums(const unsigned *__restrict__ law, const float *__restrict__ tab, int K, int QS,
+                                                          int Qb, int BV, int R, int batch, long Bp, long first, unsigned k0,
+                                                          unsigned k1, const int *__restrict__ row_ptr, const int *__restrict__ edge_var,
+                                                          const int *__restrict__ edge_h, float *__restrict__ llr,
+                                                          float *__restrict__ msg, int W, unsigned char *__restrict__ lvl,
+                                                          signed char *__restrict__ sec)
+{
+    extern __shared__ float secret_lds[];
+    q_mc_secret_sums_body(secret_lds, law, tab, K, QS, Qb, BV, R, batch, Bp, scaldpc::TrialRange{first}, k0, k1, row_ptr, edge_var, edge_h,
+                          llr, msg, W, lvl, sec);
 }
 
 // hard, sec: the decided and the secret values [N][Bp]; lvl: the drawn levels [N][Bp]; best: the value a variable decides from

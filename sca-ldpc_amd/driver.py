@@ -308,6 +308,36 @@ def hqc_oracle_sweep(Hin, N, omega, table, runs, seed, chunk=4096, bp_method="pr
     return res
 
 
+def hqc_replay(Hin, N, omega, table, trial_ids, seed, bp_method="product_sum", max_iter=100, bp_decoder=None, precision=None):
+    """The post-mortem of a sweep: decode CHOSEN trials of `hqc_oracle_sweep` (the failures of a sweep, the indices on which
+    `hqc_precision_audit` finds fp32 and float64 to disagree) again and look at everything, in two calls on one decoder:
+      1. `mc_hqc_run_soft_at(trial_ids, ..., want_inputs=True, want_stats=True, want_bits=True)`: the trials as the sweep
+         drew and decoded them -- nothing but the listed trials is drawn, decoded or copied;
+      2. `decode_batch(msg, channel_probs=probs[outcome], want_llr=True)` on what it exported: the posteriors.
+    precision: "float32" or "float64" -- handed to both calls; None: the sweeps' own default (the fp32 kernels; `precision` of a
+    `sweeps_in(precision)` class), so that both halves always decode in one arithmetic.
+    Returns dict(trial_ids int64 [T], sweep = the first call's dict (success, iters, flips, cost, msg, y, outcome, stats, bits),
+    decode = the second's (bits, iters, converged, llr)).  `decode` reproduces `sweep`: the same bits and iteration counts."""
+    g = TannerGraph.coerce(Hin)
+    if g.n != N:
+        raise ValueError(f"Hin has {g.n} columns, N = {N}")
+    # the check columns' shared priors are replaced per trial: any probability does
+    shared = np.concatenate([np.full(N, omega / N, dtype=np.float64), np.full(g.m, 0.5, dtype=np.float64)])
+    bpd = (bp_decoder or _default_bp())(g.with_identity(), max_iter=max_iter, bp_method=bp_method, channel_probs=shared)
+    if precision is None:
+        precision = getattr(bpd, "sweep_precision", None)
+    f64 = precision is not None and str(precision).lower() == "float64"
+    try:
+        sweep = bpd.mc_hqc_run_soft_at(trial_ids, omega, table, seed, max_iter=max_iter, want_inputs=True, want_stats=True,
+                                       want_bits=True, **_precision_kw(precision))
+        probs = np.asarray(table["probs"], dtype=np.float64 if f64 else np.float32)[np.asarray(sweep["outcome"])]
+        decode = bpd.decode_batch(sweep["msg"], max_iter=max_iter, want_llr=True, channel_probs=probs, **_precision_kw(precision))
+    finally:
+        if hasattr(bpd, "close"):
+            bpd.close()
+    return dict(trial_ids=np.asarray(trial_ids, dtype=np.int64), sweep=sweep, decode=decode)
+
+
 def hqc_attack_curve(first_row_support, N, rows, omega, table, runs, seed, decode_every, max_checks=None, chunk=4096,
                      bp_method="product_sum", max_iter=100, bp_decoder=None):
     """How many checks does a key need?  The reference's attack loop (`add_checks`, simulate/hqc.py:953-984: add rows, decode
@@ -321,8 +351,9 @@ def hqc_attack_curve(first_row_support, N, rows, omega, table, runs, seed, decod
     by `decode_every` rows per step (`append_rows`) up to `max_checks` (default: all of `rows`; a last partial step is not
     taken), and at every step decodes trials 0 .. runs - 1, `chunk` at a time, with the per-trial counters of
     tracking.add_decoder_stats counted on the device (`want_stats`).  Trials that already succeeded are decoded again at
-    the later steps -- a call decodes a contiguous range of trial indices -- and converge within a few iterations; their
-    later results are not recorded.  The result does not depend on `chunk`.
+    the later steps -- this function decodes contiguous ranges of trial indices -- and converge within a few iterations; their
+    later results are not recorded (`hqc_attack_curve_retiring` stops decoding a key at its first success, as the reference's
+    loop does).  The result does not depend on `chunk`.
     The curve in the reference's own arithmetic: `bp_decoder=sweeps_in("float64")` -- a decoder class whose sweeps decode in
     float64 (the float64 form works on a decoder grown by `append_rows`); this function's own parameters are what they were.
 
@@ -336,6 +367,29 @@ def hqc_attack_curve(first_row_support, N, rows, omega, table, runs, seed, decod
                            stops there (hqc.py:980-982) -- ordered by trial, then step: dicts with the keys
                            `write_decoder_stats_csv` takes (checks, oracle_calls (None without costs), HQC_STATS_COLUMNS,
                            success) and `trial`)."""
+    return _hqc_attack_curve(first_row_support, N, rows, omega, table, runs, seed, decode_every, max_checks, chunk, bp_method, max_iter,
+                             bp_decoder, retiring=False)
+
+
+def hqc_attack_curve_retiring(first_row_support, N, rows, omega, table, runs, seed, decode_every, max_checks=None, chunk=4096,
+                              bp_method="product_sum", max_iter=100, bp_decoder=None):
+    """`hqc_attack_curve` with the reference's stopping rule (hqc.py:980-982): a key is decoded until its FIRST success and
+    never again.  The loop, the decoder and the trials are `hqc_attack_curve`'s; at every step only the trial indices not yet
+    recovered are decoded, `chunk` at a time, through `BpDecoder.mc_hqc_run_soft_at` (a sweep on a list of trial indices).
+    Works with `bp_decoder=sweeps_in("float64")` as that function does.  The result does not depend on `chunk`.
+
+    Returns `hqc_attack_curve`'s dict: `steps`, `checks_needed`, `oracle_calls_needed` and `decoder_stats` are equal to that
+    function's (it records nothing about a key after its first success either), and
+      successes            int64 [S]: the keys whose FIRST success is that step (not: every key that succeeds there),
+      decoded              int64 [S]: the trials decoded at that step = the keys not recovered before it."""
+    return _hqc_attack_curve(first_row_support, N, rows, omega, table, runs, seed, decode_every, max_checks, chunk, bp_method, max_iter,
+                             bp_decoder, retiring=True)
+
+
+def _hqc_attack_curve(first_row_support, N, rows, omega, table, runs, seed, decode_every, max_checks, chunk, bp_method, max_iter,
+                      bp_decoder, retiring):
+    # the loop of hqc_attack_curve (every step decodes trials 0 .. runs - 1 in contiguous chunks) and of
+    # hqc_attack_curve_retiring (every step decodes the list of trials with no success yet)
     k = np.sort(np.asarray(first_row_support, dtype=np.int64))
     rows = np.asarray(rows, dtype=np.int64)
     step = int(decode_every)
@@ -351,6 +405,7 @@ def hqc_attack_curve(first_row_support, N, rows, omega, table, runs, seed, decod
     steps = np.arange(step, top + 1, step, dtype=np.int32)
     counted = table.get("costs") is not None
     successes = np.zeros(steps.size, dtype=np.int64)
+    decoded = np.zeros(steps.size, dtype=np.int64)
     needed = np.full(runs, -1, dtype=np.int32)
     calls = np.full(runs, -1, dtype=np.int64) if counted else None
     per_trial = [[] for _ in range(runs)]
@@ -364,15 +419,20 @@ def hqc_attack_curve(first_row_support, N, rows, omega, table, runs, seed, decod
             R = int(R)
             if s:
                 bpd.append_rows(ptr, cols[R - step : R].reshape(-1), N + R, np.full(step, 0.5, dtype=np.float64))
-            for first in range(0, runs, chunk):
-                out = bpd.mc_hqc_run_soft(min(chunk, runs - first), omega, table, seed, first_trial=first, max_iter=max_iter,
-                                          want_stats=True)
+            live = np.flatnonzero(needed < 0) if retiring else np.arange(runs, dtype=np.int64)
+            decoded[s] = live.size
+            for first in range(0, live.size, chunk):
+                ids = live[first : first + chunk]
+                if retiring:
+                    out = bpd.mc_hqc_run_soft_at(ids, omega, table, seed, max_iter=max_iter, want_stats=True)
+                else:
+                    out = bpd.mc_hqc_run_soft(ids.size, omega, table, seed, first_trial=first, max_iter=max_iter, want_stats=True)
                 ok = np.asarray(out["success"]).astype(bool)
                 st = np.asarray(out["stats"])
                 cost = np.asarray(out["cost"], dtype=np.int64) if counted else None
                 successes[s] += int(ok.sum())
-                for i in np.flatnonzero(needed[first : first + ok.size] < 0):
-                    t = first + int(i)
+                for i in np.flatnonzero(needed[ids] < 0):
+                    t = int(ids[i])
                     row = {"trial": t, "checks": R, "oracle_calls": int(cost[i]) if counted else None}
                     row.update(zip(HQC_STATS_COLUMNS, (int(v) for v in st[i])))
                     row["success"] = bool(ok[i])
@@ -384,8 +444,9 @@ def hqc_attack_curve(first_row_support, N, rows, omega, table, runs, seed, decod
     finally:
         if hasattr(bpd, "close"):
             bpd.close()
-    return dict(steps=steps, successes=successes, checks_needed=needed, oracle_calls_needed=calls,
-                decoder_stats=[row for rows_of in per_trial for row in rows_of])
+    res = dict(steps=steps, successes=successes, checks_needed=needed, oracle_calls_needed=calls,
+               decoder_stats=[row for rows_of in per_trial for row in rows_of])
+    return dict(res, decoded=decoded) if retiring else res
 
 
 def _precision_kw(precision):
@@ -394,7 +455,8 @@ def _precision_kw(precision):
 
 
 def sweeps_in(precision, bp_decoder=None):
-    """A decoder class whose Monte-Carlo sweeps (`mc_fer_run`, `mc_hqc_run`, `mc_hqc_run_soft`) decode in `precision` unless a
+    """A decoder class whose Monte-Carlo sweeps (`mc_fer_run`, `mc_hqc_run`, `mc_hqc_run_soft` and their `_at` forms on chosen
+    trials) decode in `precision` unless a
     call says otherwise: `bp_decoder` (default: the HIP class) with that one default changed, for the drivers that take a
     decoder class and no `precision` of their own -- `hqc_attack_curve(..., bp_decoder=sweeps_in("float64"))` is the
     checks-needed curve in the reference's float64 arithmetic.  `decode` / `decode_batch` are untouched.  "float64" on a min-sum
@@ -404,6 +466,8 @@ def sweeps_in(precision, bp_decoder=None):
     base = bp_decoder or _default_bp()
 
     class Sweeps(base):
+        sweep_precision = str(precision).lower()  # (what a driver that also calls `decode_batch` on a sweep's exports reads: hqc_replay)
+
         def mc_fer_run(self, *args, **kw):
             return super().mc_fer_run(*args, **dict({"precision": precision}, **kw))
 
@@ -412,6 +476,15 @@ def sweeps_in(precision, bp_decoder=None):
 
         def mc_hqc_run_soft(self, *args, **kw):
             return super().mc_hqc_run_soft(*args, **dict({"precision": precision}, **kw))
+
+        def mc_fer_run_at(self, *args, **kw):
+            return super().mc_fer_run_at(*args, **dict({"precision": precision}, **kw))
+
+        def mc_hqc_run_at(self, *args, **kw):
+            return super().mc_hqc_run_at(*args, **dict({"precision": precision}, **kw))
+
+        def mc_hqc_run_soft_at(self, *args, **kw):
+            return super().mc_hqc_run_soft_at(*args, **dict({"precision": precision}, **kw))
 
     Sweeps.__name__ = Sweeps.__qualname__ = f"{base.__name__}Sweeps{str(precision).capitalize()}"
     return Sweeps

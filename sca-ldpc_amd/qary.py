@@ -89,13 +89,16 @@ class _QaryBase:
             raise ValueError(f"{what}: levels {lv.shape} / weights {w.shape}, expected (K, {Q}) pmf rows and (K,) probabilities")
         return lv, w
 
-    def _mc_call(self, tables, first_trial, runs, seed, flags, stream, outs):
+    def _mc_call(self, tables, first_trial, runs, seed, flags, stream, outs, trial_ids=None):
+        # trial_ids: None (a contiguous call from first_trial), or the int64 list `_lib.trial_ids` returned (an _at call)
         (lb, wb), (ls, ws) = tables
-        _lib.check(self._lib.scaldpc_mc_qary_run(
+        listed = trial_ids is not None
+        entry = self._lib.scaldpc_mc_qary_run_at if listed else self._lib.scaldpc_mc_qary_run
+        _lib.check(entry(
             self._h, _lib.ptr(lb), _lib.ptr(wb), lb.shape[0], _lib.ptr(ls), _lib.ptr(ws), 0 if ls is None else ls.shape[0],
-            int(first_trial), int(runs), int(seed), flags, C.c_void_p(stream or None), *outs))
+            _lib.ptr(trial_ids) if listed else int(first_trial), int(runs), int(seed), flags, C.c_void_p(stream or None), *outs))
 
-    def _mc_host(self, tables, runs, seed, first_trial, want_levels, want_symbols):
+    def _mc_host(self, tables, runs, seed, first_trial, want_levels, want_symbols, trial_ids=None):
         runs = int(runs)
         if runs <= 0:
             raise ValueError("runs must be positive")
@@ -105,11 +108,12 @@ class _QaryBase:
             res["levels"] = np.empty((runs, self.N), dtype=np.uint8)
         if want_symbols:
             res["symbols"] = np.empty((runs, self.N), dtype=np.int8)
-        self._mc_call(tables, first_trial, runs, seed, 0, 0, [_lib.ptr(res.get(k)) for k in ("success", "errs", "wrong", "levels", "symbols")])
+        self._mc_call(tables, first_trial, runs, seed, 0, 0, [_lib.ptr(res.get(k)) for k in ("success", "errs", "wrong", "levels", "symbols")],
+                      trial_ids)
         return res
 
-    def _mc_device(self, tables, runs, seed, first_trial, stream, d_outs):
-        self._mc_call(tables, first_trial, runs, seed, _lib.F_DEVICE_IO, stream, [C.c_void_p(d or None) for d in d_outs])
+    def _mc_device(self, tables, runs, seed, first_trial, stream, d_outs, trial_ids=None):
+        self._mc_call(tables, first_trial, runs, seed, _lib.F_DEVICE_IO, stream, [C.c_void_p(d or None) for d in d_outs], trial_ids)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -198,6 +202,21 @@ class QaryDecoder(_QaryBase):
         Returns after the stream work is complete."""
         tables = (self._mc_table(levels, weights, self.Q, "levels"), (None, None))
         self._mc_device(tables, runs, seed, first_trial, stream, (d_success, d_errs, d_wrong, d_levels, d_symbols))
+
+    def mc_run_at(self, trial_ids, seed, levels, weights, want_levels=False, want_symbols=False):
+        """`mc_run` on CHOSEN trials (scaldpc_mc_qary_run_at): slot i of the result is global trial `trial_ids[i]` (any order,
+        duplicates allowed, indices up to 2^63 - 1), row for row what `mc_run` returns for that index on any range that
+        contains it.  trial_ids: a one-dimensional array of non-negative integers (ValueError otherwise, before any library
+        call; a float array is refused, not rounded).  Returns `mc_run`'s dict with len(trial_ids) rows."""
+        ids = _lib.trial_ids(trial_ids)
+        tables = (self._mc_table(levels, weights, self.Q, "levels"), (None, None))
+        return self._mc_host(tables, len(ids), seed, 0, want_levels, want_symbols, trial_ids=ids)
+
+    def mc_run_at_device(self, trial_ids, seed, levels, weights, d_success, d_errs=0, d_wrong=0, d_levels=0, d_symbols=0, stream=0):
+        """Device-pointer variant of `mc_run_at` (ints; 0 = not wanted); the trial list and the tables stay host arrays."""
+        ids = _lib.trial_ids(trial_ids)
+        tables = (self._mc_table(levels, weights, self.Q, "levels"), (None, None))
+        self._mc_device(tables, len(ids), seed, 0, stream, (d_success, d_errs, d_wrong, d_levels, d_symbols), trial_ids=ids)
 
     def min_sum_soft(self, py_channel_output, costs=True, margins=True, unmet=True):
         """The single-codeword twin of `min_sum`: symbols as a list of ints, costs [N, Q], margins [N], unmet an int."""
@@ -292,6 +311,20 @@ class QarySpecialDecoder(_QaryBase):
         tables = (self._mc_table(levels, weights, self.Q, "levels"), self._mc_table(levels_sum, weights_sum, self.QS, "levels_sum"))
         self._mc_device(tables, runs, seed, first_trial, stream, (d_success, d_errs, d_wrong, d_levels, d_symbols))
 
+    def mc_run_at(self, trial_ids, seed, levels, weights, levels_sum, weights_sum, want_levels=False, want_symbols=False):
+        """`mc_run` on CHOSEN trials (scaldpc_mc_qary_run_at): slot i of the result is global trial `trial_ids[i]`, row for row
+        what `mc_run` returns for that index on any range that contains it.  trial_ids: as QaryDecoder.mc_run_at's."""
+        ids = _lib.trial_ids(trial_ids)
+        tables = (self._mc_table(levels, weights, self.Q, "levels"), self._mc_table(levels_sum, weights_sum, self.QS, "levels_sum"))
+        return self._mc_host(tables, len(ids), seed, 0, want_levels, want_symbols, trial_ids=ids)
+
+    def mc_run_at_device(self, trial_ids, seed, levels, weights, levels_sum, weights_sum, d_success, d_errs=0, d_wrong=0, d_levels=0,
+                         d_symbols=0, stream=0):
+        """Device-pointer variant of `mc_run_at` (ints; 0 = not wanted); the trial list and the tables stay host arrays."""
+        ids = _lib.trial_ids(trial_ids)
+        tables = (self._mc_table(levels, weights, self.Q, "levels"), self._mc_table(levels_sum, weights_sum, self.QS, "levels_sum"))
+        self._mc_device(tables, len(ids), seed, 0, stream, (d_success, d_errs, d_wrong, d_levels, d_symbols), trial_ids=ids)
+
     # -- trials on drawn secrets under an oracle's law (include/scaldpc.h, scaldpc_mc_qary_run_secret) --------------------------
     @staticmethod
     def _secret_table(levels, weights, Q, what):
@@ -302,15 +335,18 @@ class QarySpecialDecoder(_QaryBase):
             raise ValueError(f"{what}: levels {lv.shape} / weights {w.shape}, expected (K, {Q}) pmf rows and ({Q}, K) outcome laws")
         return lv, w
 
-    def _secret_call(self, prior, levels, weights, levels_sum, weights_sum, first_trial, runs, seed, flags, stream, outs):
+    def _secret_call(self, prior, levels, weights, levels_sum, weights_sum, first_trial, runs, seed, flags, stream, outs, trial_ids=None):
+        # trial_ids: None (a contiguous call from first_trial), or the int64 list `_lib.trial_ids` returned (an _at call)
         pr = np.ascontiguousarray(prior, dtype=np.float64)
         if pr.shape != (self.Q,):
             raise ValueError(f"prior has shape {pr.shape}, expected ({self.Q},)")
         lb, wb = self._secret_table(levels, weights, self.Q, "levels")
         ls, ws = self._secret_table(levels_sum, weights_sum, self.QS, "levels_sum")
-        _lib.check(self._lib.scaldpc_mc_qary_run_secret(
-            self._h, _lib.ptr(pr), _lib.ptr(lb), _lib.ptr(wb), lb.shape[0], _lib.ptr(ls), _lib.ptr(ws), ls.shape[0], int(first_trial),
-            int(runs), int(seed), flags, C.c_void_p(stream or None), *outs))
+        listed = trial_ids is not None
+        entry = self._lib.scaldpc_mc_qary_run_secret_at if listed else self._lib.scaldpc_mc_qary_run_secret
+        _lib.check(entry(
+            self._h, _lib.ptr(pr), _lib.ptr(lb), _lib.ptr(wb), lb.shape[0], _lib.ptr(ls), _lib.ptr(ws), ls.shape[0],
+            _lib.ptr(trial_ids) if listed else int(first_trial), int(runs), int(seed), flags, C.c_void_p(stream or None), *outs))
 
     def mc_run_secret(self, runs, seed, prior, levels, weights, levels_sum, weights_sum, first_trial=0, want_secret=False,
                       want_levels=False, want_symbols=False):
@@ -323,6 +359,11 @@ class QarySpecialDecoder(_QaryBase):
         [runs, 2] (variables whose drawn row alone decides wrong)), with want_secret / want_levels / want_symbols also secret int8
         [runs, N], levels uint8 [runs, N], symbols int8 [runs, N]: the symbols are
         `min_sum_batch(levels[lv[:, :N-R]], levels_sum[lv[:, N-R:]])`, bit for bit."""
+        return self._secret_host(runs, seed, prior, levels, weights, levels_sum, weights_sum, first_trial, want_secret, want_levels,
+                                 want_symbols)
+
+    def _secret_host(self, runs, seed, prior, levels, weights, levels_sum, weights_sum, first_trial, want_secret, want_levels, want_symbols,
+                     trial_ids=None):
         runs = int(runs)
         if runs <= 0:
             raise ValueError("runs must be positive")
@@ -335,7 +376,7 @@ class QarySpecialDecoder(_QaryBase):
         if want_symbols:
             res["symbols"] = np.empty((runs, self.N), dtype=np.int8)
         outs = [_lib.ptr(res.get(k)) for k in ("success", "wrong", "channel_wrong", "secret", "levels", "symbols")]
-        self._secret_call(prior, levels, weights, levels_sum, weights_sum, first_trial, runs, seed, 0, 0, outs)
+        self._secret_call(prior, levels, weights, levels_sum, weights_sum, first_trial, runs, seed, 0, 0, outs, trial_ids)
         return res
 
     def mc_run_secret_device(self, runs, seed, prior, levels, weights, levels_sum, weights_sum, d_success, d_wrong=0, d_channel_wrong=0,
@@ -344,6 +385,23 @@ class QarySpecialDecoder(_QaryBase):
         arrays.  Returns after the stream work is complete."""
         outs = [C.c_void_p(d or None) for d in (d_success, d_wrong, d_channel_wrong, d_secret, d_levels, d_symbols)]
         self._secret_call(prior, levels, weights, levels_sum, weights_sum, first_trial, runs, seed, _lib.F_DEVICE_IO, stream, outs)
+
+    def mc_run_secret_at(self, trial_ids, seed, prior, levels, weights, levels_sum, weights_sum, want_secret=False, want_levels=False,
+                         want_symbols=False):
+        """`mc_run_secret` on CHOSEN trials (scaldpc_mc_qary_run_secret_at): slot i of the result is global trial `trial_ids[i]`
+        (any order, duplicates allowed, indices up to 2^63 - 1), row for row -- success, wrong, channel_wrong, secret, levels,
+        symbols -- what `mc_run_secret` returns for that index on any range that contains it.  trial_ids: as
+        QaryDecoder.mc_run_at's.  Returns `mc_run_secret`'s dict with len(trial_ids) rows."""
+        ids = _lib.trial_ids(trial_ids)
+        return self._secret_host(len(ids), seed, prior, levels, weights, levels_sum, weights_sum, 0, want_secret, want_levels, want_symbols,
+                                 trial_ids=ids)
+
+    def mc_run_secret_at_device(self, trial_ids, seed, prior, levels, weights, levels_sum, weights_sum, d_success, d_wrong=0,
+                                d_channel_wrong=0, d_secret=0, d_levels=0, d_symbols=0, stream=0):
+        """Device-pointer variant of `mc_run_secret_at` (ints; 0 = not wanted); the trial list, prior and tables stay host arrays."""
+        ids = _lib.trial_ids(trial_ids)
+        outs = [C.c_void_p(d or None) for d in (d_success, d_wrong, d_channel_wrong, d_secret, d_levels, d_symbols)]
+        self._secret_call(prior, levels, weights, levels_sum, weights_sum, 0, len(ids), seed, _lib.F_DEVICE_IO, stream, outs, trial_ids=ids)
 
     def min_sum_soft(self, py_channel_output, py_channel_output_sum, costs=True, margins=True, unmet=True):
         p, ps = np.asarray(py_channel_output), np.asarray(py_channel_output_sum)
