@@ -375,22 +375,13 @@ class BpDecoder:
         iters = np.empty(runs, dtype=np.int32)
         msg = np.empty((runs, self.n), dtype=np.uint8) if want_inputs else None
         y = np.empty((runs, omega), dtype=np.int32) if want_inputs else None
-        if f64:
-            _lib.check(
-                self._lib.scaldpc_mc_hqc_run_f64(
-                    self._h, int(omega), float(eps), int(first_trial), int(runs), int(seed),
-                    self.max_iter if max_iter is None else int(max_iter), _lib.F_EARLY_EXIT if early_exit else 0, None,
-                    _lib.ptr(succ), _lib.ptr(iters), _lib.ptr(msg), _lib.ptr(y),
-                )  # fmt: skip
-            )
-            return {"success": succ, "iters": iters, "msg": msg, "y": y}
-        _lib.check(
-            self._lib.scaldpc_mc_hqc_run(
-                self._h, int(omega), float(eps), int(first_trial), int(runs), int(seed),
-                self.max_iter if max_iter is None else int(max_iter), self._method, self.ms_scaling_factor,
-                _lib.F_EARLY_EXIT if early_exit else 0, None, _lib.ptr(succ), _lib.ptr(iters), _lib.ptr(msg), _lib.ptr(y),
-            )  # fmt: skip
-        )
+        args = (
+            self._h, int(omega), float(eps), int(first_trial), int(runs), int(seed),
+            self.max_iter if max_iter is None else int(max_iter),
+            *(() if f64 else (self._method, self.ms_scaling_factor)),  # (no method, no alpha: product-sum only)
+            _lib.F_EARLY_EXIT if early_exit else 0, None, _lib.ptr(succ), _lib.ptr(iters), _lib.ptr(msg), _lib.ptr(y),
+        )  # fmt: skip
+        _lib.check(getattr(self._lib, "scaldpc_mc_hqc_run" + ("_f64" if f64 else ""))(*args))
         return {"success": succ, "iters": iters, "msg": msg, "y": y}
 
     def mc_hqc_run_at(self, trial_ids, omega, eps, seed, max_iter=None, early_exit=True, want_inputs=False, want_stats=False,
@@ -513,21 +504,12 @@ def _mc_fer(dec, trials, runs, at, seed, max_iter, early_exit, want_errors, prec
     succ = np.empty(runs, dtype=np.uint8)
     iters = np.empty(runs, dtype=np.int32)
     err = np.empty((runs, dec.n), dtype=np.uint8) if want_errors else None
-    if f64:
-        _lib.check(
-            getattr(dec._lib, f"scaldpc_mc_fer_run{at}_f64")(
-                dec._h, trials, runs, int(seed), dec.max_iter if max_iter is None else int(max_iter),
-                _lib.F_EARLY_EXIT if early_exit else 0, None, _lib.ptr(succ), _lib.ptr(iters), _lib.ptr(err),
-            )  # fmt: skip
-        )
-        return {"success": succ, "iters": iters, "errors": err}
-    _lib.check(
-        getattr(dec._lib, f"scaldpc_mc_fer_run{at}")(
-            dec._h, trials, runs, int(seed), dec.max_iter if max_iter is None else int(max_iter),
-            dec._method, dec.ms_scaling_factor, _lib.F_EARLY_EXIT if early_exit else 0, None, _lib.ptr(succ),
-            _lib.ptr(iters), _lib.ptr(err),
-        )  # fmt: skip
-    )
+    args = (
+        dec._h, trials, runs, int(seed), dec.max_iter if max_iter is None else int(max_iter),
+        *(() if f64 else (dec._method, dec.ms_scaling_factor)),  # (no method, no alpha: product-sum only)
+        _lib.F_EARLY_EXIT if early_exit else 0, None, _lib.ptr(succ), _lib.ptr(iters), _lib.ptr(err),
+    )  # fmt: skip
+    _lib.check(getattr(dec._lib, f"scaldpc_mc_fer_run{at}" + ("_f64" if f64 else ""))(*args))
     return {"success": succ, "iters": iters, "errors": err}
 
 
@@ -566,19 +548,15 @@ def _mc_hqc_soft(dec, trials, runs, listed, omega, table, seed, max_iter, early_
         _lib.ptr(msg), _lib.ptr(y), _lib.ptr(outcome), _lib.ptr(flips), _lib.ptr(cost),
     )  # fmt: skip
     res = {"success": succ, "iters": iters, "flips": flips, "cost": cost, "msg": msg, "y": y, "outcome": outcome}
-    if f64 or listed:  # one entry: out_stats is optional there
-        stats = np.empty((runs, len(HQC_STATS_COLUMNS)), dtype=np.int32) if want_stats or want_bits else None
-        bits = np.empty((runs, dec.n), dtype=np.uint8) if want_bits else None
-        entry = getattr(dec._lib, "scaldpc_mc_hqc_run_stats" + ("_at" if listed else "") + ("_f64" if f64 else ""))
-        _lib.check(entry(*args, _lib.ptr(stats), _lib.ptr(bits)))
-        return dict(res, stats=stats, bits=bits) if want_stats or want_bits else res
-    if want_stats or want_bits:
-        stats = np.empty((runs, len(HQC_STATS_COLUMNS)), dtype=np.int32)
-        bits = np.empty((runs, dec.n), dtype=np.uint8) if want_bits else None
-        _lib.check(dec._lib.scaldpc_mc_hqc_run_stats(*args, _lib.ptr(stats), _lib.ptr(bits)))
-        return dict(res, stats=stats, bits=bits)
-    _lib.check(dec._lib.scaldpc_mc_hqc_run_soft(*args))
-    return res
+    want = want_stats or want_bits
+    # a list or a float64 decode has one entry, whose out_stats is optional; the contiguous fp32 call without either flag is the
+    # plain sweep, whose argument list ends before out_stats / out_bits
+    with_stats = want or listed or f64
+    entry = "scaldpc_mc_hqc_run_" + ("stats" if with_stats else "soft") + ("_at" if listed else "") + ("_f64" if f64 else "")
+    stats = np.empty((runs, len(HQC_STATS_COLUMNS)), dtype=np.int32) if want else None
+    bits = np.empty((runs, dec.n), dtype=np.uint8) if want_bits else None
+    _lib.check(getattr(dec._lib, entry)(*args, *((_lib.ptr(stats), _lib.ptr(bits)) if with_stats else ())))
+    return dict(res, stats=stats, bits=bits) if want else res
 
 
 bp_decoder = BpDecoder

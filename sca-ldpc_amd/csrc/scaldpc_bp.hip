@@ -1696,6 +1696,25 @@ int copy_outputs(const scaldpc_bp *h, const Outputs &out, const Outputs &dev, in
     return 0;
 }
 
+// The same for an optional per-trial output of the Monte-Carlo sweeps (out null: not wanted, *dev null): the caller's own array
+// with SCALDPC_F_DEVICE_IO, else the handle's block, grown to `count` elements ...
+template <typename T, bool P>
+int mc_stage(Buf<T, P> &block, T *out, size_t count, bool dev_io, T **dev)
+{
+    *dev = out;
+    if (!out || dev_io) return 0;
+    SC_TRY(grow(block, count));
+    *dev = block.get();
+    return 0;
+}
+// ... from which `count` elements then go to the caller
+template <typename T>
+int mc_unstage(T *out, const T *dev, size_t count, bool dev_io, hipStream_t s)
+{
+    if (out && !dev_io) SC_HIP(hipMemcpyAsync(out, dev, sizeof(T) * count, hipMemcpyDeviceToHost, s));
+    return 0;
+}
+
 }  // namespace
 
 // ===========================================================================
@@ -2492,10 +2511,63 @@ int scaldpc_bp_decode_batch_f64(scaldpc_bp *h, const uint8_t *in, int32_t input_
 
 // ---------------------------------------------------------------------------
 // Monte-Carlo entry points (K6)
+//
+// Two sweeps, each written once.  mc_fer_body: draw an error, take its syndrome, decode, compare.  mc_hqc_body: draw a secret,
+// take its syndrome, add noise to the checks, build the message, decode, then stats / bits / compare.  What the 13 entries
+// differ in goes in as values: the trials (TrialSrc, scaldpc_trials.h: a range or a list), the decode (McDecode) and, for HQC,
+// the noise (McHqcNoise) and the outputs (McHqcOut).  The trials are drawn by the same kernels whatever the decode -- precision
+// is a property of the decode, not of the trial -- and it decides three things only: the order of the argument checks
+// (mc_args), the sizing (mc_size) and the decode itself (mc_decode).
 // ---------------------------------------------------------------------------
 namespace {
 
 // (bernoulli_threshold: scaldpc_mc_law.h)
+
+// How a sweep's trials are decoded: by the fp32 kernels (run_core) with a method and its alpha, or in the reference's own
+// arithmetic, the float64 ratio domain (ref64_run: product-sum only, so no method and no alpha).
+struct McDecode {
+    bool f64 = false;
+    int32_t method = SCALDPC_BP_PRODUCT_SUM;
+    float alpha = 0.0f;
+    static McDecode fp32(int32_t method, float alpha) { return {false, method, alpha}; }
+    static McDecode float64() { return {true}; }
+};
+
+// The noise on the checks of an HQC sweep.  table == false: every check is flipped with probability eps, and the decoder keeps
+// the handle's shared priors.  table: every check draws an outcome of the caller's table (include/scaldpc.h states the law),
+// which brings the reported bit, its prior into the call's plane, and -- with costs -- the oracle calls it spent.  probs is
+// float [K] for an fp32 decode (mc_hqc_law), probs64 double [K] for a float64 one (mc_hqc_law64).
+struct McHqcNoise {
+    bool table = false;
+    double eps = 0.0;
+    const double *weights = nullptr;
+    const uint8_t *flips = nullptr;
+    const float *probs = nullptr;
+    const double *probs64 = nullptr;
+    const int32_t *costs = nullptr;
+    int32_t K = 0;
+    bool counted() const { return costs != nullptr; }
+    static McHqcNoise flip(double eps) { return {false, eps}; }
+    static McHqcNoise drawn(const double *weights, const uint8_t *flips, const float *probs, const int32_t *costs, int32_t K)
+    {
+        return {true, 0.0, weights, flips, probs, nullptr, costs, K};
+    }
+    static McHqcNoise drawn(const double *weights, const uint8_t *flips, const double *probs64, const int32_t *costs, int32_t K)
+    {
+        return {true, 0.0, weights, flips, nullptr, probs64, costs, K};
+    }
+};
+
+// The outputs of an HQC sweep (null: not wanted; success is required).  The eps forms have the first four.
+struct McHqcOut {
+    uint8_t *success = nullptr;
+    int32_t *iters = nullptr;
+    uint8_t *msg = nullptr;
+    int32_t *y = nullptr;
+    uint8_t *outcome = nullptr;
+    int32_t *flips = nullptr, *cost = nullptr, *stats = nullptr;
+    uint8_t *bits = nullptr;
+};
 
 // the trial source's own refusals (scaldpc_trials.h); a list is looked at once batch is known to be positive
 int mc_trials_arg(const TrialSrc &ts, int32_t batch)
@@ -2505,19 +2577,32 @@ int mc_trials_arg(const TrialSrc &ts, int32_t batch)
     return 0;
 }
 
-int mc_common_args(scaldpc_bp *h, const TrialSrc &ts, int32_t batch, int32_t method, float alpha, uint32_t flags,
-                   uint8_t *out_success)
+// The refusals every sweep shares.  An fp32 entry looks at its pointers first and at method and alpha last; a float64 entry
+// (no method, no alpha) looks at the handle last, so that every one of its refusals can be seen without a device.
+int mc_args(const scaldpc_bp *h, const TrialSrc &ts, int32_t batch, const McDecode &d, uint32_t flags, const uint8_t *out_success)
 {
-    if (!h || !out_success) return fail(SCALDPC_EINVAL, "NULL argument");
+    const bool null_arg = !h || !out_success;
+    if (!d.f64 && null_arg) return fail(SCALDPC_EINVAL, "NULL argument");
     if (flags & ~(SCALDPC_F_EARLY_EXIT | SCALDPC_F_DEVICE_IO))
         return fail(SCALDPC_EINVAL, "flags: SCALDPC_F_EARLY_EXIT and SCALDPC_F_DEVICE_IO are taken");
     if (!ts.listed) SC_TRY(mc_trials_arg(ts, batch));
     if (batch <= 0) return fail(SCALDPC_EINVAL, "batch must be positive (got %d)", batch);
     if (ts.listed) SC_TRY(mc_trials_arg(ts, batch));
-    if (method != SCALDPC_BP_PRODUCT_SUM && method != SCALDPC_BP_MIN_SUM)
-        return fail(SCALDPC_EINVAL, "unknown bp method %d", method);
-    if (!(alpha >= 0.0f)) return fail(SCALDPC_EINVAL, "ms_scaling_factor must be >= 0");
+    if (null_arg) return fail(SCALDPC_EINVAL, "NULL argument");
+    if (d.f64) return 0;
+    if (d.method != SCALDPC_BP_PRODUCT_SUM && d.method != SCALDPC_BP_MIN_SUM)
+        return fail(SCALDPC_EINVAL, "unknown bp method %d", d.method);
+    if (!(d.alpha >= 0.0f)) return fail(SCALDPC_EINVAL, "ms_scaling_factor must be >= 0");
     return 0;
+}
+
+// the law of a table-form noise, in the decode's precision; every refusal of the table is here, and nothing touches the device
+int mc_noise_law(const McHqcNoise &nz, bool f64, int R, bool want_cost, McHqcLaw *law, McHqcLaw64 *law64)
+{
+    char why[160];
+    const int bad = f64 ? mc_hqc_law64(nz.weights, nz.flips, nz.probs64, nz.costs, nz.K, R, want_cost, law64, why, sizeof why)
+                        : mc_hqc_law(nz.weights, nz.flips, nz.probs, nz.costs, nz.K, R, want_cost, law, why, sizeof why);
+    return bad ? fail(SCALDPC_EINVAL, "%s", why) : 0;
 }
 
 // the Bernoulli thresholds of the shared priors (the FER sweeps' noise), built on first use
@@ -2556,16 +2641,18 @@ int mc_finish(scaldpc_bp *h, int batch, int T, int nv, bool dev_io, hipStream_t 
     return 0;
 }
 
-int mc_export_bits(scaldpc_bp *h, const u64 *planes, int batch, int T, bool dev_io, hipStream_t s, uint8_t *out)
+// planes (XOR xor_with, where given) -> uint8 [batch][n] for the caller.  last: no export of the call follows this one, so a
+// host export need not wait for its copy before the staging block d_out_bits is used again (mc_finish synchronises).
+int mc_export_bits(scaldpc_bp *h, const u64 *planes, const u64 *xor_with, int batch, int T, bool dev_io, bool last, hipStream_t s,
+                   uint8_t *out)
 {
     Outputs o, dev;
     o.bits = out;
     SC_TRY(stage_outputs(h, o, batch, dev_io, false, &dev));
-    hipLaunchKernelGGL(k_unpack_bits, dim3((h->n + 255) / 256, T), dim3(256), 0, s, planes, (const u64 *)nullptr, h->n,
-                       batch, dev.bits);
+    hipLaunchKernelGGL(k_unpack_bits, dim3((h->n + 255) / 256, T), dim3(256), 0, s, planes, xor_with, h->n, batch, dev.bits);
     LAUNCH_CHECK();
     SC_TRY(copy_outputs(h, o, dev, batch, dev_io, s));
-    if (!dev_io) SC_HIP(hipStreamSynchronize(s));  // d_out_bits is reused below
+    if (!dev_io && !last) SC_HIP(hipStreamSynchronize(s));  // d_out_bits is reused below
     return 0;
 }
 
@@ -2592,14 +2679,53 @@ int draw_hqc_secret(scaldpc_bp *h, int N, int omega, int batch, int T, const Dev
     LAUNCH_CHECK();
     return 0;
 }
-
-}  // namespace
-
-// scaldpc_mc_fer_run and scaldpc_mc_fer_run_at: one body, the trials from either source
-static int mc_fer_run_body(scaldpc_bp *h, const TrialSrc &ts, int32_t batch, uint64_t seed, int32_t max_iter_arg, int32_t method,
-                           float alpha, uint32_t flags, void *stream, uint8_t *out_success, int32_t *out_iters, uint8_t *out_error)
+// an outcome per check of the table's law: the reported bit into synd and its prior into the decode's plane -- the LLR into
+// h->d_pprior (k_mc_hqc_outcome), or the ratio into h->d_pratio (k_mc_hqc_outcome64)
+int draw_hqc_outcome(scaldpc_bp *h, bool f64, const McHqcLaw &law, const McHqcLaw64 &law64, int R, int batch, int T, const DeviceTrials &tr,
+                     unsigned k0, unsigned k1, int *acc_flips, int *acc_cost, uint8_t *dout, hipStream_t s)
 {
-    SC_TRY(mc_common_args(h, ts, batch, method, alpha, flags, out_success));
+    if (f64 && tr.ids)
+        return launch_mc_hqc_outcome64_at(law64, h->d_synd, h->d_pratio, R, batch, T, tr.ids, k0, k1, acc_flips, acc_cost, dout, s);
+    if (f64) return launch_mc_hqc_outcome64(law64, h->d_synd, h->d_pratio, R, batch, T, tr.first, k0, k1, acc_flips, acc_cost, dout, s);
+    if (tr.ids) return launch_mc_hqc_outcome_at(law, h->d_synd, h->d_pprior, R, batch, T, tr.ids, k0, k1, acc_flips, acc_cost, dout, s);
+    hipLaunchKernelGGL(k_mc_hqc_outcome, dim3((R + 63) / 64, T), dim3(256), 0, s, law, h->d_synd.get(), h->d_pprior.get(), R, batch,
+                       tr.first, k0, k1, acc_flips, acc_cost, dout);
+    LAUNCH_CHECK();
+    return 0;
+}
+
+// (mc_stage / mc_unstage, the staging of a sweep's optional outputs, are templates and stand with stage_outputs, ahead of the C ABI)
+
+// the iteration after which an early-exit float64 sweep hands its stragglers over (0: never)
+int mc_f64_handover_at(const scaldpc_bp *h) { return h->kn.compact_after < 0 ? 4 : h->kn.compact_after; }
+
+// Tile group and workspace of a sweep whose last prob_cols columns bring per-trial priors (0: the handle's shared priors):
+// size_call as decode_batch_impl sizes a soft call, or what scaldpc_bp_decode_batch_f64 sizes.
+int mc_size(scaldpc_bp *h, const Call &c, const McDecode &d, int prob_cols, bool early, int *G)
+{
+    if (!d.f64) return size_call(h, c, prob_cols, early, d.method, false, G);
+    *G = ref64_group(h, c.T);
+    return ref64_ensure(h, c.T, *G, c.max_iter, false, prob_cols);
+}
+
+// The decode of a sweep on the planes its trial kernels have staged (h->d_synd, and with prob_cols the prior plane of the
+// decode's precision): run_core, or scaldpc_bp_decode_batch_f64's loop (ref64_run), whose stragglers are handed over to dense
+// tiles once, after iteration "compact_after" (ref64_handover).
+int mc_decode(scaldpc_bp *h, const McDecode &d, int batch, int T, int G, int max_iter, bool early, int prob_cols, hipStream_t s)
+{
+    if (!d.f64)
+        return run_core(h, batch, T, G, max_iter, d.method, d.alpha, early, false, s, prob_cols ? h->d_pprior.get() : nullptr,
+                        prob_cols ? h->n - prob_cols : 0);
+    const Ref64Planes pl{h->d_synd, h->d_hard, h->d_done, h->d_conv, h->d_unsat, h->d_iters, nullptr,
+                         prob_cols ? h->d_pratio.get() : nullptr, prob_cols};
+    return ref64_run(h, pl, batch, T, G, max_iter, early, mc_f64_handover_at(h), s);
+}
+
+// Every FER entry: the trials from either source, decoded either way.
+int mc_fer_body(scaldpc_bp *h, const TrialSrc &ts, int32_t batch, uint64_t seed, int32_t max_iter_arg, const McDecode &d, uint32_t flags,
+                void *stream, uint8_t *out_success, int32_t *out_iters, uint8_t *out_error)
+{
+    SC_TRY(mc_args(h, ts, batch, d, flags, out_success));
     std::lock_guard<std::mutex> lk(h->mu);
     SC_TRY(check_usable(h));
     DeviceGuard dg(h->device);
@@ -2610,8 +2736,9 @@ static int mc_fer_run_body(scaldpc_bp *h, const TrialSrc &ts, int32_t batch, uin
     SyncOnError settle{s};
     SC_TRY(refresh_full(h));
     const bool dev_io = flags & SCALDPC_F_DEVICE_IO, early = flags & SCALDPC_F_EARLY_EXIT;
-    const int T = c.T, G = c.G, max_iter = c.max_iter;
-    SC_TRY(ensure_workspace(h, T, G, false, max_iter));
+    const int T = c.T, max_iter = c.max_iter;
+    int G;
+    SC_TRY(mc_size(h, c, d, 0, early, &G));
     SC_TRY(grow(h->d_mc, (size_t)T * h->n));
     SC_TRY(ensure_thresholds(h));
     DeviceTrials tr;
@@ -2620,105 +2747,27 @@ static int mc_fer_run_body(scaldpc_bp *h, const TrialSrc &ts, int32_t batch, uin
     // error ~ Bernoulli(p_i) per position (decode.py:166-167), syndrome = H error (decode.py:168)
     SC_TRY(draw_bernoulli(false, h->d_mc, h->n, batch, T, tr, k0, k1, (const u64 *)h->d_thr, 0ull, s));
     SC_TRY(launch_syndrome(h, h->d_mc, h->d_synd, T, s));
-    if (out_error) SC_TRY(mc_export_bits(h, h->d_mc, batch, T, dev_io, s, out_error));
-    SC_TRY(run_core(h, batch, T, G, max_iter, method, alpha, early, false, s));
+    if (out_error) SC_TRY(mc_export_bits(h, h->d_mc, nullptr, batch, T, dev_io, false, s, out_error));
+    SC_TRY(mc_decode(h, d, batch, T, G, max_iter, early, 0, s));
     // success iff decoding == error everywhere (decode.py:173-175)
     SC_TRY(mc_finish(h, batch, T, h->n, dev_io, s, out_success, out_iters));
     return settle.done();
 }
 
-int scaldpc_mc_fer_run(scaldpc_bp *h, int64_t first_trial, int32_t batch, uint64_t seed, int32_t max_iter_arg,
-                       int32_t method, float alpha, uint32_t flags, void *stream, uint8_t *out_success,
-                       int32_t *out_iters, uint8_t *out_error)
+// Every HQC entry.  The eps form flips each check with probability eps (k_mc_bernoulli<true>) and decodes on the handle's shared
+// priors; the table form draws an outcome per check conditional on its true bit (draw_hqc_outcome), which also fills the prior
+// plane of the check columns, and the decode is the soft call's, on that plane from column N on.  o.stats / o.bits: what
+// scaldpc_mc_hqc_run_stats adds (k_mc_hqc_stats on the planes the decode leaves; the decoded word as decode_batch_impl unpacks
+// it).  With an output null, nothing is launched, cleared or allocated for it; the eps form has no flip / cost accumulators.
+int mc_hqc_body(scaldpc_bp *h, const TrialSrc &ts, int32_t omega, const McHqcNoise &nz, int32_t batch, uint64_t seed, int32_t max_iter_arg,
+                const McDecode &d, uint32_t flags, void *stream, const McHqcOut &o)
 {
-    return mc_fer_run_body(h, TrialSrc::range(first_trial), batch, seed, max_iter_arg, method, alpha, flags, stream, out_success,
-                           out_iters, out_error);
-}
-
-int scaldpc_mc_fer_run_at(scaldpc_bp *h, const int64_t *trial_ids, int32_t batch, uint64_t seed, int32_t max_iter_arg,
-                          int32_t method, float alpha, uint32_t flags, void *stream, uint8_t *out_success, int32_t *out_iters,
-                          uint8_t *out_error)
-{
-    return mc_fer_run_body(h, TrialSrc::list(trial_ids), batch, seed, max_iter_arg, method, alpha, flags, stream, out_success,
-                           out_iters, out_error);
-}
-
-int scaldpc_mc_hqc_run(scaldpc_bp *h, int32_t omega, double eps, int64_t first_trial, int32_t batch, uint64_t seed,
-                       int32_t max_iter_arg, int32_t method, float alpha, uint32_t flags, void *stream,
-                       uint8_t *out_success, int32_t *out_iters, uint8_t *out_msg, int32_t *out_y)
-{
-    SC_TRY(mc_common_args(h, TrialSrc::range(first_trial), batch, method, alpha, flags, out_success));
-    std::lock_guard<std::mutex> lk(h->mu);
-    SC_TRY(check_usable(h));
-    DeviceGuard dg(h->device);
-    CacheBypass guard(h->async_used);
-    Call c;
-    SC_TRY(begin_call(h, batch, max_iter_arg, stream, &c));
-    const hipStream_t s = c.s;
-    SyncOnError settle{s};
-    SC_TRY(refresh_full(h));
-    if (h->identity_from < 0) return fail(SCALDPC_EINVAL, "parity-check matrix is not of the form [Hin | I] (hqc.py:680)");
-    const int N = h->identity_from;
-    if (omega < 0 || omega > N) return fail(SCALDPC_EINVAL, "omega must be in [0, N]");
-    if (!(eps >= 0.0 && eps <= 1.0)) return fail(SCALDPC_EINVAL, "eps must be a probability");
-    if ((size_t)omega * 64 * 4 > 64 * 1024) return fail(SCALDPC_EDEGREE, "omega %d too large for the LDS-resident sampler", omega);
-    const bool dev_io = flags & SCALDPC_F_DEVICE_IO, early = flags & SCALDPC_F_EARLY_EXIT;
-    const int T = c.T, G = c.G, max_iter = c.max_iter;
-    SC_TRY(ensure_workspace(h, T, G, false, max_iter));
-    SC_TRY(grow(h->d_mc, (size_t)T * h->n));
-    int *dy = nullptr;
-    if (out_y) {
-        dy = out_y;
-        if (!dev_io) {
-            SC_TRY(grow(h->d_ylist, (size_t)batch * std::max(omega, 1)));
-            dy = h->d_ylist;
-        }
-    }
-    const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
-    // x = [y | 0]: omega distinct positions;  checks = Hin y = H x  (hqc.py:1253-1257)
-    SC_HIP(hipMemsetAsync(h->d_mc, 0, sizeof(u64) * (size_t)T * h->n, s));
-    if (omega) {
-        hipLaunchKernelGGL(k_mc_hqc_secret, dim3(T), dim3(64), (size_t)omega * 64 * sizeof(int), s, h->d_mc, h->n, N, omega,
-                           batch, (long)first_trial, k0, k1, dy);
-        LAUNCH_CHECK();
-    }
-    SC_TRY(launch_syndrome(h, h->d_mc, h->d_synd, T, s));
-    // each oracle answer wrong with probability eps
-    hipLaunchKernelGGL(k_mc_bernoulli<true>, dim3((h->m + 63) / 64, T), dim3(256), 0, s, h->d_synd, h->m, batch,
-                       (long)first_trial, 0u, k0, k1, (const u64 *)nullptr, bernoulli_threshold(eps));
-    LAUNCH_CHECK();
-    // msg = [0]*N ++ checks (hqc.py:703-705); its syndrome under H = [Hin | I] is `checks` itself
-    SC_HIP(hipMemsetAsync(h->d_recv, 0, sizeof(u64) * (size_t)T * h->n, s));
-    SC_HIP(hipMemcpy2DAsync(h->d_recv + N, sizeof(u64) * h->n, h->d_synd, sizeof(u64) * h->m, sizeof(u64) * h->m, T,
-                            hipMemcpyDeviceToDevice, s));
-    if (out_msg) SC_TRY(mc_export_bits(h, h->d_recv, batch, T, dev_io, s, out_msg));
-    SC_TRY(run_core(h, batch, T, G, max_iter, method, alpha, early, false, s));
-    if (out_y && !dev_io) {
-        SC_HIP(hipMemcpyAsync(out_y, dy, sizeof(int) * (size_t)batch * omega, hipMemcpyDeviceToHost, s));
-    }
-    // decoded[:N] = e[:N] XOR msg[:N] = e[:N] must equal the indicator of y (hqc.py:742-749)
-    SC_TRY(mc_finish(h, batch, T, N, dev_io, s, out_success, out_iters));
-    return settle.done();
-}
-
-// scaldpc_mc_hqc_run up to the syndrome; then every check draws an outcome of the oracle conditional on its true bit
-// (k_mc_hqc_outcome in the place of k_mc_bernoulli<true>), which also fills the prior plane of the check columns, and the
-// decode is the soft call's: run_core on h->d_pprior from column N on, sized by size_call as decode_batch_impl sizes it.
-// out_stats / out_bits: what scaldpc_mc_hqc_run_stats adds (k_mc_hqc_stats on the planes the decode leaves; the decoded word as
-// decode_batch_impl unpacks it).  Both null -- scaldpc_mc_hqc_run_soft -- and nothing is launched, cleared or allocated for them.
-static int mc_hqc_run_soft_body(scaldpc_bp *h, int32_t omega, const double *weights, const uint8_t *flips, const float *probs,
-                                const int32_t *costs, int32_t K, const TrialSrc &ts, int32_t batch, uint64_t seed,
-                                int32_t max_iter_arg, int32_t method, float alpha, uint32_t flags, void *stream,
-                                uint8_t *out_success, int32_t *out_iters, uint8_t *out_msg, int32_t *out_y, uint8_t *out_outcome,
-                                int32_t *out_flips, int32_t *out_cost, int32_t *out_stats, uint8_t *out_bits)
-{
-    SC_TRY(mc_common_args(h, ts, batch, method, alpha, flags, out_success));
+    SC_TRY(mc_args(h, ts, batch, d, flags, o.success));
     std::lock_guard<std::mutex> lk(h->mu);
     SC_TRY(check_usable(h));
     McHqcLaw law;
-    char why[160];
-    if (mc_hqc_law(weights, flips, probs, costs, K, h->m, out_cost != nullptr, &law, why, sizeof why))
-        return fail(SCALDPC_EINVAL, "%s", why);
+    McHqcLaw64 law64;
+    if (nz.table) SC_TRY(mc_noise_law(nz, d.f64, h->m, o.cost != nullptr, &law, &law64));
     DeviceGuard dg(h->device);
     CacheBypass guard(h->async_used);
     Call c;
@@ -2729,34 +2778,19 @@ static int mc_hqc_run_soft_body(scaldpc_bp *h, int32_t omega, const double *weig
     if (h->identity_from < 0) return fail(SCALDPC_EINVAL, "parity-check matrix is not of the form [Hin | I] (hqc.py:680)");
     const int N = h->identity_from, R = h->m;
     if (omega < 0 || omega > N) return fail(SCALDPC_EINVAL, "omega must be in [0, N]");
+    if (!nz.table && !(nz.eps >= 0.0 && nz.eps <= 1.0)) return fail(SCALDPC_EINVAL, "eps must be a probability");
     if ((size_t)omega * 64 * 4 > 64 * 1024) return fail(SCALDPC_EDEGREE, "omega %d too large for the LDS-resident sampler", omega);
     const bool dev_io = flags & SCALDPC_F_DEVICE_IO, early = flags & SCALDPC_F_EARLY_EXIT;
-    const int T = c.T, max_iter = c.max_iter;
+    const int T = c.T, max_iter = c.max_iter, prob_cols = nz.table ? R : 0;
     int G;
-    SC_TRY(size_call(h, c, R, early, method, false, &G));
+    SC_TRY(mc_size(h, c, d, prob_cols, early, &G));
     SC_TRY(grow(h->d_mc, (size_t)T * h->n));
-    SC_TRY(grow(h->d_mc_acc, (size_t)2 * batch));
-    int *dy = nullptr;
-    if (out_y) {
-        dy = out_y;
-        if (!dev_io) {
-            SC_TRY(grow(h->d_ylist, (size_t)batch * std::max(omega, 1)));
-            dy = h->d_ylist;
-        }
-    }
-    uint8_t *dout = nullptr;
-    if (out_outcome) {
-        dout = out_outcome;
-        if (!dev_io) {
-            SC_TRY(grow(h->d_mc_outcome, (size_t)batch * R));
-            dout = h->d_mc_outcome;
-        }
-    }
-    int *dstats = out_stats;
-    if (out_stats && !dev_io) {
-        SC_TRY(grow(h->d_mc_stats, (size_t)5 * batch));
-        dstats = h->d_mc_stats;
-    }
+    if (nz.table) SC_TRY(grow(h->d_mc_acc, (size_t)2 * batch));
+    int *dy, *dstats;
+    uint8_t *dout;
+    SC_TRY(mc_stage(h->d_ylist, o.y, (size_t)batch * std::max(omega, 1), dev_io, &dy));
+    SC_TRY(mc_stage(h->d_mc_outcome, o.outcome, (size_t)batch * R, dev_io, &dout));
+    SC_TRY(mc_stage(h->d_mc_stats, o.stats, (size_t)5 * batch, dev_io, &dstats));
     DeviceTrials tr;
     SC_TRY(stage_trials(h->d_trial_ids, ts, batch, s, &tr));
     const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
@@ -2764,47 +2798,64 @@ static int mc_hqc_run_soft_body(scaldpc_bp *h, int32_t omega, const double *weig
     SC_HIP(hipMemsetAsync(h->d_mc, 0, sizeof(u64) * (size_t)T * h->n, s));
     if (omega) SC_TRY(draw_hqc_secret(h, N, omega, batch, T, tr, k0, k1, dy, s));
     SC_TRY(launch_syndrome(h, h->d_mc, h->d_synd, T, s));
-    // each check: an outcome of the (wrapped) oracle given its true bit -> the reported bit and its certainty (hqc.py:782-871)
-    int *const acc_flips = h->d_mc_acc, *const acc_cost = costs ? acc_flips + batch : nullptr;
-    SC_HIP(hipMemsetAsync(acc_flips, 0, sizeof(int) * (size_t)2 * batch, s));
-    if (tr.ids) {
-        SC_TRY(launch_mc_hqc_outcome_at(law, h->d_synd, h->d_pprior, R, batch, T, tr.ids, k0, k1, acc_flips, acc_cost, dout, s));
-    } else {
-        hipLaunchKernelGGL(k_mc_hqc_outcome, dim3((R + 63) / 64, T), dim3(256), 0, s, law, h->d_synd.get(), h->d_pprior.get(), R, batch,
-                           tr.first, k0, k1, acc_flips, acc_cost, dout);
-        LAUNCH_CHECK();
+    int *const acc_flips = h->d_mc_acc, *const acc_cost = nz.counted() ? acc_flips + batch : nullptr;
+    if (nz.table) {
+        // each check: an outcome of the (wrapped) oracle given its true bit -> the reported bit and its certainty (hqc.py:782-871)
+        SC_HIP(hipMemsetAsync(acc_flips, 0, sizeof(int) * (size_t)2 * batch, s));
+        SC_TRY(draw_hqc_outcome(h, d.f64, law, law64, R, batch, T, tr, k0, k1, acc_flips, acc_cost, dout, s));
+    } else {  // each oracle answer wrong with probability eps
+        SC_TRY(draw_bernoulli(true, h->d_synd, R, batch, T, tr, k0, k1, (const u64 *)nullptr, bernoulli_threshold(nz.eps), s));
     }
     // msg = [0]*N ++ reported (hqc.py:703-705); its syndrome under H = [Hin | I] is `reported` itself
     SC_HIP(hipMemsetAsync(h->d_recv, 0, sizeof(u64) * (size_t)T * h->n, s));
     SC_HIP(hipMemcpy2DAsync(h->d_recv + N, sizeof(u64) * h->n, h->d_synd, sizeof(u64) * h->m, sizeof(u64) * h->m, T,
                             hipMemcpyDeviceToDevice, s));
-    if (out_msg) SC_TRY(mc_export_bits(h, h->d_recv, batch, T, dev_io, s, out_msg));
-    SC_TRY(run_core(h, batch, T, G, max_iter, method, alpha, early, false, s, h->d_pprior.get(), N));
+    if (o.msg) SC_TRY(mc_export_bits(h, h->d_recv, nullptr, batch, T, dev_io, false, s, o.msg));
+    SC_TRY(mc_decode(h, d, batch, T, G, max_iter, early, prob_cols, s));
     const hipMemcpyKind back = dev_io ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    if (out_y && !dev_io) SC_HIP(hipMemcpyAsync(out_y, dy, sizeof(int) * (size_t)batch * omega, back, s));
-    if (out_outcome && !dev_io) SC_HIP(hipMemcpyAsync(out_outcome, dout, (size_t)batch * R, back, s));
-    if (out_flips) SC_HIP(hipMemcpyAsync(out_flips, acc_flips, sizeof(int) * (size_t)batch, back, s));
-    if (out_cost) SC_HIP(hipMemcpyAsync(out_cost, acc_cost, sizeof(int) * (size_t)batch, back, s));
-    if (out_stats) {
-        // the counters of hqc.py:709-758, from the decisions every path (compact passes included) has left in d_hard
+    SC_TRY(mc_unstage(o.y, dy, (size_t)batch * omega, dev_io, s));
+    SC_TRY(mc_unstage(o.outcome, dout, (size_t)batch * R, dev_io, s));
+    if (o.flips) SC_HIP(hipMemcpyAsync(o.flips, acc_flips, sizeof(int) * (size_t)batch, back, s));
+    if (o.cost) SC_HIP(hipMemcpyAsync(o.cost, acc_cost, sizeof(int) * (size_t)batch, back, s));
+    if (o.stats) {
+        // the counters of hqc.py:709-758, from the decisions every path (compact passes, the hand-over) has left in d_hard
         SC_HIP(hipMemsetAsync(dstats, 0, sizeof(int) * (size_t)5 * batch, s));
         hipLaunchKernelGGL(k_mc_hqc_stats, dim3((h->n + 4 * MC_STATS_RUN - 1) / (4 * MC_STATS_RUN), T), dim3(256), 0, s,
                            h->d_hard.get(), h->d_mc.get(), h->d_recv.get(), h->n, N, batch, dstats);
         LAUNCH_CHECK();
-        if (!dev_io) SC_HIP(hipMemcpyAsync(out_stats, dstats, sizeof(int) * (size_t)5 * batch, back, s));
+        SC_TRY(mc_unstage(o.stats, dstats, (size_t)5 * batch, dev_io, s));
     }
-    if (out_bits) {  // decoded = e XOR msg, as scaldpc_bp_decode_batch returns it for out_msg
-        Outputs o, dev;
-        o.bits = out_bits;
-        SC_TRY(stage_outputs(h, o, batch, dev_io, false, &dev));
-        hipLaunchKernelGGL(k_unpack_bits, dim3((h->n + 255) / 256, T), dim3(256), 0, s, h->d_hard, h->d_recv, h->n, batch,
-                           dev.bits);
-        LAUNCH_CHECK();
-        SC_TRY(copy_outputs(h, o, dev, batch, dev_io, s));
-    }
+    // decoded = e XOR msg, as the decode entry of the same precision returns it for out_msg
+    if (o.bits) SC_TRY(mc_export_bits(h, h->d_hard, h->d_recv, batch, T, dev_io, true, s, o.bits));
     // decoded[:N] = e[:N] XOR msg[:N] = e[:N] must equal the indicator of y (hqc.py:742-749)
-    SC_TRY(mc_finish(h, batch, T, N, dev_io, s, out_success, out_iters));
+    SC_TRY(mc_finish(h, batch, T, N, dev_io, s, o.success, o.iters));
     return settle.done();
+}
+
+}  // namespace
+
+int scaldpc_mc_fer_run(scaldpc_bp *h, int64_t first_trial, int32_t batch, uint64_t seed, int32_t max_iter_arg,
+                       int32_t method, float alpha, uint32_t flags, void *stream, uint8_t *out_success,
+                       int32_t *out_iters, uint8_t *out_error)
+{
+    return mc_fer_body(h, TrialSrc::range(first_trial), batch, seed, max_iter_arg, McDecode::fp32(method, alpha), flags, stream,
+                       out_success, out_iters, out_error);
+}
+
+int scaldpc_mc_fer_run_at(scaldpc_bp *h, const int64_t *trial_ids, int32_t batch, uint64_t seed, int32_t max_iter_arg,
+                          int32_t method, float alpha, uint32_t flags, void *stream, uint8_t *out_success, int32_t *out_iters,
+                          uint8_t *out_error)
+{
+    return mc_fer_body(h, TrialSrc::list(trial_ids), batch, seed, max_iter_arg, McDecode::fp32(method, alpha), flags, stream,
+                       out_success, out_iters, out_error);
+}
+
+int scaldpc_mc_hqc_run(scaldpc_bp *h, int32_t omega, double eps, int64_t first_trial, int32_t batch, uint64_t seed,
+                       int32_t max_iter_arg, int32_t method, float alpha, uint32_t flags, void *stream,
+                       uint8_t *out_success, int32_t *out_iters, uint8_t *out_msg, int32_t *out_y)
+{
+    return mc_hqc_body(h, TrialSrc::range(first_trial), omega, McHqcNoise::flip(eps), batch, seed, max_iter_arg,
+                       McDecode::fp32(method, alpha), flags, stream, {out_success, out_iters, out_msg, out_y});
 }
 
 int scaldpc_mc_hqc_run_soft(scaldpc_bp *h, int32_t omega, const double *weights, const uint8_t *flips, const float *probs,
@@ -2813,9 +2864,9 @@ int scaldpc_mc_hqc_run_soft(scaldpc_bp *h, int32_t omega, const double *weights,
                             uint8_t *out_success, int32_t *out_iters, uint8_t *out_msg, int32_t *out_y, uint8_t *out_outcome,
                             int32_t *out_flips, int32_t *out_cost)
 {
-    return mc_hqc_run_soft_body(h, omega, weights, flips, probs, costs, K, TrialSrc::range(first_trial), batch, seed, max_iter_arg,
-                                method, alpha, flags, stream, out_success, out_iters, out_msg, out_y, out_outcome, out_flips, out_cost,
-                                nullptr, nullptr);
+    return mc_hqc_body(h, TrialSrc::range(first_trial), omega, McHqcNoise::drawn(weights, flips, probs, costs, K), batch, seed,
+                       max_iter_arg, McDecode::fp32(method, alpha), flags, stream,
+                       {out_success, out_iters, out_msg, out_y, out_outcome, out_flips, out_cost});
 }
 
 int scaldpc_mc_hqc_run_stats(scaldpc_bp *h, int32_t omega, const double *weights, const uint8_t *flips, const float *probs,
@@ -2825,9 +2876,9 @@ int scaldpc_mc_hqc_run_stats(scaldpc_bp *h, int32_t omega, const double *weights
                              int32_t *out_flips, int32_t *out_cost, int32_t *out_stats, uint8_t *out_bits)
 {
     if (!out_stats) return fail(SCALDPC_EINVAL, "out_stats is NULL");
-    return mc_hqc_run_soft_body(h, omega, weights, flips, probs, costs, K, TrialSrc::range(first_trial), batch, seed, max_iter_arg,
-                                method, alpha, flags, stream, out_success, out_iters, out_msg, out_y, out_outcome, out_flips, out_cost,
-                                out_stats, out_bits);
+    return mc_hqc_body(h, TrialSrc::range(first_trial), omega, McHqcNoise::drawn(weights, flips, probs, costs, K), batch, seed,
+                       max_iter_arg, McDecode::fp32(method, alpha), flags, stream,
+                       {out_success, out_iters, out_msg, out_y, out_outcome, out_flips, out_cost, out_stats, out_bits});
 }
 
 // (out_stats may be NULL here, as in the float64 entry: with it NULL this is scaldpc_mc_hqc_run_soft on chosen trials)
@@ -2837,208 +2888,33 @@ int scaldpc_mc_hqc_run_stats_at(scaldpc_bp *h, int32_t omega, const double *weig
                                 uint8_t *out_success, int32_t *out_iters, uint8_t *out_msg, int32_t *out_y, uint8_t *out_outcome,
                                 int32_t *out_flips, int32_t *out_cost, int32_t *out_stats, uint8_t *out_bits)
 {
-    return mc_hqc_run_soft_body(h, omega, weights, flips, probs, costs, K, TrialSrc::list(trial_ids), batch, seed, max_iter_arg,
-                                method, alpha, flags, stream, out_success, out_iters, out_msg, out_y, out_outcome, out_flips, out_cost,
-                                out_stats, out_bits);
+    return mc_hqc_body(h, TrialSrc::list(trial_ids), omega, McHqcNoise::drawn(weights, flips, probs, costs, K), batch, seed,
+                       max_iter_arg, McDecode::fp32(method, alpha), flags, stream,
+                       {out_success, out_iters, out_msg, out_y, out_outcome, out_flips, out_cost, out_stats, out_bits});
 }
 
-// ---------------------------------------------------------------------------
-// The same sweeps decoded in the reference's own arithmetic (float64 ratio domain): the trials are drawn by the kernels above --
-// precision is a property of the decode, not of the trial -- and decoded by scaldpc_bp_decode_batch_f64's loop (ref64_run), whose
-// stragglers are handed over to dense tiles once, after iteration "compact_after" (ref64_handover).
-// ---------------------------------------------------------------------------
-namespace {
-
-// The refusals the float64 sweeps share with the fp32 entries (there is no method and no alpha: the form is product-sum only).
-// The handle is looked at last, so that every one of them can be seen without a device.
-int mc_f64_args(const scaldpc_bp *h, const TrialSrc &ts, int32_t batch, uint32_t flags, const uint8_t *out_success)
-{
-    if (flags & ~(SCALDPC_F_EARLY_EXIT | SCALDPC_F_DEVICE_IO))
-        return fail(SCALDPC_EINVAL, "flags: SCALDPC_F_EARLY_EXIT and SCALDPC_F_DEVICE_IO are taken");
-    if (!ts.listed) SC_TRY(mc_trials_arg(ts, batch));
-    if (batch <= 0) return fail(SCALDPC_EINVAL, "batch must be positive (got %d)", batch);
-    if (ts.listed) SC_TRY(mc_trials_arg(ts, batch));
-    if (!h || !out_success) return fail(SCALDPC_EINVAL, "NULL argument");
-    return 0;
-}
-
-// the iteration after which an early-exit float64 sweep hands its stragglers over (0: never)
-int mc_f64_handover_at(const scaldpc_bp *h) { return h->kn.compact_after < 0 ? 4 : h->kn.compact_after; }
-
-// the decode of a float64 sweep on the planes its trial kernels have staged (h->d_synd; pratio = h->d_pratio or null)
-int mc_run_f64(scaldpc_bp *h, int batch, int T, int G, int max_iter, bool early, const double *pratio, int prob_cols, hipStream_t s)
-{
-    const Ref64Planes pl{h->d_synd, h->d_hard, h->d_done, h->d_conv, h->d_unsat, h->d_iters, nullptr, pratio, prob_cols};
-    return ref64_run(h, pl, batch, T, G, max_iter, early, mc_f64_handover_at(h), s);
-}
-
-// Both float64 HQC sweeps.  law = null: scaldpc_mc_hqc_run_f64 -- every check flipped with probability eps, the handle's shared
-// float64 priors.  Otherwise scaldpc_mc_hqc_run_stats_f64: every check draws an outcome of the table, which brings its ratio
-// into the plane h->d_pratio (k_mc_hqc_outcome64), and the five outputs from out_outcome on may be asked for.
-int mc_hqc_run_f64_body(scaldpc_bp *h, int32_t omega, const McHqcLaw64 *law, double eps, bool counted, const TrialSrc &ts,
-                        int32_t batch, uint64_t seed, int32_t max_iter_arg, uint32_t flags, void *stream, uint8_t *out_success,
-                        int32_t *out_iters, uint8_t *out_msg, int32_t *out_y, uint8_t *out_outcome, int32_t *out_flips,
-                        int32_t *out_cost, int32_t *out_stats, uint8_t *out_bits)
-{
-    DeviceGuard dg(h->device);
-    CacheBypass guard(h->async_used);
-    Call c;
-    SC_TRY(begin_call(h, batch, max_iter_arg, stream, &c));
-    const hipStream_t s = c.s;
-    SyncOnError settle{s};
-    SC_TRY(refresh_full(h));
-    if (h->identity_from < 0) return fail(SCALDPC_EINVAL, "parity-check matrix is not of the form [Hin | I] (hqc.py:680)");
-    const int N = h->identity_from, R = h->m;
-    if (omega < 0 || omega > N) return fail(SCALDPC_EINVAL, "omega must be in [0, N]");
-    if (!law && !(eps >= 0.0 && eps <= 1.0)) return fail(SCALDPC_EINVAL, "eps must be a probability");
-    if ((size_t)omega * 64 * 4 > 64 * 1024) return fail(SCALDPC_EDEGREE, "omega %d too large for the LDS-resident sampler", omega);
-    const bool dev_io = flags & SCALDPC_F_DEVICE_IO, early = flags & SCALDPC_F_EARLY_EXIT;
-    const int T = c.T, max_iter = c.max_iter, G = ref64_group(h, T);
-    SC_TRY(ref64_ensure(h, T, G, max_iter, false, law ? R : 0));
-    SC_TRY(grow(h->d_mc, (size_t)T * h->n));
-    if (law) SC_TRY(grow(h->d_mc_acc, (size_t)2 * batch));
-    int *dy = nullptr;
-    if (out_y) {
-        dy = out_y;
-        if (!dev_io) {
-            SC_TRY(grow(h->d_ylist, (size_t)batch * std::max(omega, 1)));
-            dy = h->d_ylist;
-        }
-    }
-    uint8_t *dout = out_outcome;
-    if (out_outcome && !dev_io) {
-        SC_TRY(grow(h->d_mc_outcome, (size_t)batch * R));
-        dout = h->d_mc_outcome;
-    }
-    int *dstats = out_stats;
-    if (out_stats && !dev_io) {
-        SC_TRY(grow(h->d_mc_stats, (size_t)5 * batch));
-        dstats = h->d_mc_stats;
-    }
-    DeviceTrials tr;
-    SC_TRY(stage_trials(h->d_trial_ids, ts, batch, s, &tr));
-    const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
-    // x = [y | 0]: omega distinct positions;  true bits c = Hin y = H x  (hqc.py:1253-1257)
-    SC_HIP(hipMemsetAsync(h->d_mc, 0, sizeof(u64) * (size_t)T * h->n, s));
-    if (omega) SC_TRY(draw_hqc_secret(h, N, omega, batch, T, tr, k0, k1, dy, s));
-    SC_TRY(launch_syndrome(h, h->d_mc, h->d_synd, T, s));
-    int *const acc_flips = h->d_mc_acc, *const acc_cost = counted ? acc_flips + batch : nullptr;
-    if (law) {  // an outcome per check: the reported bit and the ratio of its certainty
-        SC_HIP(hipMemsetAsync(acc_flips, 0, sizeof(int) * (size_t)2 * batch, s));
-        if (tr.ids)
-            SC_TRY(launch_mc_hqc_outcome64_at(*law, h->d_synd, h->d_pratio, R, batch, T, tr.ids, k0, k1, acc_flips, acc_cost, dout, s));
-        else
-            SC_TRY(launch_mc_hqc_outcome64(*law, h->d_synd, h->d_pratio, R, batch, T, tr.first, k0, k1, acc_flips, acc_cost, dout, s));
-    } else {  // each oracle answer wrong with probability eps
-        SC_TRY(draw_bernoulli(true, h->d_synd, R, batch, T, tr, k0, k1, (const u64 *)nullptr, bernoulli_threshold(eps), s));
-    }
-    // msg = [0]*N ++ reported (hqc.py:703-705); its syndrome under H = [Hin | I] is `reported` itself
-    SC_HIP(hipMemsetAsync(h->d_recv, 0, sizeof(u64) * (size_t)T * h->n, s));
-    SC_HIP(hipMemcpy2DAsync(h->d_recv + N, sizeof(u64) * h->n, h->d_synd, sizeof(u64) * h->m, sizeof(u64) * h->m, T,
-                            hipMemcpyDeviceToDevice, s));
-    if (out_msg) SC_TRY(mc_export_bits(h, h->d_recv, batch, T, dev_io, s, out_msg));
-    SC_TRY(mc_run_f64(h, batch, T, G, max_iter, early, law ? h->d_pratio.get() : nullptr, law ? R : 0, s));
-    const hipMemcpyKind back = dev_io ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    if (out_y && !dev_io) SC_HIP(hipMemcpyAsync(out_y, dy, sizeof(int) * (size_t)batch * omega, back, s));
-    if (out_outcome && !dev_io) SC_HIP(hipMemcpyAsync(out_outcome, dout, (size_t)batch * R, back, s));
-    if (out_flips) SC_HIP(hipMemcpyAsync(out_flips, acc_flips, sizeof(int) * (size_t)batch, back, s));
-    if (out_cost) SC_HIP(hipMemcpyAsync(out_cost, acc_cost, sizeof(int) * (size_t)batch, back, s));
-    if (out_stats) {  // the counters of hqc.py:709-758, from the decisions the loop and the hand-over have left in d_hard
-        SC_HIP(hipMemsetAsync(dstats, 0, sizeof(int) * (size_t)5 * batch, s));
-        hipLaunchKernelGGL(k_mc_hqc_stats, dim3((h->n + 4 * MC_STATS_RUN - 1) / (4 * MC_STATS_RUN), T), dim3(256), 0, s,
-                           h->d_hard.get(), h->d_mc.get(), h->d_recv.get(), h->n, N, batch, dstats);
-        LAUNCH_CHECK();
-        if (!dev_io) SC_HIP(hipMemcpyAsync(out_stats, dstats, sizeof(int) * (size_t)5 * batch, back, s));
-    }
-    if (out_bits) {  // decoded = e XOR msg, as scaldpc_bp_decode_batch_f64 returns it for out_msg
-        Outputs o, dev;
-        o.bits = out_bits;
-        SC_TRY(stage_outputs(h, o, batch, dev_io, false, &dev));
-        hipLaunchKernelGGL(k_unpack_bits, dim3((h->n + 255) / 256, T), dim3(256), 0, s, h->d_hard, h->d_recv, h->n, batch,
-                           dev.bits);
-        LAUNCH_CHECK();
-        SC_TRY(copy_outputs(h, o, dev, batch, dev_io, s));
-    }
-    // decoded[:N] = e[:N] XOR msg[:N] = e[:N] must equal the indicator of y (hqc.py:742-749)
-    SC_TRY(mc_finish(h, batch, T, N, dev_io, s, out_success, out_iters));
-    return settle.done();
-}
-
-}  // namespace
-
-// scaldpc_mc_fer_run_f64 and scaldpc_mc_fer_run_at_f64: one body, the trials from either source
-static int mc_fer_run_f64_body(scaldpc_bp *h, const TrialSrc &ts, int32_t batch, uint64_t seed, int32_t max_iter_arg, uint32_t flags,
-                               void *stream, uint8_t *out_success, int32_t *out_iters, uint8_t *out_error)
-{
-    SC_TRY(mc_f64_args(h, ts, batch, flags, out_success));
-    std::lock_guard<std::mutex> lk(h->mu);
-    SC_TRY(check_usable(h));
-    DeviceGuard dg(h->device);
-    CacheBypass guard(h->async_used);
-    Call c;
-    SC_TRY(begin_call(h, batch, max_iter_arg, stream, &c));
-    const hipStream_t s = c.s;
-    SyncOnError settle{s};
-    SC_TRY(refresh_full(h));
-    const bool dev_io = flags & SCALDPC_F_DEVICE_IO, early = flags & SCALDPC_F_EARLY_EXIT;
-    const int T = c.T, max_iter = c.max_iter, G = ref64_group(h, T);
-    SC_TRY(ref64_ensure(h, T, G, max_iter, false, 0));
-    SC_TRY(grow(h->d_mc, (size_t)T * h->n));
-    SC_TRY(ensure_thresholds(h));
-    DeviceTrials tr;
-    SC_TRY(stage_trials(h->d_trial_ids, ts, batch, s, &tr));
-    const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
-    // error ~ Bernoulli(p_i) per position (decode.py:166-167), syndrome = H error (decode.py:168)
-    SC_TRY(draw_bernoulli(false, h->d_mc, h->n, batch, T, tr, k0, k1, (const u64 *)h->d_thr, 0ull, s));
-    SC_TRY(launch_syndrome(h, h->d_mc, h->d_synd, T, s));
-    if (out_error) SC_TRY(mc_export_bits(h, h->d_mc, batch, T, dev_io, s, out_error));
-    SC_TRY(mc_run_f64(h, batch, T, G, max_iter, early, nullptr, 0, s));
-    // success iff decoding == error everywhere (decode.py:173-175)
-    SC_TRY(mc_finish(h, batch, T, h->n, dev_io, s, out_success, out_iters));
-    return settle.done();
-}
+// The same sweeps decoded in the reference's own arithmetic (McDecode::float64())
 
 int scaldpc_mc_fer_run_f64(scaldpc_bp *h, int64_t first_trial, int32_t batch, uint64_t seed, int32_t max_iter_arg, uint32_t flags,
                            void *stream, uint8_t *out_success, int32_t *out_iters, uint8_t *out_error)
 {
-    return mc_fer_run_f64_body(h, TrialSrc::range(first_trial), batch, seed, max_iter_arg, flags, stream, out_success, out_iters,
-                               out_error);
+    return mc_fer_body(h, TrialSrc::range(first_trial), batch, seed, max_iter_arg, McDecode::float64(), flags, stream, out_success,
+                       out_iters, out_error);
 }
 
 int scaldpc_mc_fer_run_at_f64(scaldpc_bp *h, const int64_t *trial_ids, int32_t batch, uint64_t seed, int32_t max_iter_arg,
                               uint32_t flags, void *stream, uint8_t *out_success, int32_t *out_iters, uint8_t *out_error)
 {
-    return mc_fer_run_f64_body(h, TrialSrc::list(trial_ids), batch, seed, max_iter_arg, flags, stream, out_success, out_iters,
-                               out_error);
+    return mc_fer_body(h, TrialSrc::list(trial_ids), batch, seed, max_iter_arg, McDecode::float64(), flags, stream, out_success,
+                       out_iters, out_error);
 }
 
 int scaldpc_mc_hqc_run_f64(scaldpc_bp *h, int32_t omega, double eps, int64_t first_trial, int32_t batch, uint64_t seed,
                            int32_t max_iter_arg, uint32_t flags, void *stream, uint8_t *out_success, int32_t *out_iters,
                            uint8_t *out_msg, int32_t *out_y)
 {
-    SC_TRY(mc_f64_args(h, TrialSrc::range(first_trial), batch, flags, out_success));
-    std::lock_guard<std::mutex> lk(h->mu);
-    SC_TRY(check_usable(h));
-    return mc_hqc_run_f64_body(h, omega, nullptr, eps, false, TrialSrc::range(first_trial), batch, seed, max_iter_arg, flags, stream, out_success,
-                               out_iters, out_msg, out_y, nullptr, nullptr, nullptr, nullptr, nullptr);
-}
-
-// scaldpc_mc_hqc_run_stats_f64 and scaldpc_mc_hqc_run_stats_at_f64: one body, the trials from either source
-static int mc_hqc_run_stats_f64_body(scaldpc_bp *h, int32_t omega, const double *weights, const uint8_t *flips, const double *probs,
-                                     const int32_t *costs, int32_t K, const TrialSrc &ts, int32_t batch, uint64_t seed,
-                                     int32_t max_iter_arg, uint32_t flags, void *stream, uint8_t *out_success, int32_t *out_iters,
-                                     uint8_t *out_msg, int32_t *out_y, uint8_t *out_outcome, int32_t *out_flips, int32_t *out_cost,
-                                     int32_t *out_stats, uint8_t *out_bits)
-{
-    SC_TRY(mc_f64_args(h, ts, batch, flags, out_success));
-    std::lock_guard<std::mutex> lk(h->mu);
-    SC_TRY(check_usable(h));
-    McHqcLaw64 law;
-    char why[160];
-    if (mc_hqc_law64(weights, flips, probs, costs, K, h->m, out_cost != nullptr, &law, why, sizeof why))
-        return fail(SCALDPC_EINVAL, "%s", why);
-    return mc_hqc_run_f64_body(h, omega, &law, 0.0, costs != nullptr, ts, batch, seed, max_iter_arg, flags, stream,
-                               out_success, out_iters, out_msg, out_y, out_outcome, out_flips, out_cost, out_stats, out_bits);
+    return mc_hqc_body(h, TrialSrc::range(first_trial), omega, McHqcNoise::flip(eps), batch, seed, max_iter_arg, McDecode::float64(),
+                       flags, stream, {out_success, out_iters, out_msg, out_y});
 }
 
 int scaldpc_mc_hqc_run_stats_f64(scaldpc_bp *h, int32_t omega, const double *weights, const uint8_t *flips, const double *probs,
@@ -3047,9 +2923,9 @@ int scaldpc_mc_hqc_run_stats_f64(scaldpc_bp *h, int32_t omega, const double *wei
                                  uint8_t *out_msg, int32_t *out_y, uint8_t *out_outcome, int32_t *out_flips, int32_t *out_cost,
                                  int32_t *out_stats, uint8_t *out_bits)
 {
-    return mc_hqc_run_stats_f64_body(h, omega, weights, flips, probs, costs, K, TrialSrc::range(first_trial), batch, seed, max_iter_arg,
-                                     flags, stream, out_success, out_iters, out_msg, out_y, out_outcome, out_flips, out_cost, out_stats,
-                                     out_bits);
+    return mc_hqc_body(h, TrialSrc::range(first_trial), omega, McHqcNoise::drawn(weights, flips, probs, costs, K), batch, seed,
+                       max_iter_arg, McDecode::float64(), flags, stream,
+                       {out_success, out_iters, out_msg, out_y, out_outcome, out_flips, out_cost, out_stats, out_bits});
 }
 
 int scaldpc_mc_hqc_run_stats_at_f64(scaldpc_bp *h, int32_t omega, const double *weights, const uint8_t *flips, const double *probs,
@@ -3058,9 +2934,9 @@ int scaldpc_mc_hqc_run_stats_at_f64(scaldpc_bp *h, int32_t omega, const double *
                                     uint8_t *out_msg, int32_t *out_y, uint8_t *out_outcome, int32_t *out_flips, int32_t *out_cost,
                                     int32_t *out_stats, uint8_t *out_bits)
 {
-    return mc_hqc_run_stats_f64_body(h, omega, weights, flips, probs, costs, K, TrialSrc::list(trial_ids), batch, seed, max_iter_arg,
-                                     flags, stream, out_success, out_iters, out_msg, out_y, out_outcome, out_flips, out_cost, out_stats,
-                                     out_bits);
+    return mc_hqc_body(h, TrialSrc::list(trial_ids), omega, McHqcNoise::drawn(weights, flips, probs, costs, K), batch, seed,
+                       max_iter_arg, McDecode::float64(), flags, stream,
+                       {out_success, out_iters, out_msg, out_y, out_outcome, out_flips, out_cost, out_stats, out_bits});
 }
 
 int scaldpc_bp_configure(scaldpc_bp *h, const char *key, const char *value)

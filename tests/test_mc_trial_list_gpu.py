@@ -359,6 +359,26 @@ def test_refusals_of_the_binary_entries(entry):
         assert after[k] == before[k], k
 
 
+@pytest.mark.parametrize("entry", ["fer", "soft", "fer64", "soft64"])
+def test_binary_device_pointers_against_the_host_call(entry):
+    """SCALDPC_F_DEVICE_IO on the four binary list entries with every optional output asked for: each device array holds what
+    the host-pointer call of the same entry returns (106 slots: a full tile and a ragged one), and an entry writes only its own."""
+    import torch
+
+    name = "F" if entry.startswith("fer") else "H2"
+    dec = _decoder(name, "product_sum")
+    raw = dict(method=lib.BP_PRODUCT_SUM)
+    host = _outs(IDS.size, dec.n, mc_ref.instance(name)["omega"], dec.m)
+    written = ("success", "iters", "bits_in") if entry.startswith("fer") else tuple(host)
+    assert _raw_bp(dec, entry, host, IDS, **raw) == lib.OK
+    assert not any(_intact({k: host[k]}) for k in written) and _intact({k: v for k, v in host.items() if k not in written})
+    dev = {k: torch.from_numpy(v).cuda() for k, v in _outs(IDS.size, dec.n, mc_ref.instance(name)["omega"], dec.m).items()}
+    torch.cuda.synchronize()  # stream = NULL means the handle's own stream: order it after torch's copies
+    assert _raw_bp(dec, entry, {k: v.data_ptr() for k, v in dev.items()}, IDS, flags=lib.F_EARLY_EXIT | lib.F_DEVICE_IO, **raw) == lib.OK
+    same({k: v.cpu().numpy() for k, v in dev.items()}, host, f"{entry}, device pointers")
+    dec.close()
+
+
 @pytest.mark.parametrize("entry", ["levels", "secret"])
 def test_refusals_of_the_qary_entries(entry):
     c, _, _, _ = case1()
