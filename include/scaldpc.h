@@ -301,9 +301,22 @@ int scaldpc_bp_last_stats(scaldpc_bp *h, int64_t *out);
  * (entry point added under SCALDPC_VERSION 104: nothing that existed changed) */
 #define SCALDPC_SCHEDULE_WORDS 24
 int scaldpc_bp_last_schedule(scaldpc_bp *h, int64_t *out);
+/* Settled codewords in the last decode or Monte-Carlo call (knob "settle"; host values, no device work).  A fixed-iteration
+ * call on the record-form min-sum kernels tracks, per 64-codeword tile, the first iteration t >= 3 at which the tile is
+ * FROZEN: check pass t stored the records and arg-min bytes it overwrote and variable pass t - 1 the sign masks it
+ * overwrote, bit for bit, for every real codeword of the tile -- from there on every pass repeats the one before.
+ *   frozen_at[min(cap, tiles)]  the frozen-at number of every tile, 0 = it never froze
+ *   info[0]  tiles of the call (0 = the call did not track: early exit, another path or form, "settle" 0 -- which is
+ *            also what the default means on a graph that is not [Hin | I] --, max_iter below the first test, an
+ *            SCALDPC_F_ASYNC call)
+ *   info[1]  kernel launches the settle horizon kept from being enqueued
+ *   info[2]  tiles decoded again because they were not frozen by the horizon
+ *   info[3]  the horizon K the call ran with (0 = none: device-side skipping only)
+ * Results never depend on any of this. */
+int scaldpc_bp_last_settle(scaldpc_bp *h, int32_t *frozen_at, int32_t cap, int64_t *info);
 /* Tuning / test knobs of one handle.  A new handle takes its defaults from the environment ONCE, at
  * creation (SCALDPC_PATH, SCALDPC_SPLIT, SCALDPC_GROUP_MB, SCALDPC_EL_MAX, SCALDPC_COMPACT_AFTER,
- * SCALDPC_FIRST_FUSED, SCALDPC_FUSE_TEST, SCALDPC_MINSUM_REC); the decode entry points never read the environment.
+ * SCALDPC_FIRST_FUSED, SCALDPC_FUSE_TEST, SCALDPC_MINSUM_REC, SCALDPC_SETTLE, SCALDPC_SETTLE_HORIZON); the decode entry points never read the environment.
  * Every knob selects a path, a size or a form that some graph or call still falls back to; the switches of variants
  * that were measured and rejected (round 3's test_overlap, var_form, rec_maskpos, rec_xmap, rec_sc1, fuse_finalize,
  * speculate, minsum_loop) are gone with their code (round 4; numbers in profiles/HISTORY.md), and so are the A/B-only
@@ -328,6 +341,18 @@ int scaldpc_bp_last_schedule(scaldpc_bp *h, int64_t *out);
  *                   zero-syndrome codeword) and the row's syndrome bit; 0 = check pass (reading the priors) + plain
  *                   variable pass, both in the message form (what graphs with a row or column wider than 64 use anyway,
  *                   and every scaldpc_bp_decode_batch_soft call: the table is a function of the shared priors).
+ *   "settle"        fixed-iteration calls on the record-form min-sum kernels, whose message state reaches a bit-exact
+ *                   fixed point on graphs with degree-1 columns: 0 = every pass runs; 1 = check and variable passes
+ *                   return at once for tiles that are frozen (scaldpc_bp_last_settle), the last variable pass and the
+ *                   final test run as ever (the skipping needs no host; for the query the tiles' words are read back
+ *                   with one synchronise at the end of the call, except in an SCALDPC_F_ASYNC call); 2 = and from a handle's second call on the same priors, max_iter
+ *                   and alpha a tile group enqueues only iterations 1 ... K, K = largest frozen-at number of the last
+ *                   call + 2, and its closing passes -- while at least 7/8 of the tiles freeze by K and 2 K < max_iter.
+ *                   Tiles not frozen by K are decoded again with all their iterations.
+ *                   -1 (default) = 2 on a graph H = [Hin | I] (every row has an edge into a column of degree 1, which
+ *                   is what bounds the messages), 0 on any other graph: it has no reason to settle and would only pay
+ *                   for the compares.
+ *   "settle_horizon" K > 0: that horizon, forced (0 = learned)
  *   Results never depend on any of these. */
 int scaldpc_bp_configure(scaldpc_bp *h, const char *key, const char *value);
 /* Where a handle lives, out[4]: the device it was created on; the device (hipPointerGetAttributes)

@@ -459,12 +459,25 @@ class BpDecoder:
                 "left_open": w[10], "fixed_chained": w[11], "clears": w[12], "open_at_clear": w[13], "ring_rows": w[14],
                 "row_parallel_polls": w[15], "ring_takes": w[16]}  # fmt: skip
 
+    def last_settle(self):
+        """Settled codewords in the last call (scaldpc_bp_last_settle): frozen_at = per 64-codeword tile the first iteration
+        from which every pass repeated the one before (0 = never; empty = the call did not track), launches_saved = kernel
+        launches the settle horizon did not enqueue, tiles_rerun = tiles decoded again because the horizon was too short for
+        them, horizon = the K the call ran with (0 = none)."""
+        info = (C.c_int64 * 4)()
+        _lib.check(self._lib.scaldpc_bp_last_settle(self._h, None, 0, info))
+        tiles = int(info[0])
+        at = (C.c_int32 * max(tiles, 1))()
+        _lib.check(self._lib.scaldpc_bp_last_settle(self._h, at, tiles, info))
+        return {"frozen_at": [int(x) for x in at[:tiles]], "launches_saved": int(info[1]), "tiles_rerun": int(info[2]),
+                "horizon": int(info[3])}
+
     def last_row_parallel(self):
         return self.last_stats()["row_parallel"]
 
     def configure(self, **knobs):
         """Tuning / test knobs of this decoder (include/scaldpc.h, scaldpc_bp_configure): path, split,
-        group_mb, el_max, compact_after, first_fused, fuse_test, minsum_rec.  A new decoder takes its
+        group_mb, el_max, compact_after, first_fused, fuse_test, minsum_rec, settle, settle_horizon.  A new decoder takes its
         defaults from the SCALDPC_* environment once, at construction; results never depend on them."""
         for k, v in knobs.items():
             _lib.check(self._lib.scaldpc_bp_configure(self._h, k.encode(), str(v).encode()))

@@ -106,6 +106,8 @@ struct Knobs {
     int fuse_test = 1;        // early-exit tile loop: the convergence test of iteration it rides on the check pass of it + 1 wherever the host does not need the verdict in between
     int first_fused = 1;      // iteration 1 of the tile kernels without its check pass (k_var_first from the first-message table); 0 = check pass + plain variable pass
     int minsum_rec = 1;       // min-sum on the tile kernels: check pass writes per-row records + lane masks instead of messages (k_check_minsum_rec / k_var_rec); 0 = message form
+    int settle = -1;          // fixed-iteration record-form calls: -1 = 2 on a graph [Hin | I], 0 on any other (settle_mode); 0 = every pass runs; 1 = passes return at once for tiles whose message state has stopped changing (Settle); 2 = and a learned horizon keeps them from being enqueued
+    int settle_horizon = 0;   // > 0: the horizon K, forced (tiles it is wrong for are decoded again: results never depend on it)
 };
 
 // The handle's streams and events, released when the handle goes.  scaldpc_bp derives from it, so every buffer member
@@ -261,6 +263,18 @@ struct scaldpc_bp : HandleStreams {
     Buf<int> d_rem64;
     PinnedBuf<int> h_rem64;
     bool ratio_valid = false;
+    // Settled codewords (Settle, scaldpc_bp_kernels.h; the rules: scaldpc_bp_sched.h).  d_settle = [tile][SETTLE_WORDS]
+    // words of the call's tiles, h_settle their host copy; settle_next = the horizon the next call runs with (0 = it
+    // learns), valid for the key below; what the last call did is kept for scaldpc_bp_last_settle.
+    Buf<unsigned> d_settle;
+    PinnedBuf<unsigned> h_settle;
+    int settle_next = 0;
+    int settle_key_iter = 0, settle_key_soft = 0;
+    float settle_key_alpha = -1.0f;
+    bool settle_no_host = false;  // the call in progress must not synchronise (SCALDPC_F_ASYNC): device-side skipping only
+    std::vector<int> settle_frozen_at;  // per tile of the last call, 0 = never froze; empty = the call did not track
+    long settle_saved = 0, settle_rerun = 0;
+    int settle_K = 0;
     int last_group = 0;  // tiles of the last decoded group (for scaldpc_bp_time_kernels)
     bool last_early = false;  // ... and whether that decode ran with early exit (its variable passes then all write decisions)
     std::mutex mu;
@@ -290,6 +304,8 @@ bool set_knob(Knobs &k, const char *key, const char *val)
     else if (!strcmp(key, "first_fused")) k.first_fused = (int)x != 0;
     else if (!strcmp(key, "minsum_rec")) k.minsum_rec = (int)x != 0;
     else if (!strcmp(key, "fuse_test")) k.fuse_test = (int)x != 0;
+    else if (!strcmp(key, "settle") && x >= -1 && x <= 2) k.settle = (int)x;
+    else if (!strcmp(key, "settle_horizon") && x >= 0) k.settle_horizon = (int)x;
     else return false;
     return true;
 }
@@ -299,7 +315,8 @@ void knobs_from_env(Knobs &k)
     static const char *const names[][2] = {{"SCALDPC_PATH", "path"}, {"SCALDPC_SPLIT", "split"},
                                            {"SCALDPC_GROUP_MB", "group_mb"}, {"SCALDPC_EL_MAX", "el_max"},
                                            {"SCALDPC_COMPACT_AFTER", "compact_after"}, {"SCALDPC_FIRST_FUSED", "first_fused"},
-                                           {"SCALDPC_FUSE_TEST", "fuse_test"}, {"SCALDPC_MINSUM_REC", "minsum_rec"}};
+                                           {"SCALDPC_FUSE_TEST", "fuse_test"}, {"SCALDPC_MINSUM_REC", "minsum_rec"},
+                                           {"SCALDPC_SETTLE", "settle"}, {"SCALDPC_SETTLE_HORIZON", "settle_horizon"}};
     for (auto &nm : names)
         if (const char *e = getenv(nm[0])) (void)set_knob(k, nm[1], e);
 }
@@ -770,9 +787,10 @@ bool check_can_test(const scaldpc_bp *h, int method)
 
 // ft: non-null = this pass also runs the convergence test of the previous iteration (check_can_test(h, method), never `first`)
 // sp: non-null = a soft call; its FIRST check pass (the only one that reads priors) takes them per codeword
+// stl: settled codewords (record-form passes of a fixed-iteration call; the default = off, as scaldpc_bp_time_kernels runs)
 int launch_check(scaldpc_bp *h, int method, float alpha, int G, const u64 *synd_g, const u64 *done_g, int skip_done,
                  hipStream_t s, bool first = false, int tile0 = 0, const FusedTest *ft = nullptr, const SoftPrior *sp = nullptr,
-                 bool boot = false)
+                 bool boot = false, const Settle &stl = Settle{})
 {
     if (h->E == 0) return 0;
     float *const msg0 = h->d_msg + (size_t)tile0 * h->E * TW;  // tile0: first tile of a sub-group inside the group's array
@@ -806,7 +824,7 @@ int launch_check(scaldpc_bp *h, int method, float alpha, int G, const u64 *synd_
             with_bool(boot, [&](auto bt) {
                 with_bool(test, [&](auto par) {
                     hipLaunchKernelGGL((k_check_minsum_rec<cap, bt, par>), grid, block, 0, s, h->d_row_list, msg0, synd_g, done_g,
-                                       skip_done, h->m, h->E, alpha, h->d_col_idx, rec0, mask0, h->d_csr_pos, cprior, ft0);
+                                       skip_done, h->m, h->E, alpha, h->d_col_idx, rec0, mask0, h->d_csr_pos, cprior, ft0, stl);
                 });
             });
         });
@@ -877,7 +895,7 @@ int ensure_first_table(scaldpc_bp *h, int method, float alpha1, hipStream_t s)
 //             left them
 int launch_var(scaldpc_bp *h, int G, float *post_g, u64 *hard_g, const u64 *done_g, int skip_done, int write_out,
                hipStream_t s, int tile0 = 0, const u64 *first_synd = nullptr, bool rec = false, bool light = false,
-               const SoftPrior *sp = nullptr, bool final_pass = false)
+               const SoftPrior *sp = nullptr, bool final_pass = false, const Settle &stl = Settle{})
 {
     float *const msg0 = h->d_msg + (size_t)tile0 * h->E * TW;
     float *const scr0 = h->d_scratch ? h->d_scratch + (size_t)tile0 * h->E * TW : nullptr;
@@ -907,7 +925,7 @@ int launch_var(scaldpc_bp *h, int G, float *post_g, u64 *hard_g, const u64 *done
                     hipLaunchKernelGGL((k_var_rec<cap, decltype(P), fin>), gridr, dim3(256), 0, s, h->d_var_meta, h->d_var_rows,
                                        h->d_csc_list, h->d_csc_row, prior, msg0, h->d_rec + (size_t)tile0 * rec_tile_floats(h->m),
                                        h->d_mask + (size_t)tile0 * h->E, post_g, hard_g, done_g, skip_done, h->n, h->m, h->E,
-                                       write_out, blk0, xmap);
+                                       write_out, blk0, xmap, stl);
                 });
             });
         });
@@ -1142,8 +1160,16 @@ struct Lanes {
 //        bit 1 = the group after this one will continue them: no join at the end.  Without the per-group join / fork the lane
 //        that runs a kernel ahead flows straight into the next group instead of idling for the other lane's last pass (and
 //        the other lane for its first): ~75 us per group of 3.7 ms on the HQC-128 bench.
+// sl: settled codewords (a fixed-iteration level on the record-form kernels; the default = off).  With sl.horizon = K > 0
+//     the group enqueues iterations 1 ... K -- the check pass of K closes test K -- and then its closing sequence: the last
+//     variable pass and the final test, as iteration max_iter.  The caller decodes again what was not frozen by K.
+struct SettlePlan {
+    unsigned *words = nullptr;  // [tile][SETTLE_WORDS] of the level's tiles, zero when the level starts
+    int first_test = 0, horizon = 0;
+};
 int iterate_tiles(scaldpc_bp *h, Lanes &lanes, const TileState &st, int g0, int g, int max_iter, int method, float alpha,
-                  bool early, int defer_after, bool *deferred, int real_codewords, PollState &ps, int chain)
+                  bool early, int defer_after, bool *deferred, int real_codewords, PollState &ps, int chain,
+                  const SettlePlan &sl = SettlePlan{})
 {
     const hipStream_t s = lanes.s;
     const int skip = early ? 1 : 0;
@@ -1182,9 +1208,13 @@ int iterate_tiles(scaldpc_bp *h, Lanes &lanes, const TileState &st, int g0, int 
     // (re-)establish the one-kernel offset between neighbouring lanes -- in a chained group too: carrying the offset over
     // instead measured +0.5 % on the config-5 sweep and -2 % on the fixed-iteration bench, profiles/r04/ab_chain_unseen_groups.log
     bool set_phase = true;
+    const bool tracked = sl.words && recf && !early;
+    const int K = tracked ? sl.horizon : 0, last_test = K ? K : max_iter;
+    if (K) h->settle_saved += (long)nl * settle_launches_saved(K, max_iter);
     for (int it = 1; it <= max_iter; it++) {
         const bool last = it == max_iter;
-        const bool no_check = first_fuse && it == 1;
+        if (!settle_enqueued(it, K, max_iter)) continue;  // beyond the horizon
+        const bool no_check = (first_fuse && it == 1) || !settle_has_check(it, K, max_iter);
         const bool poll = poll_point(it, defer_after, ps);
         lanes.open = nl > 1;  // (this iteration enqueues on them)
         for (int k = 0; k < nl && !no_check; k++) {
@@ -1198,22 +1228,31 @@ int iterate_tiles(scaldpc_bp *h, Lanes &lanes, const TileState &st, int g0, int 
             const SoftPrior spv = soft ? soft_prior(h, st, ta) : SoftPrior{};
             const bool first = fused && it == 1, boot = recf && !first && !rec_booted[k];
             if (boot) rec_booted[k] = true;
+            Settle stc{};
+            if (tracked)
+                stc = Settle{sl.words + (size_t)ta * SETTLE_WORDS, settle_check_done(it, sl.first_test),
+                             boot ? 0 : settle_check_mark(it, sl.first_test, last_test)};
             SC_TRY(launch_check(h, method, alpha_for(alpha, it), gs[k], st.synd + (size_t)ta * h->m, st.done + ta, skip, lanes[k],
-                                first, t0[k], ft.hard ? &ft : nullptr, soft ? &spv : nullptr, boot));
+                                first, t0[k], ft.hard ? &ft : nullptr, soft ? &spv : nullptr, boot, stc));
             if (set_phase && k + 1 < nl) {
                 SC_HIP(hipEventRecord(h->ev_phase[k + 1], lanes[k]));
                 SC_HIP(hipStreamWaitEvent(lanes[k + 1], h->ev_phase[k + 1], 0));
             }
         }
         if (!no_check) set_phase = false;  // (a first iteration without check passes leaves the offset to the second)
+        if (!settle_has_var(it, K)) continue;  // (the closing variable pass takes this one's place: settle_horizon_usable)
         for (int k = 0; k < nl; k++) {
             const int ta = g0 + t0[k];
             // (the record form starts with iteration 2: an iteration 1 that has a check pass ran it in the message form)
             const SoftPrior spv = soft ? soft_prior(h, st, ta) : SoftPrior{};
+            Settle stv{};
+            if (tracked && !last)
+                stv = Settle{sl.words + (size_t)ta * SETTLE_WORDS, settle_var_done(it, sl.first_test, last_test),
+                             settle_var_mark(it, sl.first_test, last_test)};
             SC_TRY(launch_var(h, gs[k], st.post ? st.post + (size_t)ta * h->n * TW : nullptr, st.hard + (size_t)ta * h->n,
                               st.done + ta, skip, (early || last) ? 1 : 0, lanes[k], t0[k],
-                              no_check ? st.synd + (size_t)ta * h->m : nullptr, it > 1 && recf, it > 1,
-                              soft ? &spv : nullptr, last));
+                              first_fuse && it == 1 ? st.synd + (size_t)ta * h->m : nullptr, it > 1 && recf, it > 1,
+                              soft ? &spv : nullptr, last, stv));
             if (ride && !last && !poll) {
                 verdict_pending[k] = true;  // the next check pass of this lane carries the test
             } else if (early || last) {  // convergence test + latch, one launch
@@ -1318,6 +1357,33 @@ int decode_level(scaldpc_bp *h, int lvl, const TileState &st, int batch, int T, 
     // nowhere before (runs_unseen, from the same PollState and rules iterate_tiles decides by) enqueues its launches
     // without ever synchronising.
     Lanes lanes(h, s);
+    // Settled codewords: a fixed-iteration level on the record-form kernels tracks which tiles' message state has stopped
+    // changing (Settle), its passes return at once for those, and with a horizon K -- forced, or learned from the handle's
+    // last call (settle_next_horizon) -- what would return at once is not enqueued at all.
+    SettlePlan sl;
+    const int settle = settle_mode(h->kn.settle, h->identity_from >= 0);
+    if (lvl == 0 && !early && settle > 0 && rec_form(h, method)) {
+        // the first iteration from which alpha_for() is one float to the call's end (the schedule never decreases)
+        int alpha_from = 1;
+        while (alpha_from < max_iter && alpha_for(alpha, alpha_from) != alpha_for(alpha, max_iter)) alpha_from++;
+        sl.first_test = settle_first_test(alpha_from);
+        const int soft = st.pprior ? 1 : 0;
+        if (h->settle_key_iter != max_iter || h->settle_key_alpha != alpha || h->settle_key_soft != soft) {
+            h->settle_next = 0;  // another max_iter / alpha / kind of priors: learn again
+            h->settle_key_iter = max_iter;
+            h->settle_key_alpha = alpha;
+            h->settle_key_soft = soft;
+        }
+        if (sl.first_test <= max_iter) {
+            SC_TRY(h->d_settle.ensure((size_t)T * SETTLE_WORDS));
+            SC_HIP(hipMemsetAsync(h->d_settle, 0, sizeof(unsigned) * (size_t)T * SETTLE_WORDS, s));  // once per level, as unsat
+            sl.words = h->d_settle;
+            if (settle >= 2 && !h->settle_no_host) {
+                const int K = h->kn.settle_horizon > 0 ? h->kn.settle_horizon : h->settle_next;
+                if (settle_horizon_usable(K, sl.first_test, max_iter)) sl.horizon = K;
+            }
+        }
+    }
     for (int g0 = 0; g0 < T; g0 += Gl) {
         const int g = std::min(Gl, T - g0);
         const int real = std::min(batch - g0 * TW, g * TW);
@@ -1326,11 +1392,53 @@ int decode_level(scaldpc_bp *h, int lvl, const TileState &st, int batch, int T, 
         // (no chaining across the wrap of the "still running" counter rows, which clears them all: chain_bits)
         const int chain = chain_bits(early, lanes2, g == Gl, g0 == 0, next_full, lanes.open, defer_after, max_iter, poll, h->rem);
         h->sched.note_group(lvl, early, chain);
-        SC_TRY(iterate_tiles(h, lanes, st, g0, g, max_iter, method, alpha, early, defer_after, &d, real, poll, chain));
+        SC_TRY(iterate_tiles(h, lanes, st, g0, g, max_iter, method, alpha, early, defer_after, &d, real, poll, chain, sl));
         if (d) {
             any = true;
             for (int t = g0; t < g0 + g; t++) deferred_tile[t] = 1;
         }
+    }
+    if (sl.words && !h->settle_no_host) {
+        // The tiles' frozen-at numbers, read back once (one synchronise).  With a horizon, every tile that was not frozen
+        // by it is decoded again from its inputs, in place, with all its iterations: the syndrome planes are intact, a
+        // fixed-iteration pass overwrites every output of a real codeword, and BP is deterministic.
+        SC_TRY(h->h_settle.ensure((size_t)T * SETTLE_WORDS));
+        auto read_back = [&](int t0, int cnt, int last_test) -> int {
+            SC_HIP(hipMemcpyAsync(h->h_settle + (size_t)t0 * SETTLE_WORDS, h->d_settle + (size_t)t0 * SETTLE_WORDS,
+                                  sizeof(unsigned) * (size_t)cnt * SETTLE_WORDS, hipMemcpyDeviceToHost, s));
+            SC_HIP(hipStreamSynchronize(s));
+            for (int t = t0; t < t0 + cnt; t++) {
+                unsigned latest = 0;
+                for (int i = 0; i < SETTLE_SHARDS; i++) latest = std::max(latest, h->h_settle[(size_t)t * SETTLE_WORDS + i]);
+                h->settle_frozen_at[t] = settle_frozen_at((int)latest, sl.first_test, last_test);
+            }
+            return 0;
+        };
+        h->settle_frozen_at.assign(T, 0);
+        h->settle_K = sl.horizon;
+        SC_TRY(read_back(0, T, sl.horizon ? sl.horizon : max_iter));
+        if (sl.horizon) {
+            SettlePlan again = sl;
+            again.horizon = 0;
+            for (int t = 0; t < T;) {
+                if (h->settle_frozen_at[t]) { t++; continue; }
+                int g = 1;
+                while (g < Gl && t + g < T && !h->settle_frozen_at[t + g]) g++;
+                SC_HIP(hipMemsetAsync(h->d_settle + (size_t)t * SETTLE_WORDS, 0, sizeof(unsigned) * (size_t)g * SETTLE_WORDS, s));
+                bool d = false;
+                SC_TRY(iterate_tiles(h, lanes, st, t, g, max_iter, method, alpha, early, defer_after, &d,
+                                     std::min(batch - t * TW, g * TW), poll, 0, again));
+                SC_TRY(read_back(t, g, max_iter));
+                h->settle_rerun += g;
+                t += g;
+            }
+        }
+        int frozen = 0, max_at = 0;
+        for (int t = 0; t < T; t++) {
+            frozen += h->settle_frozen_at[t] > 0;
+            max_at = std::max(max_at, h->settle_frozen_at[t]);
+        }
+        h->settle_next = settle >= 2 ? settle_next_horizon(T, frozen, max_at, (int)h->settle_rerun, max_iter) : 0;
     }
     if (!any) return 0;
 
@@ -1600,11 +1708,19 @@ struct Call {
     hipStream_t s;
     int max_iter, T, G;
 };
+// what scaldpc_bp_last_settle reports: cleared when a call starts, whatever path it takes
+void settle_report_reset(scaldpc_bp *h)
+{
+    h->settle_frozen_at.clear();
+    h->settle_saved = h->settle_rerun = 0;
+    h->settle_K = 0;
+}
 int begin_call(scaldpc_bp *h, int batch, int max_iter, void *stream, Call *c)
 {
     if (!h->have_prior || h->prior_n < h->n)
         return fail(SCALDPC_EINVAL, "channel probabilities not set (columns [%d, %d))", h->have_prior ? h->prior_n : 0, h->n);
     h->sched.reset();
+    settle_report_reset(h);
     c->max_iter = max_iter > 0 ? max_iter : h->n;
     c->s = stream ? (hipStream_t)stream : h->own_stream;
     c->T = (batch + TW - 1) / TW;
@@ -1774,6 +1890,7 @@ int scaldpc_bp_set_channel_probs(scaldpc_bp *h, const double *probs)
     h->h_probs.assign(probs, probs + h->n);
     h->thr_valid = false;
     h->first_valid = false;
+    h->settle_next = 0;  // (the settle horizon was learned on the priors and rows that were: learn again)
     h->ratio_valid = false;
     h->have_prior = true;
     h->prior_n = h->n;
@@ -1798,6 +1915,7 @@ int scaldpc_bp_set_channel_probs_tail(scaldpc_bp *h, int32_t first, int32_t coun
     std::copy(probs, probs + count, h->h_probs.begin() + first);
     h->thr_valid = false;
     h->first_valid = false;
+    h->settle_next = 0;  // (the settle horizon was learned on the priors and rows that were: learn again)
     h->ratio_valid = false;
     h->prior_n = std::max(h->prior_n, first + count);
     h->have_prior = true;
@@ -1966,6 +2084,7 @@ int scaldpc_bp_append_rows(scaldpc_bp *h, int32_t nrows, const int32_t *row_ptr,
     h->h_probs.resize(new_n, 0.0);
     h->thr_valid = false;
     h->first_valid = false;
+    h->settle_next = 0;  // (the settle horizon was learned on the priors and rows that were: learn again)
     h->ratio_valid = false;
     h->d_x64.reset();
     h->d_c64.reset();
@@ -2013,6 +2132,19 @@ int scaldpc_bp_last_schedule(scaldpc_bp *h, int64_t *out)
     std::lock_guard<std::mutex> lk(h->mu);
     for (int i = 0; i < SCHED_WORDS; i++) out[i] = h->sched.w[i];
     for (int i = SCHED_WORDS; i < SCALDPC_SCHEDULE_WORDS; i++) out[i] = 0;
+    return 0;
+}
+
+int scaldpc_bp_last_settle(scaldpc_bp *h, int32_t *frozen_at, int32_t cap, int64_t *info)
+{
+    if (!h || !info || cap < 0 || (cap > 0 && !frozen_at)) return fail(SCALDPC_EINVAL, "bad argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    const size_t T = h->settle_frozen_at.size();
+    for (size_t t = 0; t < T && t < (size_t)cap; t++) frozen_at[t] = h->settle_frozen_at[t];
+    info[0] = (int64_t)T;
+    info[1] = h->settle_saved;
+    info[2] = h->settle_rerun;
+    info[3] = h->settle_K;
     return 0;
 }
 
@@ -2186,7 +2318,10 @@ static int decode_batch_impl(scaldpc_bp *h, const uint8_t *in, int32_t input_kin
         LAUNCH_CHECK();
         SC_TRY(launch_syndrome(h, h->d_recv, h->d_synd, T, s));
     }
-    SC_TRY(run_core(h, batch, T, G, max_iter, method, alpha, early, out_llr != nullptr, s, pprior, first_col));
+    h->settle_no_host = (flags & SCALDPC_F_ASYNC) != 0;  // (such a call only enqueues: no read-back, no horizon)
+    const int rc_core = run_core(h, batch, T, G, max_iter, method, alpha, early, out_llr != nullptr, s, pprior, first_col);
+    h->settle_no_host = false;
+    SC_TRY(rc_core);
 
     // ---- outputs --------------------------------------------------------------
     SC_TRY(stage_outputs(h, out, batch, dev_io, true, &dev));

@@ -761,11 +761,41 @@ __global__ __launch_bounds__(256) void k_check_minsum_x(const int *__restrict__ 
 constexpr unsigned REC_NO_ARG = 255;  // (no row has an edge 255: rows of the record form have at most 64)
 static_assert(REC_TW == TW, "the record layout of scaldpc_rec_pack.h is laid out for the kernels' tile width");
 
+// SETTLED codewords (fixed-iteration calls).  After check pass t the whole message state of a codeword is
+// (rec, arg, sgn).  Test t asks: did check pass t store the records and arg-min bytes it overwrote, and did variable pass
+// t - 1 store the sign masks it overwrote, bit for bit?  Then the check-to-variable messages of t are those of t - 1, the
+// iteration is a deterministic map of the state, and every later pass repeats: the codeword is settled at t.  A tile all
+// of whose real codewords are settled at t is FROZEN at t, and every pass but the decode's last returns at once for it.
+//   words [tile][SETTLE_WORDS] u32, zero at the start of a level: a wave that sees a difference in test t stores t into
+//         word (block & (SETTLE_SHARDS - 1)) of its tile -- every writer of a test writes the same value, so plain stores
+//         do; the shards keep a launch's few thousand stores off one address.  The words never decrease, so their maximum
+//         is the last test in which something of the tile changed; a tile has a 128-B line of its own.
+//   done  the latest test completed before this launch on its stream (0 = none): the tile is frozen when its maximum is
+//         below it.  (A wave of check pass t may read a word another wave of the same pass has just set to t: that tile
+//         changed in test t, so it was not frozen at t - 1 either and its maximum was t - 1 = done already.)
+//   mark  the test this launch is a half of (0 = it is not tracked: a BOOT pass, or a pass at which alpha still moves)
+// words == nullptr: all of it off.  A wave-uniform branch on a kernel argument, no instantiation of its own.
+constexpr int SETTLE_WORDS = 32, SETTLE_SHARDS = 8;
+struct Settle {
+    unsigned *words = nullptr;  // of the launch's first tile
+    int done = 0, mark = 0;
+};
+__device__ __forceinline__ bool settle_frozen(const unsigned *__restrict__ w, int done)
+{
+    unsigned mx = 0;
+#pragma unroll
+    for (int i = 0; i < SETTLE_SHARDS; i++) mx = w[i] > mx ? w[i] : mx;  // (uniform address: scalar loads, issued with the wave's first)
+    return (int)mx < done;
+}
+
+// mark_word (steady passes only; null = not tracked): where the wave stores `mark` if a REAL codeword's records or arg-min
+// byte differ from the ones it overwrites (real = lane mask of the tile's codewords that are not padding)
 template <int DEG, bool BOOT>
 __device__ __forceinline__ void check_minsum_row_rec(const float *p, u64 synd_mask, float alpha, float *__restrict__ rec,
                                                      float *__restrict__ rec2, unsigned char *__restrict__ arg,
                                                      u64 *__restrict__ sgn, int lane, const int *__restrict__ pos,
-                                                     bool const_last = false, float x_last = 0.0f)
+                                                     bool const_last = false, float x_last = 0.0f,
+                                                     unsigned *mark_word = nullptr, unsigned mark = 0, u64 real = 0)
 {
     // BOOT: the sign masks are laid out in the variable pass's order (position of the edge in the re-laid edge list: a
     // column's masks are contiguous there); lane k fetches edge k's position up front
@@ -784,6 +814,19 @@ __device__ __forceinline__ void check_minsum_row_rec(const float *p, u64 synd_ma
         x[DEG - 1] = x_last;
     else
         x[DEG - 1] = p[(size_t)(DEG - 1) * TW];
+    // A tracked pass (mark_word, wave-uniform) fetches the records and the arg-min byte it is about to overwrite.  Rows of up
+    // to 32 edges (EARLY) issue the three loads here, with the row's own, so that their latency hides behind both sweeps:
+    // those builds have registers to spare.  Longer rows fetch them late (below).
+    constexpr bool EARLY = DEG <= 32;
+    bool tracked = false;
+    if constexpr (!BOOT) tracked = mark_word != nullptr;
+    unsigned o1 = 0, o2 = 0, oa = 0;
+    if constexpr (!BOOT && EARLY)
+        if (tracked) {
+            o1 = __float_as_uint(rec[lane]);
+            o2 = __float_as_uint(rec2[lane]);
+            oa = arg[lane];
+        }
     float m1 = FLT_MAX, m2 = FLT_MAX;
     const float fmax = FLT_MAX;
     u64 par = ((u64)(unsigned)rfl((int)(synd_mask >> 32)) << 32) | (unsigned)rfl((int)synd_mask);  // (uniform by construction: keep it on the scalar side)
@@ -805,13 +848,23 @@ __device__ __forceinline__ void check_minsum_row_rec(const float *p, u64 synd_ma
         asm("v_med3_f32 %0, %1, %2, %0" : "+v"(m2) : "v"(a), "v"(m1));
         asm("v_min_f32 %0, %0, %1" : "+v"(m1) : "v"(a));
     }
+    float s1, s2;
     {
         // the row's parity goes into the records' sign bit: one select with a negated source each, on the scalar mask
         const bool odd = __builtin_amdgcn_inverse_ballot_w64(par);
         const float r1 = m1 * alpha, r2 = m2 * alpha;
-        rec[lane] = odd ? -r1 : r1;
-        rec2[lane] = odd ? -r2 : r2;
+        s1 = odd ? -r1 : r1;
+        s2 = odd ? -r2 : r2;
     }
+    // A tracked pass over a row of more than 32 edges fetches the records it overwrites and stores the new ones eight edges
+    // into sweep 2 instead of in front of it: every edge of that sweep frees a register, and in front of it the 64-edge
+    // build has none to spare (its occupancy hangs on 72).  The loads are tied behind the sweep's steps so far through an
+    // empty asm on their lane offset; the old arg-min byte and the compare come behind the sweep.
+    if (!tracked || EARLY) {
+        rec[lane] = s1;
+        rec2[lane] = s2;
+    }
+    constexpr int AT = DEG - 8;
     unsigned idx = REC_NO_ARG;
 #pragma unroll
     for (int k = DEG - 1; k >= 0; k--) {
@@ -819,8 +872,26 @@ __device__ __forceinline__ void check_minsum_row_rec(const float *p, u64 synd_ma
         // instead of a run of compares ahead of the selects with a live SGPR pair each)
         asm("" : "+v"(x[k]) : "v"(idx));
         idx = (fabsf(x[k]) == m1) ? (unsigned)k : idx;
+        if constexpr (!BOOT && !EARLY)
+            if (k == AT && tracked) {
+                int lo = lane;
+                asm volatile("" : "+v"(lo) : "v"(idx));
+                o1 = __float_as_uint(rec[lo]);
+                o2 = __float_as_uint(rec2[lo]);
+                rec[lo] = s1;
+                rec2[lo] = s2;
+            }
     }
-    arg[lane] = (unsigned char)idx;
+    if constexpr (!BOOT) {
+        if (tracked) {
+            if constexpr (!EARLY) oa = arg[lane];
+            arg[lane] = (unsigned char)idx;
+            const bool changed = o1 != __float_as_uint(s1) || o2 != __float_as_uint(s2) || oa != idx;
+            if ((__ballot(changed) & real) != 0 && lane == 0) *mark_word = mark;
+        } else
+            arg[lane] = (unsigned char)idx;
+    } else
+        arg[lane] = (unsigned char)idx;
     if constexpr (BOOT) {
         unsigned nlo = 0, nhi = 0;  // lane k keeps edge k's mask
         // The v_writelanes below are the compiler's own instructions (writelane(), top of this file): a v_writelane reading
@@ -857,17 +928,27 @@ __global__ __launch_bounds__(256) void k_check_minsum_rec(const int *__restrict_
                                                           const int *__restrict__ col_idx,
                                                           float *__restrict__ rec, u64 *__restrict__ sgn,
                                                           const int *__restrict__ csr_pos,
-                                                          const float *__restrict__ const_prior, FusedTest ft = FusedTest{})
+                                                          const float *__restrict__ const_prior, FusedTest ft = FusedTest{},
+                                                          Settle st = Settle{})
 {
     const int lane = threadIdx.x & 63;
     const int tl = blockIdx.y;
     const int *md = list + (size_t)rfl((int)blockIdx.x * 4 + (int)(threadIdx.x >> 6)) * 4;  // uniform address: scalar loads
     u64 dw = 0;
+    unsigned *mark_word = nullptr;  // (settled codewords: fixed-iteration calls, which never come with PAR)
     if constexpr (PAR) {
         dw = done[tl];
         if (skip_done && dw == ~0ull) return;
     } else {
         if (skip_done && done[tl] == ~0ull) return;
+        if (st.words) {
+            unsigned *w = st.words + (size_t)tl * SETTLE_WORDS;
+            if (settle_frozen(w, st.done)) return;  // the tile is frozen: this pass would store what is there
+            if (!BOOT && st.mark) {
+                mark_word = w + (blockIdx.x & (SETTLE_SHARDS - 1));
+                dw = done[tl];  // (fixed iterations: the padding lanes)
+            }
+        }
     }
     const int r = md[0];
     u64 bad = 0;
@@ -892,7 +973,8 @@ __global__ __launch_bounds__(256) void k_check_minsum_rec(const int *__restrict_
         // record-form kernels come out with other registers and an instruction more or less)
 #define MR(D)                                                                                                   \
     case D:                                                                                                     \
-        if constexpr (D <= CAP) check_minsum_row_rec<D, BOOT>(p, sw, alpha, rc, rc2, ar, sg, lane, ps, cl, xl); \
+        if constexpr (D <= CAP)                                                                                 \
+            check_minsum_row_rec<D, BOOT>(p, sw, alpha, rc, rc2, ar, sg, lane, ps, cl, xl, mark_word, (unsigned)st.mark, ~dw); \
         break;
 #define MR8(D) MR(D) MR(D + 1) MR(D + 2) MR(D + 3) MR(D + 4) MR(D + 5) MR(D + 6) MR(D + 7)
         switch (deg) {
@@ -1550,7 +1632,8 @@ template <int D, bool LAST>
 __device__ __forceinline__ float var_col_rec(float *tile_base, const float *__restrict__ rec_base, unsigned rec2_off,
                                              const unsigned char *__restrict__ arg_base, u64 *sgn_col, unsigned lane,
                                              const int *__restrict__ rc, const int4 *__restrict__ row4,
-                                             const int *__restrict__ ce1, const int *__restrict__ cr1, float pr)
+                                             const int *__restrict__ ce1, const int *__restrict__ cr1, float pr,
+                                             unsigned *mark_word = nullptr, unsigned mark = 0, u64 real = 0)
 {
     int eid[D], rw[D];
     {
@@ -1620,6 +1703,12 @@ __device__ __forceinline__ float var_col_rec(float *tile_base, const float *__re
         suf += mm[k];
     }
     if ((int)lane < D) sgn_col[lane] = ((u64)nhi << 32) | nlo;
+    // settled codewords (Settle): lane j holds the mask of edge j it read and the one it stores; mark_word non-null
+    // (wave-uniform) = this pass is tracked, and a difference in a real codeword's bit marks the tile
+    if (mark_word) {
+        const unsigned dlo = (nlo ^ (unsigned)slo) & (unsigned)real, dhi = (nhi ^ (unsigned)shi) & (unsigned)(real >> 32);
+        if (__ballot((int)lane < D && (dlo | dhi) != 0) != 0 && lane == 0) *mark_word = mark;
+    }
     return temp;
 }
 
@@ -1632,7 +1721,7 @@ __global__ __launch_bounds__(256) void k_var_rec(const int *__restrict__ list, c
                                                  typename P::Arg prior_arg, float *msg, const float *__restrict__ rec,
                                                  u64 *sgn, float *__restrict__ post,
                                                  u64 *__restrict__ hard, const u64 *__restrict__ done, int skip_done, int n, int m,
-                                                 long E, int write_out, int blk0, int xmap)
+                                                 long E, int write_out, int blk0, int xmap, Settle stl = Settle{})
 {
     const P prior{prior_arg};
     const unsigned lane = threadIdx.x & 63u;
@@ -1650,6 +1739,13 @@ __global__ __launch_bounds__(256) void k_var_rec(const int *__restrict__ list, c
     const int *rc = list + (size_t)ri * VAR_REC;
     const u64 dn = done[tl];
     if (skip_done && dn == ~0ull) return;
+    // settled codewords (Settle; never with LAST: the decode's last pass runs on the frozen state as ever)
+    unsigned *mark_word = nullptr;
+    if (!LAST && stl.words) {
+        unsigned *w = stl.words + (size_t)tl * SETTLE_WORDS;
+        if (settle_frozen(w, stl.done)) return;  // the tile is frozen: this pass would store what is there
+        if (stl.mark) mark_word = w + ((unsigned)bx & (SETTLE_SHARDS - 1));
+    }
     const int v = rc[0];
     if (v < 0) return;
     const int cb = rc[1];
@@ -1665,7 +1761,8 @@ __global__ __launch_bounds__(256) void k_var_rec(const int *__restrict__ list, c
     const unsigned r2 = (unsigned)m * (TW * (unsigned)sizeof(float));  // rec_m2_off(m) in bytes
 #define VR(D)                                                                                                \
     case D:                                                                                                  \
-        if constexpr (D <= CAP) L = var_col_rec<D, LAST>(tb, rb, r2, ab, st + cb, lane, rc, w4, ce, cr, pr); \
+        if constexpr (D <= CAP)                                                                              \
+            L = var_col_rec<D, LAST>(tb, rb, r2, ab, st + cb, lane, rc, w4, ce, cr, pr, mark_word, (unsigned)stl.mark, ~dn); \
         break;
 #define VR8(D) VR(D) VR(D + 1) VR(D + 2) VR(D + 3) VR(D + 4) VR(D + 5) VR(D + 6) VR(D + 7)
     switch (d) {

@@ -193,6 +193,68 @@ struct SchedCounters {
     }
 };
 
+// ---------------------------------------------------------------------------
+// Settled codewords (fixed-iteration calls on the record-form kernels; the device side is `Settle`,
+// scaldpc_bp_kernels.h).  Test t (t >= SETTLE_FIRST) has two halves -- variable pass t - 1 compares the sign masks it
+// stores with the ones it overwrites, check pass t its records and arg-min bytes -- and a tile in which neither saw a
+// difference is frozen at t.  tests/settle_sched_main.cc walks the rules below under the sanitizers and
+// tests/test_settle_schedule.py holds them to a restatement in Python.
+// ---------------------------------------------------------------------------
+constexpr int SETTLE_FIRST = 3;  // check pass 2 is the bootstrap pass: it has nothing to compare with
+// The first test a call can track.  Tracking is valid only across passes with the same alpha: alpha_from = the first
+// iteration from which alpha_for() is one float to the call's end (1 with a given alpha; with the 1 - 2^-it schedule the
+// iteration at which the float becomes 1.0f).  Test t needs check passes t - 1 and t to share it.
+inline int settle_first_test(int alpha_from)
+{
+    const int t = alpha_from + 1;
+    return t < SETTLE_FIRST ? SETTLE_FIRST : t;
+}
+// What the passes of iteration `it` are told: `done` = the latest test completed before the pass on its stream (0 = none),
+// `mark` = the test it is a half of (0 = the pass is not tracked).  last_test = the last test of the group: its last
+// check pass that is not the bootstrap one, i.e. max_iter, or the horizon.
+inline int settle_check_done(int it, int first_test) { return it - 1 >= first_test ? it - 1 : 0; }
+inline int settle_check_mark(int it, int first_test, int last_test) { return it >= first_test && it <= last_test ? it : 0; }
+inline int settle_var_done(int it, int first_test, int last_test) { return it >= first_test && it <= last_test ? it : 0; }
+inline int settle_var_mark(int it, int first_test, int last_test) { return settle_check_mark(it + 1, first_test, last_test); }
+// The frozen-at number of a tile after a group whose tests ran from first_test to last_test: latest = the maximum of its
+// words = the last test in which something of it changed (0 = none did).  0 = the tile never froze.
+inline int settle_frozen_at(int latest, int first_test, int last_test)
+{
+    if (last_test < first_test || latest >= last_test) return 0;
+    return latest + 1 > first_test ? latest + 1 : first_test;
+}
+// Can a group stop at horizon K -- iterations 1 ... K, then the closing sequence (the last variable pass and the final
+// test, as iteration max_iter)?  Test K must exist, and something must be left out.  (The closing variable pass takes
+// the place of variable pass K: on a tile frozen by K that one would have returned at once, and any other tile is decoded
+// again.)
+inline bool settle_horizon_usable(int K, int first_test, int max_iter) { return K >= first_test && K + 1 < max_iter; }
+// Which passes a group with horizon K (0 = none) enqueues: iteration `it` at all; its check pass (where the iteration has
+// one anyway); its variable pass.
+inline bool settle_enqueued(int it, int K, int max_iter) { return !(K && it > K && it < max_iter); }
+inline bool settle_has_check(int it, int K, int max_iter) { return !(K && it == max_iter); }
+inline bool settle_has_var(int it, int K) { return !(K && it == K); }
+// launches of one lane that a group with horizon K does not enqueue: variable pass K, the pairs of K + 1 ... max_iter - 1
+// and the check pass of max_iter
+inline int settle_launches_saved(int K, int max_iter) { return 2 * (max_iter - K); }
+// The horizon the NEXT call runs with, learned from the last one (0 = none: the call runs with device-side skipping alone
+// and is learned from again).  tiles = tiles of the call, frozen = those with a frozen-at number (re-run ones with the
+// number their re-run found), max_frozen_at = the largest of them, rerun = tiles the call had to decode again because
+// they were not frozen by its horizon.
+inline int settle_next_horizon(int tiles, int frozen, int max_frozen_at, int rerun, int max_iter)
+{
+    if (tiles <= 0 || max_frozen_at <= 0) return 0;
+    if (8 * rerun > tiles) return 0;  // more than 1/8 re-run: the horizon costs more than it saves
+    const int K = max_frozen_at + 2;
+    if (8 * frozen < 7 * tiles) return 0;  // at least 7/8 of the tiles froze by K
+    if (2 * K >= max_iter) return 0;
+    return K;
+}
+
+// The `settle` knob in force: 0 / 1 / 2 as given; -1 (the default) = 2 on a graph [Hin | I], where every row has an edge
+// into a column of degree 1 and the message state is bounded, and 0 on any other graph, which has no reason to settle and
+// would only pay for the tracking.
+inline int settle_mode(int knob, bool identity_block) { return knob >= 0 ? knob : identity_block ? 2 : 0; }
+
 // Poll points of the row-parallel loop: `ip` = the iteration whose verdict the host may look at.  Poll densely where
 // convergence is likely, sparsely afterwards.
 inline bool el_poll_point(int ip) { return (ip >= 3 && ip <= 6) || (ip > 6 && ip <= 16 && ip % 2 == 0) || (ip > 16 && ip % 16 == 0); }
