@@ -893,9 +893,11 @@ int ensure_first_table(scaldpc_bp *h, int method, float alpha1, hipStream_t s)
 // final_pass: no check pass follows this one on these tiles (the last iteration of a decode, always with write_out): the
 //             record form then runs its store-free instantiation, which leaves messages and sign masks as the pass before
 //             left them
+// keep_hard: a record-form pass without output still merges its columns' decisions into hard_g, from the sum it has anyway
+//             (settled codewords: the closing pass of a frozen tile then finds them there, k_var_rec).  It stays slim.
 int launch_var(scaldpc_bp *h, int G, float *post_g, u64 *hard_g, const u64 *done_g, int skip_done, int write_out,
                hipStream_t s, int tile0 = 0, const u64 *first_synd = nullptr, bool rec = false, bool light = false,
-               const SoftPrior *sp = nullptr, bool final_pass = false, const Settle &stl = Settle{})
+               const SoftPrior *sp = nullptr, bool final_pass = false, const Settle &stl = Settle{}, bool keep_hard = false)
 {
     float *const msg0 = h->d_msg + (size_t)tile0 * h->E * TW;
     float *const scr0 = h->d_scratch ? h->d_scratch + (size_t)tile0 * h->E * TW : nullptr;
@@ -925,7 +927,7 @@ int launch_var(scaldpc_bp *h, int G, float *post_g, u64 *hard_g, const u64 *done
                     hipLaunchKernelGGL((k_var_rec<cap, decltype(P), fin>), gridr, dim3(256), 0, s, h->d_var_meta, h->d_var_rows,
                                        h->d_csc_list, h->d_csc_row, prior, msg0, h->d_rec + (size_t)tile0 * rec_tile_floats(h->m),
                                        h->d_mask + (size_t)tile0 * h->E, post_g, hard_g, done_g, skip_done, h->n, h->m, h->E,
-                                       write_out, blk0, xmap, stl);
+                                       (write_out || keep_hard) ? 1 : 0, blk0, xmap, stl);
                 });
             });
         });
@@ -1205,12 +1207,15 @@ int iterate_tiles(scaldpc_bp *h, Lanes &lanes, const TileState &st, int g0, int 
     bool verdict_pending[MAX_LANES] = {};  // lane k's last variable pass has not been tested yet: its next check pass will
     const bool recf = rec_form(h, method);
     bool rec_booted[MAX_LANES] = {};  // lane k has run its first record-form check pass (the one that also writes the sign masks)
-    // (re-)establish the one-kernel offset between neighbouring lanes -- in a chained group too: carrying the offset over
-    // instead measured +0.5 % on the config-5 sweep and -2 % on the fixed-iteration bench, profiles/r04/ab_chain_unseen_groups.log
-    bool set_phase = true;
     const bool tracked = sl.words && recf && !early;
     const int K = tracked ? sl.horizon : 0, last_test = K ? K : max_iter;
+    // (re-)establish the one-kernel offset between neighbouring lanes -- in a chained group too (phase_reestablished,
+    // scaldpc_bp_sched.h, with the measurements)
+    bool set_phase = phase_reestablished(chain, K, max_iter);
     if (K) h->settle_saved += (long)nl * settle_launches_saved(K, max_iter);
+    // A tracked group of a call that wants no posteriors: every record-form variable pass leaves its columns' decisions, and
+    // the closing pass returns for the columns of a frozen tile that have them (k_var_rec).
+    const bool keep_hard = tracked && st.post == nullptr;
     for (int it = 1; it <= max_iter; it++) {
         const bool last = it == max_iter;
         if (!settle_enqueued(it, K, max_iter)) continue;  // beyond the horizon
@@ -1249,10 +1254,12 @@ int iterate_tiles(scaldpc_bp *h, Lanes &lanes, const TileState &st, int g0, int 
             if (tracked && !last)
                 stv = Settle{sl.words + (size_t)ta * SETTLE_WORDS, settle_var_done(it, sl.first_test, last_test),
                              settle_var_mark(it, sl.first_test, last_test)};
+            else if (keep_hard)  // the closing pass: it comes behind the check pass that completes the group's last test
+                stv = Settle{sl.words + (size_t)ta * SETTLE_WORDS, last_test, 0};
             SC_TRY(launch_var(h, gs[k], st.post ? st.post + (size_t)ta * h->n * TW : nullptr, st.hard + (size_t)ta * h->n,
                               st.done + ta, skip, (early || last) ? 1 : 0, lanes[k], t0[k],
                               first_fuse && it == 1 ? st.synd + (size_t)ta * h->m : nullptr, it > 1 && recf, it > 1,
-                              soft ? &spv : nullptr, last, stv));
+                              soft ? &spv : nullptr, last, stv, keep_hard && !last));
             if (ride && !last && !poll) {
                 verdict_pending[k] = true;  // the next check pass of this lane carries the test
             } else if (early || last) {  // convergence test + latch, one launch

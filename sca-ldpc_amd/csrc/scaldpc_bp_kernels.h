@@ -87,7 +87,14 @@ __device__ __forceinline__ void for_exact_degree(int deg, F &&f)
 // input / output reshaping
 // ---------------------------------------------------------------------------
 // uint8 [batch][len] (one row per codeword, as decode() receives them) -> planes [tile][x].
-// wave = (tile, 16 consecutive x): lane c walks one 16-byte stretch of codeword c.
+// wave = (tile, 16 consecutive x): lane c owns one 16-byte stretch of codeword c and fetches it WIDE.  A row starts at any
+// alignment (len is odd on the HQC graphs, the caller's pointer is any), so the lane reads the five aligned dwords that
+// cover its stretch, all in flight together, and shifts its 16 bytes out of them: a byte load per x (16 dependent-free
+// but separate wave loads, each touching 64 cache lines for one byte apiece) made this kernel eight times slower than
+// its mirror image k_unpack_bits.  A lane whose five dwords are not wholly inside [in, in + batch * len) -- the first
+// stretch behind an unaligned `in`, the last 20 bytes of the array -- reads its bytes one by one: nothing outside the
+// array is ever read.  Padding lanes (codeword >= batch) read nothing and ballot 0.  Lane j keeps the word of x0 + j, so
+// the wave stores its words with one coalesced store.
 // grid (ceil(len/64), T), block 256.
 __global__ __launch_bounds__(256) void k_pack_bits(const uint8_t *__restrict__ in, int len, int batch,
                                                    u64 *__restrict__ out)
@@ -97,13 +104,32 @@ __global__ __launch_bounds__(256) void k_pack_bits(const uint8_t *__restrict__ i
     const int t = blockIdx.y;
     if (x0 >= len) return;
     const long b = (long)t * TW + lane;
-    const uint8_t *p = in + (size_t)(b < batch ? b : 0) * len + x0;
     const int nx = min(16, len - x0);
-    for (int j = 0; j < nx; j++) {
-        const int bit = (b < batch) ? (p[j] & 1) : 0;
-        const u64 w = __ballot(bit);
-        if (lane == 0) out[(size_t)t * len + x0 + j] = w;
+    unsigned w[4] = {0u, 0u, 0u, 0u};  // the lane's bytes x0 ... x0 + 15, little endian (bytes from nx on: whatever, unused)
+    if (b < batch) {
+        const uint8_t *p = in + (size_t)b * len + x0;
+        const size_t lo = (size_t)in, hi = lo + (size_t)batch * len, pa = (size_t)p;
+        const unsigned mis = (unsigned)(pa & 3u);
+        const size_t a = pa - mis;
+        if (a >= lo && a + 20 <= hi) {
+            const unsigned *q = (const unsigned *)a;
+            unsigned d[5];
+#pragma unroll
+            for (int i = 0; i < 5; i++) d[i] = q[i];
+#pragma unroll
+            for (int i = 0; i < 4; i++) w[i] = (unsigned)(((((u64)d[i + 1]) << 32) | d[i]) >> (8u * mis));
+        } else {
+            for (int j = 0; j < nx; j++) w[j >> 2] |= (unsigned)p[j] << (8 * (j & 3));
+        }
     }
+    u64 mine = 0;
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+        if (j >= nx) break;  // (wave-uniform)
+        const u64 word = __ballot((w[j >> 2] >> (8 * (j & 3))) & 1u);
+        if (lane == j) mine = word;
+    }
+    if (lane < nx) out[(size_t)t * len + x0 + lane] = mine;
 }
 
 // hard decision planes (XOR received planes) -> uint8 [batch][n].
@@ -1739,17 +1765,29 @@ __global__ __launch_bounds__(256) void k_var_rec(const int *__restrict__ list, c
     const int *rc = list + (size_t)ri * VAR_REC;
     const u64 dn = done[tl];
     if (skip_done && dn == ~0ull) return;
-    // settled codewords (Settle; never with LAST: the decode's last pass runs on the frozen state as ever)
+    // settled codewords (Settle).  A pass that is not the last returns for a frozen tile: it would store what is there.
+    // The LAST pass is handed the words only where every earlier record-form variable pass of the tile has left its
+    // columns' decisions in `hard` (launch_var, keep_hard; stl.done = the group's last test): the last of them that ran on
+    // a tile frozen at t, pass t - 1, summed the very records and sign masks this pass would gather, in the same order,
+    // so its decisions ARE this pass's.  Those passes leave out the columns of degree <= 1 (launch_var, slim), so on a
+    // frozen tile this pass still decides those, and returns for every other column.
     unsigned *mark_word = nullptr;
-    if (!LAST && stl.words) {
+    bool decided = false;
+    if (stl.words) {
         unsigned *w = stl.words + (size_t)tl * SETTLE_WORDS;
-        if (settle_frozen(w, stl.done)) return;  // the tile is frozen: this pass would store what is there
-        if (stl.mark) mark_word = w + ((unsigned)bx & (SETTLE_SHARDS - 1));
+        const bool frozen = settle_frozen(w, stl.done);
+        if constexpr (LAST)
+            decided = frozen;
+        else {
+            if (frozen) return;
+            if (stl.mark) mark_word = w + ((unsigned)bx & (SETTLE_SHARDS - 1));
+        }
     }
     const int v = rc[0];
     if (v < 0) return;
     const int cb = rc[1];
     const int d = rc[2];
+    if (LAST && decided && d > 1) return;
     float *tb = msg + (size_t)tl * E * TW;
     const float *rb = rec + (size_t)tl * rec_tile_floats(m);  // the tile's block: [m1 | m2][row][64], arg
     const unsigned char *ab = (const unsigned char *)(rb + rec_arg_off(m));
@@ -1775,7 +1813,12 @@ __global__ __launch_bounds__(256) void k_var_rec(const int *__restrict__ list, c
     if (write_out) {
         const u64 hb = __ballot(L <= 0.0f);
         const size_t hi = (size_t)tl * n + v;
-        if (lane == 0) hard[hi] = (hard[hi] & dn) | (hb & ~dn);
+        // (dn == 0, wave-uniform: nothing to keep, so no load in front of the store -- the passes that leave their decisions
+        // for the closing pass pay for a store alone on a full tile of a fixed-iteration call)
+        if (dn == 0) {
+            if (lane == 0) hard[hi] = hb;
+        } else if (lane == 0)
+            hard[hi] = (hard[hi] & dn) | (hb & ~dn);
         if (post && !((dn >> lane) & 1)) post[hi * TW + lane] = L;
     }
 }

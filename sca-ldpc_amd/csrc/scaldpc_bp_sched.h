@@ -154,6 +154,26 @@ inline int chain_bits(bool early, bool lanes2, bool full, bool first, bool next_
     return chain;
 }
 
+// Does a group (re-)establish the one-kernel offset between neighbouring lanes -- lane k + 1 waits, once, for lane k's first
+// check pass -- when it starts (iterate_tiles)?  A group that continues nobody's lanes has to: its lanes start together.
+// A chained group finds whatever offset its predecessor's lanes ended with.
+//   chain     the group's chain bits (chain_bits)
+//   horizon   the settle horizon in force (0 = none): the group enqueues iterations 1 ... horizon and its closing sequence
+//   max_iter  the call's iteration count
+// The rule in force: always.  Carrying the offset over in chained groups was measured twice: with groups of 50 iterations
+// (3.7 ms; profiles/r04/ab_chain_unseen_groups.log: + 0.5 % on the config-5 sweep, - 2 % on the fixed-iteration bench) and
+// with groups cut to a settle horizon of 12 (0.6 ms; profiles/minsum_settle_passes/README.md: 0.03 ms of 10.0 on HQC-128,
+// 0.13 of 19.7 on HQC-192, both inside the run-to-run spread; the tanh rule unchanged).  Neither the horizon nor the
+// iteration count moves the verdict, so neither enters the rule; they stay inputs, for whoever measures it next.
+// tests/test_phase_schedule.py holds the rule to a restatement, tests/phase_sched_main.cc walks it under the sanitizers.
+inline bool phase_reestablished(int chain, int horizon, int max_iter)
+{
+    (void)chain;
+    (void)horizon;
+    (void)max_iter;
+    return true;
+}
+
 // Counters of the schedule a call ran (scaldpc_bp_last_schedule), host integers only.
 enum SchedWord {
     SCHED_GROUPS = 0,         // [4] tile groups run at compaction level 0 .. 3
