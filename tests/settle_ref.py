@@ -53,7 +53,8 @@ def run(g, prior, synd, max_iter, alpha=1.0):
     """All `max_iter` iterations on every row of `synd` (uint8 [batch, m]); prior = LLRs float32 [n], or [batch, n] per codeword.
     Returns dict:
     post      float32 [max_iter + 1, batch, n]: the posterior after iteration it (index 0 unused)
-    same      bool [max_iter + 1, batch]: same[t] = the two compares of test t found no difference (t >= 3)"""
+    same      bool [max_iter + 1, batch]: same[t] = the two compares of test t found no difference (t >= 3)
+    same_but_arg  the same with the arg-min indices left out of the compare: what a test that forgot them would see"""
     prior = np.asarray(prior, dtype=np.float32)
     synd = np.asarray(synd, dtype=np.uint8)
     B, m, n, E = synd.shape[0], g.m, g.n, g.nnz
@@ -64,6 +65,7 @@ def run(g, prior, synd, max_iter, alpha=1.0):
     x = np.broadcast_to(prior[..., col_idx], (B, E)).copy()  # variable-to-check messages; before iteration 1: the priors
     post = np.zeros((max_iter + 1, B, n), dtype=np.float32)
     same = np.zeros((max_iter + 1, B), dtype=bool)
+    same_but_arg = np.zeros((max_iter + 1, B), dtype=bool)
     rec_prev = None
     sgn_prev, sgn_same = x <= 0, np.zeros(B, dtype=bool)
     for it in range(1, max_iter + 1):
@@ -83,8 +85,10 @@ def run(g, prior, synd, max_iter, alpha=1.0):
         rec = (r1.view(np.uint32), r2.view(np.uint32), arg)
         if rec_prev is not None:
             rec_same = np.ones(B, dtype=bool)
-            for u, v in zip(rec, rec_prev):
+            for u, v in zip(rec[:2], rec_prev[:2]):
                 rec_same &= (u == v).all(axis=1)
+            same_but_arg[it] = rec_same & sgn_same
+            rec_same &= (rec[2] == rec_prev[2]).all(axis=1)
             same[it] = rec_same & sgn_same
         rec_prev = rec
         # ---- the messages the variable pass rebuilds: (arg-min ? rec2 : rec1) with the edge's own sign flipped in --------
@@ -109,7 +113,7 @@ def run(g, prior, synd, max_iter, alpha=1.0):
         sgn = x <= 0
         sgn_same = (sgn == sgn_prev).all(axis=1)
         sgn_prev = sgn
-    return {"post": post, "same": same}
+    return {"post": post, "same": same, "same_but_arg": same_but_arg}
 
 
 def settled_at(same, first, last):
