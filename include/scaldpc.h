@@ -336,6 +336,10 @@ int scaldpc_bp_last_settle(scaldpc_bp *h, int32_t *frozen_at, int32_t cap, int64
  *                   masks (sign, arg-min: 0.25 B per codeword) instead of 4 B per edge and codeword; the variable pass
  *                   rebuilds every message from them, bit for bit.  0 = messages both ways (what graphs with a row
  *                   wider than 64 or a column wider than 32 use anyway).
+ *                   2 = 1, and columns of 33 ... 64 edges stay in the record form: a second variable launch takes
+ *                   them (k_var<64, ..> in a record mode, over the widest degree bucket), the narrower columns run the kernels they
+ *                   run under 1.  Opt-in: on a graph without such a column 2 is 1, launch for launch; any value other
+ *                   than 0 and 2 means 1.  Results never depend on it.
  *   "first_fused"   1 (default) = iteration 1 of the tile kernels runs without its check pass: the first variable
  *                   pass takes the first check-to-variable messages from a per-edge table (the message of a
  *                   zero-syndrome codeword) and the row's syndrome bit; 0 = check pass (reading the priors) + plain

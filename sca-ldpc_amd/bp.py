@@ -478,7 +478,9 @@ class BpDecoder:
     def configure(self, **knobs):
         """Tuning / test knobs of this decoder (include/scaldpc.h, scaldpc_bp_configure): path, split,
         group_mb, el_max, compact_after, first_fused, fuse_test, minsum_rec, settle, settle_horizon.  A new decoder takes its
-        defaults from the SCALDPC_* environment once, at construction; results never depend on them."""
+        defaults from the SCALDPC_* environment once, at construction; results never depend on them.
+        minsum_rec=2 (passed through as it is): 1, and columns of 33 ... 64 edges stay in min-sum's record form -- opt-in;
+        by default, and under 1, a graph with such a column runs the message form."""
         for k, v in knobs.items():
             _lib.check(self._lib.scaldpc_bp_configure(self._h, k.encode(), str(v).encode()))
 

@@ -105,7 +105,7 @@ struct Knobs {
     int compact_after = -1;   // -1 = default (4); 0 = no compact pass.  The fp32 scheduler: the iteration FROM which a hand-over may happen; the float64 sweeps: the iteration AT which the one hand-over happens (ref64_handover)
     int fuse_test = 1;        // early-exit tile loop: the convergence test of iteration it rides on the check pass of it + 1 wherever the host does not need the verdict in between
     int first_fused = 1;      // iteration 1 of the tile kernels without its check pass (k_var_first from the first-message table); 0 = check pass + plain variable pass
-    int minsum_rec = 1;       // min-sum on the tile kernels: check pass writes per-row records + lane masks instead of messages (k_check_minsum_rec / k_var_rec); 0 = message form
+    int minsum_rec = 1;       // min-sum on the tile kernels: check pass writes per-row records + lane masks instead of messages (k_check_minsum_rec / k_var_rec); 0 = message form; 2 = 1, and columns of 33 ... 64 edges stay in the record form (rec_form)
     int settle = -1;          // fixed-iteration record-form calls: -1 = 2 on a graph [Hin | I], 0 on any other (settle_mode); 0 = every pass runs; 1 = passes return at once for tiles whose message state has stopped changing (Settle); 2 = and a learned horizon keeps them from being enqueued
     int settle_horizon = 0;   // > 0: the horizon K, forced (tiles it is wrong for are decoded again: results never depend on it)
 };
@@ -302,7 +302,7 @@ bool set_knob(Knobs &k, const char *key, const char *val)
     else if (!strcmp(key, "el_max")) k.el_max = (int)x;
     else if (!strcmp(key, "compact_after")) k.compact_after = (int)x;
     else if (!strcmp(key, "first_fused")) k.first_fused = (int)x != 0;
-    else if (!strcmp(key, "minsum_rec")) k.minsum_rec = (int)x != 0;
+    else if (!strcmp(key, "minsum_rec")) k.minsum_rec = x == 2.0 ? 2 : (int)x != 0;  // (2: wide columns too; else 0 / 1)
     else if (!strcmp(key, "fuse_test")) k.fuse_test = (int)x != 0;
     else if (!strcmp(key, "settle") && x >= -1 && x <= 2) k.settle = (int)x;
     else if (!strcmp(key, "settle_horizon") && x >= 0) k.settle_horizon = (int)x;
@@ -674,9 +674,11 @@ int ensure_el_tables(scaldpc_bp *h)
 // exact-degree check kernels, the scalar-id variable kernel.
 bool rec_form(const scaldpc_bp *h, int method)
 {
-    // (columns of 33-64 edges: message form -- the exact-degree variable pass is compiled up to 32)
+    // (columns of 33-64 edges: message form -- the exact-degree variable pass is compiled up to 32 -- unless minsum_rec
+    // is 2: then a second launch takes them, k_var<64, ..> in its record mode over the (32, 64] bucket, launch_var)
     // (and the variable pass's row words hold 24 bits of row beside the edge's index in it: rec_rows_fit)
-    return method == SCALDPC_BP_MIN_SUM && h->kn.minsum_rec && h->E > 0 && h->max_row_deg <= 64 && h->max_col_deg <= 32 &&
+    const int col_cap = h->kn.minsum_rec == 2 ? 64 : 32;
+    return method == SCALDPC_BP_MIN_SUM && h->kn.minsum_rec && h->E > 0 && h->max_row_deg <= 64 && h->max_col_deg <= col_cap &&
            !h->hg_var.has_generic && rec_rows_fit(h->m, h->max_row_deg);
 }
 
@@ -916,26 +918,53 @@ int launch_var(scaldpc_bp *h, int G, float *post_g, u64 *hard_g, const u64 *done
         // block of an HQC graph: 4000 of 21669 column waves per tile).
         const int n1 = (h->var_bk.nb > 0 && h->var_bk.maxd[0] == 1) ? h->var_bk.blk[1] : 0;
         const bool slim = light && !write_out && n1 > 0 && n1 < nblk;
-        const int nb_launch = slim ? nblk - n1 : nblk;
+        // wide: the blocks of the (32, 64] bucket (minsum_rec = 2, rec_form; the last bucket, no any-degree one behind it).
+        // They get a launch of their own -- k_var<64, ..>, the kernel that already keeps 64 edges in registers, in its record
+        // mode (RecWide) -- so that the exact-degree code of the columns up to 32 stays what it is; the narrow launch runs
+        // over the other buckets' blocks, compiled for the widest of THEM.  The buckets have block boundaries of their
+        // own: a slice is a first block and a count, like the slim pass's.
+        const int nbk = h->var_bk.nb;
+        const int nwide = (nbk > 0 && h->var_bk.maxd[nbk - 1] > 32) ? nblk - h->var_bk.blk[nbk - 1] : 0;
+        const int narrow_deg = nwide ? (nbk > 1 ? h->var_bk.maxd[nbk - 2] : 0) : h->max_col_deg;
+        const int nb_launch = (slim ? nblk - n1 : nblk) - nwide;
         // XCD-aware tile placement where the launch's tiles divide the 8 XCDs (fetch 38.0 -> 29.5 MB per launch, profiles/r03/ab_rec_xmap.log)
         const bool xm = G == 2 || G == 4 || G == 8;
-        const dim3 gridr((unsigned)(xm ? (nb_launch + 7) / 8 * 8 : nb_launch), G);
-        const int blk0 = slim && !h->var_reversed ? n1 : 0, xmap = xm ? nb_launch : 0;
-        with_cap<16, 32>(h->max_col_deg, [&](auto cap) {  // (columns wider than 32 take the message form: rec_form)
+        // (heaviest first, var_reversed: the wide blocks lead the records and the degree-1 bucket ends them)
+        const int blk0 = h->var_reversed ? nwide : (slim ? n1 : 0), wide0 = h->var_reversed ? 0 : nblk - nwide;
+        auto slice = [&](auto cap, int first, int count) {  // blocks [first, first + count) of the records
+            const dim3 gridr((unsigned)(xm ? (count + 7) / 8 * 8 : count), G);
             with_prior(h, sp, [&](auto P, auto prior) {
                 with_bool(final_pass && write_out, [&](auto fin) {
                     hipLaunchKernelGGL((k_var_rec<cap, decltype(P), fin>), gridr, dim3(256), 0, s, h->d_var_meta, h->d_var_rows,
                                        h->d_csc_list, h->d_csc_row, prior, msg0, h->d_rec + (size_t)tile0 * rec_tile_floats(h->m),
                                        h->d_mask + (size_t)tile0 * h->E, post_g, hard_g, done_g, skip_done, h->n, h->m, h->E,
-                                       (write_out || keep_hard) ? 1 : 0, blk0, xmap, stl);
+                                       (write_out || keep_hard) ? 1 : 0, first, xm ? count : 0, stl);
                 });
             });
-        });
+        };
+        if (nb_launch > 0) with_cap<16, 32>(narrow_deg, [&](auto cap) { slice(cap, blk0, nb_launch); });
+        if (nwide > 0) {  // k_var<64, P> in its record mode (RecWide)
+            RecWide rw;
+            rw.var_rows = h->d_var_rows;
+            rw.csc_row = h->d_csc_row;
+            rw.rec = h->d_rec + (size_t)tile0 * rec_tile_floats(h->m);
+            rw.sgn = h->d_mask + (size_t)tile0 * h->E;
+            rw.m = h->m;
+            rw.blk0 = wide0;
+            rw.xmap = xm ? nwide : 0;
+            rw.last = final_pass && write_out;
+            rw.stl = stl;
+            const dim3 gridw((unsigned)(xm ? (nwide + 7) / 8 * 8 : nwide), G);
+            with_prior(h, sp, [&](auto P, auto prior) {
+                hipLaunchKernelGGL((k_var<64, decltype(P)>), gridw, dim3(256), 0, s, h->d_var_meta, h->d_csc_list, prior, msg0, scr0,
+                                   post_g, hard_g, done_g, skip_done, h->n, h->E, (write_out || keep_hard) ? 1 : 0, rw);
+            });
+        }
     } else {
         with_cap<16, 32, 64>(h->max_col_deg, [&](auto cap) {
             with_prior(h, sp, [&](auto P, auto prior) {
                 hipLaunchKernelGGL((k_var<cap, decltype(P)>), dim3(nblk, G), dim3(256), 0, s, h->d_var_meta, h->d_csc_list, prior, msg0,
-                                   scr0, post_g, hard_g, done_g, skip_done, h->n, h->E, write_out);
+                                   scr0, post_g, hard_g, done_g, skip_done, h->n, h->E, write_out, RecWide{});
             });
         });
     }

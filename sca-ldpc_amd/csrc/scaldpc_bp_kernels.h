@@ -1491,6 +1491,25 @@ __device__ __forceinline__ float var_col_generic(float *mt, float *st, const int
     return temp;
 }
 
+// The WIDE launch of the min-sum record form (minsum_rec = 2: columns of 33 ... 64 edges, see var_col_rec_wide below).
+// k_var<64, P> is the kernel that already holds a column of 64 edges in registers (mm[64], pp[64]: 136 VGPRs), so the
+// record-form pass of such columns is a MODE of it, not an instantiation of k_var_rec: rec non-null = this launch runs
+// over blocks [blk0, ..) of the column records -- the (32, 64] bucket -- and rebuilds the messages from the records, as
+// k_var_rec does for the columns up to 32.  The narrower builds of k_var never look at it.
+struct RecWide {
+    const int *var_rows = nullptr, *csc_row = nullptr;  // k_var_rec's var_rows / csc_row
+    const float *rec = nullptr;                         // the group's records; null = the message form (plain k_var)
+    u64 *sgn = nullptr;
+    int m = 0, blk0 = 0, xmap = 0;                      // rows; first block of the slice; blocks per tile under the XCD map (0 = none)
+    int last = 0;                                       // k_var_rec's LAST
+    Settle stl = Settle{};
+};
+template <class P>
+__device__ __forceinline__ void var_rec_wide_wave(const int *__restrict__ list, const int *__restrict__ csc_edge, const P &prior,
+                                                  float *msg, float *__restrict__ post, u64 *__restrict__ hard,
+                                                  const u64 *__restrict__ done, int skip_done, int n, long E, int write_out,
+                                                  const RecWide &rw);
+
 // One fused launch over all column-degree buckets.  wave = (column, tile), lane = codeword.
 // grid (column records / 4, G), block 256 = 4 columns of one bucket.
 // write_out: also emit hard-decision planes (merged under the done mask) and, if
@@ -1501,9 +1520,14 @@ __global__ __launch_bounds__(256) void k_var(const int *__restrict__ list, const
                                              typename P::Arg prior_arg, float *msg, float *scratch,
                                              float *__restrict__ post, u64 *__restrict__ hard,
                                              const u64 *__restrict__ done, int skip_done, int n, long E,
-                                             int write_out)
+                                             int write_out, RecWide rw = RecWide{})
 {
     const P prior{prior_arg};
+    if constexpr (CAP >= 64)
+        if (rw.rec) {  // (wave-uniform: a kernel argument)
+            var_rec_wide_wave(list, csc_edge, prior, msg, post, hard, done, skip_done, n, E, write_out, rw);
+            return;
+        }
     const int lane = threadIdx.x & 63;
     const int tl = blockIdx.y;
     // one record per WAVE of the launch (VAR_REC ints: descriptor + the first VAR_INLINE edge ids), at
@@ -1736,6 +1760,169 @@ __device__ __forceinline__ float var_col_rec(float *tile_base, const float *__re
         if (__ballot((int)lane < D && (dlo | dhi) != 0) != 0 && lane == 0) *mark_word = mark;
     }
     return temp;
+}
+
+// The WIDE column: var_col_rec for a column of d = 33 ... 64 edges (minsum_rec = 2; a few dozen columns in tens of
+// thousands on the attack's graphs, so this is sized for registers and code size, not for issue slots).  Same inputs, same
+// outputs, the same operations on every value in the same order -- prefix from the prior ascending, suffix descending,
+// stored message pp[k] + suf, posterior prior + mm[0] + mm[1] + ...; sign masks in and out in lane k as there.  ONE body
+// for all 32 degrees: edges 0 ... 31 are there for every such column, the ones behind them are predicated on the
+// wave-uniform `k < d`.  Only mm[64] and pp[64] live across the column; row words, arg-min bytes and edge ids are taken
+// 16 at a time (scalar loads: the record's inline words for the first 16, csc_row / csc_edge for the others -- the lists
+// are padded, a 16-word read that starts inside a column stays inside them), first for the gathers and again, from the
+// last chunk down, for the stores.  LAST keeps no array at all: it sums each chunk as it arrives.
+template <bool LAST>
+__device__ __forceinline__ float var_col_rec_wide(float *tile_base, const float *__restrict__ rec_base, unsigned rec2_off,
+                                                  const unsigned char *__restrict__ arg_base, u64 *sgn_col, unsigned lane,
+                                                  const int *__restrict__ rc, const int4 *__restrict__ row4,
+                                                  const int *__restrict__ ce1, const int *__restrict__ cr1, int d, float pr,
+                                                  unsigned *mark_word = nullptr, unsigned mark = 0, u64 real = 0)
+{
+    constexpr int W = 64, CH = 16, SURE = 32;  // SURE: edges every column that comes here has
+    u64 sg = 0;
+    if ((int)lane < d) sg = sgn_col[lane];
+    const int slo = (int)(unsigned)sg, shi = (int)(unsigned)(sg >> 32);
+    const unsigned off1 = lane * 4u, off2 = off1 + rec2_off;
+    float mm[W];
+    float sum = pr;
+#pragma unroll
+    for (int c = 0; c < W / CH; c++) {
+        if (c * CH >= SURE && c * CH >= d) break;
+        int rw[CH];
+        if (c == 0) {
+            const int4 ra = row4[0], rb = row4[1], rc4 = row4[2], re = row4[3];
+            const int rw16[16] = {ra.x, ra.y, ra.z, ra.w, rb.x, rb.y, rb.z, rb.w, rc4.x, rc4.y, rc4.z, rc4.w, re.x, re.y, re.z, re.w};
+#pragma unroll
+            for (int k = 0; k < CH; k++) rw[k] = rw16[k];
+        } else {
+#pragma unroll
+            for (int k = 0; k < CH; k++) rw[k] = cr1[c * CH + k];
+        }
+        unsigned ab[CH];
+#pragma unroll
+        for (int k = 0; k < CH; k++)
+            if (c * CH + k < SURE || c * CH + k < d) ab[k] = sbase_b(arg_base + (size_t)rec_row_of(rfl(rw[k])) * TW)[lane];
+#pragma unroll
+        for (int k = 0; k < CH; k++)
+            if (c * CH + k < SURE || c * CH + k < d) {
+                const unsigned off = ab[k] == (unsigned)rec_index_of(rfl(rw[k])) ? off2 : off1;
+                mm[c * CH + k] = *(const gfloat *)((const gbyte *)sbase(rec_base + (size_t)rec_row_of(rfl(rw[k])) * TW) + off);
+            }
+#pragma unroll
+        for (int k = 0; k < CH; k++)
+            if (c * CH + k < SURE || c * CH + k < d) {
+                const int e = c * CH + k;
+                const u64 ng = ((u64)(unsigned)__builtin_amdgcn_readlane(shi, e) << 32) | (unsigned)__builtin_amdgcn_readlane(slo, e);
+                mm[e] = __builtin_amdgcn_inverse_ballot_w64(ng) ? -mm[e] : mm[e];
+                if constexpr (LAST) sum += mm[e];
+            }
+    }
+    if constexpr (LAST) return sum;
+    float pp[W];
+    float temp = pr;
+#pragma unroll
+    for (int k = 0; k < W; k++)
+        if (k < SURE || k < d) {
+            pp[k] = temp;
+            temp += mm[k];
+        }
+    float suf = 0.0f;
+    unsigned nlo = 0, nhi = 0;  // lane k keeps edge k's new sign mask
+#pragma unroll
+    for (int c = W / CH - 1; c >= 0; c--) {
+        if (c * CH >= SURE && c * CH >= d) continue;
+        int eid[CH];
+        if (c == 0) {
+            const int4 *rec4 = (const int4 *)rc;
+            const int4 a = rec4[1], b = rec4[2], c4 = rec4[3], e4 = rec4[4];
+            const int in16[16] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c4.x, c4.y, c4.z, c4.w, e4.x, e4.y, e4.z, e4.w};
+#pragma unroll
+            for (int k = 0; k < CH; k++) eid[k] = in16[k];
+        } else {
+#pragma unroll
+            for (int k = 0; k < CH; k++) eid[k] = ce1[c * CH + k];
+        }
+#pragma unroll
+        for (int k = CH - 1; k >= 0; k--)
+            if (c * CH + k < SURE || c * CH + k < d) {
+                const int e = c * CH + k;
+                gfloat *q = sbase(tile_base + (size_t)rfl(eid[k]) * TW) + lane;
+                const float out = pp[e] + suf;
+                __hip_atomic_store(q, out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (sc1, as in var_col_rec)
+                const u64 nm = __ballot(out <= 0.0f);  // a float compare on the stored value: +-0 is "negative", NaN is not
+                nlo = writelane((unsigned)nm, e, nlo);
+                nhi = writelane((unsigned)(nm >> 32), e, nhi);
+                suf += mm[e];
+            }
+    }
+    if ((int)lane < d) sgn_col[lane] = ((u64)nhi << 32) | nlo;
+    // settled codewords (Settle), as in var_col_rec
+    if (mark_word) {
+        const unsigned dlo = (nlo ^ (unsigned)slo) & (unsigned)real, dhi = (nhi ^ (unsigned)shi) & (unsigned)(real >> 32);
+        if (__ballot((int)lane < d && (dlo | dhi) != 0) != 0 && lane == 0) *mark_word = mark;
+    }
+    return temp;
+}
+
+// A wave of the WIDE record-form launch (RecWide, k_var<64, P>): k_var_rec's wave -- slice of the records, XCD map, settled
+// tiles, output -- around var_col_rec_wide, with LAST a run-time value (wave-uniform: both bodies are compiled in).
+template <class P>
+__device__ __forceinline__ void var_rec_wide_wave(const int *__restrict__ list, const int *__restrict__ csc_edge, const P &prior,
+                                                  float *msg, float *__restrict__ post, u64 *__restrict__ hard,
+                                                  const u64 *__restrict__ done, int skip_done, int n, long E, int write_out,
+                                                  const RecWide &rw)
+{
+    const unsigned lane = threadIdx.x & 63u;
+    int tl = blockIdx.y, bx = blockIdx.x;
+    if (rw.xmap) {  // (as in k_var_rec)
+        const unsigned G = gridDim.y, L = blockIdx.y * gridDim.x + blockIdx.x, xcd = L & 7u, slot = L >> 3;
+        tl = (int)(xcd % G);
+        bx = (int)(slot * (8u / G) + xcd / G);
+        if (bx >= rw.xmap) return;
+    }
+    const int ri = rfl((bx + rw.blk0) * 4 + (int)(threadIdx.x >> 6));
+    const int *rc = list + (size_t)ri * VAR_REC;
+    const u64 dn = done[tl];
+    if (skip_done && dn == ~0ull) return;
+    const bool last = rw.last != 0;
+    unsigned *mark_word = nullptr;
+    bool decided = false;
+    if (rw.stl.words) {  // settled codewords, as in k_var_rec
+        unsigned *w = rw.stl.words + (size_t)tl * SETTLE_WORDS;
+        const bool frozen = settle_frozen(w, rw.stl.done);
+        if (last)
+            decided = frozen;
+        else {
+            if (frozen) return;
+            if (rw.stl.mark) mark_word = w + ((unsigned)bx & (SETTLE_SHARDS - 1));
+        }
+    }
+    const int v = rc[0];
+    if (v < 0) return;
+    const int cb = rc[1];
+    const int d = rc[2];
+    if (d <= 32 || d > 64) return;  // (never: the slice is the (32, 64] bucket)
+    if (last && decided) return;
+    float *tb = msg + (size_t)tl * E * TW;
+    const float *rb = rw.rec + (size_t)tl * rec_tile_floats(rw.m);
+    const unsigned char *ab = (const unsigned char *)(rb + rec_arg_off(rw.m));
+    u64 *st = rw.sgn + (size_t)tl * E;
+    const int *ce = csc_edge + cb, *cr = rw.csc_row + cb;
+    const int4 *w4 = (const int4 *)(rw.var_rows + (size_t)ri * VAR_INLINE);
+    const float pr = prior(v, tl, (int)lane);
+    const unsigned r2 = (unsigned)rw.m * (TW * (unsigned)sizeof(float));
+    const float L = last ? var_col_rec_wide<true>(tb, rb, r2, ab, st + cb, lane, rc, w4, ce, cr, d, pr)
+                         : var_col_rec_wide<false>(tb, rb, r2, ab, st + cb, lane, rc, w4, ce, cr, d, pr, mark_word,
+                                                   (unsigned)rw.stl.mark, ~dn);
+    if (write_out) {
+        const u64 hb = __ballot(L <= 0.0f);
+        const size_t hi = (size_t)tl * n + v;
+        if (dn == 0) {
+            if (lane == 0) hard[hi] = hb;
+        } else if (lane == 0)
+            hard[hi] = (hard[hi] & dn) | (hb & ~dn);
+        if (post && !((dn >> lane) & 1)) post[hi * TW + lane] = L;
+    }
 }
 
 // grid (column records / 4, G), block 256 = 4 column records (k_var's launch shape and records).
