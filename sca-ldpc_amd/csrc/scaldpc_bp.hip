@@ -35,6 +35,7 @@
 
 #include <algorithm>
 #include <cfloat>
+#include <chrono>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -173,7 +174,6 @@ struct scaldpc_bp : HandleStreams {
     // small host calls (one tile, a handful of codewords): fused reshaping kernels, one pinned staging buffer
     PinnedBuf<uint8_t> h_io;
     Buf<uint8_t> d_out_all;
-    bool small_prepared = false;  // k_small_prepare already reset the state this call (run_core / the early-exit loop skip theirs)
     // Monte-Carlo helpers
     pvec<double> h_probs;
     Buf<u64> d_thr, d_mc, d_diff;
@@ -271,7 +271,6 @@ struct scaldpc_bp : HandleStreams {
     int settle_next = 0;
     int settle_key_iter = 0, settle_key_soft = 0;
     float settle_key_alpha = -1.0f;
-    bool settle_no_host = false;  // the call in progress must not synchronise (SCALDPC_F_ASYNC): device-side skipping only
     std::vector<int> settle_frozen_at;  // per tile of the last call, 0 = never froze; empty = the call did not track
     long settle_saved = 0, settle_rerun = 0;
     int settle_K = 0;
@@ -729,13 +728,48 @@ int el_limit(const scaldpc_bp *h, int method)
 
 #define LAUNCH_CHECK() SC_HIP(hipGetLastError())
 
+// One decode call, from its entry point (begin_call) down to the launches.  A compact level runs on a copy with its own
+// batch and T.
+struct DecodeCall {
+    hipStream_t s = nullptr;
+    int batch = 0, T = 0, G = 0, max_iter = 0, method = 0;  // codewords, tiles of 64 of them, tiles per cache-resident group
+    float alpha = 0.0f;
+    bool early = false, want_post = false;
+    bool state_ready = false;  // the call's state planes and counters are already reset (k_small_prepare): nothing below resets them
+    bool no_sync = false;      // this call may not synchronise (SCALDPC_F_ASYNC): settled codewords by device-side skipping only
+};
+
+// The state planes of a call's (or a compact level's) tiles.
+struct TileState {
+    const u64 *synd;
+    u64 *hard, *done, *conv, *unsat;
+    int *iters;
+    float *post;
+    // a soft call: prior LLRs per codeword for the columns [first_col, n), float [tile][n - first_col][64] (null: shared priors)
+    const float *pprior = nullptr;
+    int first_col = 0;
+    // the same planes from tile `ta` on -- what a launch whose first tile is ta works on (null stays null)
+    TileState at(const scaldpc_bp *h, int ta) const
+    {
+        const size_t t = (size_t)ta;
+        return TileState{synd + t * h->m, hard + t * h->n, done + t, conv + t, unsat + t * parity_waves(h), iters + t * TW,
+                         post ? post + t * h->n * TW : nullptr, pprior ? pprior + t * (h->n - first_col) * TW : nullptr, first_col};
+    }
+};
+// the convergence test of iteration `it` on a view's tiles; *remaining counts who still runs after it; latch = early exit
+FusedTest fused_test(const scaldpc_bp *h, const TileState &tv, int *remaining, int it, bool latch)
+{
+    return FusedTest{tv.hard, tv.unsat, tv.done, tv.conv, tv.iters, remaining, h->n, parity_waves(h), it, latch ? 1 : 0};
+}
+
 // Compile-time dispatch of the launches.  with_cap<16, 32, 64>(deg, f) calls f(std::integral_constant<int, CAP>) with the
 // first CAP of the ladder that holds a node degree `deg` (the last CAP takes anything wider: the kernels' any-degree
 // fallback); every kernel is instantiated for exactly the ladder its launch names.  with_bool / with_method hand f a
 // runtime bool / update rule as a compile-time one; with_prior hands it the prior source of the call as a type (a value of
-// it, for decltype) with the kernel argument that goes with it: sp non-null = a soft call, SoftPrior and *sp; else
-// SharedPrior and the handle's priors.  with_first_prior is for the check kernels, whose FIRST pass alone reads priors:
-// f(FIRST, source, argument), and FIRST = false comes with SharedPrior only -- no <.., false, .., SoftPrior> instantiation.
+// it, for decltype) with the kernel argument that goes with it: plane non-null = a soft call, SoftPrior over the plane (of
+// the launch's first tile) for the columns from first_col on; else SharedPrior and the handle's priors.  with_first_prior is
+// for the check kernels, whose FIRST pass alone reads priors, on the tiles of a view: f(FIRST, source, argument), and
+// FIRST = false comes with SharedPrior only -- no <.., false, .., SoftPrior> instantiation.
 template <int CAP, int... WIDER, typename F>
 void with_cap(int deg, F &&f)
 {
@@ -758,15 +792,15 @@ void with_method(int method, F &&f)
     else f(std::integral_constant<int, SCALDPC_BP_PRODUCT_SUM>{});
 }
 template <typename F>
-void with_prior(const scaldpc_bp *h, const SoftPrior *sp, F &&f)
+void with_prior(const scaldpc_bp *h, const float *plane, int first_col, F &&f)
 {
-    sp ? f(SoftPrior{}, *sp) : f(SharedPrior{}, (const float *)h->d_prior);
+    plane ? f(SoftPrior{}, SoftPrior{h->d_prior, plane, first_col, h->n - first_col}) : f(SharedPrior{}, (const float *)h->d_prior);
 }
 template <typename F>
-void with_first_prior(const scaldpc_bp *h, bool first, const SoftPrior *sp, F &&f)
+void with_first_prior(const scaldpc_bp *h, bool first, const TileState &tv, F &&f)
 {
     if (first)
-        with_prior(h, sp, [&](auto P, auto prior) { f(std::true_type{}, P, prior); });
+        with_prior(h, tv.pprior, tv.first_col, [&](auto P, auto prior) { f(std::true_type{}, P, prior); });
     else
         f(std::false_type{}, SharedPrior{}, (const float *)h->d_prior);
 }
@@ -787,64 +821,67 @@ bool check_can_test(const scaldpc_bp *h, int method)
     return true;
 }
 
-// ft: non-null = this pass also runs the convergence test of the previous iteration (check_can_test(h, method), never `first`)
-// sp: non-null = a soft call; its FIRST check pass (the only one that reads priors) takes them per codeword
-// stl: settled codewords (record-form passes of a fixed-iteration call; the default = off, as scaldpc_bp_time_kernels runs)
-int launch_check(scaldpc_bp *h, int method, float alpha, int G, const u64 *synd_g, const u64 *done_g, int skip_done,
-                 hipStream_t s, bool first = false, int tile0 = 0, const FusedTest *ft = nullptr, const SoftPrior *sp = nullptr,
-                 bool boot = false, const Settle &stl = Settle{})
+// One check pass over G tiles.
+struct CheckPass {
+    float alpha = 0.0f;
+    // The first check pass of these tiles in a call -- iteration 1 with first_fused off, or of a soft call: the only one that
+    // reads priors (a soft call's per codeword, from the view), and in min-sum it writes MESSAGES whatever the form, followed
+    // by the message form's variable pass -- the records start with iteration 2.
+    bool first = false;
+    int tile0 = 0;  // first tile of the launch inside the group's message / record arrays
+    FusedTest test{};  // hard non-null = the pass also runs the test of the iteration before (check_can_test, never `first`)
+    // The first record-form pass of these tiles in a call: the sign masks a k_var_rec would have left are not there yet
+    // (the messages come from k_var_first / k_var), so this pass writes them too.
+    bool boot = false;
+    Settle settle{};  // settled codewords (record-form passes of a fixed-iteration call); the default = off
+};
+int launch_check(scaldpc_bp *h, const TileState &tv, int G, int method, int skip_done, hipStream_t s, const CheckPass &p)
 {
     if (h->E == 0) return 0;
-    float *const msg0 = h->d_msg + (size_t)tile0 * h->E * TW;  // tile0: first tile of a sub-group inside the group's array
-    float *const scr0 = h->d_scratch ? h->d_scratch + (size_t)tile0 * h->E * TW : nullptr;
+    float *const msg0 = h->d_msg + (size_t)p.tile0 * h->E * TW;
+    float *const scr0 = h->d_scratch ? h->d_scratch + (size_t)p.tile0 * h->E * TW : nullptr;
     const dim3 grid(h->row_bk.blk[h->row_bk.nb], G), block(256);  // one wave per row descriptor
-    const bool test = ft && !first;
+    const bool test = p.test.hard && !p.first;
     if (method != SCALDPC_BP_MIN_SUM) {  // (first: fused_init holds, so the rows are register-resident)
         with_cap<16, 32, 64>(h->max_row_deg, [&](auto cap) {
             if (test)
-                hipLaunchKernelGGL((k_check_tanh<cap, false, true, SharedPrior>), grid, block, 0, s, h->d_row_list, msg0, scr0, synd_g,
-                                   done_g, skip_done, h->m, h->E, h->d_col_idx, h->d_prior, *ft);
+                hipLaunchKernelGGL((k_check_tanh<cap, false, true, SharedPrior>), grid, block, 0, s, h->d_row_list, msg0, scr0, tv.synd,
+                                   tv.done, skip_done, h->m, h->E, h->d_col_idx, h->d_prior, p.test);
             else
-                with_first_prior(h, first, sp, [&](auto fst, auto P, auto prior) {
+                with_first_prior(h, p.first, tv, [&](auto fst, auto P, auto prior) {
                     hipLaunchKernelGGL((k_check_tanh<cap, fst, false, decltype(P)>), grid, block, 0, s, h->d_row_list, msg0, scr0,
-                                       synd_g, done_g, skip_done, h->m, h->E, h->d_col_idx, prior, FusedTest{});
+                                       tv.synd, tv.done, skip_done, h->m, h->E, h->d_col_idx, prior, FusedTest{});
                 });
         });
-    } else if (rec_form(h, method) && !first) {
-        // (a first check pass -- iteration 1 with first_fused off, or of a soft call -- reads the priors and writes
-        // MESSAGES: the message form's kernel, followed by the message form's variable pass; the records start with
-        // iteration 2)
-        // boot: the first record-form pass of these tiles in a call -- the sign masks a k_var_rec would have left are
-        // not there yet (the messages come from k_var_first / k_var), so this pass writes them too
-        float *const rec0 = h->d_rec + (size_t)tile0 * rec_tile_floats(h->m);
-        u64 *const mask0 = h->d_mask + (size_t)tile0 * h->E;
-        const FusedTest ft0 = test ? *ft : FusedTest{};
+    } else if (rec_form(h, method) && !p.first) {
+        float *const rec0 = h->d_rec + (size_t)p.tile0 * rec_tile_floats(h->m);
+        u64 *const mask0 = h->d_mask + (size_t)p.tile0 * h->E;
         // the constant last edge of a marked row is read from the shared priors as they are NOW (set_channel_probs on a live
         // decoder needs no rebuild); a soft call's columns of degree 1 may carry per-codeword priors: no constant there
-        const float *const cprior = sp ? nullptr : h->d_prior;
+        const float *const cprior = tv.pprior ? nullptr : h->d_prior;
         with_cap<16, 32, 64>(h->max_row_deg, [&](auto cap) {
-            with_bool(boot, [&](auto bt) {
+            with_bool(p.boot, [&](auto bt) {
                 with_bool(test, [&](auto par) {
-                    hipLaunchKernelGGL((k_check_minsum_rec<cap, bt, par>), grid, block, 0, s, h->d_row_list, msg0, synd_g, done_g,
-                                       skip_done, h->m, h->E, alpha, h->d_col_idx, rec0, mask0, h->d_csr_pos, cprior, ft0, stl);
+                    hipLaunchKernelGGL((k_check_minsum_rec<cap, bt, par>), grid, block, 0, s, h->d_row_list, msg0, tv.synd, tv.done,
+                                       skip_done, h->m, h->E, p.alpha, h->d_col_idx, rec0, mask0, h->d_csr_pos, cprior, p.test, p.settle);
                 });
             });
         });
     } else if (h->max_row_deg <= ROW_CAP) {
         with_cap<16, 32, 64>(h->max_row_deg, [&](auto cap) {
             if (test)
-                hipLaunchKernelGGL((k_check_minsum_x<cap, false, true, SharedPrior>), grid, block, 0, s, h->d_row_list, msg0, synd_g,
-                                   done_g, skip_done, h->m, h->E, alpha, h->d_col_idx, h->d_prior, *ft);
+                hipLaunchKernelGGL((k_check_minsum_x<cap, false, true, SharedPrior>), grid, block, 0, s, h->d_row_list, msg0, tv.synd,
+                                   tv.done, skip_done, h->m, h->E, p.alpha, h->d_col_idx, h->d_prior, p.test);
             else
-                with_first_prior(h, first, sp, [&](auto fst, auto P, auto prior) {
+                with_first_prior(h, p.first, tv, [&](auto fst, auto P, auto prior) {
                     hipLaunchKernelGGL((k_check_minsum_x<cap, fst, false, decltype(P)>), grid, block, 0, s, h->d_row_list, msg0,
-                                       synd_g, done_g, skip_done, h->m, h->E, alpha, h->d_col_idx, prior, FusedTest{});
+                                       tv.synd, tv.done, skip_done, h->m, h->E, p.alpha, h->d_col_idx, prior, FusedTest{});
                 });
         });
     } else {  // a row wider than 64: the loop form
-        with_first_prior(h, first, sp, [&](auto fst, auto P, auto prior) {
-            hipLaunchKernelGGL((k_check_minsum<fst, decltype(P)>), dim3((h->m + 3) / 4, G), block, 0, s, h->d_row_ptr, msg0, synd_g,
-                               done_g, skip_done, h->m, h->E, alpha, h->d_col_idx, prior);
+        with_first_prior(h, p.first, tv, [&](auto fst, auto P, auto prior) {
+            hipLaunchKernelGGL((k_check_minsum<fst, decltype(P)>), dim3((h->m + 3) / 4, G), block, 0, s, h->d_row_ptr, msg0, tv.synd,
+                               tv.done, skip_done, h->m, h->E, p.alpha, h->d_col_idx, prior);
         });
     }
     LAUNCH_CHECK();
@@ -890,81 +927,67 @@ int ensure_first_table(scaldpc_bp *h, int method, float alpha1, hipStream_t s)
     return 0;
 }
 
-// first_synd: non-null = iteration 1 without its check pass (the group's syndrome planes; ensure_first_table first)
-// sp: non-null = a soft call (never with first_synd: the first-message table is a function of shared priors)
-// final_pass: no check pass follows this one on these tiles (the last iteration of a decode, always with write_out): the
-//             record form then runs its store-free instantiation, which leaves messages and sign masks as the pass before
-//             left them
-// keep_hard: a record-form pass without output still merges its columns' decisions into hard_g, from the sum it has anyway
-//             (settled codewords: the closing pass of a frozen tile then finds them there, k_var_rec).  It stays slim.
-int launch_var(scaldpc_bp *h, int G, float *post_g, u64 *hard_g, const u64 *done_g, int skip_done, int write_out,
-               hipStream_t s, int tile0 = 0, const u64 *first_synd = nullptr, bool rec = false, bool light = false,
-               const SoftPrior *sp = nullptr, bool final_pass = false, const Settle &stl = Settle{}, bool keep_hard = false)
+// One variable pass over G tiles.
+struct VarPass {
+    int write_out = 0;  // also emit the decisions (merged under the done mask) and, where the view has a plane for them, the posteriors
+    int tile0 = 0;      // first tile of the launch inside the group's message / record arrays
+    // Iteration 1 without its check pass (k_var_first, from the first-message table and the view's syndrome planes;
+    // ensure_first_table first).  Never in a soft call: the table is a function of shared priors.
+    bool first_synd = false;
+    bool rec = false;    // the check pass left records, not messages (rec_form)
+    bool light = false;  // a pass after iteration 1: without output, the record form leaves the degree-1 bucket out (rec_var_slices)
+    // No check pass follows this one on these tiles (the last iteration of a decode, always with write_out): the record form
+    // then runs its store-free instantiation, which leaves messages and sign masks as the pass before left them.
+    bool final_pass = false;
+    // A record-form pass without output still merges its columns' decisions into the view's hard planes, from the sum it has
+    // anyway (settled codewords: the closing pass of a frozen tile then finds them there, k_var_rec).  It stays slim.
+    bool keep_hard = false;
+    Settle settle{};  // settled codewords; the default = off
+};
+int launch_var(scaldpc_bp *h, const TileState &tv, int G, int skip_done, hipStream_t s, const VarPass &p)
 {
-    float *const msg0 = h->d_msg + (size_t)tile0 * h->E * TW;
-    float *const scr0 = h->d_scratch ? h->d_scratch + (size_t)tile0 * h->E * TW : nullptr;
-    const int nblk = h->var_bk.blk[h->var_bk.nb];
-    if (first_synd) {
+    float *const msg0 = h->d_msg + (size_t)p.tile0 * h->E * TW;
+    float *const scr0 = h->d_scratch ? h->d_scratch + (size_t)p.tile0 * h->E * TW : nullptr;
+    const Buckets &bk = h->var_bk;
+    const int nblk = bk.blk[bk.nb];
+    if (p.first_synd) {
         const int nrec = 4 * nblk;  // one record per wave of a plain k_var launch; two per wave here
         const dim3 grid2((unsigned)((nrec + 7) / 8), G);
         with_cap<16, 32, 64>(h->max_col_deg, [&](auto cap) {
-            hipLaunchKernelGGL((k_var_first<cap>), grid2, dim3(256), 0, s, h->d_var_meta, h->d_csc_list, h->d_prior, msg0, post_g,
-                               hard_g, done_g, skip_done, h->n, h->E, write_out, (const int2 *)h->d_first_tab, first_synd, h->m, nrec);
+            hipLaunchKernelGGL((k_var_first<cap>), grid2, dim3(256), 0, s, h->d_var_meta, h->d_csc_list, h->d_prior, msg0, tv.post,
+                               tv.hard, tv.done, skip_done, h->n, h->E, p.write_out, (const int2 *)h->d_first_tab, tv.synd, h->m, nrec);
         });
-    } else if (rec) {  // the check pass left records, not messages (rec_form)
-        // light: a pass without output after iteration 1.  A column of degree <= 1 always sends its prior; iteration 1
-        // has written that into the message array and the record check pass never overwrites it (its sign mask is the
-        // bootstrap check pass's, and stays true), so such a pass has nothing to do for the first bucket (the identity
-        // block of an HQC graph: 4000 of 21669 column waves per tile).
-        const int n1 = (h->var_bk.nb > 0 && h->var_bk.maxd[0] == 1) ? h->var_bk.blk[1] : 0;
-        const bool slim = light && !write_out && n1 > 0 && n1 < nblk;
-        // wide: the blocks of the (32, 64] bucket (minsum_rec = 2, rec_form; the last bucket, no any-degree one behind it).
-        // They get a launch of their own -- k_var<64, ..>, the kernel that already keeps 64 edges in registers, in its record
-        // mode (RecWide) -- so that the exact-degree code of the columns up to 32 stays what it is; the narrow launch runs
-        // over the other buckets' blocks, compiled for the widest of THEM.  The buckets have block boundaries of their
-        // own: a slice is a first block and a count, like the slim pass's.
-        const int nbk = h->var_bk.nb;
-        const int nwide = (nbk > 0 && h->var_bk.maxd[nbk - 1] > 32) ? nblk - h->var_bk.blk[nbk - 1] : 0;
-        const int narrow_deg = nwide ? (nbk > 1 ? h->var_bk.maxd[nbk - 2] : 0) : h->max_col_deg;
-        const int nb_launch = (slim ? nblk - n1 : nblk) - nwide;
-        // XCD-aware tile placement where the launch's tiles divide the 8 XCDs (fetch 38.0 -> 29.5 MB per launch, profiles/r03/ab_rec_xmap.log)
-        const bool xm = G == 2 || G == 4 || G == 8;
-        // (heaviest first, var_reversed: the wide blocks lead the records and the degree-1 bucket ends them)
-        const int blk0 = h->var_reversed ? nwide : (slim ? n1 : 0), wide0 = h->var_reversed ? 0 : nblk - nwide;
-        auto slice = [&](auto cap, int first, int count) {  // blocks [first, first + count) of the records
-            const dim3 gridr((unsigned)(xm ? (count + 7) / 8 * 8 : count), G);
-            with_prior(h, sp, [&](auto P, auto prior) {
-                with_bool(final_pass && write_out, [&](auto fin) {
-                    hipLaunchKernelGGL((k_var_rec<cap, decltype(P), fin>), gridr, dim3(256), 0, s, h->d_var_meta, h->d_var_rows,
-                                       h->d_csc_list, h->d_csc_row, prior, msg0, h->d_rec + (size_t)tile0 * rec_tile_floats(h->m),
-                                       h->d_mask + (size_t)tile0 * h->E, post_g, hard_g, done_g, skip_done, h->n, h->m, h->E,
-                                       (write_out || keep_hard) ? 1 : 0, first, xm ? count : 0, stl);
+    } else if (p.rec) {
+        // k_var_rec on the narrow slice of the column records, k_var<64, ..> in its record mode on the wide one (rec_var_slices)
+        const RecVarSlices sl = rec_var_slices(bk.nb, bk.maxd, bk.blk, h->var_reversed, p.light, p.write_out != 0, G, h->max_col_deg);
+        const int out = (p.write_out || p.keep_hard) ? 1 : 0;
+        float *const rec0 = h->d_rec + (size_t)p.tile0 * rec_tile_floats(h->m);
+        u64 *const mask0 = h->d_mask + (size_t)p.tile0 * h->E;
+        const bool fin_pass = p.final_pass && p.write_out;
+        if (sl.narrow_n > 0)
+            with_cap<16, 32>(sl.narrow_deg, [&](auto cap) {
+                with_prior(h, tv.pprior, tv.first_col, [&](auto P, auto prior) {
+                    with_bool(fin_pass, [&](auto fin) {
+                        hipLaunchKernelGGL((k_var_rec<cap, decltype(P), fin>), dim3((unsigned)sl.narrow_grid, G), dim3(256), 0, s,
+                                           h->d_var_meta, h->d_var_rows, h->d_csc_list, h->d_csc_row, prior, msg0, rec0, mask0, tv.post,
+                                           tv.hard, tv.done, skip_done, h->n, h->m, h->E, out, sl.narrow0, sl.xmap ? sl.narrow_n : 0,
+                                           p.settle);
+                    });
                 });
             });
-        };
-        if (nb_launch > 0) with_cap<16, 32>(narrow_deg, [&](auto cap) { slice(cap, blk0, nb_launch); });
-        if (nwide > 0) {  // k_var<64, P> in its record mode (RecWide)
-            RecWide rw;
-            rw.var_rows = h->d_var_rows;
-            rw.csc_row = h->d_csc_row;
-            rw.rec = h->d_rec + (size_t)tile0 * rec_tile_floats(h->m);
-            rw.sgn = h->d_mask + (size_t)tile0 * h->E;
-            rw.m = h->m;
-            rw.blk0 = wide0;
-            rw.xmap = xm ? nwide : 0;
-            rw.last = final_pass && write_out;
-            rw.stl = stl;
-            const dim3 gridw((unsigned)(xm ? (nwide + 7) / 8 * 8 : nwide), G);
-            with_prior(h, sp, [&](auto P, auto prior) {
-                hipLaunchKernelGGL((k_var<64, decltype(P)>), gridw, dim3(256), 0, s, h->d_var_meta, h->d_csc_list, prior, msg0, scr0,
-                                   post_g, hard_g, done_g, skip_done, h->n, h->E, (write_out || keep_hard) ? 1 : 0, rw);
+        if (sl.wide_n > 0) {
+            // (var_rows, csc_row, rec, sgn, m, blk0, xmap, last, stl)
+            const RecWide rw{h->d_var_rows, h->d_csc_row, rec0, mask0, h->m, sl.wide0, sl.xmap ? sl.wide_n : 0, fin_pass, p.settle};
+            with_prior(h, tv.pprior, tv.first_col, [&](auto P, auto prior) {
+                hipLaunchKernelGGL((k_var<64, decltype(P)>), dim3((unsigned)sl.wide_grid, G), dim3(256), 0, s, h->d_var_meta,
+                                   h->d_csc_list, prior, msg0, scr0, tv.post, tv.hard, tv.done, skip_done, h->n, h->E, out, rw);
             });
         }
     } else {
         with_cap<16, 32, 64>(h->max_col_deg, [&](auto cap) {
-            with_prior(h, sp, [&](auto P, auto prior) {
+            with_prior(h, tv.pprior, tv.first_col, [&](auto P, auto prior) {
                 hipLaunchKernelGGL((k_var<cap, decltype(P)>), dim3(nblk, G), dim3(256), 0, s, h->d_var_meta, h->d_csc_list, prior, msg0,
-                                   scr0, post_g, hard_g, done_g, skip_done, h->n, h->E, write_out, RecWide{});
+                                   scr0, tv.post, tv.hard, tv.done, skip_done, h->n, h->E, p.write_out, RecWide{});
             });
         });
     }
@@ -972,31 +995,32 @@ int launch_var(scaldpc_bp *h, int G, float *post_g, u64 *hard_g, const u64 *done
     return 0;
 }
 
-int launch_el_check(scaldpc_bp *h, int method, float alpha, int nb, const u64 *synd_g, const u64 *done_g,
-                    int skip_done, hipStream_t s, bool first, const u64 *hard_g = nullptr, int *unsat_prev = nullptr,
-                    const SoftPrior *sp = nullptr)
+// The row-parallel pair on the nb codewords of a view.  hard_g non-null (early exit): the check pass also tests H e == s on
+// the decisions of the iteration before and leaves the verdicts in unsat_prev ...
+int launch_el_check(scaldpc_bp *h, const TileState &tv, int nb, int method, float alpha, int skip_done, hipStream_t s, bool first,
+                    const u64 *hard_g, int *unsat_prev)
 {
     with_method(method, [&](auto M) {
-        with_first_prior(h, first, sp, [&](auto fst, auto P, auto prior) {
+        with_first_prior(h, first, tv, [&](auto fst, auto P, auto prior) {
             hipLaunchKernelGGL((k_el_check<M, fst, decltype(P)>), dim3((h->m + 3) / 4, nb), dim3(256), 0, s, h->d_row_ptr,
-                               h->d_col_idx, prior, h->d_emsg, synd_g, done_g, skip_done, h->m, h->E, alpha, hard_g, unsat_prev);
+                               h->d_col_idx, prior, h->d_emsg, tv.synd, tv.done, skip_done, h->m, h->E, alpha, hard_g, unsat_prev);
         });
     });
     LAUNCH_CHECK();
     return 0;
 }
-
-int launch_el_var(scaldpc_bp *h, int nb, float *post_g, u64 *hard_g, u64 *done_g, int skip_done, int write_out,
-                  hipStream_t s, const int *unsat_prev = nullptr, int it_prev = 0, u64 *conv_g = nullptr,
-                  int *iters_g = nullptr, int *remaining_prev = nullptr, const SoftPrior *sp = nullptr)
+// ... and with remaining_prev non-null (early exit) the variable pass first latches the codewords that passed the test of
+// iteration it_prev, and counts the others there.
+int launch_el_var(scaldpc_bp *h, const TileState &tv, int nb, int skip_done, int write_out, hipStream_t s, const int *unsat_prev,
+                  int it_prev, int *remaining_prev)
 {
     // grid.x a multiple of 8: block x lands on the same XCD for every codeword row, so an XCD's L2
     // keeps its share of the slot table
     const unsigned gx = (unsigned)(((h->el_waves + 3) / 4 + 7) / 8 * 8);
-    with_prior(h, sp, [&](auto P, auto prior) {
+    with_prior(h, tv.pprior, tv.first_col, [&](auto P, auto prior) {
         hipLaunchKernelGGL((k_el_var<decltype(P)>), dim3(gx, nb), dim3(256), 0, s, (const int2 *)h->d_el_slots, h->d_el_slot_col,
-                           h->el_waves, prior, h->d_emsg, post_g, hard_g, done_g, skip_done, h->E, write_out, unsat_prev, it_prev,
-                           conv_g, iters_g, remaining_prev);
+                           h->el_waves, prior, h->d_emsg, tv.post, tv.hard, tv.done, skip_done, h->E, write_out, unsat_prev, it_prev,
+                           remaining_prev ? tv.conv : nullptr, remaining_prev ? tv.iters : nullptr, remaining_prev);
     });
     LAUNCH_CHECK();
     return 0;
@@ -1022,11 +1046,12 @@ size_t small_lds(const scaldpc_bp *h)
 }
 
 // k_bp_small over `batch` codewords, one workgroup each.  PLANES: input syndromes and outputs are the tile path's bit
-// planes (Monte-Carlo entry points); else bytes per codeword in the caller's layout.  sp non-null = per-codeword priors
+// planes (Monte-Carlo entry points); else bytes per codeword in the caller's layout.  pprior non-null = per-codeword priors
 // (scaldpc_bp_decode_batch_soft; with PLANES, scaldpc_mc_hqc_run_soft).
 template <bool PLANES>
 int launch_small(scaldpc_bp *h, size_t lds, int method, int batch, const void *in, int input_kind, int max_iter, float alpha,
-                 bool early, void *bits, float *llr, int *iters, void *conv, hipStream_t s, const SoftPrior *sp = nullptr)
+                 bool early, void *bits, float *llr, int *iters, void *conv, hipStream_t s, const float *pprior = nullptr,
+                 int first_col = 0)
 {
     with_method(method, [&](auto M) {
         auto launch = [&](auto P, auto prior) {
@@ -1034,7 +1059,7 @@ int launch_small(scaldpc_bp *h, size_t lds, int method, int batch, const void *i
                                h->d_col_ptr, h->d_csc_edge, prior, h->m, h->n, (int)h->E, in, input_kind, max_iter, alpha,
                                early ? 1 : 0, bits, llr, iters, conv);
         };
-        with_prior(h, sp, launch);
+        with_prior(h, pprior, first_col, launch);
     });
     LAUNCH_CHECK();
     return 0;
@@ -1046,22 +1071,6 @@ float alpha_for(float alpha, int it)
     return alpha == 0.0f ? (float)(1.0 - std::pow(2.0, -1.0 * it)) : alpha;
 }
 
-struct TileState {
-    const u64 *synd;
-    u64 *hard, *done, *conv, *unsat;
-    int *iters;
-    float *post;
-    // a soft call: prior LLRs per codeword for the columns [first_col, n), float [tile][n - first_col][64] (null: shared priors)
-    const float *pprior = nullptr;
-    int first_col = 0;
-};
-// the prior source of a launch whose first tile is `tile` of st
-SoftPrior soft_prior(const scaldpc_bp *h, const TileState &st, int tile)
-{
-    const int cols = h->n - st.first_col;
-    return SoftPrior{h->d_prior, st.pprior + (size_t)tile * cols * TW, st.first_col, cols};
-}
-
 int ensure_el_unsat(scaldpc_bp *h, int max_iter) { return h->d_el_unsat.ensure(((size_t)max_iter + 2) * TW); }
 
 // All iterations of the row-parallel kernels on the nb codewords of `st` (ONE tile: a handful of codewords, el_limit),
@@ -1070,11 +1079,14 @@ int ensure_el_unsat(scaldpc_bp *h, int max_iter) { return h->d_el_unsat.ensure((
 // followed by the ordinary k_parity / k_finalize pair (latching only with early exit).  The host looks at "still running
 // after it-1" one iteration late, so a finished call enqueues one iteration of (skipped) launches more than a loop with
 // the test as launches of its own -- and half as many launches overall.
-int iterate_el(scaldpc_bp *h, const TileState &st, int nb, int max_iter, int method, float alpha, bool early, hipStream_t s)
+int iterate_el(scaldpc_bp *h, const DecodeCall &c, const TileState &st, int nb)
 {
+    const hipStream_t s = c.s;
+    const bool early = c.early;
+    const int max_iter = c.max_iter, skip = early ? 1 : 0;
     if (early) {
         SC_TRY(ensure_el_unsat(h, max_iter));
-        if (!h->small_prepared) {  // (k_small_prepare has zeroed both)
+        if (!c.state_ready) {  // (else k_small_prepare has zeroed both)
             SC_HIP(hipMemsetAsync(h->d_el_unsat, 0, sizeof(int) * ((size_t)max_iter + 2) * TW, s));
             SC_HIP(hipMemsetAsync(h->d_remaining, 0, sizeof(int) * ((size_t)max_iter + 2), s));
         }
@@ -1082,18 +1094,13 @@ int iterate_el(scaldpc_bp *h, const TileState &st, int nb, int max_iter, int met
     static_assert(ROW_CAP == TW, "el_ok (a row = at most one wave of edge lanes) must imply fused_init's rows <= ROW_CAP");
     // No initialisation pass: el_ok holds here (el_limit), i.e. a non-empty graph with no row wider than ROW_CAP, so
     // fused_init does for either rule -- the first check pass reads the priors.
-    const SoftPrior spv = st.pprior ? soft_prior(h, st, 0) : SoftPrior{};
-    const SoftPrior *const sp = st.pprior ? &spv : nullptr;
     for (int it = 1; it <= max_iter; it++) {
-        const bool last = it == max_iter, first = it == 1;
-        if (early) {
-            int *const up = it > 1 ? h->d_el_unsat + (size_t)(it - 1) * TW : nullptr;  // verdicts on iteration it - 1
-            SC_TRY(launch_el_check(h, method, alpha_for(alpha, it), nb, st.synd, st.done, 1, s, first, st.hard, up, sp));
-            SC_TRY(launch_el_var(h, nb, st.post, st.hard, st.done, 1, 1, s, up, it - 1, st.conv, st.iters, h->d_remaining + it - 1, sp));
-        } else {
-            SC_TRY(launch_el_check(h, method, alpha_for(alpha, it), nb, st.synd, st.done, 0, s, first, nullptr, nullptr, sp));
-            SC_TRY(launch_el_var(h, nb, st.post, st.hard, st.done, 0, last ? 1 : 0, s, nullptr, 0, nullptr, nullptr, nullptr, sp));
-        }
+        const bool last = it == max_iter;
+        // early exit only: the verdicts on iteration it - 1 (none yet in iteration 1), and what the latch of var(it) counts
+        int *const up = early && it > 1 ? h->d_el_unsat + (size_t)(it - 1) * TW : nullptr;
+        int *const rem_prev = early ? h->d_remaining + it - 1 : nullptr;
+        SC_TRY(launch_el_check(h, st, nb, c.method, alpha_for(c.alpha, it), skip, s, it == 1, early ? st.hard : nullptr, up));
+        SC_TRY(launch_el_var(h, st, nb, skip, (early || last) ? 1 : 0, s, up, early ? it - 1 : 0, rem_prev));
         if (last) {
             hipLaunchKernelGGL(k_parity<true>, dim3(parity_blocks(h->m), 1), dim3(256), 0, s, h->d_row_ptr, h->d_col_idx, st.hard,
                                h->m, h->n, const_cast<u64 *>(st.synd), st.unsat, (const u64 *)st.done);
@@ -1197,23 +1204,24 @@ struct Lanes {
 struct SettlePlan {
     unsigned *words = nullptr;  // [tile][SETTLE_WORDS] of the level's tiles, zero when the level starts
     int first_test = 0, horizon = 0;
+    unsigned *of(int tile) const { return words + (size_t)tile * SETTLE_WORDS; }  // the words of a launch whose first tile it is
 };
-int iterate_tiles(scaldpc_bp *h, Lanes &lanes, const TileState &st, int g0, int g, int max_iter, int method, float alpha,
-                  bool early, int defer_after, bool *deferred, int real_codewords, PollState &ps, int chain,
-                  const SettlePlan &sl = SettlePlan{})
+int iterate_tiles(scaldpc_bp *h, const DecodeCall &c, Lanes &lanes, const TileState &st, int g0, int g, int defer_after,
+                  bool *deferred, PollState &ps, int chain, const SettlePlan &sl)
 {
     const hipStream_t s = lanes.s;
-    const int skip = early ? 1 : 0;
+    const bool early = c.early;
+    const int max_iter = c.max_iter, method = c.method, skip = early ? 1 : 0;
     const int nl = fixed_lanes(h, g);
     SC_TRY(ensure_lanes(h, nl));
     int gs[MAX_LANES], t0[MAX_LANES];
     deal_tiles(g, nl, gs, t0);
+    TileState tv[MAX_LANES];  // lane k's tiles
+    for (int k = 0; k < nl; k++) tv[k] = st.at(h, g0 + t0[k]);
     const int pw = parity_waves(h);
     const bool fused = fused_init(h, method);
-    const bool soft = st.pprior != nullptr;
     if (h->E && !fused) {
-        const SoftPrior spv = soft ? soft_prior(h, st, g0) : SoftPrior{};
-        with_prior(h, soft ? &spv : nullptr, [&](auto P, auto prior) {
+        with_prior(h, tv[0].pprior, st.first_col, [&](auto P, auto prior) {
             hipLaunchKernelGGL((k_init_msg<decltype(P)>), dim3((unsigned)((h->E + 3) / 4), g), dim3(256), 0, s, h->d_col_idx,
                                h->d_msg.get(), h->E, prior);
         });
@@ -1226,8 +1234,8 @@ int iterate_tiles(scaldpc_bp *h, Lanes &lanes, const TileState &st, int g0, int 
     if (!(chain & 1)) SC_TRY(lanes.fork(nl));  // the other lanes start after everything enqueued on `s` so far
     // iteration 1 without its check pass: the first variable pass reads the first-message table and the syndrome planes
     // (a soft call runs iteration 1 WITH its check pass, reading the codewords' own priors: the first_fused = 0 sequence)
-    const bool first_fuse = first_fusable(h, method) && !soft;
-    if (first_fuse) SC_TRY(ensure_first_table(h, method, alpha_for(alpha, 1), s));
+    const bool first_fuse = first_fusable(h, method) && !st.pprior;
+    if (first_fuse) SC_TRY(ensure_first_table(h, method, alpha_for(c.alpha, 1), s));
     // The convergence test of iteration it rides on the check pass of it + 1 (fused_test) wherever the host does not need
     // its verdict in between: at the iterations it polls at, stops a group at, or ends with, the stand-alone launch stays.
     // (Running the test on a side stream beside the check pass instead was measured and rejected: -3.4 % on the config-5
@@ -1252,22 +1260,20 @@ int iterate_tiles(scaldpc_bp *h, Lanes &lanes, const TileState &st, int g0, int 
         const bool poll = poll_point(it, defer_after, ps);
         lanes.open = nl > 1;  // (this iteration enqueues on them)
         for (int k = 0; k < nl && !no_check; k++) {
-            const int ta = g0 + t0[k];
-            FusedTest ft{};
+            CheckPass cp;
+            cp.alpha = alpha_for(c.alpha, it);
+            cp.first = fused && it == 1;
+            cp.tile0 = t0[k];
             if (verdict_pending[k]) {
-                ft = FusedTest{st.hard + (size_t)ta * h->n, st.unsat + (size_t)ta * pw, st.done + ta, st.conv + ta,
-                               st.iters + (size_t)ta * TW, rem + (it - 1), h->n, pw, it - 1, 1};
+                cp.test = fused_test(h, tv[k], rem + (it - 1), it - 1, true);
                 verdict_pending[k] = false;
             }
-            const SoftPrior spv = soft ? soft_prior(h, st, ta) : SoftPrior{};
-            const bool first = fused && it == 1, boot = recf && !first && !rec_booted[k];
-            if (boot) rec_booted[k] = true;
-            Settle stc{};
+            cp.boot = recf && !cp.first && !rec_booted[k];
+            if (cp.boot) rec_booted[k] = true;
             if (tracked)
-                stc = Settle{sl.words + (size_t)ta * SETTLE_WORDS, settle_check_done(it, sl.first_test),
-                             boot ? 0 : settle_check_mark(it, sl.first_test, last_test)};
-            SC_TRY(launch_check(h, method, alpha_for(alpha, it), gs[k], st.synd + (size_t)ta * h->m, st.done + ta, skip, lanes[k],
-                                first, t0[k], ft.hard ? &ft : nullptr, soft ? &spv : nullptr, boot, stc));
+                cp.settle = Settle{sl.of(g0 + t0[k]), settle_check_done(it, sl.first_test),
+                                   cp.boot ? 0 : settle_check_mark(it, sl.first_test, last_test)};
+            SC_TRY(launch_check(h, tv[k], gs[k], method, skip, lanes[k], cp));
             if (set_phase && k + 1 < nl) {
                 SC_HIP(hipEventRecord(h->ev_phase[k + 1], lanes[k]));
                 SC_HIP(hipStreamWaitEvent(lanes[k + 1], h->ev_phase[k + 1], 0));
@@ -1276,33 +1282,32 @@ int iterate_tiles(scaldpc_bp *h, Lanes &lanes, const TileState &st, int g0, int 
         if (!no_check) set_phase = false;  // (a first iteration without check passes leaves the offset to the second)
         if (!settle_has_var(it, K)) continue;  // (the closing variable pass takes this one's place: settle_horizon_usable)
         for (int k = 0; k < nl; k++) {
-            const int ta = g0 + t0[k];
+            VarPass vp;
+            vp.write_out = (early || last) ? 1 : 0;
+            vp.tile0 = t0[k];
+            vp.first_synd = first_fuse && it == 1;
             // (the record form starts with iteration 2: an iteration 1 that has a check pass ran it in the message form)
-            const SoftPrior spv = soft ? soft_prior(h, st, ta) : SoftPrior{};
-            Settle stv{};
+            vp.rec = it > 1 && recf;
+            vp.light = it > 1;
+            vp.final_pass = last;
+            vp.keep_hard = keep_hard && !last;
             if (tracked && !last)
-                stv = Settle{sl.words + (size_t)ta * SETTLE_WORDS, settle_var_done(it, sl.first_test, last_test),
-                             settle_var_mark(it, sl.first_test, last_test)};
+                vp.settle = Settle{sl.of(g0 + t0[k]), settle_var_done(it, sl.first_test, last_test),
+                                   settle_var_mark(it, sl.first_test, last_test)};
             else if (keep_hard)  // the closing pass: it comes behind the check pass that completes the group's last test
-                stv = Settle{sl.words + (size_t)ta * SETTLE_WORDS, last_test, 0};
-            SC_TRY(launch_var(h, gs[k], st.post ? st.post + (size_t)ta * h->n * TW : nullptr, st.hard + (size_t)ta * h->n,
-                              st.done + ta, skip, (early || last) ? 1 : 0, lanes[k], t0[k],
-                              first_fuse && it == 1 ? st.synd + (size_t)ta * h->m : nullptr, it > 1 && recf, it > 1,
-                              soft ? &spv : nullptr, last, stv, keep_hard && !last));
+                vp.settle = Settle{sl.of(g0 + t0[k]), last_test, 0};
+            SC_TRY(launch_var(h, tv[k], gs[k], skip, lanes[k], vp));
             if (ride && !last && !poll) {
                 verdict_pending[k] = true;  // the next check pass of this lane carries the test
             } else if (early || last) {  // convergence test + latch, one launch
                 const dim3 grid(parity_blocks(h->m), gs[k]);
-                if (pw >= FT_WORDS && h->kn.fuse_test) {  // sharded accumulators / counters (fused_commit)
-                    const FusedTest pf{st.hard + (size_t)ta * h->n, st.unsat + (size_t)ta * pw, st.done + ta, st.conv + ta,
-                                       st.iters + (size_t)ta * TW, rem + it, h->n, pw, it, early ? 1 : 0};
-                    hipLaunchKernelGGL(k_parity_fin_sharded, grid, dim3(256), 0, lanes[k], h->d_row_ptr, h->d_col_idx, h->m,
-                                       st.synd + (size_t)ta * h->m, pf);
-                } else
-                    hipLaunchKernelGGL(k_parity_fin, grid, dim3(256), 0, lanes[k], h->d_row_ptr, h->d_col_idx,
-                                       st.hard + (size_t)ta * h->n, h->m, h->n, st.synd + (size_t)ta * h->m,
-                                       st.unsat + (size_t)ta * pw, pw, it, early ? 1 : 0, st.done + ta, st.conv + ta,
-                                       st.iters + (size_t)ta * TW, rem + it);
+                const FusedTest pf = fused_test(h, tv[k], rem + it, it, early);
+                if (pw >= FT_WORDS && h->kn.fuse_test)  // sharded accumulators / counters (fused_commit)
+                    hipLaunchKernelGGL(k_parity_fin_sharded, grid, dim3(256), 0, lanes[k], h->d_row_ptr, h->d_col_idx, h->m, tv[k].synd,
+                                       pf);
+                else
+                    hipLaunchKernelGGL(k_parity_fin, grid, dim3(256), 0, lanes[k], h->d_row_ptr, h->d_col_idx, pf.hard, h->m, h->n,
+                                       tv[k].synd, pf.unsat, pf.pw, pf.it_prev, pf.latch, pf.done, pf.conv, pf.iters, pf.remaining);
                 LAUNCH_CHECK();
             }
         }
@@ -1322,7 +1327,8 @@ int iterate_tiles(scaldpc_bp *h, Lanes &lanes, const TileState &st, int g0, int 
         set_phase = true;
         h->sched.w[SCHED_POLLS]++;
         // nobody left: done.  From `defer_after` on, any poll point may hand the stragglers over (after_poll)
-        const PollVerdict v = after_poll(ps, it, defer_after, max_iter, h->h_remaining[it], real_codewords, g, el_limit(h, method));
+        const PollVerdict v = after_poll(ps, it, defer_after, max_iter, h->h_remaining[it], std::min(c.batch - g0 * TW, g * TW), g,
+                                          el_limit(h, method));
         if (v == POLL_DONE) return 0;
         if (v == POLL_HAND_OVER) {
             *deferred = true;
@@ -1351,23 +1357,101 @@ int ensure_level(scaldpc_bp *h, scaldpc_bp::Level &L, int T2)
     return 0;
 }
 
-// One compaction level: the `batch` codewords of `st` (T tiles), all iterations of one
+// Settled codewords: a fixed-iteration level on the record-form kernels tracks which tiles' message state has stopped
+// changing (Settle), its passes return at once for those, and with a horizon K -- forced, or learned from the handle's
+// last call (settle_next_horizon) -- what would return at once is not enqueued at all.  Plans level `lvl`, clears the words.
+int plan_settle(scaldpc_bp *h, const DecodeCall &c, int lvl, const TileState &st, SettlePlan *sl)
+{
+    const int settle = settle_mode(h->kn.settle, h->identity_from >= 0);
+    if (lvl != 0 || c.early || settle <= 0 || !rec_form(h, c.method)) return 0;
+    // the first iteration from which alpha_for() is one float to the call's end (the schedule never decreases)
+    int alpha_from = 1;
+    while (alpha_from < c.max_iter && alpha_for(c.alpha, alpha_from) != alpha_for(c.alpha, c.max_iter)) alpha_from++;
+    sl->first_test = settle_first_test(alpha_from);
+    const int soft = st.pprior ? 1 : 0;
+    if (h->settle_key_iter != c.max_iter || h->settle_key_alpha != c.alpha || h->settle_key_soft != soft) {
+        h->settle_next = 0;  // another max_iter / alpha / kind of priors: learn again
+        h->settle_key_iter = c.max_iter;
+        h->settle_key_alpha = c.alpha;
+        h->settle_key_soft = soft;
+    }
+    if (sl->first_test > c.max_iter) return 0;
+    SC_TRY(h->d_settle.ensure((size_t)c.T * SETTLE_WORDS));
+    SC_HIP(hipMemsetAsync(h->d_settle, 0, sizeof(unsigned) * (size_t)c.T * SETTLE_WORDS, c.s));  // once per level, as unsat
+    sl->words = h->d_settle;
+    if (settle >= 2 && !c.no_sync) {
+        const int K = h->kn.settle_horizon > 0 ? h->kn.settle_horizon : h->settle_next;
+        if (settle_horizon_usable(K, sl->first_test, c.max_iter)) sl->horizon = K;
+    }
+    return 0;
+}
+
+// After a tracked level's groups: the tiles' frozen-at numbers, read back once (one synchronise).  With a horizon, every
+// tile that was not frozen by it is decoded again from its inputs, in place, with all its iterations: the syndrome planes
+// are intact, a fixed-iteration pass overwrites every output of a real codeword, and BP is deterministic.  Leaves the
+// handle's report (scaldpc_bp_last_settle) and the horizon of its next call.
+int collect_settle(scaldpc_bp *h, const DecodeCall &c, Lanes &lanes, const TileState &st, const SettlePlan &sl)
+{
+    const int T = c.T, Gl = std::min(c.G, T);
+    SC_TRY(h->h_settle.ensure((size_t)T * SETTLE_WORDS));
+    auto read_back = [&](int t0, int cnt, int last_test) -> int {
+        SC_HIP(hipMemcpyAsync(h->h_settle + (size_t)t0 * SETTLE_WORDS, sl.of(t0), sizeof(unsigned) * (size_t)cnt * SETTLE_WORDS,
+                              hipMemcpyDeviceToHost, c.s));
+        SC_HIP(hipStreamSynchronize(c.s));
+        for (int t = t0; t < t0 + cnt; t++) {
+            unsigned latest = 0;
+            for (int i = 0; i < SETTLE_SHARDS; i++) latest = std::max(latest, h->h_settle[(size_t)t * SETTLE_WORDS + i]);
+            h->settle_frozen_at[t] = settle_frozen_at((int)latest, sl.first_test, last_test);
+        }
+        return 0;
+    };
+    h->settle_frozen_at.assign(T, 0);
+    h->settle_K = sl.horizon;
+    SC_TRY(read_back(0, T, sl.horizon ? sl.horizon : c.max_iter));
+    if (sl.horizon) {
+        SettlePlan again = sl;
+        again.horizon = 0;
+        PollState poll;  // (a fixed-iteration level: no polls, no hand-over)
+        for (int t = 0; t < T;) {
+            if (h->settle_frozen_at[t]) { t++; continue; }
+            int g = 1;
+            while (g < Gl && t + g < T && !h->settle_frozen_at[t + g]) g++;
+            SC_HIP(hipMemsetAsync(sl.of(t), 0, sizeof(unsigned) * (size_t)g * SETTLE_WORDS, c.s));
+            bool d = false;
+            SC_TRY(iterate_tiles(h, c, lanes, st, t, g, 0, &d, poll, 0, again));
+            SC_TRY(read_back(t, g, c.max_iter));
+            h->settle_rerun += g;
+            t += g;
+        }
+    }
+    int frozen = 0, max_at = 0;
+    for (int t = 0; t < T; t++) {
+        frozen += h->settle_frozen_at[t] > 0;
+        max_at = std::max(max_at, h->settle_frozen_at[t]);
+    }
+    const bool learns = settle_mode(h->kn.settle, h->identity_from >= 0) >= 2;
+    h->settle_next = learns ? settle_next_horizon(T, frozen, max_at, (int)h->settle_rerun, c.max_iter) : 0;
+    return 0;
+}
+
+int hand_down(scaldpc_bp *h, const DecodeCall &c, int lvl, const TileState &st, const std::vector<char> &deferred_tile);
+
+// One compaction level: the c.batch codewords of `st` (c.T tiles), all iterations of one
 // cache-resident tile group after the other.  In early-exit runs the stragglers of
 // mostly-converged groups are gathered into dense tiles of their own and re-decoded from their
 // inputs one level down (codewords are independent and BP is deterministic: identical
 // results), and that level may shed its own stragglers again -- on the config-5 sweep the
 // second level drops the codewords that needed 5-7 iterations and leaves the ~0.5 % that never
 // converge to run their 100 iterations in 3 tiles instead of 11.
-int decode_level(scaldpc_bp *h, int lvl, const TileState &st, int batch, int T, int G, int max_iter, int method,
-                 float alpha, bool early, bool want_post, hipStream_t s)
+int decode_level(scaldpc_bp *h, const DecodeCall &c, int lvl, const TileState &st)
 {
-    const int lim = el_limit(h, method);
-    const int el = (T == 1 && batch <= lim) ? batch : 0;  // a handful of codewords: row-parallel kernels
-    const int Gl = std::min(G, T);
+    const int T = c.T, Gl = std::min(c.G, T), max_iter = c.max_iter;
+    const bool early = c.early;
+    const int el = (T == 1 && c.batch <= el_limit(h, c.method)) ? c.batch : 0;  // a handful of codewords: row-parallel kernels
     if (el)
         SC_TRY(ensure_el(h, el));
     else
-        SC_TRY(ensure_msg(h, Gl, method));
+        SC_TRY(ensure_msg(h, Gl, c.method));
     if (lvl == 0) {
         h->last_group = el ? 0 : Gl;
         h->last_early = early;
@@ -1375,12 +1459,12 @@ int decode_level(scaldpc_bp *h, int lvl, const TileState &st, int batch, int T, 
     h->stat_levels = lvl;
     if (el) {
         h->stat_el = el;
-        return iterate_el(h, st, el, max_iter, method, alpha, early, s);
+        return iterate_el(h, c, st, el);
     }
 
     const int defer_after = defer_after_of(early, lvl, h->kn.compact_after, max_iter);
     // accumulators and block counters of the convergence tests: zero once, every launch leaves them zero
-    SC_HIP(hipMemsetAsync(st.unsat, 0, sizeof(u64) * (size_t)T * parity_waves(h), s));
+    SC_HIP(hipMemsetAsync(st.unsat, 0, sizeof(u64) * (size_t)T * parity_waves(h), c.s));
     std::vector<char> deferred_tile(T, 0);
     bool any = false;
     PollState poll;
@@ -1388,121 +1472,61 @@ int decode_level(scaldpc_bp *h, int lvl, const TileState &st, int batch, int T, 
     // every pass of a lane depends only on that lane's previous pass over the same slice of the message array
     // (A/B on the HQC-128 bench, best of five runs each: 60.43 against 61.12 ms per step; tanh rule 94.5 against 95.0-95.4:
     // profiles/r04/ab_chain_groups.log)
-    const bool lanes2 = fused_init(h, method) && fixed_lanes(h, Gl) > 1;
+    const bool lanes2 = fused_init(h, c.method) && fixed_lanes(h, Gl) > 1;
     // Early-exit runs chain too where the host stays out: a group that will stop at the hand-over point UNSEEN and polls
     // nowhere before (runs_unseen, from the same PollState and rules iterate_tiles decides by) enqueues its launches
     // without ever synchronising.
-    Lanes lanes(h, s);
-    // Settled codewords: a fixed-iteration level on the record-form kernels tracks which tiles' message state has stopped
-    // changing (Settle), its passes return at once for those, and with a horizon K -- forced, or learned from the handle's
-    // last call (settle_next_horizon) -- what would return at once is not enqueued at all.
+    Lanes lanes(h, c.s);
     SettlePlan sl;
-    const int settle = settle_mode(h->kn.settle, h->identity_from >= 0);
-    if (lvl == 0 && !early && settle > 0 && rec_form(h, method)) {
-        // the first iteration from which alpha_for() is one float to the call's end (the schedule never decreases)
-        int alpha_from = 1;
-        while (alpha_from < max_iter && alpha_for(alpha, alpha_from) != alpha_for(alpha, max_iter)) alpha_from++;
-        sl.first_test = settle_first_test(alpha_from);
-        const int soft = st.pprior ? 1 : 0;
-        if (h->settle_key_iter != max_iter || h->settle_key_alpha != alpha || h->settle_key_soft != soft) {
-            h->settle_next = 0;  // another max_iter / alpha / kind of priors: learn again
-            h->settle_key_iter = max_iter;
-            h->settle_key_alpha = alpha;
-            h->settle_key_soft = soft;
-        }
-        if (sl.first_test <= max_iter) {
-            SC_TRY(h->d_settle.ensure((size_t)T * SETTLE_WORDS));
-            SC_HIP(hipMemsetAsync(h->d_settle, 0, sizeof(unsigned) * (size_t)T * SETTLE_WORDS, s));  // once per level, as unsat
-            sl.words = h->d_settle;
-            if (settle >= 2 && !h->settle_no_host) {
-                const int K = h->kn.settle_horizon > 0 ? h->kn.settle_horizon : h->settle_next;
-                if (settle_horizon_usable(K, sl.first_test, max_iter)) sl.horizon = K;
-            }
-        }
-    }
+    SC_TRY(plan_settle(h, c, lvl, st, &sl));
     for (int g0 = 0; g0 < T; g0 += Gl) {
         const int g = std::min(Gl, T - g0);
-        const int real = std::min(batch - g0 * TW, g * TW);
         bool d = false;
         const bool next_full = g0 + Gl < T && std::min(Gl, T - (g0 + Gl)) == Gl;
         // (no chaining across the wrap of the "still running" counter rows, which clears them all: chain_bits)
         const int chain = chain_bits(early, lanes2, g == Gl, g0 == 0, next_full, lanes.open, defer_after, max_iter, poll, h->rem);
         h->sched.note_group(lvl, early, chain);
-        SC_TRY(iterate_tiles(h, lanes, st, g0, g, max_iter, method, alpha, early, defer_after, &d, real, poll, chain, sl));
+        SC_TRY(iterate_tiles(h, c, lanes, st, g0, g, defer_after, &d, poll, chain, sl));
         if (d) {
             any = true;
             for (int t = g0; t < g0 + g; t++) deferred_tile[t] = 1;
         }
     }
-    if (sl.words && !h->settle_no_host) {
-        // The tiles' frozen-at numbers, read back once (one synchronise).  With a horizon, every tile that was not frozen
-        // by it is decoded again from its inputs, in place, with all its iterations: the syndrome planes are intact, a
-        // fixed-iteration pass overwrites every output of a real codeword, and BP is deterministic.
-        SC_TRY(h->h_settle.ensure((size_t)T * SETTLE_WORDS));
-        auto read_back = [&](int t0, int cnt, int last_test) -> int {
-            SC_HIP(hipMemcpyAsync(h->h_settle + (size_t)t0 * SETTLE_WORDS, h->d_settle + (size_t)t0 * SETTLE_WORDS,
-                                  sizeof(unsigned) * (size_t)cnt * SETTLE_WORDS, hipMemcpyDeviceToHost, s));
-            SC_HIP(hipStreamSynchronize(s));
-            for (int t = t0; t < t0 + cnt; t++) {
-                unsigned latest = 0;
-                for (int i = 0; i < SETTLE_SHARDS; i++) latest = std::max(latest, h->h_settle[(size_t)t * SETTLE_WORDS + i]);
-                h->settle_frozen_at[t] = settle_frozen_at((int)latest, sl.first_test, last_test);
-            }
-            return 0;
-        };
-        h->settle_frozen_at.assign(T, 0);
-        h->settle_K = sl.horizon;
-        SC_TRY(read_back(0, T, sl.horizon ? sl.horizon : max_iter));
-        if (sl.horizon) {
-            SettlePlan again = sl;
-            again.horizon = 0;
-            for (int t = 0; t < T;) {
-                if (h->settle_frozen_at[t]) { t++; continue; }
-                int g = 1;
-                while (g < Gl && t + g < T && !h->settle_frozen_at[t + g]) g++;
-                SC_HIP(hipMemsetAsync(h->d_settle + (size_t)t * SETTLE_WORDS, 0, sizeof(unsigned) * (size_t)g * SETTLE_WORDS, s));
-                bool d = false;
-                SC_TRY(iterate_tiles(h, lanes, st, t, g, max_iter, method, alpha, early, defer_after, &d,
-                                     std::min(batch - t * TW, g * TW), poll, 0, again));
-                SC_TRY(read_back(t, g, max_iter));
-                h->settle_rerun += g;
-                t += g;
-            }
-        }
-        int frozen = 0, max_at = 0;
-        for (int t = 0; t < T; t++) {
-            frozen += h->settle_frozen_at[t] > 0;
-            max_at = std::max(max_at, h->settle_frozen_at[t]);
-        }
-        h->settle_next = settle >= 2 ? settle_next_horizon(T, frozen, max_at, (int)h->settle_rerun, max_iter) : 0;
-    }
-    if (!any) return 0;
+    if (sl.words && !c.no_sync) SC_TRY(collect_settle(h, c, lanes, st, sl));
+    return any ? hand_down(h, c, lvl, st, deferred_tile) : 0;
+}
 
-    // ---- the stragglers, one level down --------------------------------------------------
+// The stragglers of the tiles marked in deferred_tile, one level down: gathered into dense tiles of their own, decoded
+// there from their inputs, and their results put back.
+int hand_down(scaldpc_bp *h, const DecodeCall &c, int lvl, const TileState &st, const std::vector<char> &deferred_tile)
+{
+    const hipStream_t s = c.s;
+    const int T = c.T;
     std::vector<u64> done_h(T);
     SC_HIP(hipMemcpyAsync(done_h.data(), st.done, sizeof(u64) * T, hipMemcpyDeviceToHost, s));
     SC_HIP(hipStreamSynchronize(s));
     pvec<int> ids, slot_of((size_t)T * TW, -1);
     for (int t = 0; t < T; t++) {
         if (!deferred_tile[t]) continue;
-        for (int c = 0; c < TW; c++) {
-            const long b = (long)t * TW + c;
-            if (b < batch && !((done_h[t] >> c) & 1)) {
+        for (int w = 0; w < TW; w++) {
+            const long b = (long)t * TW + w;
+            if (b < c.batch && !((done_h[t] >> w) & 1)) {
                 slot_of[b] = (int)ids.size();
                 ids.push_back((int)b);
             }
         }
     }
-    const int batch2 = (int)ids.size();
-    if (batch2 == 0) return 0;
-    if (lvl == 0) h->stat_deferred = batch2;
-    h->sched.w[SCHED_HANDED + lvl] = batch2;
-    const int T2 = (batch2 + TW - 1) / TW;
+    DecodeCall c2 = c;  // the level below: the stragglers alone, in dense tiles
+    c2.batch = (int)ids.size();
+    if (c2.batch == 0) return 0;
+    if (lvl == 0) h->stat_deferred = c2.batch;
+    h->sched.w[SCHED_HANDED + lvl] = c2.batch;
+    const int T2 = c2.T = (c2.batch + TW - 1) / TW;
     ids.resize((size_t)T2 * TW, -1);
     scaldpc_bp::Level &L = h->lv[lvl + 1];
     SC_TRY(ensure_level(h, L, T2));
     SC_TRY(grow(L.slot_of, (size_t)T * TW));
-    if (want_post) SC_TRY(grow(L.post, (size_t)T2 * h->n * TW));
+    if (c.want_post) SC_TRY(grow(L.post, (size_t)T2 * h->n * TW));
     const int pcols = st.pprior ? h->n - st.first_col : 0;
     if (pcols) SC_TRY(grow(L.pprior, (size_t)T2 * pcols * TW));
     SC_HIP(hipMemcpyAsync(L.ids, ids.data(), sizeof(int) * ids.size(), hipMemcpyHostToDevice, s));
@@ -1513,18 +1537,18 @@ int decode_level(scaldpc_bp *h, int lvl, const TileState &st, int batch, int T, 
         hipLaunchKernelGGL(k_gather_prior, dim3((pcols + 3) / 4, T2), dim3(256), 0, s, st.pprior, pcols, L.ids, L.pprior);
         LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(k_init_state, dim3(T2), dim3(64), 0, s, batch2, max_iter, L.done, L.conv, L.iters);
+    hipLaunchKernelGGL(k_init_state, dim3(T2), dim3(64), 0, s, c2.batch, c.max_iter, L.done, L.conv, L.iters);
     LAUNCH_CHECK();
     SC_HIP(hipMemsetAsync(L.hard, 0, sizeof(u64) * (size_t)T2 * h->n, s));
     SC_HIP(hipStreamSynchronize(s));  // ids / slot_of are locals, and the level below reuses the stream
-    const TileState st2{L.synd, L.hard, L.done, L.conv, L.unsat, L.iters, want_post ? L.post : nullptr,
+    const TileState st2{L.synd, L.hard, L.done, L.conv, L.unsat, L.iters, c.want_post ? L.post : nullptr,
                         pcols ? L.pprior.get() : nullptr, st.first_col};
-    SC_TRY(decode_level(h, lvl + 1, st2, batch2, T2, G, max_iter, method, alpha, early, want_post, s));
+    SC_TRY(decode_level(h, c2, lvl + 1, st2));
     hipLaunchKernelGGL(k_scatter_planes, dim3((h->n + 63) / 64, T), dim3(256), 0, s, st.hard, h->n, L.slot_of, L.hard);
     LAUNCH_CHECK();
     hipLaunchKernelGGL(k_scatter_state, dim3(T), dim3(64), 0, s, st.iters, st.conv, L.slot_of, L.iters, L.conv);
     LAUNCH_CHECK();
-    if (want_post) {
+    if (c.want_post) {
         hipLaunchKernelGGL(k_scatter_post, dim3(h->n, T), dim3(64), 0, s, st.post, h->n, L.slot_of, L.post);
         LAUNCH_CHECK();
     }
@@ -1535,13 +1559,12 @@ int decode_level(scaldpc_bp *h, int lvl, const TileState &st, int batch, int T, 
 // caller wants e XOR v): state reset, then decode_level.
 // Results stay on the device (h->d_hard / d_post / d_conv / d_iters).
 // pprior / first_col: a soft call's prior plane (h->d_pprior) and its first column; null = the handle's shared priors.
-int run_core(scaldpc_bp *h, int batch, int T, int G, int max_iter, int method, float alpha, bool early,
-             bool want_post, hipStream_t s, const float *pprior = nullptr, int first_col = 0)
+int run_core(scaldpc_bp *h, const DecodeCall &c, const float *pprior = nullptr, int first_col = 0)
 {
-    if (!h->small_prepared) {
-        hipLaunchKernelGGL(k_init_state, dim3(T), dim3(64), 0, s, batch, max_iter, h->d_done, h->d_conv, h->d_iters);
+    if (!c.state_ready) {
+        hipLaunchKernelGGL(k_init_state, dim3(c.T), dim3(64), 0, c.s, c.batch, c.max_iter, h->d_done, h->d_conv, h->d_iters);
         LAUNCH_CHECK();
-        SC_HIP(hipMemsetAsync(h->d_hard, 0, sizeof(u64) * (size_t)T * h->n, s));
+        SC_HIP(hipMemsetAsync(h->d_hard, 0, sizeof(u64) * (size_t)c.T * h->n, c.s));
     }
     h->last_group = 0;
     h->stat_deferred = 0;
@@ -1550,18 +1573,16 @@ int run_core(scaldpc_bp *h, int batch, int T, int G, int max_iter, int method, f
 
     // small graph: the LDS-resident single-launch decoder, plane I/O (Monte-Carlo entry points)
     if (const size_t lds = small_lds(h)) {
-        const SoftPrior spv{h->d_prior, pprior, first_col, h->n - first_col};
-        return launch_small<true>(h, lds, method, batch, h->d_synd, SCALDPC_IN_SYNDROME, max_iter, alpha, early, h->d_hard,
-                                  want_post ? h->d_post.get() : nullptr, h->d_iters, h->d_conv, s, pprior ? &spv : nullptr);
+        return launch_small<true>(h, lds, c.method, c.batch, h->d_synd, SCALDPC_IN_SYNDROME, c.max_iter, c.alpha, c.early, h->d_hard,
+                                  c.want_post ? h->d_post.get() : nullptr, h->d_iters, h->d_conv, c.s, pprior, first_col);
     }
     const TileState st{h->d_synd, h->d_hard, h->d_done, h->d_conv, h->d_unsat, h->d_iters,
-                       want_post ? h->d_post : nullptr, pprior, first_col};
-    return decode_level(h, 0, st, batch, T, G, max_iter, method, alpha, early, want_post, s);
+                       c.want_post ? h->d_post : nullptr, pprior, first_col};
+    return decode_level(h, c, 0, st);
 }
 
 }  // namespace
 
-#include <chrono>
 #define TMARK(name)                                                                                   \
     do {                                                                                              \
         static const bool on__ = getenv("SCALDPC_TIMING") != nullptr;                                 \
@@ -1738,12 +1759,9 @@ int prior_llrs(const double *probs, int first, int count, pvec<float> &llr)
     return 0;
 }
 
-// The preamble of the decoding entry points (decode_batch and the Monte-Carlo runs): priors set, max_iter default,
-// stream, tiles of 64 codewords (at most 65535: a grid dimension) and tiles per group.
-struct Call {
-    hipStream_t s;
-    int max_iter, T, G;
-};
+// The preamble of the decoding entry points (decode_batch and the Monte-Carlo runs): priors set, and of the DecodeCall the
+// batch, max_iter with its default, the stream, tiles of 64 codewords (at most 65535: a grid dimension) and tiles per group.
+// What the entry decodes with (method, alpha, early, want_post, the two flags) it fills in itself.
 // what scaldpc_bp_last_settle reports: cleared when a call starts, whatever path it takes
 void settle_report_reset(scaldpc_bp *h)
 {
@@ -1751,12 +1769,13 @@ void settle_report_reset(scaldpc_bp *h)
     h->settle_saved = h->settle_rerun = 0;
     h->settle_K = 0;
 }
-int begin_call(scaldpc_bp *h, int batch, int max_iter, void *stream, Call *c)
+int begin_call(scaldpc_bp *h, int batch, int max_iter, void *stream, DecodeCall *c)
 {
     if (!h->have_prior || h->prior_n < h->n)
         return fail(SCALDPC_EINVAL, "channel probabilities not set (columns [%d, %d))", h->have_prior ? h->prior_n : 0, h->n);
     h->sched.reset();
     settle_report_reset(h);
+    c->batch = batch;
     c->max_iter = max_iter > 0 ? max_iter : h->n;
     c->s = stream ? (hipStream_t)stream : h->own_stream;
     c->T = (batch + TW - 1) / TW;
@@ -2192,23 +2211,22 @@ int scaldpc_bp_set_tile_group(scaldpc_bp *h, int32_t tiles)
     return 0;
 }
 
-// Tile group and workspace of a call on the tile path.  prob_cols > 0: the last prob_cols columns bring per-codeword priors
+// Tile group (c.G) and workspace of a call on the tile path.  prob_cols > 0: the last prob_cols columns bring per-codeword priors
 // (scaldpc_bp_decode_batch_soft, scaldpc_mc_hqc_run_soft), whose plane h->d_pprior is sized here too.
-static int size_call(scaldpc_bp *h, const Call &c, int prob_cols, bool early, int method, bool want_post, int *G)
+static int size_call(scaldpc_bp *h, DecodeCall &c, int prob_cols)
 {
-    *G = c.G;
     if (prob_cols > 0 && h->tile_group <= 0) {
         // the plane's rows share the cache with the group's messages where its passes keep reading them: every pass of an
         // early-exit run and every message-form pass reads all of them, a record-form pass without output only the
         // columns of degree >= 2 (launch_var: `light`)
         int cols = prob_cols;
-        if (!early && rec_form(h, method)) {
+        if (!c.early && rec_form(h, c.method)) {
             cols = 0;
             for (int v = h->n - prob_cols; v < h->n; v++) cols += h->hg_cdeg[v] > 1;
         }
-        *G = auto_group(h, c.T, cols);
+        c.G = auto_group(h, c.T, cols);
     }
-    return ensure_workspace(h, c.T, *G, want_post, c.max_iter, prob_cols);
+    return ensure_workspace(h, c.T, c.G, c.want_post, c.max_iter, prob_cols);
 }
 
 // Both decode entry points.  probs / prob_cols: a soft call's per-codeword probabilities of the last prob_cols columns
@@ -2228,13 +2246,18 @@ static int decode_batch_impl(scaldpc_bp *h, const uint8_t *in, int32_t input_kin
     SC_TRY(check_usable(h));
     if (prob_cols > h->n) return fail(SCALDPC_EINVAL, "prob_cols = %d exceeds the block length n = %d", prob_cols, h->n);
     DeviceGuard dg(h->device);
-    Call c;
+    DecodeCall c;
     SC_TRY(begin_call(h, batch, max_iter_arg, stream, &c));
     const bool dev_io = flags & SCALDPC_F_DEVICE_IO;
     const bool early = flags & SCALDPC_F_EARLY_EXIT;
     if ((flags & SCALDPC_F_ASYNC) && (!dev_io || early))
         return fail(SCALDPC_EINVAL, "SCALDPC_F_ASYNC needs DEVICE_IO and no EARLY_EXIT (early exit polls the device)");
     if (flags & SCALDPC_F_ASYNC) h->async_used = true;
+    c.method = method;
+    c.alpha = alpha;
+    c.early = early;
+    c.want_post = out_llr != nullptr;
+    c.no_sync = (flags & SCALDPC_F_ASYNC) != 0;  // (such a call only enqueues: no read-back of settled tiles, no horizon)
     CacheBypass guard(h->async_used);
     const hipStream_t s = c.s;
     SyncOnError settle{s};
@@ -2291,17 +2314,15 @@ static int decode_batch_impl(scaldpc_bp *h, const uint8_t *in, int32_t input_kin
             SC_TRY(grow(h->d_pprior, (size_t)T * prob_cols * TW));
             SC_TRY(soft_convert());
         }
-        const SoftPrior spv{h->d_prior, h->d_pprior, first_col, prob_cols};
         SC_TRY(launch_small<false>(h, lds, method, batch, din, input_kind, max_iter, alpha, early, dev.bits, dev.llr, dev.iters,
-                                   dev.conv, s, soft ? &spv : nullptr));
+                                   dev.conv, s, soft ? h->d_pprior.get() : nullptr, first_col));
         SC_TRY(copy_outputs(h, out, dev, batch, dev_io, s));
         h->stat_deferred = 0;
         if (soft && !(flags & SCALDPC_F_ASYNC)) SC_TRY(soft_verdict());
         if (!(flags & SCALDPC_F_ASYNC)) SC_HIP(hipStreamSynchronize(s));
         return settle.done();
     }
-    int G;
-    SC_TRY(size_call(h, c, prob_cols, early, method, out_llr != nullptr, &G));
+    SC_TRY(size_call(h, c, prob_cols));
     if (soft) SC_TRY(soft_convert());
     const float *const pprior = soft ? h->d_pprior.get() : nullptr;
 
@@ -2322,10 +2343,8 @@ static int decode_batch_impl(scaldpc_bp *h, const uint8_t *in, int32_t input_kin
                            h->d_remaining, max_iter + 2, h->d_el_unsat, (max_iter + 2) * TW);
         LAUNCH_CHECK();
         if (recvd) SC_TRY(launch_syndrome(h, h->d_recv, h->d_synd, 1, s));
-        h->small_prepared = true;
-        const int rc = run_core(h, batch, T, G, max_iter, method, alpha, early, out_llr != nullptr, s, pprior, first_col);
-        h->small_prepared = false;
-        SC_TRY(rc);
+        c.state_ready = true;  // (k_small_prepare has reset the state planes and both counter arrays)
+        SC_TRY(run_core(h, c, pprior, first_col));
         hipLaunchKernelGGL(k_small_unpack, dim3((h->n + 255) / 256), dim3(256), 0, s, h->d_hard, recvd ? h->d_recv : (const u64 *)nullptr,
                            out_llr ? h->d_post : (const float *)nullptr, h->d_conv, h->d_iters, h->n, batch, h->d_out_all);
         LAUNCH_CHECK();
@@ -2354,10 +2373,7 @@ static int decode_batch_impl(scaldpc_bp *h, const uint8_t *in, int32_t input_kin
         LAUNCH_CHECK();
         SC_TRY(launch_syndrome(h, h->d_recv, h->d_synd, T, s));
     }
-    h->settle_no_host = (flags & SCALDPC_F_ASYNC) != 0;  // (such a call only enqueues: no read-back, no horizon)
-    const int rc_core = run_core(h, batch, T, G, max_iter, method, alpha, early, out_llr != nullptr, s, pprior, first_col);
-    h->settle_no_host = false;
-    SC_TRY(rc_core);
+    SC_TRY(run_core(h, c, pprior, first_col));
 
     // ---- outputs --------------------------------------------------------------
     SC_TRY(stage_outputs(h, out, batch, dev_io, true, &dev));
@@ -2593,7 +2609,7 @@ int scaldpc_bp_decode_batch_f64(scaldpc_bp *h, const uint8_t *in, int32_t input_
     SC_TRY(check_usable(h));
     if (prob_cols > h->n) return fail(SCALDPC_EINVAL, "prob_cols = %d exceeds the block length n = %d", prob_cols, h->n);
     DeviceGuard dg(h->device);
-    Call c;
+    DecodeCall c;
     SC_TRY(begin_call(h, batch, max_iter_arg, stream, &c));
     const bool dev_io = flags & SCALDPC_F_DEVICE_IO;
     const bool early = flags & SCALDPC_F_EARLY_EXIT;
@@ -2872,24 +2888,25 @@ int mc_f64_handover_at(const scaldpc_bp *h) { return h->kn.compact_after < 0 ? 4
 
 // Tile group and workspace of a sweep whose last prob_cols columns bring per-trial priors (0: the handle's shared priors):
 // size_call as decode_batch_impl sizes a soft call, or what scaldpc_bp_decode_batch_f64 sizes.
-int mc_size(scaldpc_bp *h, const Call &c, const McDecode &d, int prob_cols, bool early, int *G)
+int mc_size(scaldpc_bp *h, DecodeCall &c, const McDecode &d, int prob_cols, bool early)
 {
-    if (!d.f64) return size_call(h, c, prob_cols, early, d.method, false, G);
-    *G = ref64_group(h, c.T);
-    return ref64_ensure(h, c.T, *G, c.max_iter, false, prob_cols);
+    c.method = d.method;  // (what the sweep decodes with; no posteriors)
+    c.alpha = d.alpha;
+    c.early = early;
+    if (!d.f64) return size_call(h, c, prob_cols);
+    c.G = ref64_group(h, c.T);
+    return ref64_ensure(h, c.T, c.G, c.max_iter, false, prob_cols);
 }
 
 // The decode of a sweep on the planes its trial kernels have staged (h->d_synd, and with prob_cols the prior plane of the
 // decode's precision): run_core, or scaldpc_bp_decode_batch_f64's loop (ref64_run), whose stragglers are handed over to dense
 // tiles once, after iteration "compact_after" (ref64_handover).
-int mc_decode(scaldpc_bp *h, const McDecode &d, int batch, int T, int G, int max_iter, bool early, int prob_cols, hipStream_t s)
+int mc_decode(scaldpc_bp *h, const McDecode &d, const DecodeCall &c, int prob_cols)
 {
-    if (!d.f64)
-        return run_core(h, batch, T, G, max_iter, d.method, d.alpha, early, false, s, prob_cols ? h->d_pprior.get() : nullptr,
-                        prob_cols ? h->n - prob_cols : 0);
+    if (!d.f64) return run_core(h, c, prob_cols ? h->d_pprior.get() : nullptr, prob_cols ? h->n - prob_cols : 0);
     const Ref64Planes pl{h->d_synd, h->d_hard, h->d_done, h->d_conv, h->d_unsat, h->d_iters, nullptr,
                          prob_cols ? h->d_pratio.get() : nullptr, prob_cols};
-    return ref64_run(h, pl, batch, T, G, max_iter, early, mc_f64_handover_at(h), s);
+    return ref64_run(h, pl, c.batch, c.T, c.G, c.max_iter, c.early, mc_f64_handover_at(h), c.s);
 }
 
 // Every FER entry: the trials from either source, decoded either way.
@@ -2901,15 +2918,14 @@ int mc_fer_body(scaldpc_bp *h, const TrialSrc &ts, int32_t batch, uint64_t seed,
     SC_TRY(check_usable(h));
     DeviceGuard dg(h->device);
     CacheBypass guard(h->async_used);
-    Call c;
+    DecodeCall c;
     SC_TRY(begin_call(h, batch, max_iter_arg, stream, &c));
     const hipStream_t s = c.s;
     SyncOnError settle{s};
     SC_TRY(refresh_full(h));
     const bool dev_io = flags & SCALDPC_F_DEVICE_IO, early = flags & SCALDPC_F_EARLY_EXIT;
-    const int T = c.T, max_iter = c.max_iter;
-    int G;
-    SC_TRY(mc_size(h, c, d, 0, early, &G));
+    const int T = c.T;
+    SC_TRY(mc_size(h, c, d, 0, early));
     SC_TRY(grow(h->d_mc, (size_t)T * h->n));
     SC_TRY(ensure_thresholds(h));
     DeviceTrials tr;
@@ -2919,7 +2935,7 @@ int mc_fer_body(scaldpc_bp *h, const TrialSrc &ts, int32_t batch, uint64_t seed,
     SC_TRY(draw_bernoulli(false, h->d_mc, h->n, batch, T, tr, k0, k1, (const u64 *)h->d_thr, 0ull, s));
     SC_TRY(launch_syndrome(h, h->d_mc, h->d_synd, T, s));
     if (out_error) SC_TRY(mc_export_bits(h, h->d_mc, nullptr, batch, T, dev_io, false, s, out_error));
-    SC_TRY(mc_decode(h, d, batch, T, G, max_iter, early, 0, s));
+    SC_TRY(mc_decode(h, d, c, 0));
     // success iff decoding == error everywhere (decode.py:173-175)
     SC_TRY(mc_finish(h, batch, T, h->n, dev_io, s, out_success, out_iters));
     return settle.done();
@@ -2941,7 +2957,7 @@ int mc_hqc_body(scaldpc_bp *h, const TrialSrc &ts, int32_t omega, const McHqcNoi
     if (nz.table) SC_TRY(mc_noise_law(nz, d.f64, h->m, o.cost != nullptr, &law, &law64));
     DeviceGuard dg(h->device);
     CacheBypass guard(h->async_used);
-    Call c;
+    DecodeCall c;
     SC_TRY(begin_call(h, batch, max_iter_arg, stream, &c));
     const hipStream_t s = c.s;
     SyncOnError settle{s};
@@ -2952,9 +2968,8 @@ int mc_hqc_body(scaldpc_bp *h, const TrialSrc &ts, int32_t omega, const McHqcNoi
     if (!nz.table && !(nz.eps >= 0.0 && nz.eps <= 1.0)) return fail(SCALDPC_EINVAL, "eps must be a probability");
     if ((size_t)omega * 64 * 4 > 64 * 1024) return fail(SCALDPC_EDEGREE, "omega %d too large for the LDS-resident sampler", omega);
     const bool dev_io = flags & SCALDPC_F_DEVICE_IO, early = flags & SCALDPC_F_EARLY_EXIT;
-    const int T = c.T, max_iter = c.max_iter, prob_cols = nz.table ? R : 0;
-    int G;
-    SC_TRY(mc_size(h, c, d, prob_cols, early, &G));
+    const int T = c.T, prob_cols = nz.table ? R : 0;
+    SC_TRY(mc_size(h, c, d, prob_cols, early));
     SC_TRY(grow(h->d_mc, (size_t)T * h->n));
     if (nz.table) SC_TRY(grow(h->d_mc_acc, (size_t)2 * batch));
     int *dy, *dstats;
@@ -2982,7 +2997,7 @@ int mc_hqc_body(scaldpc_bp *h, const TrialSrc &ts, int32_t omega, const McHqcNoi
     SC_HIP(hipMemcpy2DAsync(h->d_recv + N, sizeof(u64) * h->n, h->d_synd, sizeof(u64) * h->m, sizeof(u64) * h->m, T,
                             hipMemcpyDeviceToDevice, s));
     if (o.msg) SC_TRY(mc_export_bits(h, h->d_recv, nullptr, batch, T, dev_io, false, s, o.msg));
-    SC_TRY(mc_decode(h, d, batch, T, G, max_iter, early, prob_cols, s));
+    SC_TRY(mc_decode(h, d, c, prob_cols));
     const hipMemcpyKind back = dev_io ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     SC_TRY(mc_unstage(o.y, dy, (size_t)batch * omega, dev_io, s));
     SC_TRY(mc_unstage(o.outcome, dout, (size_t)batch * R, dev_io, s));
@@ -3162,13 +3177,20 @@ int scaldpc_bp_time_kernels(scaldpc_bp *h, int32_t iters, int32_t method, float 
     Lanes lanes(h, s);
     int gs[2], t0[2];
     deal_tiles(g, nl, gs, t0);  // as iterate_tiles deals the tiles
+    const TileState st{h->d_synd, h->d_hard, h->d_done, h->d_conv, h->d_unsat, h->d_iters, nullptr};  // (no posteriors)
     auto check = [&](int it, int k) {
-        return launch_check(h, method, alpha_for(alpha, it + 1), gs[k], h->d_synd + (size_t)t0[k] * h->m, h->d_done + t0[k], 0,
-                            lanes[k], false, t0[k]);
+        CheckPass cp;
+        cp.alpha = alpha_for(alpha, it + 1);
+        cp.tile0 = t0[k];
+        return launch_check(h, st.at(h, t0[k]), gs[k], method, 0, lanes[k], cp);
     };
     auto var = [&](int k) {
-        return launch_var(h, gs[k], nullptr, h->d_hard + (size_t)t0[k] * h->n, h->d_done + t0[k], 0, wo, lanes[k], t0[k], nullptr,
-                          recf, true);
+        VarPass vp;
+        vp.write_out = wo;
+        vp.tile0 = t0[k];
+        vp.rec = recf;
+        vp.light = true;
+        return launch_var(h, st.at(h, t0[k]), gs[k], 0, lanes[k], vp);
     };
     // `iters` back-to-back launches of each kernel between two events: the event
     // overhead (a few us, comparable to a 65 us launch) is amortised, what remains is

@@ -275,6 +275,47 @@ inline int settle_next_horizon(int tiles, int frozen, int max_frozen_at, int rer
 // would only pay for the tracking.
 inline int settle_mode(int knob, bool identity_block) { return knob >= 0 ? knob : identity_block ? 2 : 0; }
 
+// ---------------------------------------------------------------------------
+// The record-form variable pass (launch_var, scaldpc_bp.hip): which blocks of the column records a pass runs.  The
+// records are laid out bucket by bucket -- bucket b = blocks [blk[b], blk[b + 1]), unroll bound maxd[b], ascending;
+// var_reversed: the whole order mirrored, heaviest first -- and a slice is a first block and a count.
+//   slim   a pass without output after iteration 1 (light && !write_out) leaves the degree-1 bucket out.  A column of
+//          degree <= 1 always sends its prior; iteration 1 has written that into the message array and the record check
+//          pass never overwrites it (its sign mask is the bootstrap check pass's, and stays true), so such a pass has
+//          nothing to do there (the identity block of an HQC graph: 4000 of 21669 column waves per tile).  Not when the
+//          bucket is all there is.
+//   wide   the blocks of the (32, 64] bucket (minsum_rec = 2, rec_form; the last bucket, no any-degree one behind it) get
+//          a launch of their own -- k_var<64, ..>, the kernel that already keeps 64 edges in registers, in its record mode
+//          (RecWide) -- so that the exact-degree code of the columns up to 32 stays what it is; the narrow launch runs over
+//          the other buckets' blocks, compiled for the widest of THEM (narrow_deg).
+//   xmap   XCD-aware tile placement where the launch's G tiles divide the 8 XCDs (fetch 38.0 -> 29.5 MB per launch,
+//          profiles/r03/ab_rec_xmap.log): grid.x is then rounded up to a multiple of 8.
+// tests/rec_slices_main.cc walks this under the sanitizers, tests/test_rec_slices.py holds it to a restatement in Python.
+// ---------------------------------------------------------------------------
+struct RecVarSlices {
+    int narrow0 = 0, narrow_n = 0, narrow_deg = 0, narrow_grid = 0;  // first block, blocks, the degree that picks the cap, grid.x
+    int wide0 = 0, wide_n = 0, wide_grid = 0;
+    bool xmap = false;
+};
+inline RecVarSlices rec_var_slices(int nb, const int *maxd, const int *blk, bool var_reversed, bool light, bool write_out, int G,
+                                   int max_col_deg)
+{
+    RecVarSlices r;
+    const int nblk = blk[nb];
+    const int n1 = (nb > 0 && maxd[0] == 1) ? blk[1] : 0;
+    const bool slim = light && !write_out && n1 > 0 && n1 < nblk;
+    r.wide_n = (nb > 0 && maxd[nb - 1] > 32) ? nblk - blk[nb - 1] : 0;
+    r.narrow_deg = r.wide_n ? (nb > 1 ? maxd[nb - 2] : 0) : max_col_deg;
+    r.narrow_n = (slim ? nblk - n1 : nblk) - r.wide_n;
+    // (heaviest first: the wide blocks lead the records and the degree-1 bucket ends them)
+    r.narrow0 = var_reversed ? r.wide_n : (slim ? n1 : 0);
+    r.wide0 = var_reversed ? 0 : nblk - r.wide_n;
+    r.xmap = G == 2 || G == 4 || G == 8;
+    r.narrow_grid = r.xmap ? (r.narrow_n + 7) / 8 * 8 : r.narrow_n;
+    r.wide_grid = r.xmap ? (r.wide_n + 7) / 8 * 8 : r.wide_n;
+    return r;
+}
+
 // Poll points of the row-parallel loop: `ip` = the iteration whose verdict the host may look at.  Poll densely where
 // convergence is likely, sparsely afterwards.
 inline bool el_poll_point(int ip) { return (ip >= 3 && ip <= 6) || (ip > 6 && ip <= 16 && ip % 2 == 0) || (ip > 16 && ip % 16 == 0); }
