@@ -314,9 +314,18 @@ int scaldpc_bp_last_schedule(scaldpc_bp *h, int64_t *out);
  *   info[3]  the horizon K the call ran with (0 = none: device-side skipping only)
  * Results never depend on any of this. */
 int scaldpc_bp_last_settle(scaldpc_bp *h, int32_t *frozen_at, int32_t cap, int64_t *info);
+/* Debug: the sparse gate's tables (knob "settle_sparse") of one tile as the last call left them -- a blocking copy, to be
+ * called after a synchronous call only.  info[4] = {tiles, rows, columns} the tables were laid out for (all 0 = the last
+ * call did not use them) and the variable pass from which that call gated (its check passes one later: the first test in a
+ * call that learns, then two passes before the smallest frozen-at number of the handle's last call on the same priors,
+ * max_iter and alpha); with the three arrays NULL only info is filled.  row_stamp[rows] = the last tracked check pass in
+ * which the row ran, row_dirty[rows] = the mask of its edges (by index in the row) whose message may have changed in that
+ * pass, col_flag[columns] = (last tracked variable pass in which the column ran) << 1 | (its sign masks changed there). */
+int scaldpc_bp_debug_sparse_flags(scaldpc_bp *h, int32_t tile, uint32_t *row_stamp, uint64_t *row_dirty, uint32_t *col_flag,
+                                  int64_t *info);
 /* Tuning / test knobs of one handle.  A new handle takes its defaults from the environment ONCE, at
  * creation (SCALDPC_PATH, SCALDPC_SPLIT, SCALDPC_GROUP_MB, SCALDPC_EL_MAX, SCALDPC_COMPACT_AFTER,
- * SCALDPC_FIRST_FUSED, SCALDPC_FUSE_TEST, SCALDPC_MINSUM_REC, SCALDPC_SETTLE, SCALDPC_SETTLE_HORIZON); the decode entry points never read the environment.
+ * SCALDPC_FIRST_FUSED, SCALDPC_FUSE_TEST, SCALDPC_MINSUM_REC, SCALDPC_SETTLE, SCALDPC_SETTLE_HORIZON, SCALDPC_SETTLE_SPARSE); the decode entry points never read the environment.
  * Every knob selects a path, a size or a form that some graph or call still falls back to; the switches of variants
  * that were measured and rejected (round 3's test_overlap, var_form, rec_maskpos, rec_xmap, rec_sc1, fuse_finalize,
  * speculate, minsum_loop) are gone with their code (round 4; numbers in profiles/HISTORY.md), and so are the A/B-only
@@ -357,6 +366,12 @@ int scaldpc_bp_last_settle(scaldpc_bp *h, int32_t *frozen_at, int32_t cap, int64
  *                   is what bounds the messages), 0 on any other graph: it has no reason to settle and would only pay
  *                   for the compares.
  *   "settle_horizon" K > 0: that horizon, forced (0 = learned)
+ *   "settle_sparse" tracked calls ("settle" 1 or 2): 1 = from the first test on, a check pass returns for every row none of
+ *                   whose columns ran in the variable pass before, and a variable pass for every column of 2 ... 32 edges
+ *                   none of whose messages changed in the check pass before (two small per-tile tables say which;
+ *                   scaldpc_bp_debug_sparse_flags); 0 = every row and column of a tile that is not frozen runs;
+ *                   -1 (default) = 1 where "settle" is 2 in force on a graph [Hin | I], else 0: where nothing freezes the
+ *                   gate saves nothing and a tracked call costs about 18 % more with it (a (3,6)-regular graph).
  *   Results never depend on any of these. */
 int scaldpc_bp_configure(scaldpc_bp *h, const char *key, const char *value);
 /* Where a handle lives, out[4]: the device it was created on; the device (hipPointerGetAttributes)

@@ -74,6 +74,9 @@ def _declare(lib):
     if hasattr(lib, "scaldpc_bp_last_settle"):  # (an earlier build loaded through SCALDPC_SO has no such entry)
         lib.scaldpc_bp_last_settle.argtypes = [vp, p(C.c_int32), C.c_int32, p(C.c_int64)]
         lib.scaldpc_bp_last_settle.restype = C.c_int
+    if hasattr(lib, "scaldpc_bp_debug_sparse_flags"):
+        lib.scaldpc_bp_debug_sparse_flags.argtypes = [vp, C.c_int32, p(C.c_uint32), p(C.c_uint64), p(C.c_uint32), p(C.c_int64)]
+        lib.scaldpc_bp_debug_sparse_flags.restype = C.c_int
     lib.scaldpc_bp_append_rows.argtypes = [vp, C.c_int32, vp, vp, C.c_int32]
     lib.scaldpc_bp_append_rows.restype = C.c_int
     lib.scaldpc_bp_set_channel_probs_tail.argtypes = [vp, C.c_int32, C.c_int32, vp]

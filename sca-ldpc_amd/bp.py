@@ -472,12 +472,33 @@ class BpDecoder:
         return {"frozen_at": [int(x) for x in at[:tiles]], "launches_saved": int(info[1]), "tiles_rerun": int(info[2]),
                 "horizon": int(info[3])}
 
+    def debug_sparse_flags(self):
+        """The sparse settle gate's tables after the last (synchronous) call (scaldpc_bp_debug_sparse_flags): per tile a dict
+        row_stamp uint32 [m], row_dirty uint64 [m], col_flag uint32 [n]; [] = the call did not use them."""
+        info = (C.c_int64 * 4)()
+        _lib.check(self._lib.scaldpc_bp_debug_sparse_flags(self._h, 0, None, None, None, info))
+        tiles, m, n = (int(x) for x in info[:3])
+        out = []
+        for t in range(tiles):
+            rs, rd, cf = np.zeros(m, dtype=np.uint32), np.zeros(m, dtype=np.uint64), np.zeros(n, dtype=np.uint32)
+            _lib.check(self._lib.scaldpc_bp_debug_sparse_flags(
+                self._h, t, rs.ctypes.data_as(C.POINTER(C.c_uint32)), rd.ctypes.data_as(C.POINTER(C.c_uint64)),
+                cf.ctypes.data_as(C.POINTER(C.c_uint32)), info))
+            out.append({"row_stamp": rs, "row_dirty": rd, "col_flag": cf})
+        return out
+
+    def debug_sparse_start(self):
+        """The variable pass from which the last call's sparse gate gated (0 = the call did not use the gate)."""
+        info = (C.c_int64 * 4)()
+        _lib.check(self._lib.scaldpc_bp_debug_sparse_flags(self._h, 0, None, None, None, info))
+        return int(info[3])
+
     def last_row_parallel(self):
         return self.last_stats()["row_parallel"]
 
     def configure(self, **knobs):
         """Tuning / test knobs of this decoder (include/scaldpc.h, scaldpc_bp_configure): path, split,
-        group_mb, el_max, compact_after, first_fused, fuse_test, minsum_rec, settle, settle_horizon.  A new decoder takes its
+        group_mb, el_max, compact_after, first_fused, fuse_test, minsum_rec, settle, settle_horizon, settle_sparse.  A new decoder takes its
         defaults from the SCALDPC_* environment once, at construction; results never depend on them.
         minsum_rec=2 (passed through as it is): 1, and columns of 33 ... 64 edges stay in min-sum's record form -- opt-in;
         by default, and under 1, a graph with such a column runs the message form."""

@@ -109,6 +109,7 @@ struct Knobs {
     int minsum_rec = 1;       // min-sum on the tile kernels: check pass writes per-row records + lane masks instead of messages (k_check_minsum_rec / k_var_rec); 0 = message form; 2 = 1, and columns of 33 ... 64 edges stay in the record form (rec_form)
     int settle = -1;          // fixed-iteration record-form calls: -1 = 2 on a graph [Hin | I], 0 on any other (settle_mode); 0 = every pass runs; 1 = passes return at once for tiles whose message state has stopped changing (Settle); 2 = and a learned horizon keeps them from being enqueued
     int settle_horizon = 0;   // > 0: the horizon K, forced (tiles it is wrong for are decoded again: results never depend on it)
+    int settle_sparse = -1;   // tracked levels: 1 = a pass returns for rows and columns none of whose inputs changed (Settle's sparse gate); 0 = off; -1 = on where settle is 2 on a graph [Hin | I] (settle_sparse_mode)
 };
 
 // The handle's streams and events, released when the handle goes.  scaldpc_bp derives from it, so every buffer member
@@ -267,6 +268,14 @@ struct scaldpc_bp : HandleStreams {
     // words of the call's tiles, h_settle their host copy; settle_next = the horizon the next call runs with (0 = it
     // learns), valid for the key below; what the last call did is kept for scaldpc_bp_last_settle.
     Buf<unsigned> d_settle;
+    // the sparse gate's tables (Settle: rowf [tile][m], colf [tile][n]); sparse_m / sparse_n / sparse_T = the shape they were
+    // last zeroed for (scaldpc_bp_debug_sparse_flags), 0 = the last call did not use them
+    Buf<uint4> d_rowf;
+    Buf<unsigned> d_colf;
+    int sparse_m = 0, sparse_n = 0, sparse_T = 0;
+    // the start the next call gates from (settle_sparse_next_start; 0 = the first test), forgotten with settle_next; and
+    // the one the last call ran with
+    int sparse_start_next = 0, sparse_start = 0;
     PinnedBuf<unsigned> h_settle;
     int settle_next = 0;
     int settle_key_iter = 0, settle_key_soft = 0;
@@ -305,6 +314,7 @@ bool set_knob(Knobs &k, const char *key, const char *val)
     else if (!strcmp(key, "fuse_test")) k.fuse_test = (int)x != 0;
     else if (!strcmp(key, "settle") && x >= -1 && x <= 2) k.settle = (int)x;
     else if (!strcmp(key, "settle_horizon") && x >= 0) k.settle_horizon = (int)x;
+    else if (!strcmp(key, "settle_sparse") && x >= -1 && x <= 1) k.settle_sparse = (int)x;
     else return false;
     return true;
 }
@@ -315,7 +325,8 @@ void knobs_from_env(Knobs &k)
                                            {"SCALDPC_GROUP_MB", "group_mb"}, {"SCALDPC_EL_MAX", "el_max"},
                                            {"SCALDPC_COMPACT_AFTER", "compact_after"}, {"SCALDPC_FIRST_FUSED", "first_fused"},
                                            {"SCALDPC_FUSE_TEST", "fuse_test"}, {"SCALDPC_MINSUM_REC", "minsum_rec"},
-                                           {"SCALDPC_SETTLE", "settle"}, {"SCALDPC_SETTLE_HORIZON", "settle_horizon"}};
+                                           {"SCALDPC_SETTLE", "settle"}, {"SCALDPC_SETTLE_HORIZON", "settle_horizon"},
+                                           {"SCALDPC_SETTLE_SPARSE", "settle_sparse"}};
     for (auto &nm : names)
         if (const char *e = getenv(nm[0])) (void)set_knob(k, nm[1], e);
 }
@@ -1205,6 +1216,23 @@ struct SettlePlan {
     unsigned *words = nullptr;  // [tile][SETTLE_WORDS] of the level's tiles, zero when the level starts
     int first_test = 0, horizon = 0;
     unsigned *of(int tile) const { return words + (size_t)tile * SETTLE_WORDS; }  // the words of a launch whose first tile it is
+    // the sparse gate's tables (null = off), [tile][m] and [tile][n], zero when the level starts
+    uint4 *rowf = nullptr;
+    unsigned *colf = nullptr;
+    int m = 0, n = 0;
+    int gate_start = 0;  // the variable pass from which the level gates (settle_sparse_next_start; 0 = from the first test)
+    // a tracked launch's argument: the words and tables of its first tile, what it is told about the tests, whether it gates
+    Settle pass(int tile, int done, int mark, int gate) const
+    {
+        Settle s{of(tile), done, mark};
+        if (rowf && mark) {
+            s.rowf = rowf + (size_t)tile * m;
+            s.colf = colf + (size_t)tile * n;
+            s.ncol = n;
+            s.gate = gate;
+        }
+        return s;
+    }
 };
 int iterate_tiles(scaldpc_bp *h, const DecodeCall &c, Lanes &lanes, const TileState &st, int g0, int g, int defer_after,
                   bool *deferred, PollState &ps, int chain, const SettlePlan &sl)
@@ -1244,6 +1272,7 @@ int iterate_tiles(scaldpc_bp *h, const DecodeCall &c, Lanes &lanes, const TileSt
     bool verdict_pending[MAX_LANES] = {};  // lane k's last variable pass has not been tested yet: its next check pass will
     const bool recf = rec_form(h, method);
     bool rec_booted[MAX_LANES] = {};  // lane k has run its first record-form check pass (the one that also writes the sign masks)
+    int boot_it[MAX_LANES] = {};      // ... and the iteration it did so in (0 = not yet)
     const bool tracked = sl.words && recf && !early;
     const int K = tracked ? sl.horizon : 0, last_test = K ? K : max_iter;
     // (re-)establish the one-kernel offset between neighbouring lanes -- in a chained group too (phase_reestablished,
@@ -1270,9 +1299,11 @@ int iterate_tiles(scaldpc_bp *h, const DecodeCall &c, Lanes &lanes, const TileSt
             }
             cp.boot = recf && !cp.first && !rec_booted[k];
             if (cp.boot) rec_booted[k] = true;
+            boot_it[k] = cp.boot ? it : boot_it[k];
             if (tracked)
-                cp.settle = Settle{sl.of(g0 + t0[k]), settle_check_done(it, sl.first_test),
-                                   cp.boot ? 0 : settle_check_mark(it, sl.first_test, last_test)};
+                cp.settle = sl.pass(g0 + t0[k], settle_check_done(it, sl.first_test),
+                                    cp.boot ? 0 : settle_check_mark(it, sl.first_test, last_test),
+                                    cp.boot ? 0 : settle_sparse_check_gate(it, sl.first_test, last_test, sl.gate_start));
             SC_TRY(launch_check(h, tv[k], gs[k], method, skip, lanes[k], cp));
             if (set_phase && k + 1 < nl) {
                 SC_HIP(hipEventRecord(h->ev_phase[k + 1], lanes[k]));
@@ -1292,8 +1323,9 @@ int iterate_tiles(scaldpc_bp *h, const DecodeCall &c, Lanes &lanes, const TileSt
             vp.final_pass = last;
             vp.keep_hard = keep_hard && !last;
             if (tracked && !last)
-                vp.settle = Settle{sl.of(g0 + t0[k]), settle_var_done(it, sl.first_test, last_test),
-                                   settle_var_mark(it, sl.first_test, last_test)};
+                vp.settle = sl.pass(g0 + t0[k], settle_var_done(it, sl.first_test, last_test),
+                                    settle_var_mark(it, sl.first_test, last_test),
+                                    boot_it[k] == it ? 0 : settle_sparse_var_gate(it, sl.first_test, last_test, sl.gate_start));  // (a bootstrap check pass stamped no row)
             else if (keep_hard)  // the closing pass: it comes behind the check pass that completes the group's last test
                 vp.settle = Settle{sl.of(g0 + t0[k]), last_test, 0};
             SC_TRY(launch_var(h, tv[k], gs[k], skip, lanes[k], vp));
@@ -1371,6 +1403,7 @@ int plan_settle(scaldpc_bp *h, const DecodeCall &c, int lvl, const TileState &st
     const int soft = st.pprior ? 1 : 0;
     if (h->settle_key_iter != c.max_iter || h->settle_key_alpha != c.alpha || h->settle_key_soft != soft) {
         h->settle_next = 0;  // another max_iter / alpha / kind of priors: learn again
+        h->sparse_start_next = 0;
         h->settle_key_iter = c.max_iter;
         h->settle_key_alpha = c.alpha;
         h->settle_key_soft = soft;
@@ -1379,6 +1412,21 @@ int plan_settle(scaldpc_bp *h, const DecodeCall &c, int lvl, const TileState &st
     SC_TRY(h->d_settle.ensure((size_t)c.T * SETTLE_WORDS));
     SC_HIP(hipMemsetAsync(h->d_settle, 0, sizeof(unsigned) * (size_t)c.T * SETTLE_WORDS, c.s));  // once per level, as unsat
     sl->words = h->d_settle;
+    if (settle_sparse_mode(h->kn.settle_sparse, settle, h->identity_from >= 0)) {
+        SC_TRY(h->d_rowf.ensure((size_t)c.T * h->m));
+        SC_TRY(h->d_colf.ensure((size_t)c.T * h->n));
+        SC_HIP(hipMemsetAsync(h->d_rowf, 0, sizeof(uint4) * (size_t)c.T * h->m, c.s));
+        SC_HIP(hipMemsetAsync(h->d_colf, 0, sizeof(unsigned) * (size_t)c.T * h->n, c.s));
+        sl->rowf = h->d_rowf;
+        sl->colf = h->d_colf;
+        sl->m = h->m;
+        sl->n = h->n;
+        h->sparse_m = h->m;
+        h->sparse_n = h->n;
+        h->sparse_T = c.T;
+        sl->gate_start = h->sparse_start_next > sl->first_test ? h->sparse_start_next : sl->first_test;
+        h->sparse_start = sl->gate_start;
+    }
     if (settle >= 2 && !c.no_sync) {
         const int K = h->kn.settle_horizon > 0 ? h->kn.settle_horizon : h->settle_next;
         if (settle_horizon_usable(K, sl->first_test, c.max_iter)) sl->horizon = K;
@@ -1417,6 +1465,10 @@ int collect_settle(scaldpc_bp *h, const DecodeCall &c, Lanes &lanes, const TileS
             int g = 1;
             while (g < Gl && t + g < T && !h->settle_frozen_at[t + g]) g++;
             SC_HIP(hipMemsetAsync(sl.of(t), 0, sizeof(unsigned) * (size_t)g * SETTLE_WORDS, c.s));
+            if (sl.rowf) {  // (a stale stamp equal to a pass of the re-run would read as fresh)
+                SC_HIP(hipMemsetAsync(sl.rowf + (size_t)t * sl.m, 0, sizeof(uint4) * (size_t)g * sl.m, c.s));
+                SC_HIP(hipMemsetAsync(sl.colf + (size_t)t * sl.n, 0, sizeof(unsigned) * (size_t)g * sl.n, c.s));
+            }
             bool d = false;
             SC_TRY(iterate_tiles(h, c, lanes, st, t, g, 0, &d, poll, 0, again));
             SC_TRY(read_back(t, g, c.max_iter));
@@ -1431,6 +1483,10 @@ int collect_settle(scaldpc_bp *h, const DecodeCall &c, Lanes &lanes, const TileS
     }
     const bool learns = settle_mode(h->kn.settle, h->identity_from >= 0) >= 2;
     h->settle_next = learns ? settle_next_horizon(T, frozen, max_at, (int)h->settle_rerun, c.max_iter) : 0;
+    int min_at = 0;
+    for (int t = 0; t < T; t++)
+        if (h->settle_frozen_at[t] > 0 && (min_at == 0 || h->settle_frozen_at[t] < min_at)) min_at = h->settle_frozen_at[t];
+    h->sparse_start_next = settle_sparse_next_start(min_at, sl.first_test);
     return 0;
 }
 
@@ -1768,6 +1824,8 @@ void settle_report_reset(scaldpc_bp *h)
     h->settle_frozen_at.clear();
     h->settle_saved = h->settle_rerun = 0;
     h->settle_K = 0;
+    h->sparse_m = h->sparse_n = h->sparse_T = 0;
+    h->sparse_start = 0;
 }
 int begin_call(scaldpc_bp *h, int batch, int max_iter, void *stream, DecodeCall *c)
 {
@@ -1946,6 +2004,7 @@ int scaldpc_bp_set_channel_probs(scaldpc_bp *h, const double *probs)
     h->thr_valid = false;
     h->first_valid = false;
     h->settle_next = 0;  // (the settle horizon was learned on the priors and rows that were: learn again)
+    h->sparse_start_next = 0;
     h->ratio_valid = false;
     h->have_prior = true;
     h->prior_n = h->n;
@@ -1971,6 +2030,7 @@ int scaldpc_bp_set_channel_probs_tail(scaldpc_bp *h, int32_t first, int32_t coun
     h->thr_valid = false;
     h->first_valid = false;
     h->settle_next = 0;  // (the settle horizon was learned on the priors and rows that were: learn again)
+    h->sparse_start_next = 0;
     h->ratio_valid = false;
     h->prior_n = std::max(h->prior_n, first + count);
     h->have_prior = true;
@@ -2140,6 +2200,7 @@ int scaldpc_bp_append_rows(scaldpc_bp *h, int32_t nrows, const int32_t *row_ptr,
     h->thr_valid = false;
     h->first_valid = false;
     h->settle_next = 0;  // (the settle horizon was learned on the priors and rows that were: learn again)
+    h->sparse_start_next = 0;
     h->ratio_valid = false;
     h->d_x64.reset();
     h->d_c64.reset();
@@ -2200,6 +2261,29 @@ int scaldpc_bp_last_settle(scaldpc_bp *h, int32_t *frozen_at, int32_t cap, int64
     info[1] = h->settle_saved;
     info[2] = h->settle_rerun;
     info[3] = h->settle_K;
+    return 0;
+}
+
+int scaldpc_bp_debug_sparse_flags(scaldpc_bp *h, int32_t tile, uint32_t *row_stamp, uint64_t *row_dirty, uint32_t *col_flag, int64_t *info)
+{
+    if (!h || !info || tile < 0) return fail(SCALDPC_EINVAL, "bad argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    info[0] = h->sparse_T;
+    info[1] = h->sparse_m;
+    info[2] = h->sparse_n;
+    info[3] = h->sparse_start;
+    if (!row_stamp && !row_dirty && !col_flag) return 0;
+    if (tile >= h->sparse_T || !row_stamp || !row_dirty || !col_flag) return fail(SCALDPC_EINVAL, "no sparse flags for that tile");
+    DeviceGuard dev(h->device);
+    const int m = h->sparse_m, n = h->sparse_n;
+    std::vector<uint4> rows((size_t)m);
+    // (a debug entry, after a synchronous call: blocking copies)
+    if (m) SC_HIP(hipMemcpy(rows.data(), h->d_rowf + (size_t)tile * m, sizeof(uint4) * (size_t)m, hipMemcpyDeviceToHost));
+    if (n) SC_HIP(hipMemcpy(col_flag, h->d_colf + (size_t)tile * n, sizeof(unsigned) * (size_t)n, hipMemcpyDeviceToHost));
+    for (int r = 0; r < m; r++) {
+        row_stamp[r] = rows[(size_t)r].x;
+        row_dirty[r] = ((uint64_t)rows[(size_t)r].w << 32) | rows[(size_t)r].z;
+    }
     return 0;
 }
 

@@ -801,10 +801,27 @@ static_assert(REC_TW == TW, "the record layout of scaldpc_rec_pack.h is laid out
 //         changed in test t, so it was not frozen at t - 1 either and its maximum was t - 1 = done already.)
 //   mark  the test this launch is a half of (0 = it is not tracked: a BOOT pass, or a pass at which alpha still moves)
 // words == nullptr: all of it off.  A wave-uniform branch on a kernel argument, no instantiation of its own.
+// The SPARSE gate (knob settle_sparse; the rule in full: tests/settle_sparse_ref.py, which restates it, and DESIGN.md 4).
+// Long before a tile freezes most of its rows and columns have stopped changing, so a tracked pass also says WHICH nodes
+// changed, and the next pass returns for the nodes none of whose inputs did:
+//   rowf  [tile][m] {stamp, -, dirty lo, dirty hi}: a row that runs in tracked check pass t stores stamp = t and the mask of
+//         its edges (by index in the row) whose check-to-variable message may differ from the one before in a real codeword:
+//         all ones if a first record differs bit for bit (its sign bit is the row's parity), else bit(old arg) | bit(new arg)
+//         over the codewords whose second record or arg-min byte differs
+//   colf  [tile][n] u32: a column of degree > 1 that runs in tracked variable pass t stores t << 1 | (a sign mask it stored
+//         differs from the one it overwrote in a real codeword)
+//   gate  this pass returns for a row none of whose columns is stamped with the pass before (colf >> 1 == mark - 1), for a
+//         column none of whose edges has its bit in a row flag stamped with this pass (stamp == mark - 1: variable pass t
+//         carries mark t + 1) and whose own colf is not (t - 1) << 1 | 1.  Which passes gate: settle_sparse_*_gate.
+// Plain stores, one writer per word and pass, visible at the kernel boundary on the lane's stream like the words.  A stale
+// or missing stamp can only make a node run; running is always right.  rowf == nullptr: off.
 constexpr int SETTLE_WORDS = 32, SETTLE_SHARDS = 8;
 struct Settle {
     unsigned *words = nullptr;  // of the launch's first tile
     int done = 0, mark = 0;
+    uint4 *rowf = nullptr;      // of the launch's first tile, like words
+    unsigned *colf = nullptr;
+    int ncol = 0, gate = 0;     // columns of the graph (colf's tile stride)
 };
 __device__ __forceinline__ bool settle_frozen(const unsigned *__restrict__ w, int done)
 {
@@ -821,7 +838,8 @@ __device__ __forceinline__ void check_minsum_row_rec(const float *p, u64 synd_ma
                                                      float *__restrict__ rec2, unsigned char *__restrict__ arg,
                                                      u64 *__restrict__ sgn, int lane, const int *__restrict__ pos,
                                                      bool const_last = false, float x_last = 0.0f,
-                                                     unsigned *mark_word = nullptr, unsigned mark = 0, u64 real = 0)
+                                                     unsigned *mark_word = nullptr, unsigned mark = 0, u64 real = 0,
+                                                     uint4 *row_flag = nullptr)
 {
     // BOOT: the sign masks are laid out in the variable pass's order (position of the edge in the re-laid edge list: a
     // column's masks are contiguous there); lane k fetches edge k's position up front
@@ -912,8 +930,31 @@ __device__ __forceinline__ void check_minsum_row_rec(const float *p, u64 synd_ma
         if (tracked) {
             if constexpr (!EARLY) oa = arg[lane];
             arg[lane] = (unsigned char)idx;
-            const bool changed = o1 != __float_as_uint(s1) || o2 != __float_as_uint(s2) || oa != idx;
-            if ((__ballot(changed) & real) != 0 && lane == 0) *mark_word = mark;
+            const u64 c1 = __ballot(o1 != __float_as_uint(s1)) & real;
+            const u64 c2 = __ballot(o2 != __float_as_uint(s2) || oa != idx) & real;
+            if ((c1 | c2) != 0 && lane == 0) *mark_word = mark;
+            // the sparse gate's row flag (Settle): which of the row's edges may carry another message than before.  The OR of
+            // the arg-min bits is built on the scalar side, one step per distinct arg value among the changed codewords, and
+            // only under "no first record changed, something else did".
+            if (row_flag) {
+                u64 dirty = 0;
+                if (c1 != 0)
+                    dirty = ~0ull;
+                else if (c2 != 0) {
+#pragma unroll 1
+                    for (int half = 0; half < 2; half++) {
+                        const unsigned av = half ? idx : oa;
+                        u64 rem = c2;
+#pragma unroll 1
+                        while (rem != 0) {
+                            const unsigned a = (unsigned)__builtin_amdgcn_readlane((int)av, rfl(__builtin_ctzll(rem)));
+                            if (a < 64u) dirty |= 1ull << a;
+                            rem &= ~__ballot(av == a);
+                        }
+                    }
+                }
+                if (lane == 0) *row_flag = make_uint4(mark, 0u, (unsigned)dirty, (unsigned)(dirty >> 32));
+            }
         } else
             arg[lane] = (unsigned char)idx;
     } else
@@ -962,6 +1003,7 @@ __global__ __launch_bounds__(256) void k_check_minsum_rec(const int *__restrict_
     const int *md = list + (size_t)rfl((int)blockIdx.x * 4 + (int)(threadIdx.x >> 6)) * 4;  // uniform address: scalar loads
     u64 dw = 0;
     unsigned *mark_word = nullptr;  // (settled codewords: fixed-iteration calls, which never come with PAR)
+    bool sparse = false;
     if constexpr (PAR) {
         dw = done[tl];
         if (skip_done && dw == ~0ull) return;
@@ -973,6 +1015,7 @@ __global__ __launch_bounds__(256) void k_check_minsum_rec(const int *__restrict_
             if (!BOOT && st.mark) {
                 mark_word = w + (blockIdx.x & (SETTLE_SHARDS - 1));
                 dw = done[tl];  // (fixed iterations: the padding lanes)
+                sparse = st.rowf != nullptr;
             }
         }
     }
@@ -983,6 +1026,18 @@ __global__ __launch_bounds__(256) void k_check_minsum_rec(const int *__restrict_
     if (r >= 0) {
         const int e0 = md[1];
         const int deg = md[2];
+        uint4 *rf = nullptr;
+        if constexpr (!BOOT && !PAR)
+            if (sparse) {
+                // the sparse gate (Settle): lane k looks at the column of edge k; no column stamped by the variable pass
+                // before = no input of the row changed, and the row would store what is there
+                if (st.gate) {
+                    unsigned cf = 0;
+                    if (lane < deg) cf = st.colf[(size_t)tl * st.ncol + col_idx[e0 + lane]];
+                    if (__ballot(lane < deg && (cf >> 1) == (unsigned)(st.mark - 1)) == 0) return;
+                }
+                rf = st.rowf + (size_t)tl * m + r;
+            }
         const float *p = msg + ((size_t)tl * E + e0) * TW + lane;
         float *rt = rec + (size_t)tl * rec_tile_floats(m);  // the tile's block: [m1 | m2][row][64], arg
         float *rc = rt + rec_row_off(r), *rc2 = rc + rec_m2_off(m);
@@ -1000,7 +1055,7 @@ __global__ __launch_bounds__(256) void k_check_minsum_rec(const int *__restrict_
 #define MR(D)                                                                                                   \
     case D:                                                                                                     \
         if constexpr (D <= CAP)                                                                                 \
-            check_minsum_row_rec<D, BOOT>(p, sw, alpha, rc, rc2, ar, sg, lane, ps, cl, xl, mark_word, (unsigned)st.mark, ~dw); \
+            check_minsum_row_rec<D, BOOT>(p, sw, alpha, rc, rc2, ar, sg, lane, ps, cl, xl, mark_word, (unsigned)st.mark, ~dw, rf); \
         break;
 #define MR8(D) MR(D) MR(D + 1) MR(D + 2) MR(D + 3) MR(D + 4) MR(D + 5) MR(D + 6) MR(D + 7)
         switch (deg) {
@@ -1683,7 +1738,8 @@ __device__ __forceinline__ float var_col_rec(float *tile_base, const float *__re
                                              const unsigned char *__restrict__ arg_base, u64 *sgn_col, unsigned lane,
                                              const int *__restrict__ rc, const int4 *__restrict__ row4,
                                              const int *__restrict__ ce1, const int *__restrict__ cr1, float pr,
-                                             unsigned *mark_word = nullptr, unsigned mark = 0, u64 real = 0)
+                                             unsigned *mark_word = nullptr, unsigned mark = 0, u64 real = 0,
+                                             unsigned *col_flag = nullptr)
 {
     int eid[D], rw[D];
     {
@@ -1757,7 +1813,10 @@ __device__ __forceinline__ float var_col_rec(float *tile_base, const float *__re
     // (wave-uniform) = this pass is tracked, and a difference in a real codeword's bit marks the tile
     if (mark_word) {
         const unsigned dlo = (nlo ^ (unsigned)slo) & (unsigned)real, dhi = (nhi ^ (unsigned)shi) & (unsigned)(real >> 32);
-        if (__ballot((int)lane < D && (dlo | dhi) != 0) != 0 && lane == 0) *mark_word = mark;
+        const bool sc = __ballot((int)lane < D && (dlo | dhi) != 0) != 0;
+        if (sc && lane == 0) *mark_word = mark;
+        // the sparse gate's column flag (Settle): this is variable pass mark - 1, and it ran
+        if (col_flag && lane == 0) *col_flag = ((mark - 1u) << 1) | (sc ? 1u : 0u);
     }
     return temp;
 }
@@ -1911,6 +1970,9 @@ __device__ __forceinline__ void var_rec_wide_wave(const int *__restrict__ list, 
     const int4 *w4 = (const int4 *)(rw.var_rows + (size_t)ri * VAR_INLINE);
     const float pr = prior(v, tl, (int)lane);
     const unsigned r2 = (unsigned)rw.m * (TW * (unsigned)sizeof(float));
+    // the sparse gate (Settle): a wide column is never gated and always stamps, so that its rows run in the next check pass;
+    // its "sign masks changed" bit, which only a column's own gate reads, stays 0
+    if (mark_word && rw.stl.colf && lane == 0) rw.stl.colf[(size_t)tl * rw.stl.ncol + v] = ((unsigned)rw.stl.mark - 1u) << 1;
     const float L = last ? var_col_rec_wide<true>(tb, rb, r2, ab, st + cb, lane, rc, w4, ce, cr, d, pr)
                          : var_col_rec_wide<false>(tb, rb, r2, ab, st + cb, lane, rc, w4, ce, cr, d, pr, mark_word,
                                                    (unsigned)rw.stl.mark, ~dn);
@@ -1975,11 +2037,31 @@ __global__ __launch_bounds__(256) void k_var_rec(const int *__restrict__ list, c
     const int cb = rc[1];
     const int d = rc[2];
     if (LAST && decided && d > 1) return;
+    const int *ce = csc_edge + cb, *cr = csc_row + cb;
+    unsigned *cf = nullptr;
+    if constexpr (!LAST)
+        if (mark_word && stl.colf && d > 1) {
+            // the sparse gate (Settle): lane j looks at the flag of the row of the column's j-th edge; no edge marked by
+            // this iteration's check pass and no sign mask of its own changed in its last run = the column's inputs are what
+            // they were, and it would store what is there (its decisions in `hard` included)
+            cf = stl.colf + (size_t)tl * n + v;
+            if (stl.gate) {
+                const unsigned t = (unsigned)stl.mark - 1u;
+                bool hit = false;
+                if ((int)lane < d) {
+                    const int w = cr[lane];
+                    const uint4 f = stl.rowf[(size_t)tl * m + rec_row_of(w)];
+                    const unsigned ix = (unsigned)rec_index_of(w);
+                    hit = f.x == t && (((ix < 32u ? f.z : f.w) >> (ix & 31u)) & 1u) != 0;
+                }
+                const unsigned own = *cf;
+                if (__ballot(hit) == 0 && own != (((t - 1u) << 1) | 1u)) return;
+            }
+        }
     float *tb = msg + (size_t)tl * E * TW;
     const float *rb = rec + (size_t)tl * rec_tile_floats(m);  // the tile's block: [m1 | m2][row][64], arg
     const unsigned char *ab = (const unsigned char *)(rb + rec_arg_off(m));
     u64 *st = sgn + (size_t)tl * E;
-    const int *ce = csc_edge + cb, *cr = csc_row + cb;
     const int4 *w4 = (const int4 *)(var_rows + (size_t)ri * VAR_INLINE);
     const float pr = prior(v, tl, (int)lane);
     float L = pr;
@@ -1987,7 +2069,7 @@ __global__ __launch_bounds__(256) void k_var_rec(const int *__restrict__ list, c
 #define VR(D)                                                                                                \
     case D:                                                                                                  \
         if constexpr (D <= CAP)                                                                              \
-            L = var_col_rec<D, LAST>(tb, rb, r2, ab, st + cb, lane, rc, w4, ce, cr, pr, mark_word, (unsigned)stl.mark, ~dn); \
+            L = var_col_rec<D, LAST>(tb, rb, r2, ab, st + cb, lane, rc, w4, ce, cr, pr, mark_word, (unsigned)stl.mark, ~dn, cf); \
         break;
 #define VR8(D) VR(D) VR(D + 1) VR(D + 2) VR(D + 3) VR(D + 4) VR(D + 5) VR(D + 6) VR(D + 7)
     switch (d) {

@@ -275,6 +275,55 @@ inline int settle_next_horizon(int tiles, int frozen, int max_frozen_at, int rer
 // would only pay for the tracking.
 inline int settle_mode(int knob, bool identity_block) { return knob >= 0 ? knob : identity_block ? 2 : 0; }
 
+// The sparse gate of a tracked level (knob settle_sparse; the device side: `Settle`'s row_flag / col_flag tables).  The
+// tracked passes write flags -- a pass with a mark, settle_check_mark / settle_var_mark -- and a pass GATES, i.e. its waves
+// return for nodes none of whose inputs changed, only when the pass before it on the same tiles wrote flags and it is
+// tracked itself: with start = first_test, check passes first_test + 1 ... last_test (variable pass t - 1 stamped the columns that ran; at
+// first_test every column ran, so gating that pass would skip nothing), variable passes first_test ... last_test - 1
+// (check pass t stamped its rows).  The bootstrap pass, passes under a moving alpha (before first_test), the closing pass
+// and early-exit calls (never tracked) do not gate.  tests/settle_sparse_main.cc walks these under the sanitizers,
+// tests/test_settle_sparse.py holds them to tests/settle_sparse_ref.py.
+// `start` (>= first_test) = the variable pass from which the call gates at all; its check passes gate one later.  Every
+// tracked pass writes its flags whether it gates or not, so any start from first_test on finds them.
+inline int settle_sparse_check_gate(int it, int first_test, int last_test, int start)
+{
+    const int from = start > first_test ? start : first_test;
+    return settle_check_mark(it, first_test, last_test) != 0 && settle_var_mark(it - 1, first_test, last_test) != 0 && it > from;
+}
+inline int settle_sparse_var_gate(int it, int first_test, int last_test, int start)
+{
+    const int from = start > first_test ? start : first_test;
+    return settle_var_mark(it, first_test, last_test) != 0 && settle_check_mark(it, first_test, last_test) != 0 && it >= from;
+}
+// The start the NEXT call gates from, learned like the horizon (settle_next_horizon) from the last call: the gate's two
+// dependent loads stand in front of a wave's own, which a dense pass -- one in which nearly every node still has a changed
+// input -- pays for and gets nothing back (variable passes 3 and 4 of the HQC-128 bench: + 8 ... 10 us of 53 per launch,
+// profiles/settle_sparse/README.md).  Nodes go quiet shortly before their tile freezes: on the bench batch, whose first
+// tiles freeze at test 8, variable pass 5 still runs 70 % of its columns and saves 3 us, variable pass 6 runs 3 ... 5 %.
+// So the next call gates from SETTLE_SPARSE_LEAD passes before the smallest frozen-at number of the last one.
+//   min_frozen_at  the smallest frozen-at number > 0 among the last call's tiles, 0 = no tile froze or nothing learned yet
+// 0 = gate from the first test on: a call that learns, and a call after one in which nothing froze -- there the tiles
+// cycle with part of their nodes quiet all the way, which the gate skips from the start.
+constexpr int SETTLE_SPARSE_LEAD = 2;
+inline int settle_sparse_next_start(int min_frozen_at, int first_test)
+{
+    if (min_frozen_at <= 0) return 0;
+    const int s = min_frozen_at - SETTLE_SPARSE_LEAD;
+    return s > first_test ? s : first_test;
+}
+// (Both functions lean on the bootstrap check pass coming before the first test: it is the first record-form check pass of
+// a group, iteration 2 at the latest, it carries no mark and stamps no row, and first_test >= SETTLE_FIRST = 3 -- so the
+// check pass of a gating variable pass is never the bootstrap one.  iterate_tiles passes gate = 0 with a bootstrap pass
+// all the same.)
+// The `settle_sparse` knob in force on a tracked level (settle = the settle mode in force, > 0): 0 / 1 as given; -1 (the
+// default) = on where the settle mode is 2 AND the graph is [Hin | I] -- the graphs on which `settle` turns itself on.  On
+// a graph where nothing freezes the gate only costs (+ 18 % on a tracked call, profiles/settle_sparse/README.md), so a
+// caller who forces `settle` there gets the gate only by asking for it.
+inline int settle_sparse_mode(int knob, int settle, bool identity_block)
+{
+    return settle <= 0 ? 0 : knob >= 0 ? knob : (settle >= 2 && identity_block) ? 1 : 0;
+}
+
 // ---------------------------------------------------------------------------
 // The record-form variable pass (launch_var, scaldpc_bp.hip): which blocks of the column records a pass runs.  The
 // records are laid out bucket by bucket -- bucket b = blocks [blk[b], blk[b + 1]), unroll bound maxd[b], ascending;
